@@ -13,8 +13,15 @@ vote with their whole bucket.  `hits_per_sec` and `vote_increments_per_sec` are 
 rates that do not depend on how much of the scene lies out of the model's reach.
 
   python bench.py --gpus 1 --steps 5 --warmup 1
+  python bench.py --gpus 1 --steps 5 --warmup 1 --full
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  --full adds
+what takes work of its own: the step with the scene upload inside it, the roofline figures,
+the CPU baseline and the pose recall against the oracle (the last two not with
+--no-cpu-baseline).  --dump-outputs DIR writes what the last timed step returned to a caller
+(the pose, the kept peak cells and their poses) as DIR/<name>.npy.
 
 Multi-GPU: one process per GPU; scene reference points are dealt round-robin to
 ranks (no data-path collective); per step one oslam_align_multi call per rank (C-ABI):
@@ -60,8 +67,13 @@ def main():
     ap.add_argument("--tau-d", type=float, default=0.025)
     ap.add_argument("--vote-mode", choices=["exact", "fast"], default="exact")
     ap.add_argument("--df", type=int, default=0, help="ref_point_df; 0 = 8 // gpus (weak scaling)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline and no pose recall")
+    ap.add_argument("--full", action="store_true",
+                    help="also the scene-upload step time, roofline, CPU baseline and pose recall against the oracle")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's results as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
     import torch.distributed as dist
@@ -165,58 +177,30 @@ def main():
     elapsed = float(el.item())
     total_ppfs, total_votes, total_hits = (float(x) for x in tot.tolist())
 
-    # "H2D of the scene included and also reported separately": the same step with the Scene
-    # built from host buffers inside it (upload + reference frames on the host), a few repetitions, rank-local
-    t_incl = []
-    for _ in range(3):
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        sc2 = ppf.Scene(sp, sn, d_dist=d_dist, ref_point_downsample_factor=df, params=par)
-        t2 = time.perf_counter()
-        step(sc2)
-        torch.cuda.synchronize()
-        t_incl.append((time.perf_counter() - t1, t2 - t1))
-        sc2.close()
-    ms_incl = 1e3 * float(np.median([a for a, _ in t_incl]))
-    ms_scene = 1e3 * float(np.median([b for _, b in t_incl]))
+    if args.dump_outputs and rank == 0:
+        # before anything else runs the path again: the model's result fields are those of the last timed step
+        dump_outputs(args.dump_outputs, T, model)
+
+    ms_incl = ms_scene = None
+    if args.full:
+        # "H2D of the scene included and also reported separately": the same step with the Scene
+        # built from host buffers inside it (upload + reference frames on the host), a few repetitions, rank-local
+        t_incl = []
+        for _ in range(3):
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            sc2 = ppf.Scene(sp, sn, d_dist=d_dist, ref_point_downsample_factor=df, params=par)
+            t2 = time.perf_counter()
+            step(sc2)
+            torch.cuda.synchronize()
+            t_incl.append((time.perf_counter() - t1, t2 - t1))
+            sc2.close()
+        ms_incl = 1e3 * float(np.median([a for a, _ in t_incl]))
+        ms_scene = 1e3 * float(np.median([b for _, b in t_incl]))
 
     if rank == 0:
         st = stats_acc[-1]
-        n_slices = (M + 2045) // 2046
-        launches = sum(s["vote_launches"] for s in stats_acc)
-        ms_vote_kernel = float(sum(s["ms_vote_kernel"] for s in stats_acc))   # HIP events around each launch
-        ms_key_kernel = float(sum(s["ms_key_kernel"] for s in stats_acc))
-        ms_path = float(np.mean([s["ms_vote"] for s in stats_acc]))
-        per_launch_ms = ms_vote_kernel / launches
-        steps_per_launch = args.steps / launches
-        # ---- k_vote, bytes this design cannot avoid: every bucket a run of hits needs is read once
-        # (4 B per model pair entry), 8 B of run record + 8 B of bucket record per (run, slice), 8 B per hit and
-        # slice for its angle, 16 B per emitted peak record
-        design_bytes_step = (4.0 * st["num_entries_streamed"] + 16.0 * st["num_items"] + 8.0 * st["num_hits"] * n_slices
-                             + 16.0 * st["num_emitted"])
-        design_launch = design_bytes_step * steps_per_launch
-        achieved = design_launch / (per_launch_ms * 1e-3) / 1e9
-        # ---- the same launch by SURVEY 8d's formula (8 B per vote, 8 B per probe, 16 B per record): not a
-        # ceiling for this design (an entry is 4 B and a bucket is read once per run of hits, not once per hit)
-        survey_bytes_step = 8.0 * st["num_votes"] + 8.0 * st["num_hits"] * n_slices + 16.0 * st["num_emitted"]
-        survey_launch = survey_bytes_step * steps_per_launch
-        survey_achieved = survey_launch / (per_launch_ms * 1e-3) / 1e9
-        path_bytes = 24.0 * S + 8.0 * st["num_pairs_probed"] + 8.0 * st["num_votes"] + 16.0 * st["num_emitted"]
-        votes_per_s_kernel = st["num_votes"] * args.steps / (ms_vote_kernel * 1e-3)
-        # ceilings of the vote loop (tools/micro/): one conflict-free ds_add_u32 wave-instruction
-        # (64 votes) per 4.4 cycles per CU (measured); one hit voting with a chunk = 256 votes = 13 vector
-        # instructions in both modes (exact mode finds its near-edge votes by search, outside the loop), at their
-        # stand-alone issue costs (v_sub_u32 2.33 cycles per wave-instruction, everything else in the loop 4.2-4.3:
-        # tools/micro/valu_rate_bench.hip) on one of 1024 SIMDs; 2.4 GHz.  The kernel is bound by the issue of ALL its
-        # instructions (3.7 cycles per instruction and SIMD, scalar ones included: profiles/r03_pmc_sq_k_vote.txt,
-        # r03_ab_step_loads_and_hit_loop.txt); the loop's own 20 instructions per hit and chunk are 44 % of them,
-        # which is why this fraction cannot reach 1.
-        lds_peak = 256 * 64 * 2.4e9 / 4.4
-        valu_instr = 13
-        valu_cycles = 47.5
-        valu_peak = 1024 * 256 * 2.4e9 / valu_cycles
         dt, dr = ppf.ht_dist(T, poses[0][1])
-        traffic, traffic_note = pmc_traffic(args, M, S, df)
         out = {
             "metric": "scene_ppf_votes_per_sec",
             "value": total_ppfs / elapsed,
@@ -238,8 +222,11 @@ def main():
                        "parallelism": "scene-ref-shard x%d" % world, "exchange": exchange},
             "vote_increments_per_sec": total_votes / elapsed,
             "hits_per_sec": total_hits / elapsed,
-            "ms_per_step_incl_scene": ms_incl,
-            "ms_scene_create": ms_scene,
+        }
+        if args.full:
+            out["ms_per_step_incl_scene"] = ms_incl
+            out["ms_scene_create"] = ms_scene
+        out.update({
             "per_step": {"scene_ppfs": st["num_scene_ppfs"], "pairs_probed": st["num_pairs_probed"],
                          "hits": st["num_hits"], "votes": st["num_votes"],
                          "entries_streamed": st["num_entries_streamed"], "buckets_streamed": st["num_items"],
@@ -249,46 +236,102 @@ def main():
             "pose": {"rot_err_deg": float(np.degrees(dr)), "trans_err_frac_diam": dt / diam,
                      "ok_at_reference_criterion_12deg_0.1diam": bool(dr < np.radians(12) and dt < 0.1 * diam)},
             "model_build_s": t_build,
-            "roofline": {"bound": "hbm", "kernel": "k_vote", "achieved": achieved, "peak": HBM_PEAK_GBPS,
-                         "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS,
-                         "measured_against": "design bytes vs the HBM peak; the 100 MB entry stream is served from the "
-                                             "256 MiB Infinity Cache, so this prices the stream, not HBM pins",
-                         "traffic": traffic, "traffic_note": traffic_note,
-                         "traffic_ratio": (traffic / design_launch) if traffic else None,
-                         "alg_bytes_per_launch": design_launch, "launch_ms": per_launch_ms,
-                         "launches_per_step": launches / args.steps,
-                         "alg_bytes_model": "4 B x model pair entries streamed (each bucket once per run of hits and slice) "
-                                            "+ 16 B per (run, slice) + 8 B per hit and slice + 16 B per record",
-                         "binding": "instruction issue, all kinds counted (3.7 cycles per instruction and SIMD with four "
-                                    "waves per SIMD), then LDS atomics: see roofline_valu / roofline_lds_atomic "
-                                    "(DESIGN.md 4); the entry stream comes out of the Infinity Cache",
-                         "key_kernels_ms_per_step": ms_key_kernel / args.steps,
-                         "path_kernels_ms_per_step": ms_path,
-                         "torch_event_ms_per_step": ev0.elapsed_time(ev1) / args.steps},
-            "roofline_valu": {"bound": "valu_issue", "kernel": "k_vote", "unit": "votes/s", "achieved": votes_per_s_kernel,
-                              "peak": valu_peak, "frac": votes_per_s_kernel / valu_peak,
-                              "note": "votes per second of vote-kernel time against 256 votes per %d vector instructions = "
-                                      "%.1f SIMD cycles at their measured issue costs (one vote iteration of the inner "
-                                      "loop, nothing else)" % (valu_instr, valu_cycles)},
-            "roofline_lds_atomic": {"bound": "lds_atomic", "kernel": "k_vote", "unit": "votes/s",
-                                    "achieved": votes_per_s_kernel, "peak": lds_peak, "frac": votes_per_s_kernel / lds_peak,
-                                    "note": "against the measured conflict-free ds_add_u32 rate of the chip"},
-            "roofline_survey_8d": {"bound": "hbm", "kernel": "k_vote", "achieved": survey_achieved, "peak": HBM_PEAK_GBPS,
-                                   "unit": "GB/s", "frac": survey_achieved / HBM_PEAK_GBPS,
-                                   "alg_bytes_per_launch": survey_launch,
-                                   "path_achieved_GBps": path_bytes / (ms_path * 1e-3) / 1e9,
-                                   "note": "SURVEY.md 8d's byte model (8 B per vote): above 1 by construction for a design that "
-                                           "packs an entry into 4 B and streams a bucket once per run of hits; kept for comparison"},
-        }
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(mp, mn, sp, sn, df, d_dist)
-            out["pose_recall_at_1deg"] = pose_recall(ppf, synth, mode, T, model.last_cells()[0], args, df)
+        })
+        if args.full:
+            out.update(roofline_figures(args, stats_acc, M, S, df, ev0.elapsed_time(ev1) / args.steps))
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(mp, mn, sp, sn, df, d_dist)
+                out["pose_recall_at_1deg"] = pose_recall(ppf, synth, mode, T, model.last_cells()[0], args, df)
         print(json.dumps(out), flush=True)
     if comm is not None:
         comm.close()
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(d, T, model):
+    """What the last timed step handed its caller: the returned pose and the model's result fields (the kept peak
+    cells in order with their vote counts, and the pose of each), float32 or float64, a few hundred kB."""
+    cells, cell_poses = model.last_cells()
+    # a cell code packs (reference point, model point, alpha bin) into well under 53 bits: exact as float64
+    assert len(cells) == 0 or int(cells["code"].max()) < (1 << 53)
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "pose.npy"), np.asarray(T, np.float32).reshape(4, 4))
+    np.save(os.path.join(d, "cell_code.npy"), cells["code"].astype(np.float64))
+    np.save(os.path.join(d, "cell_count.npy"), cells["count"].astype(np.float64))
+    np.save(os.path.join(d, "cell_pose.npy"), cell_poses.astype(np.float32).reshape(-1, 4, 4))
+    log("[rank 0] outputs of the last timed step: %d kept cells, written to %s" % (len(cells), d))
+
+
+def roofline_figures(args, stats_acc, M, S, df, torch_event_ms_per_step):
+    st = stats_acc[-1]
+    n_slices = (M + 2045) // 2046
+    launches = sum(s["vote_launches"] for s in stats_acc)
+    ms_vote_kernel = float(sum(s["ms_vote_kernel"] for s in stats_acc))   # HIP events around each launch
+    ms_key_kernel = float(sum(s["ms_key_kernel"] for s in stats_acc))
+    ms_path = float(np.mean([s["ms_vote"] for s in stats_acc]))
+    per_launch_ms = ms_vote_kernel / launches
+    steps_per_launch = args.steps / launches
+    # ---- k_vote, bytes this design cannot avoid (DESIGN.md 4): every bucket a run of hits needs is read once
+    # (4 B per model pair entry), 8 B of run record + 8 B of bucket record per (run, slice), 8 B per hit and
+    # slice for its angle, 16 B per emitted peak record
+    design_bytes_step = (4.0 * st["num_entries_streamed"] + 16.0 * st["num_items"] + 8.0 * st["num_hits"] * n_slices
+                         + 16.0 * st["num_emitted"])
+    design_launch = design_bytes_step * steps_per_launch
+    achieved = design_launch / (per_launch_ms * 1e-3) / 1e9
+    # ---- the same launch by SURVEY 8d's formula (8 B per vote, 8 B per probe, 16 B per record): not a
+    # ceiling for this design (an entry is 4 B and a bucket is read once per run of hits, not once per hit)
+    survey_bytes_step = 8.0 * st["num_votes"] + 8.0 * st["num_hits"] * n_slices + 16.0 * st["num_emitted"]
+    survey_launch = survey_bytes_step * steps_per_launch
+    survey_achieved = survey_launch / (per_launch_ms * 1e-3) / 1e9
+    path_bytes = 24.0 * S + 8.0 * st["num_pairs_probed"] + 8.0 * st["num_votes"] + 16.0 * st["num_emitted"]
+    votes_per_s_kernel = st["num_votes"] * args.steps / (ms_vote_kernel * 1e-3)
+    # ceilings of the vote loop (tools/micro/, DESIGN.md 4): one conflict-free ds_add_u32 wave-instruction
+    # (64 votes) per 4.4 cycles per CU (measured); one hit voting with a chunk = 256 votes = 13 vector
+    # instructions in both modes (exact mode finds its near-edge votes by search, outside the loop), at their
+    # stand-alone issue costs (v_sub_u32 2.33 cycles per wave-instruction, everything else in the loop 4.2-4.3:
+    # tools/micro/valu_rate_bench.hip) on one of 1024 SIMDs; 2.4 GHz.  The kernel is bound by the issue of ALL its
+    # instructions (3.7 cycles per instruction and SIMD, scalar ones included: profiles/r03_pmc_sq_k_vote.txt,
+    # r03_ab_step_loads_and_hit_loop.txt); the loop's own 20 instructions per hit and chunk are 44 % of them,
+    # which is why this fraction cannot reach 1.
+    lds_peak = 256 * 64 * 2.4e9 / 4.4
+    valu_instr = 13
+    valu_cycles = 47.5
+    valu_peak = 1024 * 256 * 2.4e9 / valu_cycles
+    traffic, traffic_note = pmc_traffic(args, M, S, df)
+    return {
+        "roofline": {"bound": "hbm", "kernel": "k_vote", "achieved": achieved, "peak": HBM_PEAK_GBPS,
+                     "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS,
+                     "measured_against": "design bytes vs the HBM peak; the 100 MB entry stream is served from the "
+                                         "256 MiB Infinity Cache, so this prices the stream, not HBM pins",
+                     "traffic": traffic, "traffic_note": traffic_note,
+                     "traffic_ratio": (traffic / design_launch) if traffic else None,
+                     "alg_bytes_per_launch": design_launch, "launch_ms": per_launch_ms,
+                     "launches_per_step": launches / args.steps,
+                     "alg_bytes_model": "4 B x model pair entries streamed (each bucket once per run of hits and slice) "
+                                        "+ 16 B per (run, slice) + 8 B per hit and slice + 16 B per record",
+                     "binding": "instruction issue, all kinds counted (3.7 cycles per instruction and SIMD with four "
+                                "waves per SIMD), then LDS atomics: see roofline_valu / roofline_lds_atomic "
+                                "(DESIGN.md 4); the entry stream comes out of the Infinity Cache",
+                     "key_kernels_ms_per_step": ms_key_kernel / args.steps,
+                     "path_kernels_ms_per_step": ms_path,
+                     "torch_event_ms_per_step": torch_event_ms_per_step},
+        "roofline_valu": {"bound": "valu_issue", "kernel": "k_vote", "unit": "votes/s", "achieved": votes_per_s_kernel,
+                          "peak": valu_peak, "frac": votes_per_s_kernel / valu_peak,
+                          "note": "votes per second of vote-kernel time against 256 votes per %d vector instructions = "
+                                  "%.1f SIMD cycles at their measured issue costs (one vote iteration of the inner "
+                                  "loop, nothing else)" % (valu_instr, valu_cycles)},
+        "roofline_lds_atomic": {"bound": "lds_atomic", "kernel": "k_vote", "unit": "votes/s",
+                                "achieved": votes_per_s_kernel, "peak": lds_peak, "frac": votes_per_s_kernel / lds_peak,
+                                "note": "against the measured conflict-free ds_add_u32 rate of the chip"},
+        "roofline_survey_8d": {"bound": "hbm", "kernel": "k_vote", "achieved": survey_achieved, "peak": HBM_PEAK_GBPS,
+                               "unit": "GB/s", "frac": survey_achieved / HBM_PEAK_GBPS,
+                               "alg_bytes_per_launch": survey_launch,
+                               "path_achieved_GBps": path_bytes / (ms_path * 1e-3) / 1e9,
+                               "note": "SURVEY.md 8d's byte model (8 B per vote): above 1 by construction for a design that "
+                                       "packs an entry into 4 B and streams a bucket once per run of hits; kept for comparison"},
+    }
 
 
 def pmc_traffic(args, M, S, df):

@@ -1,5 +1,5 @@
 """Turn two rocprofv3 PMC passes (--pmc FETCH_SIZE / --pmc WRITE_SIZE, csv output) over
-`python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline` into profiles/rNN_pmc_traffic.json.
+`python3 bench.py --steps 2 --warmup 1 --full --no-cpu-baseline` into profiles/rNN_pmc_traffic.json.
 
 usage: python tools/make_pmc_traffic.py FETCH_DIR WRITE_DIR OUT.json [model_points scene_points df mode tau_d]
 
