@@ -320,6 +320,77 @@ int oslam_local_peaks(oslam_model *m, uint32_t global_max, oslam_cell *cells_out
 int oslam_align_finish(oslam_model *m, oslam_scene *s, const oslam_cell *cells, size_t n,
                        uint32_t global_max, float T_rowmajor[16], oslam_stats *stats);
 
+/* ---- pose refinement and presence score (after oslam_align / oslam_db_align; the reference has no such stage,
+ * Drost's method and SLAM++ follow the vote with ICP).  A voting pose is the centre of an accumulator bin (12 degree
+ * angle bins, translation quantised by d_dist); this stage refines it by point-to-plane ICP against the scene cloud
+ * and scores it by the share of model points that find a scene point near them.  Everything runs on the device of
+ * the model and scene, on the library stream (oslam_set_stream).  Poses are row-major, model -> scene.
+ *
+ * Correspondence of model point i (p, n) under a float32 pose T = [R | t] at radius r:
+ *     p'x = ((R00*px + R01*py) + R02*pz) + t0, likewise y, z; n' the same expression without t (all float32).
+ *     A scene point (q, nq) qualifies when, with d = q - p', (dx*dx + dy*dy) + dz*dz <= r*r (r*r rounded to float)
+ *     and (n'x*nqx + n'y*nqy) + n'z*nqz >= min_normal_dot.  The correspondence is the qualifying point with the
+ *     smallest d*d; ties go to the lowest scene index.  The device reproduces this bit for bit.
+ * Step (Gauss-Newton on the point-to-plane residual, radius max_corr_dist * d_dist of the model):
+ *     c = the model centroid (mean of its points in double) transformed by the current pose, rounded to float;
+ *     r_i = nq . (p'_i - q_i), J_i = [(p'_i - c) x nq, nq]; A = sum J^T J, b = -sum J^T r, summed in float per
+ *     workgroup of 256 model points (fixed order) and in double across workgroups (index order).  Solve
+ *     (A + mu I) x = b, mu = 1e-6 trace(A) / 6, by Cholesky in double; x = (omega, v).  Fewer than 6 correspondences
+ *     (or a failed factorisation) stop the member with its pose kept.  Otherwise T <- [dR | c - dR c + v] T with
+ *     dR = Rodrigues(omega), then the rotation is re-orthonormalised by Gram-Schmidt over its columns x, y, z.
+ *     The pose stays in double between iterations; each iteration's correspondences use its float32 rounding.
+ *     An applied step counts as an iteration; the member has converged when |omega| < stop_rot and
+ *     |v| < stop_trans * d_dist, and stops at max_iterations.
+ * Score: the correspondences at radius inlier_dist * d_dist are the inliers; fitness = inliers / model points,
+ *     rmse = sqrt(sum d*d / inliers) (0 without inliers).  fitness_in is the score at T_in.  found = fitness >=
+ *     min_fitness.  Model point weights do not enter.
+ * Arguments are checked before any handle is read or any device call is made: NULL pointers, parameters that are not
+ * finite, max_corr_dist or inlier_dist <= 0, inlier_dist > max_corr_dist, max_iterations > 1000, and a T_in that is
+ * not finite or not rigid (rotation orthonormal to 1e-3 with determinant > 0, last row 0 0 0 1) are OSLAM_E_INVALID.
+ * The scene's d_dist may be 0 (a database scene); each model uses its own d_dist.
+ * Cost: the scene gets a dense uniform grid (cell edge >= the largest correspondence radius of the call, enlarged so
+ * that the grid has at most 2^24 cells), built on the device and cached on the scene (at most 4 grids, freed with it).
+ * Kernels enqueued per call (res->launches): at most 2 * max_iterations + 2, plus 5 when the scene grid has to be
+ * built; the same for 1 member and for 100.  Host synchronisations: at most 1 + max_iterations / 4 (an "all members
+ * done" word is read after every 4th iteration; the call ends early when it is set). */
+typedef struct oslam_refine_params {
+    unsigned max_iterations;   /* default 30 */
+    float max_corr_dist;       /* correspondence radius in units of the model's d_dist, default 2.0 */
+    float min_normal_dot;      /* gate on (R n_model) . n_scene, default 0.8 */
+    float inlier_dist;         /* radius of the score, in units of d_dist, default 0.5 (<= max_corr_dist) */
+    float min_fitness;         /* found = fitness >= min_fitness; default 0.3 (on the seeded scenes of
+                                * tests/test_refine_host.py a present model scores 0.33-0.60 after refinement, an
+                                * absent one at most 0.25) */
+    float stop_rot;            /* converged when |omega| < stop_rot (rad) ... default 1e-5 */
+    float stop_trans;          /* ... and |v| < stop_trans * d_dist, default 1e-4 */
+    int reserved[4];
+} oslam_refine_params;
+
+typedef struct oslam_refine_result {
+    float fitness_in;          /* score at the input pose */
+    float fitness;             /* inliers / model points at the returned pose */
+    float rmse;                /* point-to-point RMS over the inliers, scene units */
+    uint32_t inliers, correspondences, iterations;   /* correspondences: of the last step (radius max_corr_dist) */
+    int32_t converged, found;
+    uint32_t launches;         /* kernels this call enqueued (the whole call, shared by all members) */
+    float ms_total;            /* whole call, host clock */
+} oslam_refine_result;
+
+int oslam_refine_params_default(oslam_refine_params *p);
+/* rp may be NULL (defaults).  T_out receives the refined pose (T_in when the member stopped at once). */
+int oslam_refine(oslam_model *m, oslam_scene *s, const float T_in[16], const oslam_refine_params *rp,
+                 float T_out[16], oslam_refine_result *res);
+/* Every member of the database in one set of launches: T_in / T_out [n][16], res [n] (n = members, in the order of
+ * oslam_db_create).  A member whose T_in is all zeros (nothing matched in oslam_db_align) is skipped: T_out zeros,
+ * found 0, iterations 0; the call still returns OSLAM_OK.  Member j's results equal oslam_refine of model j alone
+ * bit for bit. */
+int oslam_db_refine(oslam_db *db, oslam_scene *s, const float *T_in /* [n][16] */,
+                    const oslam_refine_params *rp, float *T_out, oslam_refine_result *res /* [n] */);
+/* test tap: idx_out[M] = scene index of each model point's correspondence under T at `radius` (scene units), -1 =
+ * none */
+int oslam_refine_correspondences(oslam_model *m, oslam_scene *s, const float T[16], float radius,
+                                 float min_normal_dot, int32_t *idx_out);
+
 /* ---- parity taps (tests): values the reference materialises as arrays.
  * Scene::getHashKeys row r (scene.cu:49-54): keys_out[n] of reference point r,
  * computed by the GPU key kernel with this d_dist (key 0 on the diagonal). */

@@ -18,6 +18,7 @@
 
 #include "oslam.h"
 #include "oslam_comm.h"
+#include "oslam_internal.h"
 #include "oslam_kernels.h"
 #include "oslam_pose.h"
 #include "ppf_core.h"
@@ -32,6 +33,8 @@ int oslam_set_stream(void *hip_stream)
     g_stream = hip_stream;
     return OSLAM_OK;
 }
+
+void *oslam_stream(void) { return g_stream; }
 
 static int fail(int code, const char *what)
 {
@@ -112,65 +115,6 @@ int oslam_d_dist_from_cloud(const float *xyz, size_t n, size_t stride_bytes, flo
     *d_dist_out = tau_d * ext;        /* alignment.cpp:250-253 */
     return OSLAM_OK;
 }
-
-/* ------------------------------------------------------------------------ */
-typedef struct cloud_buf {
-    int n;
-    float *h_xyz, *h_nrm;             /* packed [n][3] host copies (pose stage) */
-    float *d_soa;                     /* 6*n floats: px py pz nx ny nz */
-    oslamk_cloud k;
-} cloud_buf;
-
-struct oslam_model {
-    int dev;
-    cloud_buf c;
-    float d_dist, inv_d_dist;
-    oslam_params params;
-    oslamk_table table;
-    oslamk_entries ent;
-    uint32_t n_entries;
-    uint64_t num_model_keys;
-    float *weights;
-    /* align workspace */
-    oslamk_counters *d_counters;
-    oslamk_cell *d_out;
-    uint32_t out_cap;
-    oslam_cell *h_out;
-    /* multi-GPU: peaks of the last oslam_align_local (in h_out), survivors of this rank (device) */
-    size_t n_local;
-    uint32_t local_max;
-    oslamk_cell *d_union;
-    size_t union_cap;
-    /* frames T_g of the model points [M][16] and the point weights, for the pose tail on the device */
-    float *d_Tm16, *d_weights;
-    /* last result: on the host, or still on the device (pose tail ran there) until a tap asks for it */
-    oslam_cell *last_cells;
-    float *last_poses;
-    size_t n_last;
-    int last_on_device;
-    oslamk_cell *d_pose_cells;
-    float *d_pose_T;
-    size_t pose_cap;
-    /* host copy of the table for the bucket tap */
-    oslamk_slot *h_slots;
-    /* member of a database group: table.ukeys / reach belong to the group (oslam_db) */
-    int shared_union;
-    /* its key tables are gone (a database was destroyed without giving them back, or rebuilding them failed):
-     * the model can only be destroyed */
-    int unusable;
-};
-
-struct oslam_scene {
-    int dev;
-    cloud_buf c;
-    float d_dist;
-    unsigned df;
-    int rank, world;
-    int n_ref;
-    uint32_t *h_ref_idx, *d_ref_idx;
-    float *d_tsg;
-    float *d_Ts16;                    /* frames of every reference-point candidate (index % df == 0, all ranks) */
-};
 
 static int pick_device(int dev_req, int *dev_out)
 {
@@ -940,6 +884,7 @@ void oslam_scene_destroy(oslam_scene *s)
 {
     if (!s) return;
     (void)hipSetDevice(s->dev);
+    oslam_refine_release_grids(s);
     cloud_free(&s->c);
     free(s->h_ref_idx);
     oslam_dev_free(s->d_ref_idx);
@@ -2125,20 +2070,6 @@ done:
  * slots), and nothing waits on the host between the models of a group.  Models with a d_dist of their own
  * are groups of one and take the single-model path.
  * ---------------------------------------------------------------------- */
-typedef struct db_group {
-    int n;
-    size_t *members;                  /* indices into db->models */
-    uint32_t *ukeys, *reach, *kmap, *uids;   /* the group's union table, reachable-distance bitset, key map and key numbers (n > 1) */
-} db_group;
-
-struct oslam_db {
-    int dev;
-    size_t n;
-    oslam_model **models;             /* borrowed */
-    int n_groups;
-    db_group *groups;
-};
-
 static int same_group(const oslam_model *a, const oslam_model *b)
 {
     return a->dev == b->dev && a->d_dist == b->d_dist && a->params.vote_mode == b->params.vote_mode;

@@ -300,6 +300,60 @@ void oslamk_pose_release(void);
 int oslamk_selftest(const float *x, const float *y, const float *x2, size_t n, float *out_acos,
                     float *out_atan2, uint32_t *out_quant, uint32_t *out_bin, void *stream);
 
+/* ---- refinement stage (oslam_refine.hip; semantics in include/oslam.h at oslam_refine) ---- */
+#define OSLAMK_REFINE_THREADS 256    /* model points per workgroup of the correspondence kernels */
+#define OSLAMK_REFINE_SUMS 29        /* per point: J^T J upper triangle (21, row-major), J^T r (6), count, r^2 */
+#define OSLAMK_REFINE_STRIDE 32      /* floats per (member, workgroup) of the step slab */
+#define OSLAMK_SCAN_ITEMS 4096       /* grid cells per workgroup of the exclusive scan (256 threads x 16) */
+#define OSLAMK_GRID_MAX_CELLS (1u << 24)
+#define OSLAMK_REFINE_STEP 0         /* correspondence kernel modes */
+#define OSLAMK_REFINE_SCORE 1
+#define OSLAMK_REFINE_TAP 2
+
+/* Dense uniform grid over a scene's bounding box: cell (cx, cy, cz) = floor((x - lo) * inv_edge) per axis (in double,
+ * clamped to the grid), flat index (cz * dim[1] + cy) * dim[0] + cx; the points of cell c are pts[start[c] ..
+ * start[c + 1]) in any order (the correspondence rule does not depend on it). */
+typedef struct oslamk_grid {
+    double lo[3];
+    double inv_edge;
+    int dim[3];
+    uint32_t n_cells;
+    int n;                     /* scene points */
+    uint32_t *start;           /* [n_cells + 1] */
+    float *pts;                /* [n][8]: x y z (scene index, int bits) nx ny nz 0 */
+    uint32_t *local;           /* build work space: [n_cells + 1] counts, then their scan inside each 4096-cell block */
+    uint32_t *bsum;            /* [(n_cells + 1 + 4095) / 4096] block totals, then their exclusive scan */
+    uint32_t *cell_of, *rank;  /* [n]: cell of each point, its place among the points of that cell */
+} oslamk_grid;
+
+/* One member of a refinement call.  The host fills everything; the solve kernel updates the state fields. */
+typedef struct oslamk_refine_member {
+    double T[12];              /* rows of [R | t] in double: the pose between iterations */
+    double cm[3];              /* model centroid (double mean of the points) */
+    oslamk_cloud m;            /* the model's points and normals (SoA in HBM) */
+    float Tf[12];              /* float32 rounding of T: what the correspondences use */
+    float c[3];                /* float32 rounding of T * cm */
+    float r2_corr, r2_score;   /* radius^2 of the step and of the score (float) */
+    float min_dot;
+    float stop_rot, stop_trans;   /* stop_trans in scene units */
+    uint32_t max_iter;
+    uint32_t n_blocks;         /* workgroups of this member: ceil(m.n / OSLAMK_REFINE_THREADS) */
+    int32_t active;            /* 0: skipped (all-zero T_in) */
+    int32_t done, iterations, converged, n_corr;
+} oslamk_refine_member;
+
+/* grid of the scene cloud c: g->lo, inv_edge, dim, n_cells and the device arrays are set by the caller */
+int oslamk_refine_grid_build(const oslamk_grid *g, oslamk_cloud c, void *stream);
+/* mode STEP: slab[(j * max_blocks + b) * OSLAMK_REFINE_STRIDE + k] = sums of member j's workgroup b (done members are
+ * skipped); mode SCORE: slab[(j * max_blocks + b) * 2 + {0, 1}] = inliers, sum of d^2 (inactive members skipped);
+ * mode TAP: idx_out[i] of member 0 */
+int oslamk_refine_corr(int mode, const oslamk_grid *g, const oslamk_refine_member *d_mem, uint32_t n_mem,
+                       uint32_t max_blocks, float *slab, int32_t *idx_out, void *stream);
+/* one wave per member that is not done: sums its slab in double, solves, updates the pose; *n_done counts the members
+ * that have become done */
+int oslamk_refine_solve(oslamk_refine_member *d_mem, uint32_t n_mem, uint32_t max_blocks, const float *slab,
+                        uint32_t *n_done, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,398 @@
+/*
+ * oslam_refine.hip -- the refinement stage's kernels (semantics: include/oslam.h at oslam_refine; host side:
+ * oslam_refine.c).
+ *
+ *   scene grid     k_grid_count (cell and rank of every scene point, integer atomics), k_scan_local +
+ *                  k_scan_top (exclusive scan of the cell counts: 4096 cells per workgroup, then the block
+ *                  totals in one workgroup), k_grid_scatter (cell starts, points in cell order)
+ *   correspond     k_refine_corr: one thread per model point, every member of the call in one grid (y = member,
+ *                  x = block of 256 model points); the 27-cell walk, then the 29 (step) or 2 (score) partial sums
+ *                  through a fixed wave64 shuffle tree and a fixed LDS order into a (member, workgroup) slab.  No
+ *                  float atomics: the sums are bitwise reproducible
+ *   solve          k_refine_solve: one wave per member sums its slab in double in workgroup order, solves the 6x6
+ *                  system by Cholesky and updates the double pose
+ */
+#include <hip/hip_runtime.h>
+
+#include <math.h>
+#include <stdint.h>
+
+#include "oslam_kernels.h"
+
+/* ---------------------------------------------------------------- scene grid */
+__device__ __forceinline__ int grid_axis(float x, double lo, double inv, int dim)
+{
+    double f = floor(((double)x - lo) * inv);
+    f = fmin(fmax(f, -2.0), (double)dim + 1.0);       /* far outside (or NaN): a cell the walk clamps away */
+    return (int)f;
+}
+
+__global__ __launch_bounds__(256) void k_grid_count(const oslamk_grid g, oslamk_cloud c)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= c.n) return;
+    int cx = grid_axis(c.px[i], g.lo[0], g.inv_edge, g.dim[0]);
+    int cy = grid_axis(c.py[i], g.lo[1], g.inv_edge, g.dim[1]);
+    int cz = grid_axis(c.pz[i], g.lo[2], g.inv_edge, g.dim[2]);
+    cx = min(max(cx, 0), g.dim[0] - 1);
+    cy = min(max(cy, 0), g.dim[1] - 1);
+    cz = min(max(cz, 0), g.dim[2] - 1);
+    const uint32_t cell = ((uint32_t)cz * (uint32_t)g.dim[1] + (uint32_t)cy) * (uint32_t)g.dim[0] + (uint32_t)cx;
+    g.cell_of[i] = cell;
+    g.rank[i] = atomicAdd(&g.local[cell], 1u);
+}
+
+/* exclusive scan of one value per thread across the workgroup (blockDim.x a multiple of 64, at most 1024) */
+__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *sh, uint32_t *total)
+{
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    uint32_t x = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t y = __shfl_up(x, off);
+        if (lane >= off) x += y;
+    }
+    if (lane == 63) sh[w] = x;
+    __syncthreads();
+    uint32_t before = 0, tot = 0;
+    for (int k = 0; k < nw; k++) {
+        const uint32_t s = sh[k];
+        if (k < w) before += s;
+        tot += s;
+    }
+    *total = tot;
+    return before + x - v;
+}
+
+/* local[0 .. n_items): exclusive scan inside each block of 4096 items, in place; bsum[block] = the block's total */
+__global__ __launch_bounds__(256) void k_scan_local(uint32_t *local, uint32_t n_items, uint32_t *bsum)
+{
+    __shared__ uint32_t sh[4];
+    const uint32_t base = blockIdx.x * OSLAMK_SCAN_ITEMS + threadIdx.x * 16u;
+    uint32_t v[16], s = 0, tot;
+#pragma unroll
+    for (int k = 0; k < 16; k++) {
+        v[k] = base + k < n_items ? local[base + k] : 0u;
+        s += v[k];
+    }
+    uint32_t run = block_excl_scan(s, sh, &tot);
+#pragma unroll
+    for (int k = 0; k < 16; k++) {
+        if (base + k < n_items) local[base + k] = run;
+        run += v[k];
+    }
+    if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
+}
+
+/* bsum[0 .. nb): exclusive scan in place, one workgroup of 1024 threads (nb <= 1024 * 8) */
+__global__ __launch_bounds__(1024) void k_scan_top(uint32_t *bsum, uint32_t nb)
+{
+    __shared__ uint32_t sh[16];
+    const uint32_t per = (nb + 1023u) / 1024u;
+    const uint32_t base = threadIdx.x * per;
+    uint32_t s = 0, tot;
+    for (uint32_t k = 0; k < per; k++)
+        if (base + k < nb) s += bsum[base + k];
+    uint32_t run = block_excl_scan(s, sh, &tot);
+    for (uint32_t k = 0; k < per; k++)
+        if (base + k < nb) {
+            const uint32_t x = bsum[base + k];
+            bsum[base + k] = run;
+            run += x;
+        }
+}
+
+__global__ __launch_bounds__(256) void k_grid_scatter(const oslamk_grid g, oslamk_cloud c)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i <= g.n_cells) g.start[i] = g.local[i] + g.bsum[i / OSLAMK_SCAN_ITEMS];
+    if (i < (uint32_t)c.n) {
+        const uint32_t cell = g.cell_of[i];
+        const uint32_t pos = g.local[cell] + g.bsum[cell / OSLAMK_SCAN_ITEMS] + g.rank[i];
+        float4 *dst = reinterpret_cast<float4 *>(g.pts) + 2 * (size_t)pos;
+        dst[0] = make_float4(c.px[i], c.py[i], c.pz[i], __int_as_float((int)i));
+        dst[1] = make_float4(c.nx[i], c.ny[i], c.nz[i], 0.0f);
+    }
+}
+
+/* ---------------------------------------------------------------- correspondences + partial sums */
+template <int MODE>
+__global__ __launch_bounds__(OSLAMK_REFINE_THREADS) void k_refine_corr(const oslamk_grid g, const oslamk_refine_member *mem,
+                                                                      uint32_t max_blocks, float *slab, int32_t *idx_out)
+{
+    constexpr int NS = MODE == OSLAMK_REFINE_STEP ? OSLAMK_REFINE_SUMS : 2;
+    constexpr int STRIDE = MODE == OSLAMK_REFINE_STEP ? OSLAMK_REFINE_STRIDE : 2;
+    __shared__ float sh[OSLAMK_REFINE_THREADS / 64][NS];
+    const uint32_t j = blockIdx.y;
+    const oslamk_refine_member *d = &mem[j];
+    /* whole workgroups leave together: the conditions depend on the block only */
+    if (MODE == OSLAMK_REFINE_STEP && d->done) return;
+    if (MODE == OSLAMK_REFINE_SCORE && !d->active) return;
+    if (blockIdx.x >= d->n_blocks) return;
+    const int i = (int)(blockIdx.x * OSLAMK_REFINE_THREADS + threadIdx.x);
+    const float4 *pts = reinterpret_cast<const float4 *>(g.pts);
+
+    float s[NS];
+#pragma unroll
+    for (int k = 0; k < NS; k++) s[k] = 0.0f;
+
+    if (i < d->m.n) {
+        float T[12];
+#pragma unroll
+        for (int k = 0; k < 12; k++) T[k] = d->Tf[k];
+        const float r2 = MODE == OSLAMK_REFINE_SCORE ? d->r2_score : d->r2_corr;
+        const float min_dot = d->min_dot;
+        const float px = d->m.px[i], py = d->m.py[i], pz = d->m.pz[i];
+        const float nx = d->m.nx[i], ny = d->m.ny[i], nz = d->m.nz[i];
+        const float qx = ((T[0] * px + T[1] * py) + T[2] * pz) + T[3];
+        const float qy = ((T[4] * px + T[5] * py) + T[6] * pz) + T[7];
+        const float qz = ((T[8] * px + T[9] * py) + T[10] * pz) + T[11];
+        const float mx = (T[0] * nx + T[1] * ny) + T[2] * nz;
+        const float my = (T[4] * nx + T[5] * ny) + T[6] * nz;
+        const float mz = (T[8] * nx + T[9] * ny) + T[10] * nz;
+
+        const int cx = grid_axis(qx, g.lo[0], g.inv_edge, g.dim[0]);
+        const int cy = grid_axis(qy, g.lo[1], g.inv_edge, g.dim[1]);
+        const int cz = grid_axis(qz, g.lo[2], g.inv_edge, g.dim[2]);
+        const int x0 = max(cx - 1, 0), x1 = min(cx + 1, g.dim[0] - 1);
+        const int y0 = max(cy - 1, 0), y1 = min(cy + 1, g.dim[1] - 1);
+        const int z0 = max(cz - 1, 0), z1 = min(cz + 1, g.dim[2] - 1);
+        float best = INFINITY;
+        int best_idx = 0x7fffffff;
+        uint32_t best_pos = 0;
+        if (x0 <= x1 && y0 <= y1 && z0 <= z1) {
+            for (int zz = z0; zz <= z1; zz++)
+                for (int yy = y0; yy <= y1; yy++) {
+                    const uint32_t row = ((uint32_t)zz * (uint32_t)g.dim[1] + (uint32_t)yy) * (uint32_t)g.dim[0];
+                    const uint32_t e = g.start[row + (uint32_t)x1 + 1u];
+                    for (uint32_t k = g.start[row + (uint32_t)x0]; k < e; k++) {
+                        const float4 a = pts[2 * (size_t)k];
+                        const float dx = a.x - qx, dy = a.y - qy, dz = a.z - qz;
+                        const float d2 = (dx * dx + dy * dy) + dz * dz;
+                        if (!(d2 <= r2)) continue;
+                        const float4 b = pts[2 * (size_t)k + 1];
+                        const float dot = (mx * b.x + my * b.y) + mz * b.z;
+                        const int idx = __float_as_int(a.w);
+                        if (dot >= min_dot && (d2 < best || (d2 == best && idx < best_idx))) {
+                            best = d2;
+                            best_idx = idx;
+                            best_pos = k;
+                        }
+                    }
+                }
+        }
+        const bool found = best_idx != 0x7fffffff;
+        if (MODE == OSLAMK_REFINE_TAP) {
+            idx_out[i] = found ? best_idx : -1;
+        } else if (MODE == OSLAMK_REFINE_SCORE) {
+            if (found) {
+                s[0] = 1.0f;
+                s[1] = best;
+            }
+        } else if (found) {
+            const float4 a = pts[2 * (size_t)best_pos];
+            const float4 b = pts[2 * (size_t)best_pos + 1];
+            const float ex = qx - a.x, ey = qy - a.y, ez = qz - a.z;
+            const float r = (b.x * ex + b.y * ey) + b.z * ez;
+            const float ux = qx - d->c[0], uy = qy - d->c[1], uz = qz - d->c[2];
+            float J[6];
+            J[0] = uy * b.z - uz * b.y;
+            J[1] = uz * b.x - ux * b.z;
+            J[2] = ux * b.y - uy * b.x;
+            J[3] = b.x;
+            J[4] = b.y;
+            J[5] = b.z;
+            int k = 0;
+#pragma unroll
+            for (int u = 0; u < 6; u++)
+#pragma unroll
+                for (int v = u; v < 6; v++) s[k++] = J[u] * J[v];
+#pragma unroll
+            for (int u = 0; u < 6; u++) s[21 + u] = J[u] * r;
+            s[27] = 1.0f;
+            s[28] = r * r;
+        }
+    }
+    if (MODE == OSLAMK_REFINE_TAP) return;
+
+    /* fixed-order reduction: shuffle tree inside each wave, then the waves in index order */
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < NS; k++) {
+        float v = s[k];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
+        s[k] = v;
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < NS; k++) sh[w][k] = s[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < NS) {
+        float v = sh[0][threadIdx.x];
+#pragma unroll
+        for (int ww = 1; ww < OSLAMK_REFINE_THREADS / 64; ww++) v += sh[ww][threadIdx.x];
+        slab[((size_t)j * max_blocks + blockIdx.x) * STRIDE + threadIdx.x] = v;
+    }
+}
+
+/* ---------------------------------------------------------------- solve */
+__device__ void rot_apply(const double R[9], const double x[3], double y[3])
+{
+    for (int a = 0; a < 3; a++) y[a] = (R[3 * a] * x[0] + R[3 * a + 1] * x[1]) + R[3 * a + 2] * x[2];
+}
+
+__device__ void member_stop(oslamk_refine_member *d, uint32_t *n_done)
+{
+    d->done = 1;
+    atomicAdd(n_done, 1u);
+}
+
+__global__ __launch_bounds__(64) void k_refine_solve(oslamk_refine_member *mem, uint32_t max_blocks, const float *slab,
+                                                     uint32_t *n_done)
+{
+    __shared__ double S[OSLAMK_REFINE_SUMS];
+    oslamk_refine_member *d = &mem[blockIdx.x];
+    if (d->done) return;
+    const int lane = threadIdx.x;
+    if (lane < OSLAMK_REFINE_SUMS) {
+        const float *p = slab + (size_t)blockIdx.x * max_blocks * OSLAMK_REFINE_STRIDE + lane;
+        double acc = 0.0;
+        for (uint32_t b = 0; b < d->n_blocks; b++) acc += (double)p[(size_t)b * OSLAMK_REFINE_STRIDE];
+        S[lane] = acc;
+    }
+    __syncthreads();
+    if (lane != 0) return;
+
+    const double count = S[27];
+    d->n_corr = (int32_t)count;
+    if (count < 6.0) { member_stop(d, n_done); return; }
+    double A[36], x[6], L[36];
+    int k = 0;
+    for (int u = 0; u < 6; u++)
+        for (int v = u; v < 6; v++) {
+            A[6 * u + v] = S[k];
+            A[6 * v + u] = S[k];
+            k++;
+        }
+    const double mu = 1e-6 * (((((A[0] + A[7]) + A[14]) + A[21]) + A[28]) + A[35]) / 6.0;
+    for (int u = 0; u < 6; u++) A[7 * u] += mu;
+    /* Cholesky A = L L^T */
+    for (int u = 0; u < 6; u++) {
+        for (int v = 0; v <= u; v++) {
+            double t = A[6 * u + v];
+            for (int q = 0; q < v; q++) t -= L[6 * u + q] * L[6 * v + q];
+            if (u == v) {
+                if (!(t > 0.0)) { member_stop(d, n_done); return; }
+                L[7 * u] = sqrt(t);
+            } else {
+                L[6 * u + v] = t / L[7 * v];
+            }
+        }
+    }
+    double y[6];
+    for (int u = 0; u < 6; u++) {
+        double t = -S[21 + u];                      /* b = -sum J^T r */
+        for (int q = 0; q < u; q++) t -= L[6 * u + q] * y[q];
+        y[u] = t / L[7 * u];
+    }
+    for (int u = 5; u >= 0; u--) {
+        double t = y[u];
+        for (int q = u + 1; q < 6; q++) t -= L[6 * q + u] * x[q];
+        x[u] = t / L[7 * u];
+    }
+
+    /* dR = Rodrigues(omega) */
+    const double th = sqrt((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2]);
+    double dR[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    if (th > 0.0) {
+        const double kx = x[0] / th, ky = x[1] / th, kz = x[2] / th;
+        const double cs = cos(th), sn = sin(th), vc = 1.0 - cs;
+        dR[0] = cs + kx * kx * vc;      dR[1] = kx * ky * vc - kz * sn; dR[2] = kx * kz * vc + ky * sn;
+        dR[3] = ky * kx * vc + kz * sn; dR[4] = cs + ky * ky * vc;      dR[5] = ky * kz * vc - kx * sn;
+        dR[6] = kz * kx * vc - ky * sn; dR[7] = kz * ky * vc + kx * sn; dR[8] = cs + kz * kz * vc;
+    }
+    double R[9], t[3], c[3], Rn[9], tn[3], dRc[3], dRt[3];
+    for (int a = 0; a < 3; a++) {
+        R[3 * a] = d->T[4 * a]; R[3 * a + 1] = d->T[4 * a + 1]; R[3 * a + 2] = d->T[4 * a + 2];
+        t[a] = d->T[4 * a + 3];
+    }
+    rot_apply(R, d->cm, c);
+    for (int a = 0; a < 3; a++) c[a] += t[a];
+    rot_apply(dR, c, dRc);
+    rot_apply(dR, t, dRt);
+    for (int a = 0; a < 3; a++) {
+        for (int b = 0; b < 3; b++)
+            Rn[3 * a + b] = (dR[3 * a] * R[b] + dR[3 * a + 1] * R[3 + b]) + dR[3 * a + 2] * R[6 + b];
+        tn[a] = dRt[a] + ((c[a] - dRc[a]) + x[3 + a]);
+    }
+    /* Gram-Schmidt over the columns x, y, z */
+    for (int col = 0; col < 3; col++) {
+        for (int prev = 0; prev < col; prev++) {
+            const double p = (Rn[prev] * Rn[col] + Rn[3 + prev] * Rn[3 + col]) + Rn[6 + prev] * Rn[6 + col];
+            for (int a = 0; a < 3; a++) Rn[3 * a + col] -= p * Rn[3 * a + prev];
+        }
+        const double nrm = sqrt((Rn[col] * Rn[col] + Rn[3 + col] * Rn[3 + col]) + Rn[6 + col] * Rn[6 + col]);
+        for (int a = 0; a < 3; a++) Rn[3 * a + col] /= nrm;
+    }
+    for (int a = 0; a < 3; a++) {
+        d->T[4 * a] = Rn[3 * a]; d->T[4 * a + 1] = Rn[3 * a + 1]; d->T[4 * a + 2] = Rn[3 * a + 2];
+        d->T[4 * a + 3] = tn[a];
+    }
+    for (int q = 0; q < 12; q++) d->Tf[q] = (float)d->T[q];
+    rot_apply(Rn, d->cm, c);
+    for (int a = 0; a < 3; a++) d->c[a] = (float)(c[a] + tn[a]);
+    d->iterations += 1;
+    const double vn = sqrt((x[3] * x[3] + x[4] * x[4]) + x[5] * x[5]);
+    if (th < (double)d->stop_rot && vn < (double)d->stop_trans) {
+        d->converged = 1;
+        member_stop(d, n_done);
+    } else if ((uint32_t)d->iterations >= d->max_iter) {
+        member_stop(d, n_done);
+    }
+}
+
+/* ---------------------------------------------------------------- launchers */
+extern "C" int oslamk_refine_grid_build(const oslamk_grid *g, oslamk_cloud c, void *stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    const uint32_t n_items = g->n_cells + 1u;
+    const uint32_t nb = (n_items + OSLAMK_SCAN_ITEMS - 1) / OSLAMK_SCAN_ITEMS;
+    const uint32_t n_threads = (n_items > (uint32_t)c.n ? n_items : (uint32_t)c.n);
+    hipError_t e;
+    if (c.n <= 0 || g->n_cells == 0 || g->n_cells > OSLAMK_GRID_MAX_CELLS || nb > 1024u * 8u) return (int)hipErrorInvalidValue;
+    e = hipMemsetAsync(g->local, 0, sizeof(uint32_t) * n_items, stream);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(k_grid_count, dim3((unsigned)((c.n + 255) / 256)), dim3(256), 0, stream, *g, c);
+    hipLaunchKernelGGL(k_scan_local, dim3(nb), dim3(256), 0, stream, g->local, n_items, g->bsum);
+    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(1024), 0, stream, g->bsum, nb);
+    hipLaunchKernelGGL(k_grid_scatter, dim3((n_threads + 255) / 256), dim3(256), 0, stream, *g, c);
+    return (int)hipGetLastError();
+}
+
+extern "C" int oslamk_refine_corr(int mode, const oslamk_grid *g, const oslamk_refine_member *d_mem, uint32_t n_mem,
+                                  uint32_t max_blocks, float *slab, int32_t *idx_out, void *stream)
+{
+    if (n_mem == 0 || max_blocks == 0) return 0;
+    if (n_mem > 65535u) return (int)hipErrorInvalidValue;
+    const dim3 grid(max_blocks, n_mem);
+    if (mode == OSLAMK_REFINE_STEP)
+        hipLaunchKernelGGL(k_refine_corr<OSLAMK_REFINE_STEP>, grid, dim3(OSLAMK_REFINE_THREADS), 0, (hipStream_t)stream, *g,
+                           d_mem, max_blocks, slab, idx_out);
+    else if (mode == OSLAMK_REFINE_SCORE)
+        hipLaunchKernelGGL(k_refine_corr<OSLAMK_REFINE_SCORE>, grid, dim3(OSLAMK_REFINE_THREADS), 0, (hipStream_t)stream, *g,
+                           d_mem, max_blocks, slab, idx_out);
+    else
+        hipLaunchKernelGGL(k_refine_corr<OSLAMK_REFINE_TAP>, grid, dim3(OSLAMK_REFINE_THREADS), 0, (hipStream_t)stream, *g,
+                           d_mem, max_blocks, slab, idx_out);
+    return (int)hipGetLastError();
+}
+
+extern "C" int oslamk_refine_solve(oslamk_refine_member *d_mem, uint32_t n_mem, uint32_t max_blocks, const float *slab,
+                                   uint32_t *n_done, void *stream)
+{
+    if (n_mem == 0) return 0;
+    hipLaunchKernelGGL(k_refine_solve, dim3(n_mem), dim3(64), 0, (hipStream_t)stream, d_mem, max_blocks, slab, n_done);
+    return (int)hipGetLastError();
+}

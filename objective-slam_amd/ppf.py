@@ -51,6 +51,21 @@ class Stats(C.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class RefineParams(C.Structure):
+    _fields_ = [("max_iterations", C.c_uint), ("max_corr_dist", C.c_float), ("min_normal_dot", C.c_float),
+                ("inlier_dist", C.c_float), ("min_fitness", C.c_float), ("stop_rot", C.c_float), ("stop_trans", C.c_float),
+                ("reserved", C.c_int * 4)]
+
+
+class RefineResult(C.Structure):
+    _fields_ = [("fitness_in", C.c_float), ("fitness", C.c_float), ("rmse", C.c_float), ("inliers", C.c_uint32),
+                ("correspondences", C.c_uint32), ("iterations", C.c_uint32), ("converged", C.c_int32),
+                ("found", C.c_int32), ("launches", C.c_uint32), ("ms_total", C.c_float)]
+
+    def asdict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 CELL_DTYPE = np.dtype([("code", "<u8"), ("count", "<u4"), ("pad", "<u4")])
 
 # every function include/oslam.h declares: (name, restype, argtypes)
@@ -100,6 +115,10 @@ _SIGNATURES = {
     "oslam_db_destroy": (None, [_vp]),
     "oslam_db_align": (_i, [_vp, _vp, _vp, _vp]),
     "oslam_db_size": (_i, [_vp, C.POINTER(_sz), C.POINTER(_sz)]),
+    "oslam_refine_params_default": (_i, [C.POINTER(RefineParams)]),
+    "oslam_refine": (_i, [_vp, _vp, _vp, C.POINTER(RefineParams), _vp, C.POINTER(RefineResult)]),
+    "oslam_db_refine": (_i, [_vp, _vp, _vp, C.POINTER(RefineParams), _vp, _vp]),
+    "oslam_refine_correspondences": (_i, [_vp, _vp, _vp, _f, _f, _vp]),
     "oslam_scene_keys": (_i, [_vp, _sz, _vp]),
     "oslam_model_keys": (_i, [_vp, _sz, _vp]),
     "oslam_model_bucket": (_i, [_vp, C.c_uint32, _vp, _sz, C.POINTER(_sz)]),
@@ -151,6 +170,21 @@ def default_params(**kw):
             raise TypeError("unknown parameter %r" % k)
         setattr(p, k, v)
     return p
+
+
+def default_refine_params(**kw):
+    """oslam_refine_params_default, then the fields given as keywords."""
+    p = RefineParams()
+    _check(lib().oslam_refine_params_default(C.byref(p)))
+    for k, v in kw.items():
+        if not hasattr(p, k) or k == "reserved":
+            raise TypeError("unknown refine parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def _pose16(T):
+    return np.ascontiguousarray(np.asarray(T, np.float32).reshape(16))
 
 
 def _cloud_args(points, normals=None):
@@ -301,6 +335,20 @@ class Model:
         self.stats = st.asdict()
         return self.best_T
 
+    def refine(self, scene, T=None, params=None):
+        """Point-to-plane ICP of the pose T (default: best_T of the last ppf_lookup) against the scene, and its presence
+        score (oslam_refine).  -> (refined T 4x4, result dict: fitness_in, fitness, rmse, inliers, iterations, found ...)."""
+        if T is None:
+            T = self.best_T
+        if T is None:
+            raise ValueError("no pose: run ppf_lookup first or pass T")
+        Ti = _pose16(T)
+        To = np.zeros(16, np.float32)
+        r = RefineResult()
+        p = params if params is not None else default_refine_params()
+        _check(lib().oslam_refine(self._h, scene._h, _p(Ti), C.byref(p), _p(To), C.byref(r)))
+        return To.reshape(4, 4), r.asdict()
+
     def align_local(self, scene, cap=None):
         """This rank's votes.  cap=None: returns (number of peaks above the LOCAL threshold, local maximum) and
         leaves the records with the model for local_peaks(); with a cap: (records, local maximum), and
@@ -438,6 +486,18 @@ class Database:
             m.best_T, m.stats = t, d
         return T, stats
 
+    def refine(self, scene, T, params=None):
+        """Every member's pose T[j] refined against the scene in one set of launches (oslam_db_refine); members whose
+        T[j] is all zeros are skipped.  -> (T [n,4,4], list of result dicts, found bool [n])."""
+        n = len(self.models)
+        Ti = np.ascontiguousarray(np.asarray(T, np.float32).reshape(n, 16))
+        To = np.zeros((n, 4, 4), np.float32)
+        res = (RefineResult * n)()
+        p = params if params is not None else default_refine_params()
+        _check(lib().oslam_db_refine(self._h, scene._h, _p(Ti), C.byref(p), _p(To), res))
+        out = [r.asdict() for r in res]
+        return To, out, np.array([bool(r["found"]) for r in out])
+
     def align_multi(self, scene, comm, n_total):
         """This rank's models (j = rank, rank + world, ... of n_total) against the whole scene, then every pose to
         every rank through the communicator (oslam_db_align_multi).  -> (poses [n_total,4,4], found [n_total])."""
@@ -518,6 +578,15 @@ class Comm:
             self.close()
         except Exception:
             pass
+
+
+def refine_correspondences(model, scene, T, radius, min_normal_dot):
+    """Scene index of every model point's correspondence under T at `radius` (scene units), -1 = none
+    (oslam_refine_correspondences: the rule of oslam_refine, as a test tap)."""
+    out = np.zeros(model.n, np.int32)
+    _check(lib().oslam_refine_correspondences(model._h, scene._h, _p(_pose16(T)), float(radius), float(min_normal_dot),
+                                              _p(out)))
+    return out
 
 
 def kernel_source_hash():

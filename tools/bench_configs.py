@@ -7,6 +7,8 @@ configuration; these are not bench lines).  Needs a HIP device.
                                          share (1/8 of the reference points) of N models, ref_point_df 20
   python tools/bench_configs.py cfg5     streaming: 640x480 depth frames -> points+normals -> voxel grid
                                          -> registration against a resident model database; frames/s
+  python tools/bench_configs.py refine   the refinement stage: oslam_refine on the bench registration (5k model, 100k
+                                         scene) from its voting pose, and the db50 stream with db.align + db.refine
 One JSON line each."""
 import importlib, json, os, sys, time
 
@@ -233,6 +235,77 @@ def db50(frames=10):
     return out
 
 
+def refine(calls=20, frames=10):
+    """The refinement stage (oslam_refine): one model on the bench registration, refined from its voting pose (median
+    over `calls` calls, the scene grid already cached), and the db50 stream with db.align + db.refine per frame."""
+    def err(T, truth, d):
+        dt, dr = ppf.ht_dist(T, truth)
+        return float(np.degrees(dr)), float(dt / d)
+    mp, mn = synth.make_model(0, 5000)
+    d = synth.d_dist_for(mp, 0.025)
+    sp, sn, poses = synth.make_scene([0], 100000, 2002, instance_points=5000, noise_sigma=0.1 * d)
+    mo = ppf.Model(mp, mn, d_dist=d)
+    sc = ppf.Scene(sp, sn, d_dist=d, ref_point_downsample_factor=8)
+    T0 = mo.ppf_lookup(sc).copy()
+    t = time.perf_counter(); _, first = mo.refine(sc, T0); ms_first = 1e3 * (time.perf_counter() - t)
+    ts, lib_ms = [], []
+    for _ in range(calls):
+        t = time.perf_counter(); T1, info = mo.refine(sc, T0); ts.append(1e3 * (time.perf_counter() - t))
+        lib_ms.append(info["ms_total"])
+    r0, t0 = err(T0, poses[0][1], d)
+    r1, t1 = err(T1, poses[0][1], d)
+    out = {"config": "refinement stage (oslam_refine / oslam_db_refine)",
+           "bench_registration": {"model_points": 5000, "scene_points": 100000, "calls": calls,
+                                  "median_ms": float(np.median(ts)), "median_ms_total_in_library": float(np.median(lib_ms)),
+                                  "first_call_ms_with_grid_build": ms_first, "launches": info["launches"],
+                                  "launches_first_call": first["launches"], "iterations": info["iterations"],
+                                  "converged": bool(info["converged"]), "fitness_in": info["fitness_in"],
+                                  "fitness": info["fitness"], "rmse_over_d_dist": info["rmse"] / d,
+                                  "rot_err_deg_vote": r0, "trans_err_d_vote": t0, "rot_err_deg_refined": r1,
+                                  "trans_err_d_refined": t1}}
+    mo.close()
+    sc.close()
+    n_models = 50
+    raw = [synth.make_model(k, 1500) for k in range(n_models)]
+    d = synth.d_dist_for(raw[0][0], 0.05)
+    grids = [ppf.voxel_grid(c[0], c[1], leaf=d) for c in raw]
+    dense, _ = synth.make_model(0, 300000)
+    rng = synth.SplitMix64(93)
+    imgs, truths = [], []
+    for f in range(frames):
+        T = np.eye(4, dtype=np.float32)
+        T[:3, :3] = synth.random_rotation(rng)
+        T[:3, 3] = [0.5 * np.cos(0.7 * f), 0.3 * np.sin(0.7 * f), 5.5 + 0.1 * f]
+        imgs.append(synth.render_depth(dense @ T[:3, :3].T + T[:3, 3], background_z=9.0, splat=1))
+        truths.append(T)
+    models = [ppf.Model(g[0], g[1], d_dist=d) for g in grids]
+    db = ppf.Database(models)
+
+    def frame(img):
+        sc = ppf.Scene.from_depth(img, 525.0, 525.0, 319.5, 239.5, leaf=d, d_dist=0.0, ref_point_downsample_factor=4,
+                                  z_min=0.5, z_max=12.0, max_jump=0.08)
+        Ta, _ = db.align(sc)
+        t = time.perf_counter(); Tr, res, found = db.refine(sc, Ta); ms = 1e3 * (time.perf_counter() - t)
+        sc.close()
+        return Tr, res, found, ms
+    frame(imgs[0])
+    t = time.perf_counter(); rs = [frame(im) for im in imgs]; el = time.perf_counter() - t
+    out["db50_stream"] = {"frames": frames, "models": n_models, "frames_per_s": frames / el,
+                          "ms_refine_per_frame": float(np.mean([r[3] for r in rs])),
+                          "ms_refine_per_frame_median": float(np.median([r[3] for r in rs])),
+                          "launches_per_call": [r[1][0]["launches"] for r in rs],
+                          "iterations_model0": [r[1][0]["iterations"] for r in rs],
+                          "found_members_per_frame": [[int(j) for j in np.flatnonzero(r[2])] for r in rs],
+                          "fitness_model0": [round(r[1][0]["fitness"], 3) for r in rs],
+                          "max_fitness_absent": [round(max(x["fitness"] for x in r[1][1:]), 3) for r in rs],
+                          "rot_err_deg_model0_refined": [round(err(r[0][0], truths[f], d)[0], 3) for f, r in enumerate(rs)]}
+    db.close()
+    for m in models:
+        m.close()
+    return out
+
+
 if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "cfg3"
-    print(json.dumps({"cfg2": cfg2, "cfg3": cfg3, "cfg3db": cfg3db, "cfg4": cfg4, "cfg5": cfg5, "planes": planes, "db50": db50}[which]()), flush=True)
+    print(json.dumps({"cfg2": cfg2, "cfg3": cfg3, "cfg3db": cfg3db, "cfg4": cfg4, "cfg5": cfg5, "planes": planes, "db50": db50,
+                      "refine": refine}[which]()), flush=True)
