@@ -292,7 +292,8 @@ int oslam_comm_info(const oslam_comm *c, int *rank, int *world, int *broken);
  * loopback transport are released with an error, RCCL peers stay in their collective until they abort too. */
 int oslam_comm_abort(oslam_comm *c);
 /* test tap: the next exchange on this handle fails locally at `stage` (1 = after the votes, 2 = while
- * selecting the survivors, 3 = while growing the record buffer), as an allocation failure would */
+ * selecting the survivors, 3 = while growing the record buffer), as an allocation failure would.
+ * oslam_db_align_multi honours stage 1 (after this rank's registrations); either call clears the tap */
 int oslam_comm_inject_failure(oslam_comm *c, int stage);
 
 /* A database split by MODEL instead of by reference point (SURVEY 8e's alternative; what the scenes x models

@@ -330,6 +330,16 @@ int oslam_comm_inject_failure(oslam_comm *c, int stage)
     return OSLAM_OK;
 }
 
+int oslam_comm_error(const oslam_comm *c, int own, int stage)
+{
+    static const char *const injected[] = {"", "injected failure (vote stage)", "injected failure (selection stage)",
+                                           "injected failure (growing the record buffer)"};
+    if (own != OSLAM_OK) return own;
+    if (stage > OSLAM_STAGE_NONE && stage <= OSLAM_STAGE_GROW && c->inject_stage == stage)
+        return oslam_fail(OSLAM_E_DEVICE, injected[stage]);
+    return oslam_fail(OSLAM_E_PEER, "a peer rank failed: the registration was abandoned on every rank");
+}
+
 int oslam_comm_abort(oslam_comm *c)
 {
     if (!c) return oslam_fail(OSLAM_E_INVALID, "NULL handle");

@@ -2,7 +2,7 @@
  * oslam_comm.h -- the collectives of the multi-GPU exchange behind a table of operations
  * (internal to liboslam_hip.so; the public handle is `oslam_comm` of include/oslam.h).
  *
- * The exchange of one registration (oslam_align_multi) needs three operations on device buffers:
+ * The exchange of one registration (oslam_align_multi, oslam_align.c) needs three operations on device buffers:
  * an all-reduce(MAX) of a few words, an all-gather of a few words per rank, and an all-gather
  * with a different size per rank.  Two transports implement them:
  *   - RCCL (one process per GPU, xGMI): what a multi-GPU node runs;
@@ -47,16 +47,21 @@ struct oslam_comm {
 
 /* stages of the exchange at which a rank can fail on its own (oslam_comm_inject_failure) */
 #define OSLAM_STAGE_NONE 0
-#define OSLAM_STAGE_VOTE 1             /* before the maxima are exchanged */
+#define OSLAM_STAGE_VOTE 1             /* after the votes, before the first exchange */
 #define OSLAM_STAGE_SELECT 2           /* before the survivor counts are exchanged */
 #define OSLAM_STAGE_GROW 3             /* while making room for the union */
+
+/* What a rank returns once the error word of a collective came back set: its own error `own` (already recorded),
+ * else the failure injected at `stage`, else OSLAM_E_PEER (a peer failed).  A rank whose own HIP call fails outside
+ * the collectives cannot tell its peers any more: it gives the communicator up with oslam_comm_abort. */
+int oslam_comm_error(const oslam_comm *c, int own, int stage);
 
 /* a collective over c; on failure the communicator is aborted and marked broken */
 int oslam_comm_all_reduce_max(oslam_comm *c, uint32_t *d_buf, size_t n, void *stream);
 int oslam_comm_all_gather(oslam_comm *c, const uint32_t *d_send, uint32_t *d_recv, size_t n, void *stream);
 int oslam_comm_all_gather_v(oslam_comm *c, const void *d_send, void *d_recv, const size_t *bytes, void *stream);
 
-/* error text of the calling thread (oslam_host.c) */
+/* error text of the calling thread (oslam_host.c, declared with the other shared helpers in oslam_internal.h) */
 int oslam_fail(int code, const char *what);
 
 #endif

@@ -1,12 +1,16 @@
 /*
- * oslam_internal.h -- the handles behind include/oslam.h, shared by the translation units of
- * liboslam_hip.so that read them (oslam_host.c, oslam_refine.c).  Not installed.
+ * oslam_internal.h -- the handles behind include/oslam.h and the helpers that the host translation units of
+ * liboslam_hip.so share (oslam_host.c and the stage files next to it).  Not installed.
  */
 #ifndef OSLAM_INTERNAL_H
 #define OSLAM_INTERNAL_H
 
+#include <hip/hip_runtime_api.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <stdlib.h>
+#include <string.h>
+#include <time.h>
 
 #include "oslam.h"
 #include "oslam_kernels.h"
@@ -84,11 +88,80 @@ struct oslam_db {
     db_group *groups;
 };
 
+/* ---- error text, stream, device (oslam_host.c) ---- */
 /* records `what` for oslam_last_error and returns code */
 int oslam_fail(int code, const char *what);
+static inline int fail(int code, const char *what) { return oslam_fail(code, what); }
+/* records "call: HIP error text (file:line)" and returns OSLAM_E_DEVICE */
+int oslam_fail_call(const char *call, int err, const char *file, int line);
+
+/* HIPCHK: a call that returns a hipError_t; KCHK: an oslamk_* launcher (0 or a hipError_t).  On failure the
+ * error text names the call and its place, rc = OSLAM_E_DEVICE, and the function goes to its `done:` */
+#define KCHK(call)                                                                          \
+    do {                                                                                    \
+        const int k_ = (int)(call);                                                         \
+        if (k_ != 0) { rc = oslam_fail_call(#call, k_, __FILE__, __LINE__); goto done; }    \
+    } while (0)
+#define HIPCHK(call) KCHK(call)
+
+static inline double now_ms(void)
+{
+    struct timespec ts;
+    clock_gettime(CLOCK_MONOTONIC, &ts);
+    return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6;
+}
+
 /* the launch stream of this thread's calls (oslam_set_stream) */
 void *oslam_stream(void);
+/* binds device dev_req (clamped to the last device, ppf.cu:45) */
+int oslam_pick_device(int dev_req, int *dev_out);
+
+/* ---- clouds (oslam_cloud.c) ---- */
+void oslam_cloud_free(cloud_buf *c);
+int oslam_cloud_make(cloud_buf *c, const float *xyz, const float *nrm, size_t stride, const float *d_aos6, size_t n);
+oslamk_cloud oslam_soa_cloud(const float *d_soa, size_t n);
+/* a depth image's points in HBM as [*np][6] on device dev (*d_img: the image); the caller frees both blocks */
+int oslam_depth_points(const void *depth, int depth_is_u16, int width, int height, const oslam_camera *cam, int dev,
+                       void **d_img, float **d_pts6, uint32_t *np);
+
+/* ---- model key tables (oslam_model.c), rebuilt by the database ---- */
+int oslam_build_kmap(oslamk_table *t, float d_dist);
+int oslam_build_union(oslam_model *m, uint32_t distinct, uint32_t *d_n_keys, uint32_t *d_overflow);
+int oslam_build_uinfo(oslam_model *m);
+
 /* gives back the scene's refinement grids (oslam_refine.c); called by oslam_scene_destroy */
 void oslam_refine_release_grids(oslam_scene *s);
+
+/* ---- votes and the scratch pool of each device (oslam_vote.c) ---- */
+typedef struct scratch_pool scratch_pool;
+int oslam_check_pair(const oslam_model *m, const oslam_scene *s);
+/* the entry of a call that launches on device dev: binds it and locks its pool, held until oslam_pool_unlock */
+int oslam_pool_enter(int dev, scratch_pool **pool);
+void oslam_pool_unlock(scratch_pool *p);
+int oslam_pool_reserve_counts(scratch_pool *p, size_t n_ref);
+int oslam_run_votes_group(scratch_pool *pool, oslam_model *const *ms, int nm, oslam_scene *s, const uint32_t *d_ref_idx,
+                          const float *d_tsg, int n_ref, uint32_t fixed_gmax, uint32_t *acc_dump,
+                          oslamk_counters *cnt, float *ms_out, float *ms_vote_kernel, float *ms_key_kernel,
+                          uint32_t *launches, uint64_t *probed);
+void oslam_vote_stats(oslam_stats *st, const scratch_pool *pool, const oslam_model *m, const oslam_scene *s,
+                      const oslamk_counters *cnt, float ms_vote, float ms_vote_kernel, float ms_key_kernel,
+                      uint32_t launches, uint64_t probed);
+int oslam_vote_records(scratch_pool *pool, oslam_model *m, oslam_scene *s, oslamk_counters *cnt, size_t *n_cells,
+                       oslam_stats *st, int to_host);
+int oslam_grow_records(oslam_model *m, uint64_t need);
+/* clustering scores in the current pool (the pose stage's hook, oslam_pose.h) */
+int oslam_cluster_scores_on_device(size_t n, const float *trans, const float *quat, const float *wv,
+                                   const int32_t *cell, const uint32_t *hash_idx, float d_dist, int use_l1,
+                                   float *score);
+
+/* ---- pose tail (oslam_align.c) ---- */
+size_t oslam_pose_gpu_from(const oslam_model *m);
+void oslam_drop_last(oslam_model *m);
+int oslam_pose_tables(oslam_model *m, oslam_scene *s);
+int oslam_ensure_pose_buffers(oslam_model *m, size_t n);
+/* the 64 rotations about x of the pose tail, made on first use */
+const float *oslam_rotx(void);
+int oslam_finish_after_votes(oslam_model *m, oslam_scene *s, size_t n, uint32_t gmax, int try_device, float T[16],
+                             oslam_stats *stats);
 
 #endif /* OSLAM_INTERNAL_H */

@@ -26,7 +26,7 @@ void oslam_T_g_full(const float *xyz, const float *nrm, size_t idx0, size_t step
 /* cos, sin of alpha_idx * D - pi for alpha_idx = 0..63 (libm): the kernels' rotation table */
 void oslam_rotx_table(float cs[128]);
 
-/* Optional accelerator for the clustering scores (set by oslam_host.c while a device is bound):
+/* Optional accelerator for the clustering scores (set by oslam_align.c while a device is bound):
  * fills score[n] exactly as the host loop would, returns 0 on success.  hash_idx = n pairs
  * {cell hash, pose index} ascending. */
 typedef int (*oslam_cluster_hook)(size_t n, const float *trans, const float *quat, const float *wv,

@@ -5,12 +5,8 @@
  * done" word after every 4th iteration and the results once at the end.  The pose lives in double on the device
  * between iterations; the host only rounds the final one.
  */
-#include <hip/hip_runtime_api.h>
 #include <math.h>
 #include <pthread.h>
-#include <stdlib.h>
-#include <string.h>
-#include <time.h>
 
 #include "oslam_internal.h"
 
@@ -29,22 +25,6 @@ struct oslam_scene_grid {
 /* one refinement call at a time per process: the grid caches of the scenes are shared state */
 static pthread_mutex_t g_refine_mu = PTHREAD_MUTEX_INITIALIZER;
 static uint64_t g_calls;
-
-static double now_ms(void)
-{
-    struct timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6;
-}
-
-#define RCHK(call)                                                                                \
-    do {                                                                                          \
-        hipError_t e_ = (hipError_t)(call);                                                       \
-        if (e_ != hipSuccess) {                                                                   \
-            rc = oslam_fail(OSLAM_E_DEVICE, hipGetErrorString(e_));                               \
-            goto done;                                                                            \
-        }                                                                                         \
-    } while (0)
 
 int oslam_refine_params_default(oslam_refine_params *p)
 {
@@ -185,7 +165,7 @@ static int scene_grid(oslam_scene *s, float radius, oslamk_grid *out, int *built
     n_items = (size_t)e->g.n_cells + 1;
     nb = (n_items + OSLAMK_SCAN_ITEMS - 1) / OSLAMK_SCAN_ITEMS;
     off = 2 * align256(4 * n_items) + align256(4 * nb) + 2 * align256(4 * n) + align256(32 * n);
-    RCHK(oslam_dev_alloc(&e->block, off));
+    KCHK(oslam_dev_alloc(&e->block, off));
     base = (char *)e->block;
     e->g.start = (uint32_t *)base;   base += align256(4 * n_items);
     e->g.local = (uint32_t *)base;   base += align256(4 * n_items);
@@ -193,7 +173,7 @@ static int scene_grid(oslam_scene *s, float radius, oslamk_grid *out, int *built
     e->g.cell_of = (uint32_t *)base; base += align256(4 * n);
     e->g.rank = (uint32_t *)base;    base += align256(4 * n);
     e->g.pts = (float *)base;
-    RCHK(oslamk_refine_grid_build(&e->g, s->c.k, oslam_stream()));
+    KCHK(oslamk_refine_grid_build(&e->g, s->c.k, oslam_stream()));
     e->edge = edge;
     e->radius = radius;
     e->used = g_calls;
@@ -295,34 +275,34 @@ static int refine_members(oslam_model *const *ms, size_t n, oslam_scene *s, cons
 
     pthread_mutex_lock(&g_refine_mu);
     g_calls++;
-    RCHK(oslam_dev_alloc((void **)&dev, bytes));
+    KCHK(oslam_dev_alloc((void **)&dev, bytes));
     /* the descriptors (and the zeroed all-done word behind them) first: the copy does not wait for the grid */
-    RCHK(hipMemcpyAsync(dev, h, off_slab, hipMemcpyHostToDevice, (hipStream_t)stream));
+    HIPCHK(hipMemcpyAsync(dev, h, off_slab, hipMemcpyHostToDevice, (hipStream_t)stream));
     rc = scene_grid(s, rmax, &g, &built);
     if (rc != OSLAM_OK) goto done;
     if (built) launches += 5;
-    RCHK(oslamk_refine_corr(OSLAMK_REFINE_SCORE, &g, (oslamk_refine_member *)dev, (uint32_t)n_act, (uint32_t)max_blocks,
+    KCHK(oslamk_refine_corr(OSLAMK_REFINE_SCORE, &g, (oslamk_refine_member *)dev, (uint32_t)n_act, (uint32_t)max_blocks,
                             (float *)(dev + off_in), NULL, stream));
     launches++;
     for (it = 0; it < p->max_iterations; it++) {
-        RCHK(oslamk_refine_corr(OSLAMK_REFINE_STEP, &g, (oslamk_refine_member *)dev, (uint32_t)n_act, (uint32_t)max_blocks,
+        KCHK(oslamk_refine_corr(OSLAMK_REFINE_STEP, &g, (oslamk_refine_member *)dev, (uint32_t)n_act, (uint32_t)max_blocks,
                                 (float *)(dev + off_slab), NULL, stream));
-        RCHK(oslamk_refine_solve((oslamk_refine_member *)dev, (uint32_t)n_act, (uint32_t)max_blocks, (const float *)(dev + off_slab),
+        KCHK(oslamk_refine_solve((oslamk_refine_member *)dev, (uint32_t)n_act, (uint32_t)max_blocks, (const float *)(dev + off_slab),
                                  (uint32_t *)(dev + off_done), stream));
         launches += 2;
         if ((it + 1) % CHECK_EVERY == 0 && it + 1 < p->max_iterations) {
-            RCHK(hipMemcpyAsync(&n_done, dev + off_done, sizeof n_done, hipMemcpyDeviceToHost, (hipStream_t)stream));
-            RCHK(hipStreamSynchronize((hipStream_t)stream));
+            HIPCHK(hipMemcpyAsync(&n_done, dev + off_done, sizeof n_done, hipMemcpyDeviceToHost, (hipStream_t)stream));
+            HIPCHK(hipStreamSynchronize((hipStream_t)stream));
             if (n_done >= n_act) break;
         }
     }
-    RCHK(oslamk_refine_corr(OSLAMK_REFINE_SCORE, &g, (oslamk_refine_member *)dev, (uint32_t)n_act, (uint32_t)max_blocks,
+    KCHK(oslamk_refine_corr(OSLAMK_REFINE_SCORE, &g, (oslamk_refine_member *)dev, (uint32_t)n_act, (uint32_t)max_blocks,
                             (float *)(dev + off_out), NULL, stream));
     launches++;
-    RCHK(hipMemcpyAsync(h, dev, sizeof *h * n_act, hipMemcpyDeviceToHost, (hipStream_t)stream));
-    RCHK(hipMemcpyAsync(h_in, dev + off_in, sizeof(float) * 2 * max_blocks * n_act, hipMemcpyDeviceToHost, (hipStream_t)stream));
-    RCHK(hipMemcpyAsync(h_out, dev + off_out, sizeof(float) * 2 * max_blocks * n_act, hipMemcpyDeviceToHost, (hipStream_t)stream));
-    RCHK(hipStreamSynchronize((hipStream_t)stream));
+    HIPCHK(hipMemcpyAsync(h, dev, sizeof *h * n_act, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIPCHK(hipMemcpyAsync(h_in, dev + off_in, sizeof(float) * 2 * max_blocks * n_act, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIPCHK(hipMemcpyAsync(h_out, dev + off_out, sizeof(float) * 2 * max_blocks * n_act, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
 
     for (b = 0; b < n_act; b++) {
         const oslamk_refine_member *d = &h[b];
@@ -427,14 +407,14 @@ int oslam_refine_correspondences(oslam_model *m, oslam_scene *s, const float T[1
     off_idx = align256(sizeof h);
     pthread_mutex_lock(&g_refine_mu);
     g_calls++;
-    RCHK(oslam_dev_alloc((void **)&dev, off_idx + sizeof(int32_t) * M));
-    RCHK(hipMemcpyAsync(dev, &h, sizeof h, hipMemcpyHostToDevice, (hipStream_t)stream));
+    KCHK(oslam_dev_alloc((void **)&dev, off_idx + sizeof(int32_t) * M));
+    HIPCHK(hipMemcpyAsync(dev, &h, sizeof h, hipMemcpyHostToDevice, (hipStream_t)stream));
     rc = scene_grid(s, radius, &g, &built);
     if (rc != OSLAM_OK) goto done;
-    RCHK(oslamk_refine_corr(OSLAMK_REFINE_TAP, &g, (oslamk_refine_member *)dev, 1, h.n_blocks, NULL,
+    KCHK(oslamk_refine_corr(OSLAMK_REFINE_TAP, &g, (oslamk_refine_member *)dev, 1, h.n_blocks, NULL,
                             (int32_t *)(dev + off_idx), stream));
-    RCHK(hipMemcpyAsync(idx_out, dev + off_idx, sizeof(int32_t) * M, hipMemcpyDeviceToHost, (hipStream_t)stream));
-    RCHK(hipStreamSynchronize((hipStream_t)stream));
+    HIPCHK(hipMemcpyAsync(idx_out, dev + off_idx, sizeof(int32_t) * M, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
 done:
     if (rc != OSLAM_OK) (void)hipStreamSynchronize((hipStream_t)stream);
     if (dev) oslam_dev_free(dev);

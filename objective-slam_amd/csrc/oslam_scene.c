@@ -1,0 +1,122 @@
+/*
+ * oslam_scene.c -- a scene: from host buffers or from a depth image, with its reference points and their
+ * frames (scene.cu:24-55).
+ */
+
+#include "oslam_internal.h"
+#include "oslam_pose.h"
+
+void oslam_scene_destroy(oslam_scene *s)
+{
+    if (!s) return;
+    (void)hipSetDevice(s->dev);
+    oslam_refine_release_grids(s);
+    oslam_cloud_free(&s->c);
+    free(s->h_ref_idx);
+    oslam_dev_free(s->d_ref_idx);
+    oslam_dev_free(s->d_tsg);
+    oslam_dev_free(s->d_Ts16);
+    free(s);
+}
+
+/* Scene::Scene (scene.cu:24-55) from host buffers (xyz != NULL) or from a cloud that lies in HBM as [n][6] */
+static int scene_create_any(const float *xyz, const float *nrm, size_t stride_bytes, const float *d_aos6, size_t n,
+                            float d_dist, unsigned df, const oslam_params *params, oslam_scene **out)
+{
+    int rc = OSLAM_OK;
+    oslam_scene *s = NULL;
+    oslam_params p;
+    float *h_tsg = NULL;
+    size_t n_all, t;
+
+    *out = NULL;
+    if (!(d_dist >= 0.0f) || df == 0) return fail(OSLAM_E_INVALID, "bad scene arguments");
+    if (n < 2) return fail(OSLAM_E_INVALID, "scene needs at least 2 points");
+    if (n > (1u << 28)) return fail(OSLAM_E_LIMIT, "scene larger than 2^28 points");
+    if (params) p = *params; else oslam_params_default(&p);
+    if (p.shard_world < 1 || p.shard_rank < 0 || p.shard_rank >= p.shard_world) return fail(OSLAM_E_INVALID, "bad shard");
+    s = (oslam_scene *)calloc(1, sizeof *s);
+    if (!s) return fail(OSLAM_E_NOMEM, "host allocation failed");
+    rc = oslam_pick_device(p.dev, &s->dev);
+    if (rc != OSLAM_OK) goto done;
+    rc = oslam_cloud_make(&s->c, xyz, nrm, stride_bytes, d_aos6, n);
+    if (rc != OSLAM_OK) goto done;
+    s->d_dist = d_dist;
+    s->df = df;
+    s->rank = p.shard_rank;
+    s->world = p.shard_world;
+    /* reference points: idx % df == 0 (kernel.cu:432), dealt round-robin to ranks */
+    n_all = (n + df - 1) / df;
+    s->n_ref = 0;
+    for (t = (size_t)s->rank; t < n_all; t += (size_t)s->world) s->n_ref++;
+    s->h_ref_idx = (uint32_t *)malloc(sizeof(uint32_t) * (s->n_ref ? s->n_ref : 1));
+    h_tsg = (float *)malloc(sizeof(float) * 8 * (s->n_ref ? s->n_ref : 1));
+    if (!s->h_ref_idx || !h_tsg) { rc = fail(OSLAM_E_NOMEM, "host allocation failed"); goto done; }
+    {
+        int k = 0;
+        for (t = (size_t)s->rank; t < n_all; t += (size_t)s->world) s->h_ref_idx[k++] = (uint32_t)(t * df);
+    }
+    oslam_T_g_rows(s->c.h_xyz, s->c.h_nrm, s->h_ref_idx, (size_t)s->n_ref, h_tsg);
+    HIPCHK((hipError_t)oslam_dev_alloc((void **)&s->d_ref_idx, sizeof(uint32_t) * (s->n_ref ? s->n_ref : 1)));
+    HIPCHK((hipError_t)oslam_dev_alloc((void **)&s->d_tsg, sizeof(float) * 8 * (s->n_ref ? s->n_ref : 1)));
+    if (s->n_ref) {
+        HIPCHK(hipMemcpy(s->d_ref_idx, s->h_ref_idx, sizeof(uint32_t) * s->n_ref, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(s->d_tsg, h_tsg, sizeof(float) * 8 * s->n_ref, hipMemcpyHostToDevice));
+    }
+done:
+    free(h_tsg);
+    if (rc != OSLAM_OK) { oslam_scene_destroy(s); return rc; }
+    *out = s;
+    return OSLAM_OK;
+}
+
+int oslam_scene_create(const float *xyz, const float *nrm, size_t n, size_t stride_bytes,
+                       float d_dist, unsigned df, const oslam_params *params, oslam_scene **out)
+{
+    if (!out) return fail(OSLAM_E_INVALID, "out is NULL");
+    *out = NULL;
+    if (!xyz || !nrm || stride_bytes < 12) return fail(OSLAM_E_INVALID, "bad scene arguments");
+    return scene_create_any(xyz, nrm, stride_bytes, NULL, n, d_dist, df, params, out);
+}
+
+int oslam_scene_from_depth(const void *depth, int depth_is_u16, int width, int height, const oslam_camera *cam,
+                           float leaf, float d_dist, unsigned df, const oslam_params *params, oslam_scene **out,
+                           size_t *n_points_out)
+{
+    int rc = OSLAM_OK, k;
+    oslam_params p;
+    void *d_img = NULL;
+    float *d_pts6 = NULL, *d_soa = NULL, *d_vox6 = NULL;
+    const float *d_final;
+    uint32_t np = 0, nv = 0;
+    size_t n_final;
+    if (!out) return fail(OSLAM_E_INVALID, "out is NULL");
+    *out = NULL;
+    if (n_points_out) *n_points_out = 0;
+    if (!(leaf >= 0.0f)) return fail(OSLAM_E_INVALID, "bad depth image arguments");
+    if (params) p = *params; else oslam_params_default(&p);
+    rc = oslam_depth_points(depth, depth_is_u16, width, height, cam, p.dev, &d_img, &d_pts6, &np);
+    if (rc != OSLAM_OK) goto done;
+    d_final = d_pts6;
+    n_final = np;
+    if (leaf > 0.0f && np > 0) {
+        HIPCHK((hipError_t)oslam_dev_alloc((void **)&d_soa, sizeof(float) * 6 * (size_t)np));
+        HIPCHK((hipError_t)oslam_dev_alloc((void **)&d_vox6, sizeof(float) * 6 * (size_t)np));
+        KCHK(oslamk_aos6_to_soa(d_pts6, np, d_soa, oslam_stream()));
+        k = oslamk_voxel_grid(oslam_soa_cloud(d_soa, np), leaf, d_vox6, &nv, oslam_stream());
+        if (k == -1) { rc = fail(OSLAM_E_LIMIT, "leaf size too small for the cloud extent (voxel count overflows int32)"); goto done; }
+        if (k != 0) { rc = fail(OSLAM_E_DEVICE, hipGetErrorString((hipError_t)k)); goto done; }
+        d_final = d_vox6;
+        n_final = nv;
+    }
+    if (n_final < 2) { rc = fail(OSLAM_E_INVALID, "the depth image leaves fewer than 2 scene points"); goto done; }
+    /* the scene's arrays are made from the cloud where it lies; one copy comes back for the host's reference frames */
+    rc = scene_create_any(NULL, NULL, 0, d_final, n_final, d_dist, df, &p, out);
+    if (rc == OSLAM_OK && n_points_out) *n_points_out = n_final;
+done:
+    oslam_dev_free(d_img);
+    oslam_dev_free(d_pts6);
+    oslam_dev_free(d_soa);
+    oslam_dev_free(d_vox6);
+    return rc;
+}

@@ -1,0 +1,292 @@
+/*
+ * oslam_taps.c -- the parity taps (pair keys, buckets, the accumulator of one reference point, the last
+ * result) and the device math self-test.
+ */
+
+#include "oslam_internal.h"
+#include "oslam_pose.h"
+#include "ppf_core.h"
+
+/* parity taps */
+static int cloud_row_keys(cloud_buf *c, size_t ref, float d_dist, uint32_t *keys_out)
+{
+    int rc = OSLAM_OK;
+    uint32_t *d = NULL;
+    if (!keys_out || ref >= (size_t)c->n) return fail(OSLAM_E_INVALID, "bad reference index");
+    HIPCHK(hipMalloc((void **)&d, sizeof(uint32_t) * c->n));
+    KCHK(oslamk_row_keys(c->k, (int)ref, d_dist, 1.0f / d_dist, d, oslam_stream()));
+    HIPCHK(hipStreamSynchronize((hipStream_t)oslam_stream()));
+    HIPCHK(hipMemcpy(keys_out, d, sizeof(uint32_t) * c->n, hipMemcpyDeviceToHost));
+done:
+    if (d) (void)hipFree(d);
+    return rc;
+}
+
+int oslam_scene_keys(oslam_scene *s, size_t ref_index, uint32_t *keys_out)
+{
+    if (!s) return fail(OSLAM_E_INVALID, "NULL handle");
+    if (!(s->d_dist > 0.0f)) return fail(OSLAM_E_INVALID, "this scene was made for models of any d_dist (d_dist 0): it has no keys of its own");
+    if (hipSetDevice(s->dev) != hipSuccess) return fail(OSLAM_E_DEVICE, "hipSetDevice failed");
+    return cloud_row_keys(&s->c, ref_index, s->d_dist, keys_out);
+}
+
+int oslam_model_keys(oslam_model *m, size_t ref_index, uint32_t *keys_out)
+{
+    if (!m) return fail(OSLAM_E_INVALID, "NULL handle");
+    if (hipSetDevice(m->dev) != hipSuccess) return fail(OSLAM_E_DEVICE, "hipSetDevice failed");
+    return cloud_row_keys(&m->c, ref_index, m->d_dist, keys_out);
+}
+
+static int u32_order(const void *a, const void *b)
+{
+    uint32_t x = *(const uint32_t *)a, y = *(const uint32_t *)b;
+    return x < y ? -1 : (x > y);
+}
+
+int oslam_model_bucket(oslam_model *m, uint32_t key, uint32_t *pairs_out, size_t cap, size_t *count_out)
+{
+    int rc = OSLAM_OK;
+    size_t total = 0, written = 0, n_slots;
+    int s;
+    uint32_t *tmp = NULL;
+    uint16_t *tmi = NULL;
+    if (!m || !count_out) return fail(OSLAM_E_INVALID, "NULL argument");
+    *count_out = 0;
+    if (key == 0) return OSLAM_OK;             /* never matched: kernel.cu:491 */
+    if (hipSetDevice(m->dev) != hipSuccess) return fail(OSLAM_E_DEVICE, "hipSetDevice failed");
+    n_slots = (size_t)m->table.cap * m->table.n_slices;
+    if (!m->h_slots) {
+        m->h_slots = (oslamk_slot *)malloc(sizeof(oslamk_slot) * n_slots);
+        if (!m->h_slots) return fail(OSLAM_E_NOMEM, "host allocation failed");
+        HIPCHK(hipMemcpy(m->h_slots, m->table.slots, sizeof(oslamk_slot) * n_slots, hipMemcpyDeviceToHost));
+    }
+    for (s = 0; s < m->table.n_slices; s++) {
+        const oslamk_slot *tab = m->h_slots + (size_t)s * m->table.cap;
+        uint32_t mask = m->table.cap - 1, slot = (key * 2654435761u) >> m->table.shift, probe;
+        for (probe = 0; probe <= mask; probe++) {
+            if (tab[slot].key == key) {
+                uint32_t len = tab[slot].len, e;
+                tmp = (uint32_t *)realloc(tmp, sizeof(uint32_t) * (len ? len : 1));
+                tmi = (uint16_t *)realloc(tmi, sizeof(uint16_t) * (len ? len : 1));
+                HIPCHK(hipMemcpy(tmp, m->ent.e4 + tab[slot].start, sizeof(uint32_t) * len, hipMemcpyDeviceToHost));
+                HIPCHK(hipMemcpy(tmi, m->ent.mi + tab[slot].start, sizeof(uint16_t) * len, hipMemcpyDeviceToHost));
+                for (e = 0; e < len; e++, total++)
+                    if (pairs_out && written < cap)
+                        pairs_out[written++] = ((uint32_t)s * OSLAMK_SLICE + pc_local_of_row11(tmp[e] & PC_ROW_MASK)) * (uint32_t)m->c.n + tmi[e];
+                break;
+            }
+            if (tab[slot].key == 0) break;
+            slot = (slot + 1) & mask;
+        }
+    }
+    if (pairs_out) qsort(pairs_out, written, sizeof(uint32_t), u32_order);
+    *count_out = total;
+done:
+    free(tmp);
+    free(tmi);
+    return rc;
+}
+
+int oslam_model_bucket_words(oslam_model *m, uint32_t key, int slice, uint32_t *words_out, size_t cap, size_t *count_out)
+{
+    int rc = OSLAM_OK;
+    oslamk_slot *tab = NULL;
+    uint32_t mask, slot, probe;
+    if (!m || !count_out || slice < 0 || slice >= m->table.n_slices) return fail(OSLAM_E_INVALID, "bad argument");
+    *count_out = 0;
+    if (hipSetDevice(m->dev) != hipSuccess) return fail(OSLAM_E_DEVICE, "hipSetDevice failed");
+    tab = (oslamk_slot *)malloc(sizeof(oslamk_slot) * m->table.cap);
+    if (!tab) return fail(OSLAM_E_NOMEM, "host allocation failed");
+    HIPCHK(hipMemcpy(tab, m->table.slots + (size_t)slice * m->table.cap, sizeof(oslamk_slot) * m->table.cap, hipMemcpyDeviceToHost));
+    mask = m->table.cap - 1;
+    slot = (key * 2654435761u) >> m->table.shift;
+    for (probe = 0; probe <= mask; probe++, slot = (slot + 1) & mask) {
+        if (tab[slot].key == key) {
+            size_t n = tab[slot].len < cap ? tab[slot].len : cap;
+            *count_out = tab[slot].len;
+            if (words_out && n) HIPCHK(hipMemcpy(words_out, m->ent.e4 + tab[slot].start, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+            break;
+        }
+        if (tab[slot].key == 0) break;
+    }
+done:
+    free(tab);
+    return rc;
+}
+
+int oslam_vote_accumulator(oslam_model *m, oslam_scene *s, size_t ref_index, uint32_t *acc_out)
+{
+    int rc = OSLAM_OK;
+    uint32_t *d_dump = NULL, *d_ref = NULL, *h_dump = NULL;
+    float *d_tsg = NULL;
+    float rows[8];
+    uint32_t ref = (uint32_t)ref_index;
+    oslamk_counters cnt;
+    scratch_pool *pool = NULL;
+    size_t cells;
+    rc = oslam_check_pair(m, s);
+    if (rc != OSLAM_OK) return rc;
+    if (!acc_out || ref_index >= (size_t)s->c.n) return fail(OSLAM_E_INVALID, "bad reference index");
+    cells = (size_t)m->table.n_slices * OSLAMK_SLICE * OSLAMK_NBIN;
+    oslam_T_g_rows(s->c.h_xyz, s->c.h_nrm, &ref, 1, rows);
+    rc = oslam_pool_enter(m->dev, &pool);
+    if (rc != OSLAM_OK) return rc;
+    HIPCHK(hipMalloc((void **)&d_dump, sizeof(uint32_t) * cells));
+    HIPCHK(hipMalloc((void **)&d_ref, sizeof(uint32_t)));
+    HIPCHK(hipMalloc((void **)&d_tsg, sizeof rows));
+    HIPCHK(hipMemcpy(d_ref, &ref, sizeof ref, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_tsg, rows, sizeof rows, hipMemcpyHostToDevice));
+    /* one reference point through the same kernels; fixed_gmax = all ones: nothing is emitted */
+    rc = oslam_run_votes_group(pool, &m, 1, s, d_ref, d_tsg, 1, 0xffffffffu, d_dump, &cnt, NULL, NULL, NULL, NULL, NULL);
+    if (rc != OSLAM_OK) goto done;
+    h_dump = (uint32_t *)malloc(sizeof(uint32_t) * cells);
+    if (!h_dump) { rc = fail(OSLAM_E_NOMEM, "host allocation failed"); goto done; }
+    HIPCHK(hipMemcpy(h_dump, d_dump, sizeof(uint32_t) * cells, hipMemcpyDeviceToHost));
+    memcpy(acc_out, h_dump, sizeof(uint32_t) * OSLAMK_NBIN * (size_t)m->c.n);
+done:
+    oslam_pool_unlock(pool);
+    free(h_dump);
+    if (d_dump) (void)hipFree(d_dump);
+    if (d_ref) (void)hipFree(d_ref);
+    if (d_tsg) (void)hipFree(d_tsg);
+    return rc;
+}
+
+/* the taps read the last result from the host: fetch it if it is still on the device */
+static int materialise_last(oslam_model *m)
+{
+    int rc = OSLAM_OK;
+    const size_t n = m->n_last;
+    if (!m->last_on_device) return OSLAM_OK;
+    if (hipSetDevice(m->dev) != hipSuccess) return fail(OSLAM_E_DEVICE, "hipSetDevice failed");
+    m->last_cells = (oslam_cell *)malloc(sizeof(oslam_cell) * (n ? n : 1));
+    m->last_poses = (float *)malloc(sizeof(float) * 16 * (n ? n : 1));
+    if (!m->last_cells || !m->last_poses) { oslam_drop_last(m); return fail(OSLAM_E_NOMEM, "host allocation failed"); }
+    HIPCHK(hipMemcpy(m->last_cells, m->d_pose_cells, sizeof(oslam_cell) * n, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(m->last_poses, m->d_pose_T, sizeof(float) * 16 * n, hipMemcpyDeviceToHost));
+    m->last_on_device = 0;
+done:
+    return rc;
+}
+
+int oslam_last_result(oslam_model *m, oslam_scene *s, float *trans_out, float *rots_out, float *vote_counts_out,
+                      size_t cap, size_t *n_out, uint32_t *max_idx_out)
+{
+    int rc;
+    size_t n;
+    float T[16], *tr = NULL, *ro = NULL, *sc = NULL;
+    uint32_t best = 0;
+    if (!n_out) return fail(OSLAM_E_INVALID, "NULL argument");
+    *n_out = 0;
+    rc = oslam_check_pair(m, s);
+    if (rc != OSLAM_OK) return rc;
+    if (materialise_last(m) != OSLAM_OK) return OSLAM_E_DEVICE;
+    n = m->n_last;
+    if (max_idx_out) *max_idx_out = 0;
+    if (n == 0) return OSLAM_OK;
+    tr = (float *)calloc(3 * n, sizeof(float));
+    ro = (float *)calloc(4 * n, sizeof(float));
+    sc = (float *)calloc(n, sizeof(float));
+    if (!tr || !ro || !sc) { rc = fail(OSLAM_E_NOMEM, "host allocation failed"); goto done; }
+    rc = oslam_pose_stage_ex(m->last_cells, n, m->c.h_xyz, m->c.h_nrm, (size_t)m->c.n, s->c.h_xyz, s->c.h_nrm, (size_t)s->c.n,
+                             m->d_dist, m->params.cpu_clustering, m->params.use_l1_norm, m->params.use_averaged_clusters,
+                             m->weights, T, NULL, tr, ro, sc, &best);
+    if (rc != OSLAM_OK) { rc = fail(rc, "pose stage failed"); goto done; }
+    if (n > cap) n = cap;
+    if (trans_out) memcpy(trans_out, tr, sizeof(float) * 3 * n);
+    if (rots_out) memcpy(rots_out, ro, sizeof(float) * 4 * n);
+    if (vote_counts_out) memcpy(vote_counts_out, sc, sizeof(float) * n);
+    if (max_idx_out) *max_idx_out = best;
+    *n_out = n;
+done:
+    free(tr);
+    free(ro);
+    free(sc);
+    return rc;
+}
+
+int oslam_last_cells(oslam_model *m, oslam_cell *cells_out, float *poses_out, size_t cap, size_t *n_out)
+{
+    size_t n;
+    if (!m || !n_out) return fail(OSLAM_E_INVALID, "NULL argument");
+    if ((cells_out || poses_out) && materialise_last(m) != OSLAM_OK) return OSLAM_E_DEVICE;
+    n = m->n_last < cap ? m->n_last : cap;
+    if (cells_out) memcpy(cells_out, m->last_cells, sizeof(oslam_cell) * n);
+    if (poses_out) memcpy(poses_out, m->last_poses, sizeof(float) * 16 * n);
+    *n_out = m->n_last;
+    return OSLAM_OK;
+}
+
+/* ------------------------------------------------------------------------ */
+static uint64_t sm64(uint64_t *s)
+{
+    uint64_t z = (*s += 0x9e3779b97f4a7c15ull);
+    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+    return z ^ (z >> 31);
+}
+
+int oslam_selftest_math(size_t n, uint64_t seed, uint64_t *mismatches)
+{
+    int rc = OSLAM_OK, dev;
+    float *h = NULL, *d = NULL, *ho = NULL;
+    size_t i;
+    uint64_t bad = 0;
+    if (!mismatches || n == 0) return fail(OSLAM_E_INVALID, "bad arguments");
+    rc = oslam_pick_device(0, &dev);
+    if (rc != OSLAM_OK) return rc;
+    h = (float *)malloc(sizeof(float) * 3 * n);
+    ho = (float *)malloc(sizeof(float) * 4 * n);
+    if (!h || !ho) { rc = fail(OSLAM_E_NOMEM, "host allocation failed"); goto done; }
+    for (i = 0; i < n; i++) {
+        uint64_t r = sm64(&seed), r2 = sm64(&seed);
+        float x, y, x2;
+        switch (i & 3) {
+        case 0:   /* acos domain, dense near +-1 and +-0.5 */
+            x = (float)((double)(int32_t)(uint32_t)r / 2147483648.0);
+            y = (float)((double)(int32_t)(uint32_t)(r >> 32) / 2147483648.0 * 3.0);
+            x2 = (float)((double)(int32_t)(uint32_t)r2 / 2147483648.0 * 3.0);
+            break;
+        case 1:
+            x = 1.0f - (float)((double)(uint32_t)r / 4294967296.0) * 1e-3f;
+            if (r2 & 1) x = -x;
+            y = (float)((double)(int32_t)(uint32_t)(r >> 32) / 2147483648.0);
+            x2 = y * ((r2 & 2) ? 0.4375f : 2.4375f) * (1.0f + (float)(int)((r2 >> 8) & 15) * 1e-7f);
+            break;
+        case 2:   /* raw bit patterns */
+            x = PM_BITS_U2F((uint32_t)r);
+            y = PM_BITS_U2F((uint32_t)(r >> 32));
+            x2 = PM_BITS_U2F((uint32_t)r2);
+            break;
+        default:
+            x = (float)((double)(int32_t)(uint32_t)r / 2147483648.0 * 1.00001);
+            y = (float)((double)(int32_t)(uint32_t)(r >> 32) / 2147483648.0 * 1e-3);
+            x2 = (float)((double)(int32_t)(uint32_t)r2 / 2147483648.0 * 1e3);
+            break;
+        }
+        h[i] = x; h[n + i] = y; h[2 * n + i] = x2;
+    }
+    HIPCHK(hipMalloc((void **)&d, sizeof(float) * 7 * n));
+    HIPCHK(hipMemcpy(d, h, sizeof(float) * 3 * n, hipMemcpyHostToDevice));
+    KCHK(oslamk_selftest(d, d + n, d + 2 * n, n, d + 3 * n, d + 4 * n, (uint32_t *)(d + 5 * n),
+                         (uint32_t *)(d + 6 * n), oslam_stream()));
+    HIPCHK(hipStreamSynchronize((hipStream_t)oslam_stream()));
+    HIPCHK(hipMemcpy(ho, d + 3 * n, sizeof(float) * 4 * n, hipMemcpyDeviceToHost));
+    for (i = 0; i < n; i++) {
+        float x = h[i], y = h[n + i], x2 = h[2 * n + i];
+        float a = pm_acosf(x), t = pm_atan2f(y, x2);
+        float st = 0.0371f + pm_fabsf(x) * 0.01f;
+        uint32_t q = pc_quant_bits(pm_fabsf(y) * 7.0f, st, 1.0f / st);
+        uint32_t b = pc_alpha_bin_exact(y, x2, x, y - x2);
+        uint32_t ga = PM_BITS_F2U(ho[i]), gt = PM_BITS_F2U(ho[n + i]);
+        int a_ok = pm_isnan(a) ? pm_isnan(ho[i]) : (PM_BITS_F2U(a) == ga);
+        int t_ok = pm_isnan(t) ? pm_isnan(ho[n + i]) : (PM_BITS_F2U(t) == gt);
+        if (!a_ok || !t_ok || q != ((uint32_t *)ho)[2 * n + i] || b != ((uint32_t *)ho)[3 * n + i]) bad++;
+    }
+    *mismatches = bad;
+done:
+    free(h);
+    free(ho);
+    if (d) (void)hipFree(d);
+    return rc;
+}

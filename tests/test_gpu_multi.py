@@ -1,12 +1,13 @@
 """GPU: the multi-GPU exchange of oslam_align_multi with MORE THAN ONE RANK on a one-GPU box.
 
-The RCCL path of the library and this test run the same C function (exchange_peaks in oslam_host.c) over a
+The RCCL path of the library and this test run the same C function (exchange_peaks in oslam_align.c) over a
 table of collective operations; here the table is the in-process loopback (oslam_comm_create_loopback): N
 emulated ranks share the device, one thread per rank, each with its own model handle, scene shard and
 communicator end.  What is covered: N = 2, 3, 8; different survivor counts per rank; ranks without any
 survivor; the record buffer growing on some ranks only; the union above the device pose tail's threshold;
 a failure injected on one rank at each stage between two collectives (every rank must return, none may
-hang, the communicator stays usable); and the database split by model (oslam_db_align_multi).
+hang, the communicator stays usable); and the database split by model (oslam_db_align_multi, oslam_db.c), with
+and without a failure on one rank.
 The reference has no multi-GPU code (src/cuda/ppf.cu:45 picks one device): the expected result of every
 test is the single-GPU registration, which other tests pin to the oracle."""
 import threading
@@ -166,6 +167,42 @@ def test_an_aborted_communicator_releases_its_peers_and_refuses_further_calls(pp
             with pytest.raises(ppf.OslamError):
                 models[r].align_multi(scenes[r], comms[r])
     finally:
+        for cm in comms:
+            cm.close()
+
+
+@pytest.mark.parametrize("world", [2, 3])
+def test_a_failure_on_one_rank_releases_every_rank_of_a_split_database(ppf, built_lib, synth, world):
+    """oslam_db_align_multi with a failure injected after the votes of one rank: that rank returns its own error, every
+    other rank OSLAM_E_PEER, nobody hangs, no communicator is given up, and the same communicators then carry a split
+    database registration equal to a clean one."""
+    ids, bad = [0, 2, 4], 1
+    clouds = [synth.make_model(k, 500) for k in ids]
+    d = synth.d_dist_for(clouds[0][0], 0.05)
+    sp, sn, _ = synth.make_scene(ids[:2], 4000, 2094, instance_points=500, noise_sigma=0.05 * d)
+    sc = ppf.Scene(sp, sn, d_dist=0.0, ref_point_downsample_factor=3)
+    comms = ppf.Comm.loopback(world)
+    dbs = []
+    try:
+        for r in range(world):
+            dbs.append(ppf.Database([ppf.Model(clouds[j][0], clouds[j][1], d_dist=d) for j in range(r, len(ids), world)]))
+        run = lambda: _run_ranks(lambda r: ppf.db_align_multi(dbs[r], sc, comms[r], len(ids)), world)
+        clean = run()
+        for r in range(world):
+            assert not isinstance(clean[r], Exception), clean[r]
+        comms[bad].inject_failure(1)
+        res = run()
+        for r in range(world):
+            assert isinstance(res[r], ppf.OslamError), (r, res[r])
+            assert res[r].code == (ppf.OSLAM_E_DEVICE if r == bad else ppf.OSLAM_E_PEER), (r, res[r])
+        assert not any(cm.broken for cm in comms)
+        res = run()
+        for r in range(world):
+            assert not isinstance(res[r], Exception), res[r]
+            assert np.array_equal(res[r][0], clean[r][0]) and np.array_equal(res[r][1], clean[r][1]), r
+    finally:
+        for db in dbs:
+            db.close()
         for cm in comms:
             cm.close()
 
