@@ -36,8 +36,12 @@ extern "C" {
 /* Per-vote arithmetic of the alpha angle (reference src/cuda/kernel.cu:302-342). */
 #define OSLAM_VOTE_EXACT 0    /* accumulator identical to the reference's: alpha from quantised angles,
                                * re-evaluated with the reference's float sequence near bin edges */
-#define OSLAM_VOTE_FAST 1     /* quantised angles only (Drost's alpha_scene - alpha_model): bins can
-                               * differ from the reference's within 2e-5 bin of an edge */
+#define OSLAM_VOTE_FAST 1     /* quantised angles only (Drost's alpha_scene - alpha_model), nothing
+                               * re-evaluated: a vote's bin can differ from the reference's only when the
+                               * reference's alpha lies within 3.1e-5 bin of an edge, and then it is the
+                               * bin across that edge.  A vector that is zero, not finite or outside
+                               * 2^-40..2^40 counts as angle 0 (atan2 + pi = 0) on either side, model
+                               * or scene; exact mode gives the reference's bin for those votes too */
 
 /* Flags of the reference's CLI that reach the path (src/alignment.cpp:119-172)
  * plus this build's extensions.  oslam_params_default() fills the reference's

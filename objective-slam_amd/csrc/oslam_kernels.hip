@@ -548,7 +548,10 @@ __device__ __forceinline__ void hits_chunk(const oslamk_vote_args &a, int ref_lo
         if (hit) {
             const float vy = pc_row_dot(rows, x, y, z);     /* kernel.cu:334-336 */
             const float vz = pc_row_dot(rows + 4, x, y, z);
-            pay.theta_t22 = pc_angle_t22(vy, vz);
+            /* fast mode: a degenerate vector counts as theta = 0 (pc_theta_fast); the members of a group that share
+             * this list share the vote mode (oslam_db.c: same_group) */
+            const uint32_t th = pc_angle_t22(vy, vz);
+            pay.theta_t22 = a.mode == 1 ? pc_theta_fast(th) : th;
             pay.idx = (uint32_t)i;
         }
     }

@@ -255,9 +255,10 @@ struct VoteRegs {
          * those of the upper half 0x10000 (inc_lo / inc_hi; one of them is 0 in the rare second and third pass
          * of a workgroup whose 16-bit counters overflowed) */
         const uint32_t wa[4] = {v.x, v.y, v.z, v.w};
-        /* pc_vote_base_t32(th) = (th << 10) + a constant, which is kept in a scalar register */
+        /* pc_vote_base_t32(th) = (th << 10) + a constant, which is kept in a scalar register; fast mode casts from the
+         * unshifted base (pc_vote_base_fast_t32: nothing there moves a vote that the margin shifted across an edge) */
         uint32_t csmv;
-        asm("v_lshl_add_u32 %0, %1, 10, %2" : "=v"(csmv) : "v"(th), "s"(pc_vote_base_t32(0u)));
+        asm("v_lshl_add_u32 %0, %1, 10, %2" : "=v"(csmv) : "v"(th), "s"(MODE == 0 ? pc_vote_base_t32(0u) : pc_vote_base_fast_t32(0u)));
         const uint32_t acc_base = (uint32_t)(uintptr_t)acc;  /* the accumulator's LDS address */
         uint32_t rowb[4], inc[4];
 #pragma unroll

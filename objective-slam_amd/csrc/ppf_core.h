@@ -176,7 +176,8 @@ PM_HD unsigned pc_alpha_bin_table(float uy, float uz, float vy, float vz, const 
  * with pc_alpha_bin_table.  The margin is added to t24 first, so that one unsigned
  * compare of the position finds both sides of an edge; the bin read from the
  * shifted value is only used when the vote is not re-evaluated, where it is the
- * unshifted one.
+ * unshifted one.  (Fast mode re-evaluates nothing and casts from the unshifted
+ * value: pc_vote_base_fast_t32 below.)
  * Result: identical bins at a fraction of the arithmetic and 4 bytes per vote. */
 #define PC_T22_TURN 4194304u                  /* 2^22 units per turn */
 #define PC_T24_SCALE 7680u                    /* 30 bins * 2^8 */
@@ -249,6 +250,25 @@ PM_HD unsigned pc_alpha_bin_hybrid_ex(float uy, float uz, float vy, float vz, ui
 PM_HD unsigned pc_alpha_bin_hybrid(float uy, float uz, float vy, float vz, uint32_t row, const uint32_t *tbl)
 {
     return pc_alpha_bin_hybrid_ex(uy, uz, vy, vz, row, tbl, 0, 0);
+}
+
+/* ---- fast mode (OSLAM_VOTE_FAST): the quantised bin and nothing else ----------
+ * Nothing is re-evaluated, so the margin must not be in the base: the vote is cast from the unshifted
+ * difference (with the + 4 units that centre the row bits).  Linear in theta_v like pc_vote_base_t32, so the
+ * vote loop keeps (theta_v << 10) + pc_vote_base_fast_t32(0) with the constant in a scalar register.
+ * Degenerate vectors (PC_T22_FORCE: zero, not finite, outside 2^-40..2^40) count as theta = 0 on either
+ * side: the model entry stores 0 in both modes, the scene hit stores 0 in fast mode (k_scene_hits).
+ * Against the libm formula of kernel.cu:338-342 a bin can differ only within PC_FAST_BOUND of an edge:
+ * the 17.2 units of 2^-24 turn of the budget above (11.2 + 2 for the 2^-21-turn model angle + 4 for the
+ * row bits), 3.08e-5 bin; math_exhaustive `fast` checks it. */
+#define PC_FAST_BOUND 3.1e-5                  /* bins */
+PM_HD uint32_t pc_vote_base_fast_t32(uint32_t theta_v_t22) { return pc_vote_base_t32(theta_v_t22) - (PC_T24_MARGIN << 8); }
+PM_HD uint32_t pc_theta_fast(uint32_t theta_t22) { return theta_t22 == PC_T22_FORCE ? 0u : theta_t22; }
+/* what the fast vote loop casts for an entry in accumulator row field `row` (pc_row11) */
+PM_HD unsigned pc_alpha_bin_fast(float uy, float uz, float vy, float vz, uint32_t row)
+{
+    const uint32_t cs = pc_theta_fast(pc_angle_t22(vy, vz)), am = pc_theta_fast(pc_angle_t22(uy, uz));
+    return (unsigned)(((uint64_t)(pc_vote_base_fast_t32(cs) - pc_entry_word(am, row)) * 30u) >> 32);
 }
 
 #endif /* OSLAM_PPF_CORE_H */

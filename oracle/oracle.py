@@ -67,6 +67,16 @@ def lib():
     L.orc_fused_votes.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_long, C.c_long,
                                   C.c_long, C.c_int, C.POINTER(C.c_size_t), C.POINTER(Stats)]
     L.orc_accumulator_for_ref.argtypes = [vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_float, vp]
+    L.orc_votes_fused_mode.restype = C.c_void_p
+    L.orc_votes_fused_mode.argtypes = [vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_float, C.c_float,
+                                       C.c_long, C.c_long, C.c_long, C.c_int, C.c_int, C.POINTER(C.c_size_t),
+                                       C.POINTER(Stats)]
+    L.orc_fused_votes_mode.restype = C.c_void_p
+    L.orc_fused_votes_mode.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_long, C.c_long,
+                                       C.c_long, C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(Stats)]
+    L.orc_fused_accumulator.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_float, C.c_int, vp]
+    L.orc_fused_vote_dump.restype = C.c_size_t
+    L.orc_fused_vote_dump.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, vp, C.c_size_t]
     L.orc_trans_model_scene.restype = C.c_uint
     L.orc_trans_calc2.argtypes = [vp, C.c_size_t, vp, vp, vp, vp, vp]
     L.orc_mat2transquat.argtypes = [vp, C.c_size_t, vp, vp]
@@ -159,13 +169,20 @@ def votes_literal(mp, mn, sp, sn, df, d_dist, thresh=0.4, want_all=False):
     return cells, st.asdict()
 
 
-def votes_fused(mp, mn, sp, sn, df, d_dist, thresh=0.4, ref_begin=0, ref_step=1, ref_limit=-1, threads=0):
+def votes_fused(mp, mn, sp, sn, df, d_dist, thresh=0.4, ref_begin=0, ref_step=1, ref_limit=-1, threads=0,
+                vote_mode=0):
+    """vote_mode 1: OSLAM_VOTE_FAST's bins (oracle_ppf.c: fast_alpha_idx) instead of the reference's."""
     mp, mn, sp, sn = _c32(mp), _c32(mn), _c32(sp), _c32(sn)
     n_out = C.c_size_t(0)
     st = Stats()
-    ptr = lib().orc_votes_fused(_p(mp), _p(mn), len(mp), _p(sp), _p(sn), len(sp), int(df), float(d_dist),
-                                float(thresh), int(ref_begin), int(ref_step), int(ref_limit), int(threads),
-                                C.byref(n_out), C.byref(st))
+    if vote_mode:
+        ptr = lib().orc_votes_fused_mode(_p(mp), _p(mn), len(mp), _p(sp), _p(sn), len(sp), int(df), float(d_dist),
+                                         float(thresh), int(ref_begin), int(ref_step), int(ref_limit), int(threads),
+                                         int(vote_mode), C.byref(n_out), C.byref(st))
+    else:
+        ptr = lib().orc_votes_fused(_p(mp), _p(mn), len(mp), _p(sp), _p(sn), len(sp), int(df), float(d_dist),
+                                    float(thresh), int(ref_begin), int(ref_step), int(ref_limit), int(threads),
+                                    C.byref(n_out), C.byref(st))
     cells = _cells_from(ptr, n_out.value)
     return cells, st.asdict()
 
@@ -178,14 +195,36 @@ class FusedModel:
         self.d_dist = float(d_dist)
         self.h = lib().orc_fused_create(_p(self.mp), _p(self.mn), len(self.mp), self.d_dist)
 
-    def votes(self, sp, sn, df, thresh=0.4, ref_begin=0, ref_step=1, ref_limit=-1, threads=0):
+    def votes(self, sp, sn, df, thresh=0.4, ref_begin=0, ref_step=1, ref_limit=-1, threads=0, vote_mode=0):
         sp, sn = _c32(sp), _c32(sn)
         n_out = C.c_size_t(0)
         st = Stats()
-        ptr = lib().orc_fused_votes(self.h, _p(sp), _p(sn), len(sp), int(df), self.d_dist, float(thresh),
-                                    int(ref_begin), int(ref_step), int(ref_limit), int(threads),
-                                    C.byref(n_out), C.byref(st))
+        ptr = lib().orc_fused_votes_mode(self.h, _p(sp), _p(sn), len(sp), int(df), self.d_dist, float(thresh),
+                                         int(ref_begin), int(ref_step), int(ref_limit), int(threads), int(vote_mode),
+                                         C.byref(n_out), C.byref(st))
         return _cells_from(ptr, n_out.value), st.asdict()
+
+    def accumulator(self, sp, sn, s_r, vote_mode=0):
+        """dense [M][32] accumulator of scene reference point s_r"""
+        sp, sn = _c32(sp), _c32(sn)
+        acc = np.zeros((len(self.mp), 32), np.uint32)
+        lib().orc_fused_accumulator(self.h, _p(sp), _p(sn), len(sp), int(s_r), self.d_dist, int(vote_mode), _p(acc))
+        return acc
+
+    def vote_dump(self, sp, sn, s_r, vote_mode=0):
+        """Every vote of scene reference point s_r: dict(m_r, uy, uz, vy, vz, bin) -- the float32 operands of
+        kernel.cu:338-342 as the reference computes them, and the oracle's bin for vote_mode."""
+        sp, sn = _c32(sp), _c32(sn)
+        L = lib()
+        n = L.orc_fused_vote_dump(self.h, _p(sp), _p(sn), len(sp), int(s_r), self.d_dist, int(vote_mode),
+                                  None, None, None, 0)
+        mr = np.zeros(n, np.uint32)
+        uv = np.zeros((n, 4), np.float32)
+        b = np.zeros(n, np.uint8)
+        got = L.orc_fused_vote_dump(self.h, _p(sp), _p(sn), len(sp), int(s_r), self.d_dist, int(vote_mode),
+                                    _p(mr), _p(uv), _p(b), n)
+        assert got == n
+        return dict(m_r=mr, uy=uv[:, 0].copy(), uz=uv[:, 1].copy(), vy=uv[:, 2].copy(), vz=uv[:, 3].copy(), bin=b)
 
     def close(self):
         if self.h:
@@ -199,8 +238,14 @@ class FusedModel:
             pass
 
 
-def accumulator_for_ref(mp, mn, sp, sn, s_r, d_dist):
+def accumulator_for_ref(mp, mn, sp, sn, s_r, d_dist, vote_mode=0):
     mp, mn, sp, sn = _c32(mp), _c32(mn), _c32(sp), _c32(sn)
+    if vote_mode:
+        fm = FusedModel(mp, mn, d_dist)
+        try:
+            return fm.accumulator(sp, sn, s_r, vote_mode)
+        finally:
+            fm.close()
     acc = np.zeros((len(mp), 32), np.uint32)
     lib().orc_accumulator_for_ref(_p(mp), _p(mn), len(mp), _p(sp), _p(sn), len(sp), int(s_r), float(d_dist), _p(acc))
     return acc

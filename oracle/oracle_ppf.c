@@ -425,9 +425,51 @@ static void fused_model_free(fused_model *fm)
     free(fm->T_m_g); free(fm->ent_uy); free(fm->ent_uz); free(fm->ent_mr);
 }
 
-/* accumulate all votes of scene reference point s_r into acc[M][32] */
-static void fused_accumulate(const fused_model *fm, const orc_f3 *sp, const orc_f3 *sn, int S,
-                             int s_r, float d_dist, uint32_t *acc, uint64_t *hits, uint64_t *votes)
+/* ---------------------------------------------------------------------------
+ * OSLAM_VOTE_FAST restated (the product's ppf_core.h is not included: this is
+ * the independent statement the GPU is compared with).  Each side's angle is
+ * quantised on its own, theta = rint((atan2f(z, y) + pi) * 2^22 / 2pi) in units
+ * of 2^-22 turn (ppf_core.h:pc_angle_t22), 0 for a vector that is zero, not
+ * finite or outside 2^-40..2^40 (pc_theta_fast); the model angle is rounded to
+ * 2^-21 turn and packed above the 11-bit row field of its entry
+ * (pc_theta_u21, pc_entry_word, pc_row11 with 2046 model points per table
+ * slice); the vote is floor(30 * (base - word) / 2^32) with
+ * base = (theta_v + half a turn) << 10 plus 1024 (pc_vote_base_fast_t32).
+ * -------------------------------------------------------------------------*/
+#define ORC_T22_PER_RAD 667544.214430109f          /* 2^22 / (2 pi), ppf_core.h:PC_T22_PER_RAD */
+static uint32_t fast_theta(float y, float z)
+{
+    uint32_t by, bz, e;
+    memcpy(&by, &y, 4);
+    memcpy(&bz, &z, 4);
+    by &= 0x7fffffffu;
+    bz &= 0x7fffffffu;
+    e = (by > bz ? by : bz) >> 23;
+    float q = rintf((atan2f(z, y) + ORC_PI_F) * ORC_T22_PER_RAD);
+    if (e < 87u || e > 167u || !(q >= 0.0f && q <= 4194304.0f)) return 0u;
+    return (uint32_t)q & 0x3fffffu;
+}
+static unsigned fast_alpha_idx(float uy, float uz, float vy, float vz, uint32_t m_r)
+{
+    const uint32_t local = m_r % 2046u;
+    const uint32_t row11 = ((local / 1023u) << 10) | (local % 1023u);
+    const uint32_t tu = fast_theta(uy, uz), tv = fast_theta(vy, vz);
+    const uint32_t word = ((((tu + 1u) >> 1) & 0x1fffffu) << 11) | row11;
+    const uint32_t base = ((tv + 0x200000u) << 10) + 1024u;
+    return (unsigned)(((uint64_t)(uint32_t)(base - word) * 30u) >> 32);
+}
+
+/* accumulate all votes of scene reference point s_r into acc[M][32]; vote_mode 1: the fast statement.
+ * dump (optional, dump_cap records): per vote m_r, the float32 operands uy, uz, vy, vz and the bin */
+typedef struct {
+    uint32_t *mr;
+    float *uv;          /* [cap][4] */
+    uint8_t *bin;
+    size_t cap, n;
+} vote_dump;
+static void fused_accumulate_mode(const fused_model *fm, const orc_f3 *sp, const orc_f3 *sn, int S, int s_r,
+                                  float d_dist, int vote_mode, uint32_t *acc, uint64_t *hits, uint64_t *votes,
+                                  vote_dump *dump)
 {
     float T_s_g[4][4];
     build_T_g(sp[s_r], sn[s_r], T_s_g);
@@ -443,10 +485,26 @@ static void fused_accumulate(const fused_model *fm, const orc_f3 *sp, const orc_
         (*votes) += cnt;
         for (size_t e = first; e < first + cnt; e++) {
             orc_f3 u = {0, fm->ent_uy[e], fm->ent_uz[e]};
-            unsigned a = alpha_idx_from_uv(u, v, 0);
-            acc[(size_t)fm->ent_mr[e] * 32 + a]++;
+            unsigned a = vote_mode == 1 ? fast_alpha_idx(u.y, u.z, v.y, v.z, fm->ent_mr[e]) : alpha_idx_from_uv(u, v, 0);
+            if (acc) acc[(size_t)fm->ent_mr[e] * 32 + a]++;
+            if (dump) {
+                if (dump->n < dump->cap) {
+                    dump->mr[dump->n] = fm->ent_mr[e];
+                    dump->uv[4 * dump->n + 0] = u.y;
+                    dump->uv[4 * dump->n + 1] = u.z;
+                    dump->uv[4 * dump->n + 2] = v.y;
+                    dump->uv[4 * dump->n + 3] = v.z;
+                    dump->bin[dump->n] = (uint8_t)a;
+                }
+                dump->n++;
+            }
         }
     }
+}
+static void fused_accumulate(const fused_model *fm, const orc_f3 *sp, const orc_f3 *sn, int S,
+                             int s_r, float d_dist, uint32_t *acc, uint64_t *hits, uint64_t *votes)
+{
+    fused_accumulate_mode(fm, sp, sn, S, s_r, d_dist, 0, acc, hits, votes, 0);
 }
 
 void orc_accumulator_for_ref(const orc_f3 *mp, const orc_f3 *mn, int M, const orc_f3 *sp,
@@ -474,9 +532,9 @@ void orc_fused_free(void *h)
     free(h);
 }
 
-orc_cell *orc_fused_votes(void *h, const orc_f3 *sp, const orc_f3 *sn, int S, int df, float d_dist,
-                          float thresh, long ref_begin, long ref_step, long ref_limit, int threads,
-                          size_t *n_out, orc_stats *st)
+static orc_cell *fused_votes_mode(void *h, const orc_f3 *sp, const orc_f3 *sn, int S, int df, float d_dist,
+                                  float thresh, long ref_begin, long ref_step, long ref_limit, int threads,
+                                  int vote_mode, size_t *n_out, orc_stats *st)
 {
     const fused_model *fmp = (const fused_model *)h;
     const int M = fmp->M;
@@ -507,7 +565,7 @@ orc_cell *orc_fused_votes(void *h, const orc_f3 *sp, const orc_f3 *sn, int S, in
         for (long kk = 0; kk < n_ref; kk++) {
             int s_r = (int)(df * (ref_begin + kk * ref_step));
             memset(acc, 0, sizeof(uint32_t) * 32 * (size_t)M);
-            fused_accumulate(fmp, sp, sn, S, s_r, d_dist, acc, &hits, &votes);
+            fused_accumulate_mode(fmp, sp, sn, S, s_r, d_dist, vote_mode, acc, &hits, &votes, 0);
             ppfs += (uint64_t)(S - 1);
             uint32_t lmax = 0;
             for (size_t c = 0; c < (size_t)M * 32; c++) {
@@ -541,6 +599,51 @@ orc_cell *orc_fused_votes(void *h, const orc_f3 *sp, const orc_f3 *sn, int S, in
     st->num_votes = votes;
     st->num_unique_votes = uniq;
     return threshold_cells(cells, ncell, thresh, n_out, st);
+}
+
+orc_cell *orc_fused_votes(void *h, const orc_f3 *sp, const orc_f3 *sn, int S, int df, float d_dist,
+                          float thresh, long ref_begin, long ref_step, long ref_limit, int threads,
+                          size_t *n_out, orc_stats *st)
+{
+    return fused_votes_mode(h, sp, sn, S, df, d_dist, thresh, ref_begin, ref_step, ref_limit, threads, 0, n_out, st);
+}
+
+orc_cell *orc_fused_votes_mode(void *h, const orc_f3 *sp, const orc_f3 *sn, int S, int df, float d_dist,
+                               float thresh, long ref_begin, long ref_step, long ref_limit, int threads,
+                               int vote_mode, size_t *n_out, orc_stats *st)
+{
+    return fused_votes_mode(h, sp, sn, S, df, d_dist, thresh, ref_begin, ref_step, ref_limit, threads, vote_mode,
+                            n_out, st);
+}
+
+orc_cell *orc_votes_fused_mode(const orc_f3 *mp, const orc_f3 *mn, int M, const orc_f3 *sp,
+                               const orc_f3 *sn, int S, int df, float d_dist, float thresh,
+                               long ref_begin, long ref_step, long ref_limit, int threads, int vote_mode,
+                               size_t *n_out, orc_stats *st)
+{
+    void *h = orc_fused_create(mp, mn, M, d_dist);
+    orc_cell *cells = orc_fused_votes_mode(h, sp, sn, S, df, d_dist, thresh, ref_begin, ref_step, ref_limit,
+                                           threads, vote_mode, n_out, st);
+    orc_fused_free(h);
+    return cells;
+}
+
+void orc_fused_accumulator(void *h, const orc_f3 *sp, const orc_f3 *sn, int S, int s_r, float d_dist,
+                           int vote_mode, uint32_t *acc)
+{
+    const fused_model *fm = (const fused_model *)h;
+    uint64_t hh = 0, v = 0;
+    memset(acc, 0, sizeof(uint32_t) * 32 * (size_t)fm->M);
+    fused_accumulate_mode(fm, sp, sn, S, s_r, d_dist, vote_mode, acc, &hh, &v, 0);
+}
+
+size_t orc_fused_vote_dump(void *h, const orc_f3 *sp, const orc_f3 *sn, int S, int s_r, float d_dist,
+                           int vote_mode, uint32_t *mr, float *uv, uint8_t *bin, size_t cap)
+{
+    vote_dump d = {mr, uv, bin, cap, 0};
+    uint64_t hh = 0, v = 0;
+    fused_accumulate_mode((const fused_model *)h, sp, sn, S, s_r, d_dist, vote_mode, 0, &hh, &v, &d);
+    return d.n;
 }
 
 orc_cell *orc_votes_fused(const orc_f3 *mp, const orc_f3 *mn, int M, const orc_f3 *sp,

@@ -106,6 +106,22 @@ orc_cell *orc_fused_votes(void *h, const orc_f3 *sp, const orc_f3 *sn, int S, in
                           float thresh, long ref_begin, long ref_step, long ref_limit, int threads,
                           size_t *n_out, orc_stats *st);
 void orc_fused_free(void *h);
+/* OSLAM_VOTE_FAST (vote_mode 1; 0 = the functions above): the quantised-angle bin, degenerate vectors as
+ * theta = 0, restated in oracle_ppf.c.  Same cells, statistics and accumulators otherwise. */
+orc_cell *orc_votes_fused_mode(const orc_f3 *mp, const orc_f3 *mn, int M, const orc_f3 *sp,
+                               const orc_f3 *sn, int S, int df, float d_dist, float thresh,
+                               long ref_begin, long ref_step, long ref_limit, int threads, int vote_mode,
+                               size_t *n_out, orc_stats *st);
+orc_cell *orc_fused_votes_mode(void *h, const orc_f3 *sp, const orc_f3 *sn, int S, int df, float d_dist,
+                               float thresh, long ref_begin, long ref_step, long ref_limit, int threads,
+                               int vote_mode, size_t *n_out, orc_stats *st);
+void orc_fused_accumulator(void *h, const orc_f3 *sp, const orc_f3 *sn, int S, int s_r, float d_dist,
+                           int vote_mode, uint32_t *acc);
+/* every vote of scene reference point s_r in table order: m_r, the float32 operands (u.y, u.z, v.y, v.z) of
+ * kernel.cu:338-342 (fused_accumulate's ent_uy / ent_uz and v) and the bin of vote_mode; the first `cap`
+ * are written, the number of votes is returned */
+size_t orc_fused_vote_dump(void *h, const orc_f3 *sp, const orc_f3 *sn, int S, int s_r, float d_dist,
+                           int vote_mode, uint32_t *mr, float *uv, uint8_t *bin, size_t cap);
 /* dense accumulator [M][32] of one scene reference point (fused path) */
 void orc_accumulator_for_ref(const orc_f3 *mp, const orc_f3 *mn, int M, const orc_f3 *sp,
                              const orc_f3 *sn, int S, int s_r, float d_dist, uint32_t *acc);

@@ -9,6 +9,11 @@
  *   math_exhaustive alphabin N      pc_alpha_bin_table vs the libm formula of kernel.cu:338-342
  *   math_exhaustive hybrid N        pc_alpha_bin_hybrid vs the same formula; also prints the largest
  *                                   distance between the quantised and the reference position
+ *   math_exhaustive fast N          pc_alpha_bin_fast (what OSLAM_VOTE_FAST casts) vs the same formula on the same samples,
+ *                                   a degenerate vector replaced by one at theta = 0 (the stated rule); a differing bin
+ *                                   counts as a mismatch only when it is not the neighbour across the reference's
+ *                                   nearest edge or lies farther than PC_FAST_BOUND from it.  Prints the rate of
+ *                                   differing bins and the largest distance of one from its edge
  *   math_exhaustive acosbin STRIDE  all floats i*STRIDE: pc_acos_bin (the tabulated steps) vs the quantised libm
  *                                   acosf, acosf(c) - fmodf(acosf(c), D) == bin * D (or NaN, bin 16)
  *   math_exhaustive pairbins N      N point pairs (random, near-degenerate and degenerate): the key rebuilt from
@@ -237,6 +242,67 @@ int main(int argc, char **argv)
         }
         if (hybrid) printf("largest |quantised - reference| = %.3g bin (margin %.3g); re-evaluated %.4f%%\n", worst,
                            (double)PC_T24_MARGIN * 30.0 / 16777216.0, 100.0 * (double)slow / (double)checked);
+    } else if (!strcmp(mode, "fast")) {
+        double worst = 0.0;
+        uint64_t differ = 0, degenerate = 0, generic = 0, differ_generic = 0;
+#pragma omp parallel for reduction(+ : bad, checked, differ, degenerate, generic, differ_generic) reduction(max : worst) schedule(static)
+        for (uint64_t i = 0; i < arg; i++) {
+            /* the sample classes of `hybrid`, with the same seeds */
+            uint64_t s = i * 0xd1342543de82ef95ull + 99;
+            uint64_t r = splitmix(&s), r2 = splitmix(&s);
+            float uy, uz, vy, vz;
+            if ((i & 7) == 7) {
+                uy = PM_BITS_U2F((uint32_t)r); uz = PM_BITS_U2F((uint32_t)(r >> 32));
+                vy = PM_BITS_U2F((uint32_t)r2); vz = PM_BITS_U2F((uint32_t)(r2 >> 32));
+            } else {
+                uy = (float)((double)(int32_t)(uint32_t)r / 2147483648.0 * 3.0);
+                uz = (float)((double)(int32_t)(uint32_t)(r >> 32) / 2147483648.0 * 3.0);
+                vy = (float)((double)(int32_t)(uint32_t)r2 / 2147483648.0 * 3.0);
+                vz = (float)((double)(int32_t)(uint32_t)(r2 >> 32) / 2147483648.0 * 3.0);
+                if ((i & 7) == 1) { vy = uy; vz = uz; }
+                if ((i & 7) == 2) { vy = -uy; vz = -uz; }
+                if ((i & 7) == 3) { vy = -uz; vz = uy; }
+                if ((i & 7) == 5) {
+                    float su = ldexpf(1.0f, (int)((r2 >> 3) % 101) - 50), sv = ldexpf(1.0f, (int)((r2 >> 13) % 101) - 50);
+                    uy *= su; uz *= su; vy *= sv; vz *= sv;
+                }
+                if ((i & 7) == 4) {
+                    double a = 0.20943951023931953 * (double)((r2 >> 7) % 30), c = cos(a), sn = sin(a);
+                    vy = (float)(uy * c - uz * sn); vz = (float)(uy * sn + uz * c);
+                }
+            }
+            /* row bits at both ends of their range and at random */
+            const uint32_t rows[3] = {0u, PC_ROW_MASK, (uint32_t)(r2 >> 20) & PC_ROW_MASK};
+            /* the stated rule: a degenerate vector counts as theta = 0, i.e. atan2 + pi = 0: the vector (-1, -0) */
+            if (!cs_ok(uy, uz)) { uy = -1.0f; uz = -0.0f; degenerate++; }
+            if (!cs_ok(vy, vz)) { vy = -1.0f; vz = -0.0f; degenerate++; }
+            const float cx = uy * vz - uz * vy, dt = 0.0f * 0.0f + uy * vy + uz * vz;
+            const float al = atan2f(cx, dt) + PM_PI_F;
+            const float aq = al - fmodf(al, PM_D_ANGLE);
+            const unsigned b = (unsigned)lrintf(aq / PM_D_ANGLE);          /* 0..30: finite operands */
+            /* the reference's position in bins, its nearest edge k (30 is the edge 0) and the bin across it */
+            const double x = (double)al / (double)PM_D_ANGLE, k = rint(x), d = fabs(x - k);
+            const unsigned across = x < k ? (unsigned)k % 30u : ((unsigned)k + 29u) % 30u;
+            for (int j = 0; j < 3; j++) {
+                const unsigned a = pc_alpha_bin_fast(uy, uz, vy, vz, rows[j]);
+                const int gen = (i & 7) == 0 || (i & 7) == 6;       /* the random classes (the others sit on edges by design) */
+                checked++;
+                generic += (uint64_t)gen;
+                if (a == b % 30u) continue;           /* bin 30 of the reference is the fast path's bin 0 */
+                differ++;
+                differ_generic += (uint64_t)gen;
+                if (d > worst) worst = d;
+                if (a != across || d > PC_FAST_BOUND) {
+                    bad++;
+                    if (bad < 5) fprintf(stderr, "fast(%a,%a,%a,%a) row %u: fast=%u libm=%u, %.3g bin from an edge\n", uy, uz, vy,
+                                         vz, rows[j], a, b, d);
+                }
+            }
+        }
+        printf("fast: differing bins %.3g per vote of the random classes (%llu in all), largest distance of one from its edge "
+               "%.3g bin (bound %.3g); degenerate vectors %llu\n",
+               (double)differ_generic / (double)(generic ? generic : 1), (unsigned long long)differ, worst, PC_FAST_BOUND,
+               (unsigned long long)degenerate);
     } else {
         return 2;
     }
