@@ -396,6 +396,79 @@ int oslam_db_refine(oslam_db *db, oslam_scene *s, const float *T_in /* [n][16] *
 int oslam_refine_correspondences(oslam_model *m, oslam_scene *s, const float T[16], float radius,
                                  float min_normal_dot, int32_t *idx_out);
 
+/* ---- every instance of a model in a scene (after the votes; the reference keeps only the best pose,
+ * model.cu:292-295 / ppf.cu:74-93).  Single device only: oslam_align_multi / oslam_db_align_multi have no instance form.
+ *
+ * Candidates: the poses the clustering stage produces for the registration.
+ *   Default clustering (also use_l1_norm, use_averaged_clusters): every kept cell's pose (oslam_last_cells order) with
+ *     its translation replaced by the clustering-stage translation -- exactly as oslam_align builds its T -- scored by
+ *     its clustered score (oslam_last_result's vote_counts).  Fewer than two kept cells give no candidate.
+ *   cpu_clustering: the clusters of the greedy clustering, each with its pose (made as oslam_align makes the winner's)
+ *     and its vote total as the score (as float); candidate index = the cluster's head (a kept-cell index).
+ *   Candidate order: score descending, then candidate index ascending.
+ * Same instance: with c = the model centroid (mean of its points in double, rounded to float) and E = the model's
+ *   extent (its largest bounding-box side, as oslam_d_dist_from_cloud with tau 1), poses A and B are the same instance
+ *   when both hold:
+ *     p = ((R0*cx + R1*cy) + R2*cz) + t per row in float; d2 = (dx*dx + dy*dy) + dz*dz < sep2, where
+ *     sep2 = float((double)min_separation * E, squared in double);
+ *     and, unless max_angle == (float)pi, sum_ij A_ij*B_ij over the 3x3 blocks (row-major, in float from 0) >=
+ *     float(1 + 2 cos((double)max_angle)).  max_angle == (float)pi (the default) makes it a translation-only test.
+ * Selection: walk the candidates in order; accept one that is not the same instance as any accepted before; stop after
+ *   max_instances acceptances, or at the first candidate whose score is < min_score_ratio * score(instance 0) (float).
+ *   When instance 0's pose is all zeros (the (0,0,0) code) nothing is returned.  Hence: instance 0's pose is bit for
+ *   bit the T of oslam_align for the same model, scene and params, and *n_out == 0 exactly when oslam_align returns an
+ *   all-zero T or OSLAM_E_NO_VOTES (the same error code is returned then).  The pose tail runs on the device or the host
+ *   as for oslam_align (on the device one more kernel, k_pose_instances, after the winner); the result is the same.
+ * Refinement (rp != NULL): every accepted instance is refined with oslam_refine semantics in one set of launches;
+ *   instance j's T and refine equal oslam_refine(m, s, T_vote_j, rp) bit for bit except launches and ms_total.  Then,
+ *   in acceptance order, an instance that is the same instance (same rule, refined poses) as an earlier kept one is
+ *   dropped -- two candidates that converged onto one object -- and then those with found == 0 unless keep_not_found.
+ * Output: out[0 .. *n_out) in acceptance order.  oslam_last_cells / oslam_last_result afterwards report what they
+ *   report after oslam_align.
+ * Arguments are checked before any handle is read: NULL pointers, max_instances 0 or above OSLAM_MAX_INSTANCES,
+ *   cap < max_instances, min_separation not finite or negative, max_angle outside [0, (float)pi], min_score_ratio
+ *   outside [0, 1] are OSLAM_E_INVALID; the refinement parameters are checked as oslam_refine checks them.
+ * Defaults: max_instances 8, min_separation 0.5, max_angle pi, min_score_ratio 0.5 (not tuned by a sweep).  Observed
+ *   on one MI355X: on the seeded 2- and 3-copy scenes of tests/test_gpu_instances.py and tools/bench_configs.py
+ *   instances, the second and third copies' winning candidates scored 0.77-0.97 of the best one and their centroids lay
+ *   2 E and more apart; refined, every copy lay within 1e-3 E of its ground truth.
+ * Cost (device tail): one more launch per model, k_pose_instances (one workgroup): 125 ms at 1.2e7 kept cells and 16
+ *   rounds with min_score_ratio 0, immeasurable next to the rest at the 4e3-1.5e4 cells of the bench registrations. */
+#define OSLAM_MAX_INSTANCES 64
+typedef struct oslam_instance_params {
+    unsigned max_instances;    /* 1..OSLAM_MAX_INSTANCES, default 8 */
+    float min_separation;      /* centroid distance in units of the model's extent, default 0.5 */
+    float max_angle;           /* radians, [0, pi], default pi (translation only) */
+    float min_score_ratio;     /* [0, 1], default 0.5 */
+    int keep_not_found;        /* keep refined instances with found == 0 */
+    int reserved[4];
+} oslam_instance_params;
+
+typedef struct oslam_instance {
+    float T[16];               /* refined pose when rp != NULL, else = T_vote */
+    float T_vote[16];          /* the candidate's pose from the clustering stage */
+    float score;               /* its clustered score (greedy clustering: cluster votes) */
+    uint32_t candidate;        /* its index in the candidate order above (kept cell, or greedy head) */
+    oslam_refine_result refine;   /* zeros when not refined */
+} oslam_instance;
+
+int oslam_instance_params_default(oslam_instance_params *p);
+/* out[cap], cap >= max_instances */
+int oslam_align_instances(oslam_model *m, oslam_scene *s, const oslam_instance_params *ip,
+                          const oslam_refine_params *rp /* NULL: no refinement */, oslam_instance *out, size_t cap,
+                          size_t *n_out, oslam_stats *stats);
+/* out [n_models][cap], n_out [n_models], stats [n_models] (may be NULL): member j equals oslam_align_instances of
+ * model j alone bit for bit (ms fields aside); a member without votes gets n_out 0 and the call goes on, as in
+ * oslam_db_align.  One frame: the device tails of a group in flight together, then one refinement over every
+ * instance of every member. */
+int oslam_db_align_instances(oslam_db *db, oslam_scene *s, const oslam_instance_params *ip,
+                             const oslam_refine_params *rp, oslam_instance *out, size_t cap, size_t *n_out,
+                             oslam_stats *stats);
+/* The selection on the host, no device: T [n][16] and scores [n] indexed by candidate index (any order of scores);
+ * idx_out[cap] receives the accepted candidate indices in acceptance order. */
+int oslam_select_instances(const float *T, const float *scores, size_t n, const float centroid[3], float extent,
+                           const oslam_instance_params *ip, uint32_t *idx_out, size_t cap, size_t *n_out);
+
 /* ---- parity taps (tests): values the reference materialises as arrays.
  * Scene::getHashKeys row r (scene.cu:49-54): keys_out[n] of reference point r,
  * computed by the GPU key kernel with this d_dist (key 0 on the diagonal). */

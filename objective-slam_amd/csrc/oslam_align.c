@@ -95,7 +95,7 @@ done:
 /* Pose tail on the device over the n records in m->d_out.  Returns OSLAM_OK with *done = 1 when it
  * produced the pose; *done = 0 when fewer than two cells survive (the host path handles those). */
 static int finish_on_device(oslam_model *m, oslam_scene *s, size_t n, uint32_t gmax, float T[16], oslam_stats *st,
-                            int *done)
+                            const oslam_inst_req *req, oslamk_inst_out *sel, int *done)
 {
     int rc = OSLAM_OK, k;
     uint32_t n_kept = 0, best = 0;
@@ -106,8 +106,8 @@ static int finish_on_device(oslam_model *m, oslam_scene *s, size_t n, uint32_t g
     rc = oslam_ensure_pose_buffers(m, n);
     if (rc != OSLAM_OK) return rc;
     k = oslamk_pose_stage(m->d_out, (uint32_t)n, min_votecount, m->d_Tm16, s->d_Ts16, s->df, m->d_weights, oslam_rotx(), m->d_dist,
-                          m->params.use_l1_norm, m->d_pose_cells, m->d_pose_T, gmax, (uint32_t)m->c.n, (uint32_t)s->c.n, m->params.pose_two_sorts, &n_kept,
-                          &best, T, oslam_stream());
+                          m->params.use_l1_norm, m->d_pose_cells, m->d_pose_T, gmax, (uint32_t)m->c.n, (uint32_t)s->c.n, m->params.pose_two_sorts,
+                          req ? &req->a : NULL, &n_kept, &best, T, sel, oslam_stream());
     if (k == -2) return fail(OSLAM_E_NOMEM, "host allocation failed");
     if (k != 0) return fail(OSLAM_E_DEVICE, hipGetErrorString((hipError_t)k));
     if (n_kept < 2) return OSLAM_OK;
@@ -119,10 +119,30 @@ static int finish_on_device(oslam_model *m, oslam_scene *s, size_t n, uint32_t g
     return rc;
 }
 
+/* the instance selection on the host over the candidates of the clustering stage */
+static int select_on_host(const oslam_inst_req *req, const oslam_pose_cands *c, oslamk_inst_out *sel)
+{
+    uint32_t idx[OSLAMK_MAX_INSTANCES];
+    size_t k, n = 0;
+    const int rc = oslam_select_instances(c->T, c->score, c->n, req->a.c, req->extent, req->ip, idx, OSLAMK_MAX_INSTANCES, &n);
+    sel->n = 0;
+    if (rc != OSLAM_OK) return fail(rc, rc == OSLAM_E_NOMEM ? "host allocation failed" : "instance selection failed");
+    for (k = 0; k < n; k++) {
+        sel->idx[k] = c->index[idx[k]];
+        sel->score[k] = c->score[idx[k]];
+        memcpy(sel->T[k], c->T + 16 * (size_t)idx[k], 16 * sizeof(float));
+    }
+    sel->n = (uint32_t)n;
+    return OSLAM_OK;
+}
+
 static int finish_cells(oslam_model *m, oslam_scene *s, oslam_cell *cells, size_t n, uint32_t gmax,
-                        float T[16], oslam_stats *st)
+                        float T[16], oslam_stats *st, const oslam_inst_req *req, oslamk_inst_out *sel)
 {
     int rc;
+    oslam_pose_cands cands;
+    memset(&cands, 0, sizeof cands);
+    if (sel) sel->n = 0;
     n = oslam_filter_cells(cells, n, m->params.vote_count_threshold, gmax);
     oslam_sort_cells(cells, n);
     oslam_drop_last(m);
@@ -134,13 +154,22 @@ static int finish_cells(oslam_model *m, oslam_scene *s, oslam_cell *cells, size_
     m->n_last = n;
     if (st) { st->num_top = n; st->max_count = gmax; }
     oslam_pose_set_cluster_hook(oslam_cluster_scores_on_device);
-    rc = oslam_pose_stage(cells, n, m->c.h_xyz, m->c.h_nrm, (size_t)m->c.n, s->c.h_xyz, s->c.h_nrm,
-                          (size_t)s->c.n, m->d_dist, m->params.cpu_clustering, m->params.use_l1_norm,
-                          m->params.use_averaged_clusters, m->weights, T, m->last_poses);
+    if (req)
+        rc = oslam_pose_stage_cands(cells, n, m->c.h_xyz, m->c.h_nrm, (size_t)m->c.n, s->c.h_xyz, s->c.h_nrm,
+                                    (size_t)s->c.n, m->d_dist, m->params.cpu_clustering, m->params.use_l1_norm,
+                                    m->params.use_averaged_clusters, m->weights, T, m->last_poses, &cands);
+    else
+        rc = oslam_pose_stage(cells, n, m->c.h_xyz, m->c.h_nrm, (size_t)m->c.n, s->c.h_xyz, s->c.h_nrm,
+                              (size_t)s->c.n, m->d_dist, m->params.cpu_clustering, m->params.use_l1_norm,
+                              m->params.use_averaged_clusters, m->weights, T, m->last_poses);
     oslam_pose_set_cluster_hook(NULL);
     if (rc == OSLAM_E_NO_VOTES) return fail(rc, "no scene pair matched the model");
     if (rc != OSLAM_OK) return fail(rc, "pose stage failed");
-    return OSLAM_OK;
+    if (req) {
+        rc = select_on_host(req, &cands, sel);
+        oslam_pose_cands_free(&cands);
+    }
+    return rc;
 }
 
 int oslam_align_prepare(oslam_model *m, oslam_scene *s)
@@ -161,16 +190,17 @@ int oslam_align_prepare(oslam_model *m, oslam_scene *s)
  * the device when the set is large enough, else (or when fewer than two cells survive there) on the host.  try_device
  * 0: the caller ran the device tail already. */
 int oslam_finish_after_votes(oslam_model *m, oslam_scene *s, size_t n, uint32_t gmax, int try_device, float T[16],
-                             oslam_stats *stats)
+                             oslam_stats *stats, const oslam_inst_req *req, oslamk_inst_out *sel)
 {
     int rc = OSLAM_OK;
+    if (sel) sel->n = 0;
     if (try_device && oslam_pose_gpu_from(m) && n >= oslam_pose_gpu_from(m)) {
         int done = 0;
-        rc = finish_on_device(m, s, n, gmax, T, stats, &done);
+        rc = finish_on_device(m, s, n, gmax, T, stats, req, sel, &done);
         if (rc != OSLAM_OK || done) return rc;
     }
     if (n) HIPCHK(hipMemcpy(m->h_out, m->d_out, sizeof(oslam_cell) * n, hipMemcpyDeviceToHost));
-    rc = finish_cells(m, s, m->h_out, n, gmax, T, stats);
+    rc = finish_cells(m, s, m->h_out, n, gmax, T, stats, req, sel);
 done:
     return rc;
 }
@@ -192,7 +222,7 @@ int oslam_align(oslam_model *m, oslam_scene *s, float T[16], oslam_stats *stats)
     rc = oslam_pool_enter(m->dev, &pool);
     if (rc != OSLAM_OK) return rc;
     rc = oslam_vote_records(pool, m, s, &cnt, &n, stats, 0);
-    if (rc == OSLAM_OK) rc = oslam_finish_after_votes(m, s, n, cnt.gmax, 1, T, stats);
+    if (rc == OSLAM_OK) rc = oslam_finish_after_votes(m, s, n, cnt.gmax, 1, T, stats, NULL, NULL);
     oslam_pool_unlock(pool);
     stats->ms_total = (float)(now_ms() - t0);
     return rc;
@@ -286,14 +316,14 @@ int oslam_align_finish(oslam_model *m, oslam_scene *s, const oslam_cell *cells, 
         }
         if (ok) {
             HIPCHK(hipMemcpy(m->d_out, cells, sizeof(oslam_cell) * n, hipMemcpyHostToDevice));
-            rc = finish_on_device(m, s, n, global_max, T, stats, &done);
+            rc = finish_on_device(m, s, n, global_max, T, stats, NULL, NULL, &done);
             if (rc != OSLAM_OK || done) goto done;
         }
     }
     tmp = (oslam_cell *)malloc(sizeof(oslam_cell) * (n ? n : 1));
     if (!tmp) { rc = fail(OSLAM_E_NOMEM, "host allocation failed"); goto done; }
     memcpy(tmp, cells, sizeof(oslam_cell) * n);
-    rc = finish_cells(m, s, tmp, n, global_max, T, stats);
+    rc = finish_cells(m, s, tmp, n, global_max, T, stats, NULL, NULL);
 done:
     free(tmp);
     oslam_pool_unlock(pool);
@@ -458,7 +488,7 @@ int oslam_align_multi(oslam_model *m, oslam_scene *s, oslam_comm *c, float T[16]
     stats->num_emitted = (uint32_t)total;
     /* every rank finishes on the same union: same pose everywhere, no second exchange */
     rc = oslam_pool_enter(m->dev, &pool);
-    if (rc == OSLAM_OK) rc = oslam_finish_after_votes(m, s, total, gmax, 1, T, stats);
+    if (rc == OSLAM_OK) rc = oslam_finish_after_votes(m, s, total, gmax, 1, T, stats, NULL, NULL);
     oslam_pool_unlock(pool);
 done:
     stats->ms_total = (float)(now_ms() - t0);

@@ -167,6 +167,12 @@ done:
 
 int oslam_db_align(oslam_db *db, oslam_scene *s, float *T_out, oslam_stats *stats)
 {
+    return oslam_db_align_frame(db, s, T_out, stats, NULL, NULL);
+}
+
+int oslam_db_align_frame(oslam_db *db, oslam_scene *s, float *T_out, oslam_stats *stats, const oslam_inst_req *reqs,
+                         oslamk_inst_out *sels)
+{
     int rc = OSLAM_OK, g, k, first_err = OSLAM_OK;
     scratch_pool *pool = NULL;
     oslamk_counters *cnt = NULL;
@@ -176,6 +182,8 @@ int oslam_db_align(oslam_db *db, oslam_scene *s, float *T_out, oslam_stats *stat
     if (!db || !s || !T_out) return fail(OSLAM_E_INVALID, "NULL argument");
     memset(T_out, 0, sizeof(float) * 16 * db->n);
     if (stats) memset(stats, 0, sizeof *stats * db->n);
+    if (sels)
+        for (k = 0; k < (int)db->n; k++) sels[k].n = 0;
     for (k = 0; k < (int)db->n; k++) {
         rc = oslam_check_pair(db->models[k], s);
         if (rc != OSLAM_OK) return rc;
@@ -236,7 +244,8 @@ int oslam_db_align(oslam_db *db, oslam_scene *s, float *T_out, oslam_stats *stat
                         kk = oslamk_pose_finish_async(n_sel, ms[k]->d_pose_cells, ms[k]->d_Tm16, s->d_Ts16, s->df, ms[k]->d_weights,
                                                       ms[k]->d_dist, ms[k]->params.use_l1_norm, ms[k]->d_pose_cells,
                                                       ms[k]->d_pose_T, cnt[k].gmax, (uint32_t)ms[k]->c.n, (uint32_t)s->c.n,
-                                                      ms[k]->params.pose_two_sorts, (uint32_t)k, oslam_stream());
+                                                      ms[k]->params.pose_two_sorts, reqs ? &reqs[gr->members[k]].a : NULL,
+                                                      (uint32_t)k, oslam_stream());
                     }
                 if (kk == 0) kk = (int)hipStreamSynchronize((hipStream_t)oslam_stream());
                 if (kk != 0) { rc = fail(OSLAM_E_DEVICE, hipGetErrorString((hipError_t)kk)); break; }
@@ -257,6 +266,7 @@ int oslam_db_align(oslam_db *db, oslam_scene *s, float *T_out, oslam_stats *stat
                 if (on_dev[k]) {                            /* its chain has run: the winner is in its slot */
                     uint32_t best = 0;
                     oslamk_pose_result((uint32_t)k, &best, T);
+                    if (sels) oslamk_pose_instances((uint32_t)k, &sels[gr->members[k]]);
                     oslam_drop_last(m);
                     m->n_last = (size_t)on_dev[k];
                     m->last_on_device = 1;
@@ -265,11 +275,14 @@ int oslam_db_align(oslam_db *db, oslam_scene *s, float *T_out, oslam_stats *stat
                     continue;
                 }
                 /* the device tail has had its chance above */
-                arc = oslam_finish_after_votes(m, s, cnt[k].out_count, cnt[k].gmax, 0, T, st);
+                arc = oslam_finish_after_votes(m, s, cnt[k].out_count, cnt[k].gmax, 0, T, st, reqs ? &reqs[gr->members[k]] : NULL,
+                                               sels ? &sels[gr->members[k]] : NULL);
             } else {
                 /* a group of one -- or a member whose peak records did not fit its buffer: the single-model path */
                 arc = oslam_vote_records(pool, m, s, &cnt[k], &n, st, 0);
-                if (arc == OSLAM_OK) arc = oslam_finish_after_votes(m, s, n, cnt[k].gmax, 1, T, st);
+                if (arc == OSLAM_OK)
+                    arc = oslam_finish_after_votes(m, s, n, cnt[k].gmax, 1, T, st, reqs ? &reqs[gr->members[k]] : NULL,
+                                                   sels ? &sels[gr->members[k]] : NULL);
             }
             if (arc != OSLAM_OK && arc != OSLAM_E_NO_VOTES) rc = arc;
             else if (arc == OSLAM_E_NO_VOTES && first_err == OSLAM_OK) first_err = arc;

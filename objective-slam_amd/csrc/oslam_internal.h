@@ -59,6 +59,9 @@ struct oslam_model {
     /* its key tables are gone (a database was destroyed without giving them back, or rebuilding them failed):
      * the model can only be destroyed */
     int unusable;
+    /* centroid and extent of the instance rule (oslam_instances.c), made on first use */
+    int inst_shape;
+    float inst_c[3], inst_extent;
 };
 
 struct oslam_scene {
@@ -155,13 +158,34 @@ int oslam_cluster_scores_on_device(size_t n, const float *trans, const float *qu
                                    float *score);
 
 /* ---- pose tail (oslam_align.c) ---- */
+/* what an instance call asks of one model's tail (oslam_instances.c): the resolved rule for the device and the
+ * parameters for the host rule; the winners come back in an oslamk_inst_out */
+typedef struct oslam_inst_req {
+    oslamk_inst_args a;
+    const oslam_instance_params *ip;
+    float extent;
+} oslam_inst_req;
 size_t oslam_pose_gpu_from(const oslam_model *m);
 void oslam_drop_last(oslam_model *m);
 int oslam_pose_tables(oslam_model *m, oslam_scene *s);
 int oslam_ensure_pose_buffers(oslam_model *m, size_t n);
 /* the 64 rotations about x of the pose tail, made on first use */
 const float *oslam_rotx(void);
+/* req == NULL: the winner only; otherwise the instance selection too, into *sel */
 int oslam_finish_after_votes(oslam_model *m, oslam_scene *s, size_t n, uint32_t gmax, int try_device, float T[16],
-                             oslam_stats *stats);
+                             oslam_stats *stats, const oslam_inst_req *req, oslamk_inst_out *sel);
+
+/* ---- database frame (oslam_db.c); reqs / sels [db->n] or NULL: with the instance selection of every member ---- */
+int oslam_db_align_frame(oslam_db *db, oslam_scene *s, float *T_out, oslam_stats *stats, const oslam_inst_req *reqs,
+                         oslamk_inst_out *sels);
+
+/* ---- refinement (oslam_refine.c) ---- */
+/* rp NULL = defaults; checks them as oslam_refine does, *out = the parameters in force */
+int oslam_refine_check_params(const oslam_refine_params *rp, oslam_refine_params *out);
+int oslam_refine_check_rigid(const float T[16]);
+/* members ms[0 .. n) with T_in [n][16] (all-zero = skipped) against s, one set of launches; member j's result is
+ * oslam_refine's for it alone */
+int oslam_refine_members(oslam_model *const *ms, size_t n, oslam_scene *s, const float *T_in, const oslam_refine_params *p,
+                         float *T_out, oslam_refine_result *res);
 
 #endif /* OSLAM_INTERNAL_H */

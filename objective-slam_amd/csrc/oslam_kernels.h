@@ -269,10 +269,32 @@ size_t oslamk_cluster_table_words(int n);
 /* pose tail on the device (oslam_posegpu.hip): filter, order, poses, clustering scores, winner.
  * d_Tm16 [M][16] / d_Ts16 [ceil(S/df)][16]: the frames T_g of the model points and of the scene's
  * reference-point candidates (host libm); h_rotx_cs: oslam_rotx_table.  Returns a hipError_t, -2 = no host memory */
+/* The instance selection of oslam_align_instances (include/oslam.h), resolved for one model: at most max_instances
+ * (1..OSLAMK_MAX_INSTANCES) winners; floor = ratio * the first winner's score; two poses are the same instance when
+ * their transformed centroids c lie closer than sqrt(sep2) (d2 < sep2) and, when rot_on, their rotation sum is
+ * >= cos_thr. */
+#define OSLAMK_MAX_INSTANCES 64
+typedef struct oslamk_inst_args {
+    uint32_t max_instances;
+    float ratio, sep2, cos_thr;
+    int32_t rot_on;
+    float c[3];
+} oslamk_inst_args;
+/* what the selection leaves in a slot: n winners, each with its candidate index, score and pose (the pose with the
+ * translation of the clustering stage), in the order they were accepted */
+typedef struct oslamk_inst_out {
+    uint32_t n;
+    uint32_t idx[OSLAMK_MAX_INSTANCES];
+    float score[OSLAMK_MAX_INSTANCES];
+    float T[OSLAMK_MAX_INSTANCES][16];
+} oslamk_inst_out;
+
+/* ia: NULL = the winner only; otherwise the instance selection runs after it and *inst receives its result */
 int oslamk_pose_stage(const oslamk_cell *d_cells_in, uint32_t n_in, float min_votecount, const float *d_Tm16,
                       const float *d_Ts16, uint32_t df, const float *d_weights, const float *h_rotx_cs, float d_dist,
                       int use_l1, oslamk_cell *d_cells_out, float *d_poses, uint32_t gmax, uint32_t model_points,
-                      uint32_t scene_points, int two_sorts, uint32_t *n_out, uint32_t *best_out, float T_best[16], void *stream);
+                      uint32_t scene_points, int two_sorts, const oslamk_inst_args *ia, uint32_t *n_out, uint32_t *best_out,
+                      float T_best[16], oslamk_inst_out *inst, void *stream);
 /* gmax (the largest count among the records), model_points and scene_points bound the fields of a record: with few
  * enough bits the cells are ordered by one sort of packed keys (two_sorts != 0: never) */
 
@@ -285,9 +307,11 @@ int oslamk_pose_select_async(const oslamk_cell *d_in, uint32_t n_in, float min_v
 uint32_t oslamk_pose_selected(uint32_t slot);
 int oslamk_pose_finish_async(uint32_t n, const oslamk_cell *d_sel, const float *d_Tm16, const float *d_Ts16, uint32_t df,
                              const float *d_weights, float d_dist, int use_l1, oslamk_cell *d_cells_out, float *d_poses,
-                             uint32_t gmax, uint32_t model_points, uint32_t scene_points, int two_sorts, uint32_t slot,
-                             void *stream);
+                             uint32_t gmax, uint32_t model_points, uint32_t scene_points, int two_sorts,
+                             const oslamk_inst_args *ia, uint32_t slot, void *stream);
 void oslamk_pose_result(uint32_t slot, uint32_t *best_out, float T_best[16]);
+/* the instance selection of a chain that was given ia (after the wait) */
+void oslamk_pose_instances(uint32_t slot, oslamk_inst_out *out);
 
 /* records with count > min_votecount, compacted into d_out (capacity n_in); *n_out on the host */
 int oslamk_select_cells(const oslamk_cell *d_in, uint32_t n_in, float min_votecount, oslamk_cell *d_out, uint32_t *n_out,

@@ -440,8 +440,66 @@ static size_t grid_find(const grid_slot *g, size_t cap, const int32_t c[3])
     return sl;
 }
 
+/* the pose of a cluster from its summed translations and quaternions (transformation_clustering.cpp:124-137) */
+static void cluster_mean_pose(const float ta_sum[3], const float qa_sum[4], size_t cnt, float *T_out)
+{
+    float ta[3], qa[4], nq, x, y, z, w;
+    int i;
+    for (i = 0; i < 3; i++) ta[i] = ta_sum[i] / (float)cnt;
+    for (i = 0; i < 4; i++) qa[i] = qa_sum[i] / (float)cnt;
+    nq = sqrtf(qa[0] * qa[0] + qa[1] * qa[1] + qa[2] * qa[2] + qa[3] * qa[3]);
+    x = qa[0] / nq; y = qa[1] / nq; z = qa[2] / nq; w = qa[3] / nq;
+    {
+        float tx = 2 * x, ty = 2 * y, tz = 2 * z;
+        float twx = tx * w, twy = ty * w, twz = tz * w;
+        float txx = tx * x, txy = ty * x, txz = tz * x;
+        float tyy = ty * y, tyz = tz * y, tzz = tz * z;
+        T_out[0] = 1 - (tyy + tzz); T_out[1] = txy - twz; T_out[2] = txz + twy; T_out[3] = ta[0];
+        T_out[4] = txy + twz; T_out[5] = 1 - (txx + tzz); T_out[6] = tyz - twx; T_out[7] = ta[1];
+        T_out[8] = txz - twy; T_out[9] = tyz + twx; T_out[10] = 1 - (txx + tyy); T_out[11] = ta[2];
+        T_out[12] = 0; T_out[13] = 0; T_out[14] = 0; T_out[15] = 1;
+    }
+}
+
+/* every cluster of cluster_greedy as an instance candidate (head order): its pose as the winner's is made, its votes */
+static int greedy_candidates(const float *T, const oslam_cell *cells, size_t n, const size_t *member,
+                             const unsigned char *state, const uint32_t *cvotes, oslam_pose_cands *cands)
+{
+    float *sum = (float *)calloc(7 * n, sizeof(float));
+    size_t *cnt = (size_t *)calloc(n, sizeof(size_t)), p, k = 0, nc = 0;
+    int i, j;
+    (void)cells;
+    for (p = 0; p < n; p++) nc += state[p] == 1;
+    cands->T = (float *)malloc(sizeof(float) * 16 * (nc ? nc : 1));
+    cands->score = (float *)malloc(sizeof(float) * (nc ? nc : 1));
+    cands->index = (uint32_t *)malloc(sizeof(uint32_t) * (nc ? nc : 1));
+    if (!sum || !cnt || !cands->T || !cands->score || !cands->index) {
+        free(sum); free(cnt);
+        oslam_pose_cands_free(cands);
+        return OSLAM_E_NOMEM;
+    }
+    for (p = 0; p < n; p++) {                        /* every cluster summed in pose order, as the winner's is */
+        float R[9], q[4], *a = sum + 7 * member[p];
+        for (i = 0; i < 3; i++) for (j = 0; j < 3; j++) R[3 * i + j] = T[16 * p + 4 * i + j];
+        rot_to_quat_xyzw(R, q);
+        a[0] += T[16 * p + 3]; a[1] += T[16 * p + 7]; a[2] += T[16 * p + 11];
+        for (i = 0; i < 4; i++) a[3 + i] += q[i];
+        cnt[member[p]]++;
+    }
+    for (p = 0; p < n; p++) {
+        if (state[p] != 1) continue;
+        cluster_mean_pose(sum + 7 * p, sum + 7 * p + 3, cnt[p], cands->T + 16 * k);
+        cands->score[k] = (float)cvotes[p];
+        cands->index[k] = (uint32_t)p;
+        k++;
+    }
+    cands->n = nc;
+    free(sum); free(cnt);
+    return OSLAM_OK;
+}
+
 static int cluster_greedy(const float *T, const oslam_cell *cells, size_t n, float trans_thresh,
-                          float rot_thresh, float *T_out, uint32_t *votes_out)
+                          float rot_thresh, float *T_out, uint32_t *votes_out, oslam_pose_cands *cands)
 {
     size_t *member = (size_t *)malloc(sizeof(size_t) * n);          /* the head (a pose index) of every pose's cluster */
     uint32_t *cvotes = (uint32_t *)calloc(n, sizeof(uint32_t));       /* votes of the cluster whose head is pose p */
@@ -450,8 +508,8 @@ static int cluster_greedy(const float *T, const oslam_cell *cells, size_t n, flo
     grid_slot *grid;
     size_t cap = 64, p, win = 0, cnt = 0, next = 0;
     const double inv = trans_thresh > 0 ? 1.0 / ((double)trans_thresh * 1.0001) : 0.0;
-    float ta[3] = {0, 0, 0}, qa[4] = {0, 0, 0, 0}, nq, x, y, z, w;
-    int i, j, threads = 1;
+    float ta[3] = {0, 0, 0}, qa[4] = {0, 0, 0, 0};
+    int i, j, threads = 1, rc = OSLAM_OK;
 #ifdef _OPENMP
     if (n >= 2048) threads = g_host_threads ? g_host_threads : (omp_get_max_threads() < 16 ? omp_get_max_threads() : 16);
 #endif
@@ -524,23 +582,11 @@ static int cluster_greedy(const float *T, const oslam_cell *cells, size_t n, flo
         for (i = 0; i < 4; i++) qa[i] += q[i];
         cnt++;
     }
-    for (i = 0; i < 3; i++) ta[i] /= (float)cnt;
-    for (i = 0; i < 4; i++) qa[i] /= (float)cnt;
-    nq = sqrtf(qa[0] * qa[0] + qa[1] * qa[1] + qa[2] * qa[2] + qa[3] * qa[3]);
-    x = qa[0] / nq; y = qa[1] / nq; z = qa[2] / nq; w = qa[3] / nq;
-    {
-        float tx = 2 * x, ty = 2 * y, tz = 2 * z;
-        float twx = tx * w, twy = ty * w, twz = tz * w;
-        float txx = tx * x, txy = ty * x, txz = tz * x;
-        float tyy = ty * y, tyz = tz * y, tzz = tz * z;
-        T_out[0] = 1 - (tyy + tzz); T_out[1] = txy - twz; T_out[2] = txz + twy; T_out[3] = ta[0];
-        T_out[4] = txy + twz; T_out[5] = 1 - (txx + tzz); T_out[6] = tyz - twx; T_out[7] = ta[1];
-        T_out[8] = txz - twy; T_out[9] = tyz + twx; T_out[10] = 1 - (txx + tyy); T_out[11] = ta[2];
-        T_out[12] = 0; T_out[13] = 0; T_out[14] = 0; T_out[15] = 1;
-    }
+    cluster_mean_pose(ta, qa, cnt, T_out);
     if (votes_out) *votes_out = cvotes[win];
+    if (cands) rc = greedy_candidates(T, cells, n, member, state, cvotes, cands);
     free(member); free(cvotes); free(pc); free(nxt); free(state); free(grid);
-    return OSLAM_OK;
+    return rc;
 }
 
 static double pose_now_ms(void)
@@ -563,11 +609,11 @@ int oslam_pose_stage(const oslam_cell *cells, size_t n, const float *m_xyz, cons
  * transformation_trans after the clustering stage, rots_out [n][4] = transformation_rots (w, x, y, z),
  * scores_out [n] = vote_counts_out (clustered scores; with cpu_clustering: scores_out[0] = the votes of the
  * winning cluster), *max_idx_out = max_idx.  Any of them may be NULL. */
-int oslam_pose_stage_ex(const oslam_cell *cells, size_t n, const float *m_xyz, const float *m_nrm,
-                        size_t M, const float *s_xyz, const float *s_nrm, size_t S, float d_dist,
-                        int cpu_clustering, int use_l1_norm, int use_averaged_clusters,
-                        const float *weights, float T_out[16], float *poses_out, float *trans_out, float *rots_out,
-                        float *scores_out, uint32_t *max_idx_out)
+static int pose_stage(const oslam_cell *cells, size_t n, const float *m_xyz, const float *m_nrm,
+                      size_t M, const float *s_xyz, const float *s_nrm, size_t S, float d_dist,
+                      int cpu_clustering, int use_l1_norm, int use_averaged_clusters,
+                      const float *weights, float T_out[16], float *poses_out, float *trans_out, float *rots_out,
+                      float *scores_out, uint32_t *max_idx_out, oslam_pose_cands *cands)
 {
     float *poses;
     size_t i;
@@ -602,7 +648,7 @@ int oslam_pose_stage_ex(const oslam_cell *cells, size_t n, const float *m_xyz, c
     if (max_idx_out) *max_idx_out = 0;
     if (cpu_clustering) {
         uint32_t votes = 0;
-        if (cluster_greedy(poses, cells, n, d_dist, POSE_D, T_out, &votes) != OSLAM_OK) {      /* model.cu:262-263 */
+        if (cluster_greedy(poses, cells, n, d_dist, POSE_D, T_out, &votes, cands) != OSLAM_OK) {      /* model.cu:262-263 */
             free(poses);
             return OSLAM_E_NOMEM;
         }
@@ -610,9 +656,11 @@ int oslam_pose_stage_ex(const oslam_cell *cells, size_t n, const float *m_xyz, c
     } else if (n > 1) {
         float *trans = (float *)malloc(sizeof(float) * 3 * n);
         float *quat = (float *)malloc(sizeof(float) * 4 * n);
+        float *sc = cands && !scores_out ? (float *)malloc(sizeof(float) * n) : scores_out;
         size_t best;
-        if (!trans || !quat) {
+        if (!trans || !quat || (cands && !sc)) {
             free(trans); free(quat); free(poses);
+            if (sc != scores_out) free(sc);
             return OSLAM_E_NOMEM;
         }
         for (i = 0; i < n; i++) {
@@ -621,7 +669,26 @@ int oslam_pose_stage_ex(const oslam_cell *cells, size_t n, const float *m_xyz, c
             trans[3 * i + 2] = poses[16 * i + 11];
             pose_quat(poses + 16 * i, quat + 4 * i);
         }
-        best = cluster_by_cells(cells, n, trans, quat, d_dist, use_l1_norm, use_averaged_clusters, weights, scores_out);
+        best = cluster_by_cells(cells, n, trans, quat, d_dist, use_l1_norm, use_averaged_clusters, weights, sc);
+        if (cands && best != NO_MEMORY) {          /* every kept cell's pose, as the winner's is returned */
+            cands->T = (float *)malloc(sizeof(float) * 16 * n);
+            cands->score = (float *)malloc(sizeof(float) * n);
+            cands->index = (uint32_t *)malloc(sizeof(uint32_t) * n);
+            if (!cands->T || !cands->score || !cands->index) {
+                oslam_pose_cands_free(cands);
+                best = NO_MEMORY;
+            } else {
+                for (i = 0; i < n; i++) {
+                    float *C = cands->T + 16 * i;
+                    memcpy(C, poses + 16 * i, 16 * sizeof(float));
+                    C[3] = trans[3 * i]; C[7] = trans[3 * i + 1]; C[11] = trans[3 * i + 2];
+                    cands->index[i] = (uint32_t)i;
+                }
+                memcpy(cands->score, sc, sizeof(float) * n);
+                cands->n = n;
+            }
+        }
+        if (sc != scores_out) free(sc);
         if (best == NO_MEMORY) {
             free(trans); free(quat); free(poses);
             return OSLAM_E_NOMEM;
@@ -637,5 +704,128 @@ int oslam_pose_stage_ex(const oslam_cell *cells, size_t n, const float *m_xyz, c
     if (trace) fprintf(stderr, "[oslam pose stage] %zu cells: poses %.2f ms, clustering %.2f ms\n", n, t1 - t0, t2 - t1);
     if (poses_out) memcpy(poses_out, poses, 16 * n * sizeof(float));
     free(poses);
+    return OSLAM_OK;
+}
+
+int oslam_pose_stage_ex(const oslam_cell *cells, size_t n, const float *m_xyz, const float *m_nrm,
+                        size_t M, const float *s_xyz, const float *s_nrm, size_t S, float d_dist,
+                        int cpu_clustering, int use_l1_norm, int use_averaged_clusters,
+                        const float *weights, float T_out[16], float *poses_out, float *trans_out, float *rots_out,
+                        float *scores_out, uint32_t *max_idx_out)
+{
+    return pose_stage(cells, n, m_xyz, m_nrm, M, s_xyz, s_nrm, S, d_dist, cpu_clustering, use_l1_norm,
+                      use_averaged_clusters, weights, T_out, poses_out, trans_out, rots_out, scores_out, max_idx_out, NULL);
+}
+
+int oslam_pose_stage_cands(const oslam_cell *cells, size_t n, const float *m_xyz, const float *m_nrm,
+                           size_t M, const float *s_xyz, const float *s_nrm, size_t S, float d_dist,
+                           int cpu_clustering, int use_l1_norm, int use_averaged_clusters,
+                           const float *weights, float T_out[16], float *poses_out, oslam_pose_cands *cands)
+{
+    memset(cands, 0, sizeof *cands);
+    return pose_stage(cells, n, m_xyz, m_nrm, M, s_xyz, s_nrm, S, d_dist, cpu_clustering, use_l1_norm,
+                      use_averaged_clusters, weights, T_out, poses_out, NULL, NULL, NULL, NULL, cands);
+}
+
+void oslam_pose_cands_free(oslam_pose_cands *c)
+{
+    free(c->T); free(c->score); free(c->index);
+    memset(c, 0, sizeof *c);
+}
+
+/* ---- instance selection (include/oslam.h at oslam_align_instances) ---- */
+int oslam_instance_params_default(oslam_instance_params *p)
+{
+    if (!p) return OSLAM_E_INVALID;
+    memset(p, 0, sizeof *p);
+    p->max_instances = 8;
+    p->min_separation = 0.5f;
+    p->max_angle = POSE_PI;
+    p->min_score_ratio = 0.5f;
+    return OSLAM_OK;
+}
+
+int oslam_instance_params_check(const oslam_instance_params *ip, size_t cap)
+{
+    if (!ip) return OSLAM_E_INVALID;
+    if (ip->max_instances == 0 || ip->max_instances > OSLAM_MAX_INSTANCES || cap < ip->max_instances) return OSLAM_E_INVALID;
+    if (!isfinite(ip->min_separation) || ip->min_separation < 0.0f) return OSLAM_E_INVALID;
+    if (!(ip->max_angle >= 0.0f && ip->max_angle <= POSE_PI)) return OSLAM_E_INVALID;
+    if (!(ip->min_score_ratio >= 0.0f && ip->min_score_ratio <= 1.0f)) return OSLAM_E_INVALID;
+    return OSLAM_OK;
+}
+
+void oslam_instance_thresholds(const oslam_instance_params *ip, float extent, float *sep2, float *cos_thr, int *rot_on)
+{
+    const double sep = (double)ip->min_separation * (double)extent;
+    *sep2 = (float)(sep * sep);
+    *cos_thr = (float)(1.0 + 2.0 * cos((double)ip->max_angle));
+    *rot_on = ip->max_angle < POSE_PI;
+}
+
+void oslam_instance_centroid(const float T[16], const float c[3], float p[3])
+{
+    int k;
+    for (k = 0; k < 3; k++) p[k] = ((T[4 * k] * c[0] + T[4 * k + 1] * c[1]) + T[4 * k + 2] * c[2]) + T[4 * k + 3];
+}
+
+int oslam_same_instance(const float pa[3], const float *A, const float pb[3], const float *B, float sep2, float cos_thr,
+                        int rot_on)
+{
+    const float dx = pa[0] - pb[0], dy = pa[1] - pb[1], dz = pa[2] - pb[2];
+    float rs = 0.0f;
+    int i, j;
+    if (!((dx * dx + dy * dy) + dz * dz < sep2)) return 0;
+    if (!rot_on) return 1;
+    for (i = 0; i < 3; i++)
+        for (j = 0; j < 3; j++) rs += A[4 * i + j] * B[4 * i + j];
+    return rs >= cos_thr;
+}
+
+typedef struct { float s; uint32_t i; } score_idx;
+static int score_idx_order(const void *a, const void *b)   /* score descending, index ascending */
+{
+    const score_idx *x = (const score_idx *)a, *y = (const score_idx *)b;
+    if (x->s > y->s) return -1;
+    if (x->s < y->s) return 1;
+    return x->i < y->i ? -1 : x->i > y->i;
+}
+
+int oslam_select_instances(const float *T, const float *scores, size_t n, const float centroid[3], float extent,
+                           const oslam_instance_params *ip, uint32_t *idx_out, size_t cap, size_t *n_out)
+{
+    score_idx *ord;
+    float *p, sep2, cos_thr, floor_v = 0.0f;
+    int rot_on;
+    size_t i, k, acc = 0;
+    if (!centroid || !ip || !idx_out || !n_out || (n && (!T || !scores))) return OSLAM_E_INVALID;
+    if (oslam_instance_params_check(ip, cap) != OSLAM_OK || !isfinite(extent) || extent < 0.0f || n > 0xffffffffu)
+        return OSLAM_E_INVALID;
+    *n_out = 0;
+    if (n == 0) return OSLAM_OK;
+    oslam_instance_thresholds(ip, extent, &sep2, &cos_thr, &rot_on);
+    ord = (score_idx *)malloc(sizeof *ord * n);
+    p = (float *)malloc(sizeof(float) * 3 * n);
+    if (!ord || !p) { free(ord); free(p); return OSLAM_E_NOMEM; }
+    for (i = 0; i < n; i++) {
+        ord[i].s = scores[i];
+        ord[i].i = (uint32_t)i;
+        oslam_instance_centroid(T + 16 * i, centroid, p + 3 * i);
+    }
+    qsort(ord, n, sizeof *ord, score_idx_order);
+    for (i = 0; i < n && acc < ip->max_instances; i++) {
+        const uint32_t c = ord[i].i;
+        int same = 0;
+        if (acc && ord[i].s < floor_v) break;
+        for (k = 0; k < acc && !same; k++)
+            same = oslam_same_instance(p + 3 * c, T + 16 * (size_t)c, p + 3 * (size_t)idx_out[k], T + 16 * (size_t)idx_out[k],
+                                       sep2, cos_thr, rot_on);
+        if (same) continue;
+        if (acc == 0) floor_v = ip->min_score_ratio * ord[i].s;
+        idx_out[acc++] = c;
+    }
+    *n_out = acc;
+    free(ord);
+    free(p);
     return OSLAM_OK;
 }

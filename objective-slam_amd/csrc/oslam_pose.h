@@ -34,6 +34,26 @@ typedef int (*oslam_cluster_hook)(size_t n, const float *trans, const float *qua
                                   float *score);
 void oslam_pose_set_cluster_hook(oslam_cluster_hook hook);
 
+/* instance candidates (include/oslam.h at oslam_align_instances), in candidate order: T [n][16], score [n], index [n]
+ * (kept-cell index, or the head of a greedy cluster) */
+typedef struct oslam_pose_cands {
+    size_t n;
+    float *T, *score;
+    uint32_t *index;
+} oslam_pose_cands;
+/* oslam_pose_stage with the candidates of every pose (allocated here; oslam_pose_cands_free) */
+int oslam_pose_stage_cands(const oslam_cell *cells, size_t n, const float *m_xyz, const float *m_nrm,
+                           size_t M, const float *s_xyz, const float *s_nrm, size_t S, float d_dist,
+                           int cpu_clustering, int use_l1_norm, int use_averaged_clusters,
+                           const float *weights, float T_out[16], float *poses_out, oslam_pose_cands *cands);
+void oslam_pose_cands_free(oslam_pose_cands *c);
+/* the pieces of the selection rule, shared with the device launcher's argument set-up */
+int oslam_instance_params_check(const oslam_instance_params *ip, size_t cap);
+void oslam_instance_thresholds(const oslam_instance_params *ip, float extent, float *sep2, float *cos_thr, int *rot_on);
+void oslam_instance_centroid(const float T[16], const float c[3], float p[3]);
+int oslam_same_instance(const float pa[3], const float *A, const float pb[3], const float *B, float sep2, float cos_thr,
+                        int rot_on);
+
 #ifdef __cplusplus
 }
 #endif

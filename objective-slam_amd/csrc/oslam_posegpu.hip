@@ -9,7 +9,8 @@
  *   order     count descending, code ascending (the host's order)     two stable radix sorts
  *   K5..K8    pose, weighted votes, quaternion, translation cell + key one thread per cell
  *   K9        (cell key, index) radix sort, gather, k_cluster_scores   (oslam_kernels.hip)
- *   argmax    first maximum of the scores (model.cu:292-295)           on the host over n floats
+ *   argmax    first maximum of the scores (model.cu:292-295)           k_pose_best
+ *   instances greedy suppression (oslam_align_instances), on request    k_pose_instances
  *
  * Every float sequence is the host's (oslam_pose_math.h, -ffp-contract=off); the trigonometry is
  * not redone here: the frames T_g (libm on the host, one per point) and the 64 rotations about x
@@ -193,6 +194,130 @@ __global__ __launch_bounds__(1024) void k_pose_best(const float *score, uint32_t
     }
 }
 
+/* The instance selection of oslam_align_instances (include/oslam.h): walk the candidates in (score desc, index asc)
+ * order and accept one that is not the same instance as any accepted before, at most a.max_instances of them, none
+ * below a.ratio * the first one's score.  Done here as rounds in one workgroup: round 0 is k_pose_best's argmax; then
+ * the candidates at or above the floor are compacted (cp = transformed centroid, cs = score, ci = index, sup = a sticky
+ * "suppressed" byte); every later round tests the live candidates against the newest winner only, suppresses the
+ * same-instance ones and picks the next winner among the rest.  A candidate rejected by the walk is one that some
+ * earlier winner suppresses, so the rounds accept what the walk accepts, in the same order.  The float sequences are
+ * oslam_select_instances' (oslam_pose.c, -ffp-contract=off on both sides).  cp/cs/ci/sup live in carves of the pool that
+ * are dead once the clustering scores exist. */
+#define INST_THREADS 1024u
+__device__ __forceinline__ bool inst_better(float ov, uint32_t oi, float v, uint32_t i) { return ov > v || (ov == v && oi < i); }
+
+__device__ __forceinline__ void inst_centroid(const float *T, const float c[3], float p[3])
+{
+    for (int k = 0; k < 3; k++) p[k] = ((T[4 * k] * c[0] + T[4 * k + 1] * c[1]) + T[4 * k + 2] * c[2]) + T[4 * k + 3];
+}
+
+/* the best (score desc, index asc) of the workgroup; every thread gets it */
+__device__ void inst_reduce(float &bv, uint32_t &bi, uint32_t &bk, float *s_v, uint32_t *s_i, uint32_t *s_k)
+{
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(bv, o, 64);
+        const uint32_t oi = __shfl_xor(bi, o, 64), ok = __shfl_xor(bk, o, 64);
+        if (inst_better(ov, oi, bv, bi)) { bv = ov; bi = oi; bk = ok; }
+    }
+    if ((threadIdx.x & 63u) == 0u) { s_v[threadIdx.x >> 6] = bv; s_i[threadIdx.x >> 6] = bi; s_k[threadIdx.x >> 6] = bk; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < (int)(INST_THREADS / 64u); w++)
+            if (inst_better(s_v[w], s_i[w], bv, bi)) { bv = s_v[w]; bi = s_i[w]; bk = s_k[w]; }
+        s_v[0] = bv; s_i[0] = bi; s_k[0] = bk;
+    }
+    __syncthreads();
+    bv = s_v[0]; bi = s_i[0]; bk = s_k[0];
+    __syncthreads();                                 /* s_v is written again by the next reduction */
+}
+
+__global__ __launch_bounds__(1024) void k_pose_instances(const float *score, uint32_t n, const float *poses, const float *trans,
+                                                         oslamk_inst_args a, float *cp, float *cs, uint32_t *ci,
+                                                         unsigned char *sup, oslamk_inst_out *out)
+{
+    __shared__ float s_v[INST_THREADS / 64u];
+    __shared__ uint32_t s_i[INST_THREADS / 64u], s_k[INST_THREADS / 64u];
+    __shared__ float s_w[12];                        /* the newest winner: centroid, then rotation row-major */
+    __shared__ uint32_t s_n;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    float bv = -1.0f;                                /* scores are >= 1 */
+    uint32_t bi = 0xffffffffu, bk = 0xffffffffu, r = 0, nc;
+    auto accept = [&](uint32_t w, float v) {         /* thread 0 */
+        float T[16];
+        for (int k = 0; k < 16; k++) T[k] = poses[16 * (size_t)w + k];
+        T[3] = trans[3 * (size_t)w];
+        T[7] = trans[3 * (size_t)w + 1];
+        T[11] = trans[3 * (size_t)w + 2];
+        out->idx[r] = w;
+        out->score[r] = v;
+        for (int k = 0; k < 16; k++) out->T[r][k] = T[k];
+        inst_centroid(T, a.c, s_w);
+        for (int k = 0; k < 3; k++)
+            for (int j = 0; j < 3; j++) s_w[3 + 3 * k + j] = T[4 * k + j];
+    };
+    if (tid == 0) s_n = 0;
+    for (uint32_t i = tid; i < n; i += INST_THREADS) {
+        const float v = score[i];
+        if (inst_better(v, i, bv, bi)) { bv = v; bi = i; }
+    }
+    inst_reduce(bv, bi, bk, s_v, s_i, s_k);
+    if (tid == 0) accept(bi, bv);
+    r = 1;
+    if (a.max_instances > 1) {
+        const float floor_v = a.ratio * bv;
+        const uint32_t w0 = bi;
+        for (uint32_t base = 0; base < n; base += INST_THREADS) {
+            const uint32_t i = base + tid;
+            const bool keep = i < n && i != w0 && !(score[i] < floor_v);
+            const unsigned long long mask = __ballot(keep);
+            uint32_t off = 0;
+            if (lane == 0 && mask) off = atomicAdd(&s_n, (uint32_t)__popcll(mask));
+            off = __shfl(off, 0, 64);
+            if (keep) {
+                const uint32_t k = off + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
+                float T[16], p[3];
+                for (int q = 0; q < 12; q++) T[q] = poses[16 * (size_t)i + q];
+                T[3] = trans[3 * (size_t)i];
+                T[7] = trans[3 * (size_t)i + 1];
+                T[11] = trans[3 * (size_t)i + 2];
+                inst_centroid(T, a.c, p);
+                for (int q = 0; q < 3; q++) cp[3 * (size_t)k + q] = p[q];
+                cs[k] = score[i];
+                ci[k] = i;
+                sup[k] = 0;
+            }
+        }
+        __syncthreads();
+        nc = s_n;
+        for (; r < a.max_instances; r++) {
+            bv = -1.0f;
+            bi = bk = 0xffffffffu;
+            for (uint32_t k = tid; k < nc; k += INST_THREADS) {
+                if (sup[k]) continue;
+                const float dx = cp[3 * (size_t)k] - s_w[0], dy = cp[3 * (size_t)k + 1] - s_w[1], dz = cp[3 * (size_t)k + 2] - s_w[2];
+                bool same = (dx * dx + dy * dy) + dz * dz < a.sep2;
+                if (same && a.rot_on) {
+                    const float *P = poses + 16 * (size_t)ci[k];
+                    float rs = 0.0f;
+                    for (int q = 0; q < 3; q++)
+                        for (int j = 0; j < 3; j++) rs += P[4 * q + j] * s_w[3 + 3 * q + j];
+                    same = rs >= a.cos_thr;
+                }
+                if (same) { sup[k] = 1; continue; }
+                if (inst_better(cs[k], ci[k], bv, bi)) { bv = cs[k]; bi = ci[k]; bk = k; }
+            }
+            inst_reduce(bv, bi, bk, s_v, s_i, s_k);
+            if (bi == 0xffffffffu) break;            /* the same for every thread: it came through LDS */
+            if (tid == 0) {
+                sup[bk] = 1;
+                accept(bi, bv);
+            }
+            __syncthreads();
+        }
+    }
+    if (tid == 0) out->n = r;
+}
+
 #define PCHK(call)                   \
     do {                             \
         hipError_t e_ = (call);      \
@@ -218,6 +343,7 @@ struct pose_pool {
     uint32_t slots;
     float *h_pin;              /* pinned [slots][POSE_SLOT_WORDS]: word 0 the count, words 1.. the winner's record */
     float *d_small;            /* [0..127] the rotation table, then [slots][POSE_SLOT_WORDS] */
+    oslamk_inst_out *h_inst, *d_inst;   /* [slots]: the instance selection of each slot's chain (pinned / device) */
     int rot_loaded;
 };
 static pose_pool g_pool[64];
@@ -285,12 +411,17 @@ extern "C" int oslamk_pose_reserve(uint32_t n_max, uint32_t slots, const float *
         const uint32_t want = slots < 64 ? 64 : slots + slots / 2;
         if (p->h_pin) (void)hipHostFree(p->h_pin);
         if (p->d_small) (void)hipFree(p->d_small);
+        if (p->h_inst) (void)hipHostFree(p->h_inst);
+        if (p->d_inst) (void)hipFree(p->d_inst);
         p->h_pin = NULL;
         p->d_small = NULL;
+        p->h_inst = p->d_inst = NULL;
         p->slots = 0;
         p->rot_loaded = 0;
         PCHK(hipHostMalloc((void **)&p->h_pin, sizeof(float) * POSE_SLOT_WORDS * want, hipHostMallocDefault));
         PCHK(hipMalloc((void **)&p->d_small, sizeof(float) * (128 + (size_t)POSE_SLOT_WORDS * want)));
+        PCHK(hipHostMalloc((void **)&p->h_inst, sizeof(oslamk_inst_out) * want, hipHostMallocDefault));
+        PCHK(hipMalloc((void **)&p->d_inst, sizeof(oslamk_inst_out) * want));
         p->slots = want;
     }
     if (p->cap < c.total) {
@@ -364,13 +495,15 @@ static uint32_t bits_for(uint64_t max_value)
 extern "C" int oslamk_pose_finish_async(uint32_t n, const oslamk_cell *d_sel, const float *d_Tm16, const float *d_Ts16,
                                         uint32_t df, const float *d_weights, float d_dist, int use_l1,
                                         oslamk_cell *d_cells_out, float *d_poses, uint32_t gmax, uint32_t model_points,
-                                        uint32_t scene_points, int two_sorts, uint32_t slot, void *stream_)
+                                        uint32_t scene_points, int two_sorts, const oslamk_inst_args *ia, uint32_t slot,
+                                        void *stream_)
 {
     hipStream_t stream = (hipStream_t)stream_;
     pose_pool *p = cur_pool();
     int rc = 0;
     pose_carve c;
     if (!p || slot >= p->slots || n < 2) return (int)hipErrorInvalidValue;
+    if (ia && (ia->max_instances == 0 || ia->max_instances > OSLAMK_MAX_INSTANCES)) return (int)hipErrorInvalidValue;
     carve_for(n, &c);
     if (c.total > p->cap) return (int)hipErrorInvalidValue;        /* oslamk_pose_reserve was given less */
     {
@@ -415,6 +548,13 @@ extern "C" int oslamk_pose_finish_async(uint32_t n, const oslamk_cell *d_sel, co
         hipLaunchKernelGGL(k_pose_best, dim3(bb), dim3(1024), 0, stream, score, n, d_poses, trans, d_best,
                            (float *)(d + c.part), (uint32_t *)(d + c.part + 4 * BEST_BLOCKS), whole + 2);
         PCHK(hipMemcpyAsync(p->h_pin + (size_t)POSE_SLOT_WORDS * slot + 1, d_best, 17 * sizeof(float), hipMemcpyDeviceToHost, stream));
+        if (ia) {
+            /* before the next chain on the stream reuses the carves: sq (16 B per record) holds the centroids, sw the
+             * scores, sidx the indices, hash the suppression bytes */
+            hipLaunchKernelGGL(k_pose_instances, dim3(1), dim3(INST_THREADS), 0, stream, score, n, d_poses, trans, *ia,
+                               sq, sw, sidx, (unsigned char *)hash, p->d_inst + slot);
+            PCHK(hipMemcpyAsync(p->h_inst + slot, p->d_inst + slot, sizeof(oslamk_inst_out), hipMemcpyDeviceToHost, stream));
+        }
         PCHK(hipGetLastError());
     }
 done:
@@ -427,6 +567,14 @@ extern "C" void oslamk_pose_result(uint32_t slot, uint32_t *best_out, float T_be
     if (!p || slot >= p->slots) return;
     memcpy(best_out, p->h_pin + (size_t)POSE_SLOT_WORDS * slot + 1, sizeof(uint32_t));
     memcpy(T_best, p->h_pin + (size_t)POSE_SLOT_WORDS * slot + 2, 16 * sizeof(float));
+}
+
+extern "C" void oslamk_pose_instances(uint32_t slot, oslamk_inst_out *out)
+{
+    pose_pool *p = cur_pool();
+    out->n = 0;
+    if (!p || slot >= p->slots) return;
+    memcpy(out, p->h_inst + slot, sizeof *out);
 }
 
 /* the records with count > min_votecount, compacted in their order into d_out (device, capacity n_in) */
@@ -455,6 +603,8 @@ extern "C" void oslamk_pose_release(void)
     if (p->tmp) (void)hipFree(p->tmp);
     if (p->h_pin) (void)hipHostFree(p->h_pin);
     if (p->d_small) (void)hipFree(p->d_small);
+    if (p->h_inst) (void)hipHostFree(p->h_inst);
+    if (p->d_inst) (void)hipFree(p->d_inst);
     memset(p, 0, sizeof *p);
 }
 
@@ -465,14 +615,15 @@ extern "C" void oslamk_pose_release(void)
 extern "C" int oslamk_pose_stage(const oslamk_cell *d_cells_in, uint32_t n_in, float min_votecount, const float *d_Tm16,
                                  const float *d_Ts16, uint32_t df, const float *d_weights, const float *h_rotx_cs,
                                  float d_dist, int use_l1, oslamk_cell *d_cells_out, float *d_poses, uint32_t gmax,
-                                 uint32_t model_points, uint32_t scene_points, int two_sorts, uint32_t *n_out,
-                                 uint32_t *best_out, float T_best[16], void *stream_)
+                                 uint32_t model_points, uint32_t scene_points, int two_sorts, const oslamk_inst_args *ia,
+                                 uint32_t *n_out, uint32_t *best_out, float T_best[16], oslamk_inst_out *inst, void *stream_)
 {
     hipStream_t stream = (hipStream_t)stream_;
     int rc = 0;
     uint32_t n;
     *n_out = 0;
     *best_out = 0;
+    if (inst) inst->n = 0;
     if (n_in == 0) return 0;
     rc = oslamk_pose_reserve(n_in, 1, h_rotx_cs, stream_);
     if (rc != 0) return rc;
@@ -483,10 +634,11 @@ extern "C" int oslamk_pose_stage(const oslamk_cell *d_cells_in, uint32_t n_in, f
     *n_out = n;
     if (n < 2) return 0;                               /* the caller's host path handles 0 and 1 cells */
     rc = oslamk_pose_finish_async(n, d_cells_out, d_Tm16, d_Ts16, df, d_weights, d_dist, use_l1, d_cells_out, d_poses, gmax,
-                                  model_points, scene_points, two_sorts, 0, stream_);
+                                  model_points, scene_points, two_sorts, ia, 0, stream_);
     if (rc != 0) return rc;
     PCHK(hipStreamSynchronize(stream));
     oslamk_pose_result(0, best_out, T_best);
+    if (ia && inst) oslamk_pose_instances(0, inst);
 done:
     return rc;
 }

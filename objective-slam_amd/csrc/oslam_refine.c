@@ -40,7 +40,7 @@ int oslam_refine_params_default(oslam_refine_params *p)
     return OSLAM_OK;
 }
 
-static int check_params(const oslam_refine_params *rp, oslam_refine_params *out)
+int oslam_refine_check_params(const oslam_refine_params *rp, oslam_refine_params *out)
 {
     if (rp) *out = *rp;
     else oslam_refine_params_default(out);
@@ -64,7 +64,7 @@ static int is_zero_pose(const float T[16])
 }
 
 /* finite, rotation orthonormal to 1e-3 with determinant > 0, last row 0 0 0 1 */
-static int check_rigid(const float T[16])
+int oslam_refine_check_rigid(const float T[16])
 {
     int a, b, k;
     double det;
@@ -213,8 +213,8 @@ static void centroid(const oslam_model *m, double cm[3])
 }
 
 /* The members ms[0 .. n) (T_in[j*16], all-zero = skipped) against scene s: the whole stage. */
-static int refine_members(oslam_model *const *ms, size_t n, oslam_scene *s, const float *T_in, const oslam_refine_params *p,
-                          float *T_out, oslam_refine_result *res)
+int oslam_refine_members(oslam_model *const *ms, size_t n, oslam_scene *s, const float *T_in, const oslam_refine_params *p,
+                         float *T_out, oslam_refine_result *res)
 {
     int rc = OSLAM_OK, built = 0;
     const double t0 = now_ms();
@@ -355,11 +355,11 @@ int oslam_refine(oslam_model *m, oslam_scene *s, const float T_in[16], const osl
     oslam_refine_params p;
     int rc;
     if (!m || !s || !T_in || !T_out) return oslam_fail(OSLAM_E_INVALID, "NULL argument");
-    rc = check_params(rp, &p);
-    if (rc == OSLAM_OK) rc = check_rigid(T_in);
+    rc = oslam_refine_check_params(rp, &p);
+    if (rc == OSLAM_OK) rc = oslam_refine_check_rigid(T_in);
     if (rc == OSLAM_OK) rc = check_model(m, s);
     if (rc != OSLAM_OK) return rc;
-    return refine_members(&m, 1, s, T_in, &p, T_out, res);
+    return oslam_refine_members(&m, 1, s, T_in, &p, T_out, res);
 }
 
 int oslam_db_refine(oslam_db *db, oslam_scene *s, const float *T_in, const oslam_refine_params *rp, float *T_out,
@@ -369,15 +369,15 @@ int oslam_db_refine(oslam_db *db, oslam_scene *s, const float *T_in, const oslam
     size_t j;
     int rc;
     if (!db || !s || !T_in || !T_out) return oslam_fail(OSLAM_E_INVALID, "NULL argument");
-    rc = check_params(rp, &p);
+    rc = oslam_refine_check_params(rp, &p);
     if (rc != OSLAM_OK) return rc;
     for (j = 0; j < db->n; j++) {
         if (is_zero_pose(T_in + 16 * j)) continue;
-        rc = check_rigid(T_in + 16 * j);
+        rc = oslam_refine_check_rigid(T_in + 16 * j);
         if (rc == OSLAM_OK) rc = check_model(db->models[j], s);
         if (rc != OSLAM_OK) return rc;
     }
-    return refine_members(db->models, db->n, s, T_in, &p, T_out, res);
+    return oslam_refine_members(db->models, db->n, s, T_in, &p, T_out, res);
 }
 
 int oslam_refine_correspondences(oslam_model *m, oslam_scene *s, const float T[16], float radius, float min_normal_dot,
@@ -391,7 +391,7 @@ int oslam_refine_correspondences(oslam_model *m, oslam_scene *s, const float T[1
     size_t M, off_idx;
     if (!m || !s || !T || !idx_out) return oslam_fail(OSLAM_E_INVALID, "NULL argument");
     if (!(radius > 0.0f) || !isfinite(radius) || !isfinite(min_normal_dot)) return oslam_fail(OSLAM_E_INVALID, "bad radius or normal gate");
-    rc = check_rigid(T);
+    rc = oslam_refine_check_rigid(T);
     if (rc == OSLAM_OK) rc = check_model(m, s);
     if (rc != OSLAM_OK) return rc;
     if (hipSetDevice(s->dev) != hipSuccess) return oslam_fail(OSLAM_E_DEVICE, "hipSetDevice failed");

@@ -58,6 +58,29 @@ def match_within_threshold(rows, diameters, dist_thresh_factor=DIST_THRESH_FACTO
         r.append([r[3][0] <= dist_thresh_factor * diameters[r[1]], dr <= rot_thresh])
 
 
+def match_instances(found, truths, extent, dist_thresh_factor=DIST_THRESH_FACTOR, rot_thresh=TWELVEDEG):
+    """Detections against ground-truth poses, each truth matched to at most one detection and each detection to at
+    most one truth: truth i (in order) takes the first still free detection (in order) with |dt| <= dist_thresh_factor *
+    extent and rotation angle <= rot_thresh (ht_dist; the criterion of match_within_threshold, with `extent` the
+    model diameter).  found: detections as 4x4 poses or (T, info) pairs (Model.find_instances).
+    -> (matched: per truth the index of its detection or None, unmatched: indices of detections matched to no truth)"""
+    dets = [f[0] if isinstance(f, tuple) else f for f in found]
+    free = list(range(len(dets)))
+    matched = []
+    for G in truths:
+        hit = None
+        for k in free:
+            dt, dr = ppf.ht_dist(np.asarray(dets[k], np.float32), np.asarray(G, np.float32))
+            dr = dr if dr <= np.pi else 2 * np.pi - dr
+            if dt <= dist_thresh_factor * extent and dr <= rot_thresh:
+                hit = k
+                break
+        if hit is not None:
+            free.remove(hit)
+        matched.append(hit)
+    return matched, free
+
+
 def percent_match_below(rows):
     """Rows sorted by occlusion -> cumulative share of matches (analyze_mian.py:66-74)."""
     m = [1 if all(r[4]) else 0 for r in rows]

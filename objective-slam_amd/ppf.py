@@ -66,6 +66,23 @@ class RefineResult(C.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class InstanceParams(C.Structure):
+    _fields_ = [("max_instances", C.c_uint), ("min_separation", C.c_float), ("max_angle", C.c_float),
+                ("min_score_ratio", C.c_float), ("keep_not_found", C.c_int), ("reserved", C.c_int * 4)]
+
+
+class Instance(C.Structure):
+    _fields_ = [("T", C.c_float * 16), ("T_vote", C.c_float * 16), ("score", C.c_float), ("candidate", C.c_uint32),
+                ("refine", RefineResult)]
+
+    def astuple(self):
+        """-> (T 4x4, info dict: T_vote 4x4, score, candidate, refine dict)"""
+        T = np.array(self.T, np.float32).reshape(4, 4)
+        return T, {"T_vote": np.array(self.T_vote, np.float32).reshape(4, 4), "score": float(self.score),
+                   "candidate": int(self.candidate), "refine": self.refine.asdict()}
+
+
+MAX_INSTANCES = 64
 CELL_DTYPE = np.dtype([("code", "<u8"), ("count", "<u4"), ("pad", "<u4")])
 
 # every function include/oslam.h declares: (name, restype, argtypes)
@@ -119,6 +136,11 @@ _SIGNATURES = {
     "oslam_refine": (_i, [_vp, _vp, _vp, C.POINTER(RefineParams), _vp, C.POINTER(RefineResult)]),
     "oslam_db_refine": (_i, [_vp, _vp, _vp, C.POINTER(RefineParams), _vp, _vp]),
     "oslam_refine_correspondences": (_i, [_vp, _vp, _vp, _f, _f, _vp]),
+    "oslam_instance_params_default": (_i, [C.POINTER(InstanceParams)]),
+    "oslam_align_instances": (_i, [_vp, _vp, C.POINTER(InstanceParams), C.POINTER(RefineParams), _vp, _sz, C.POINTER(_sz),
+                                   _vp]),
+    "oslam_db_align_instances": (_i, [_vp, _vp, C.POINTER(InstanceParams), C.POINTER(RefineParams), _vp, _sz, _vp, _vp]),
+    "oslam_select_instances": (_i, [_vp, _vp, _sz, _vp, _f, C.POINTER(InstanceParams), _vp, _sz, C.POINTER(_sz)]),
     "oslam_scene_keys": (_i, [_vp, _sz, _vp]),
     "oslam_model_keys": (_i, [_vp, _sz, _vp]),
     "oslam_model_bucket": (_i, [_vp, C.c_uint32, _vp, _sz, C.POINTER(_sz)]),
@@ -181,6 +203,44 @@ def default_refine_params(**kw):
             raise TypeError("unknown refine parameter %r" % k)
         setattr(p, k, v)
     return p
+
+
+def default_instance_params(**kw):
+    """oslam_instance_params_default, then the fields given as keywords."""
+    p = InstanceParams()
+    _check(lib().oslam_instance_params_default(C.byref(p)))
+    for k, v in kw.items():
+        if not hasattr(p, k) or k == "reserved":
+            raise TypeError("unknown instance parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def _instance_args(refine, params, refine_params):
+    ip = params if params is not None else default_instance_params()
+    rp = None
+    if refine:
+        rp = refine_params if refine_params is not None else default_refine_params()
+    return ip, rp
+
+
+def select_instances(T, scores, centroid, extent, params=None, cap=None):
+    """The host selection rule alone (oslam_select_instances, no GPU): T [n,4,4] and scores [n] indexed by candidate;
+    -> accepted candidate indices in acceptance order (uint32 array).  Raises OslamError on invalid arguments."""
+    ip = params if params is not None else default_instance_params()
+    Ta = np.ascontiguousarray(np.asarray(T, np.float32).reshape(-1, 16))
+    sc = np.ascontiguousarray(scores, np.float32).reshape(-1)
+    if len(sc) != len(Ta):
+        raise ValueError("T and scores differ in length")
+    c = np.ascontiguousarray(centroid, np.float32).reshape(3)
+    cap = int(ip.max_instances) if cap is None else int(cap)
+    idx = np.zeros(max(cap, 1), np.uint32)
+    n = C.c_size_t(0)
+    rc = lib().oslam_select_instances(_p(Ta) if len(Ta) else None, _p(sc) if len(sc) else None, len(sc), _p(c),
+                                      float(extent), C.byref(ip), _p(idx), cap, C.byref(n))
+    if rc != OSLAM_OK:
+        raise OslamError(rc, "instance selection rejected its arguments" if rc == OSLAM_E_INVALID else "instance selection failed")
+    return idx[: n.value].copy()
 
 
 def _pose16(T):
@@ -349,6 +409,22 @@ class Model:
         _check(lib().oslam_refine(self._h, scene._h, _p(Ti), C.byref(p), _p(To), C.byref(r)))
         return To.reshape(4, 4), r.asdict()
 
+    def find_instances(self, scene, refine=True, params=None, refine_params=None):
+        """Every instance of the model in the scene (oslam_align_instances): -> list of (T 4x4, info dict) in
+        acceptance order; info: T_vote, score, candidate, refine (zeros without refinement).  Instance 0's T_vote is
+        the pose ppf_lookup returns; an empty list when nothing matched."""
+        ip, rp = _instance_args(refine, params, refine_params)
+        cap = int(ip.max_instances)
+        out = (Instance * max(cap, 1))()
+        n = C.c_size_t(0)
+        st = Stats()
+        rc = lib().oslam_align_instances(self._h, scene._h, C.byref(ip), C.byref(rp) if rp is not None else None, out,
+                                         cap, C.byref(n), C.byref(st))
+        if rc != OSLAM_E_NO_VOTES:
+            _check(rc)
+        self.stats = st.asdict()
+        return [out[k].astuple() for k in range(n.value)]
+
     def align_local(self, scene, cap=None):
         """This rank's votes.  cap=None: returns (number of peaks above the LOCAL threshold, local maximum) and
         leaves the records with the model for local_peaks(); with a cap: (records, local maximum), and
@@ -497,6 +573,21 @@ class Database:
         _check(lib().oslam_db_refine(self._h, scene._h, _p(Ti), C.byref(p), _p(To), res))
         out = [r.asdict() for r in res]
         return To, out, np.array([bool(r["found"]) for r in out])
+
+    def find_instances(self, scene, refine=True, params=None, refine_params=None):
+        """Every instance of every member in one frame (oslam_db_align_instances): -> one list per member, as
+        Model.find_instances returns it."""
+        ip, rp = _instance_args(refine, params, refine_params)
+        n = len(self.models)
+        cap = int(ip.max_instances)
+        out = (Instance * max(n * cap, 1))()
+        n_out = np.zeros(max(n, 1), np.uintp)
+        st = (Stats * max(n, 1))()
+        _check(lib().oslam_db_align_instances(self._h, scene._h, C.byref(ip), C.byref(rp) if rp is not None else None,
+                                              out, cap, _p(n_out), st))
+        for m, d in zip(self.models, st):
+            m.stats = d.asdict()
+        return [[out[j * cap + k].astuple() for k in range(int(n_out[j]))] for j in range(n)]
 
     def align_multi(self, scene, comm, n_total):
         """This rank's models (j = rank, rank + world, ... of n_total) against the whole scene, then every pose to
