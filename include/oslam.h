@@ -396,6 +396,84 @@ int oslam_db_refine(oslam_db *db, oslam_scene *s, const float *T_in /* [n][16] *
 int oslam_refine_correspondences(oslam_model *m, oslam_scene *s, const float T[16], float radius,
                                  float min_normal_dot, int32_t *idx_out);
 
+/* ---- verification against a depth image: visibility-aware presence (after oslam_refine; Drost-style pipelines
+ * re-score their hypotheses view by view after ICP).  A depth frame shows one side of an object, so the share of all
+ * model points near the scene cloud (oslam_refine's fitness) cannot tell a present object from an absent one that
+ * fits a part of it.  The image can: a model point that faces the camera should appear at its pixel's depth, and a
+ * pixel that lies farther than the point contradicts the pose (the camera saw through the object).
+ *
+ * A view holds the depth image on the device as float z.  It shares the camera frame of oslam_depth_to_cloud (the
+ * camera at the origin looking along +z, so the clouds of oslam_scene_from_depth are in the same coordinates), with
+ * the same conventions: z = raw * depth_scale in float, valid in [z_min, z_max]; max_jump is not used.  A view is
+ * independent of any scene: a point-cloud scene with a known sensor can be verified as well.
+ *
+ * Rule.  Model point i is (p, n); T is a float32 row-major model -> scene (camera) pose.  p' and n' are computed
+ * exactly as oslam_refine does: p'x = ((R00*px + R01*py) + R02*pz) + t0, likewise y and z; n' the same without t.
+ * tol = (float)((double)depth_tol * d_dist) with the model's d_dist.  Each point gets exactly one class, tested in
+ * this order:
+ *   0 BACK       (n'x*p'x + n'y*p'y) + n'z*p'z >= 0 (the surface faces away from the camera)
+ *   1 OUT        p'z outside [z_min, z_max], or the pixel fu = floorf(((p'x*fx)/p'z + cx) + 0.5f), fv likewise with
+ *                fy and cy, outside the image (0 <= fu < width, 0 <= fv < height, tested in float)
+ *   2 SUPPORTED  some valid pixel z_o of the (2 window + 1)^2 pixels around (fu, fv), clipped to the image, has
+ *                fabsf(z_o - p'z) <= tol
+ *   3 OCCLUDED   otherwise some valid pixel of the window has z_o < p'z - tol (something nearer covers the point)
+ *   4 CONFLICT   otherwise some valid pixel of the window exists (all lie farther: the camera saw through the object)
+ *   5 UNKNOWN    no valid pixel in the window
+ * Scores (float32 divisions of the counts converted to float; 0 when the denominator is 0):
+ *   view_fitness = supported / (supported + conflict)   is what the camera saw consistent with the object?
+ *   coverage = supported / (supported + occluded + conflict)   does the visible evidence cover it?  (A small absent
+ *     model placed inside a present object has its facing points on the observed surface or behind it: a high
+ *     view_fitness, a low coverage.)
+ *   found = supported >= min_supported && view_fitness >= min_view_fitness && coverage >= min_coverage.
+ * Arguments are checked before any handle is read or any device call is made: NULL pointers, parameters that are
+ * not finite, depth_tol <= 0, window > 3, ratios outside [0, 1] and a T that is not rigid (the test of oslam_refine)
+ * are OSLAM_E_INVALID; so are a model and a view on different devices.
+ * Cost: building a view uploads the image and runs one kernel (k_view_z).  A call enqueues one memset, one kernel
+ * (k_verify: every member in one grid) and one copy back, with one host wait: launches == 1 for 1 member and for 100.
+ * Integer counters only: the results are deterministic. */
+typedef struct oslam_view oslam_view;
+int oslam_view_create(const void *depth, int depth_is_u16, int width, int height, const oslam_camera *cam, int dev,
+                      oslam_view **out);
+int oslam_view_destroy(oslam_view *v);
+
+#define OSLAM_VERIFY_BACK 0
+#define OSLAM_VERIFY_OUT 1
+#define OSLAM_VERIFY_SUPPORTED 2
+#define OSLAM_VERIFY_OCCLUDED 3
+#define OSLAM_VERIFY_CONFLICT 4
+#define OSLAM_VERIFY_UNKNOWN 5
+
+typedef struct oslam_verify_params {
+    float depth_tol;           /* in units of the model's d_dist, default 1.0 */
+    unsigned window;           /* half-width of the pixel window, 0..3, default 1 */
+    float min_view_fitness;    /* default 0.92 } calibrated on the CPU on seeded depth frames with a 10-model database */
+    float min_coverage;        /* default 0.5  } (tests/test_verify_host.py): present >= 0.935 / 0.509, absent <= 0.899 */
+    unsigned min_supported;    /* default 50   } / 0.495; supported does not separate (present >= 116, absent up to 144):
+                                *                it is a floor against a handful of chance agreements */
+    int reserved[4];
+} oslam_verify_params;
+
+typedef struct oslam_verify_result {
+    uint32_t back, out, supported, occluded, conflict, unknown;   /* they sum to the model's points */
+    float view_fitness, coverage;
+    int32_t found;
+    uint32_t launches;         /* kernels this call enqueued (the whole call, shared by all members) */
+    float ms_total;            /* whole call, host clock */
+} oslam_verify_result;
+
+int oslam_verify_params_default(oslam_verify_params *p);
+/* vp may be NULL (defaults). */
+int oslam_verify(oslam_model *m, const oslam_view *v, const float T[16], const oslam_verify_params *vp,
+                 oslam_verify_result *res);
+/* Every member in one set of launches: T [n][16] in oslam_db_create order, res [n].  A member whose T is all zeros is
+ * skipped (zeros, found 0) and the call still returns OSLAM_OK.  Member j equals oslam_verify of model j bit for bit
+ * (launches and ms_total aside). */
+int oslam_db_verify(oslam_db *db, const oslam_view *v, const float *T, const oslam_verify_params *vp,
+                    oslam_verify_result *res);
+/* test tap: class_out[M] = the class of each model point (OSLAM_VERIFY_BACK .. OSLAM_VERIFY_UNKNOWN) */
+int oslam_verify_classes(oslam_model *m, const oslam_view *v, const float T[16], const oslam_verify_params *vp,
+                         uint8_t *class_out);
+
 /* ---- every instance of a model in a scene (after the votes; the reference keeps only the best pose,
  * model.cu:292-295 / ppf.cu:74-93).  Single device only: oslam_align_multi / oslam_db_align_multi have no instance form.
  *

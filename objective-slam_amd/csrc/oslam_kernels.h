@@ -378,6 +378,33 @@ int oslamk_refine_corr(int mode, const oslamk_grid *g, const oslamk_refine_membe
 int oslamk_refine_solve(oslamk_refine_member *d_mem, uint32_t n_mem, uint32_t max_blocks, const float *slab,
                         uint32_t *n_done, void *stream);
 
+/* ---- verification stage (oslam_verify.hip; semantics in include/oslam.h at oslam_verify) ---- */
+#define OSLAMK_VERIFY_THREADS 256    /* model points per workgroup of k_verify */
+#define OSLAMK_VERIFY_CLASSES 6
+
+/* the camera of a view and its z image: w * h floats, z of a valid pixel (> 0 since z_min > 0), 0 = invalid */
+typedef struct oslamk_view {
+    const float *z;
+    int w, h;
+    float fx, fy, cx, cy, z_min, z_max;
+} oslamk_view;
+
+/* one member of a verification call */
+typedef struct oslamk_verify_member {
+    oslamk_cloud m;            /* the model's points and normals (SoA in HBM, the cloud oslam_refine reads) */
+    float T[12];               /* rows of [R | t], float32 */
+    float tol;                 /* (float)((double)depth_tol * d_dist) */
+    uint32_t n_blocks;         /* ceil(m.n / OSLAMK_VERIFY_THREADS); 0 = skipped */
+} oslamk_verify_member;
+
+/* d_raw: the image in HBM (uint16 or float, w x h row-major) -> d_z (float, w x h) */
+int oslamk_view_z(const void *d_raw, int is_u16, int w, int h, float scale, float z_min, float z_max, float *d_z,
+                  void *stream);
+/* counts (class_out NULL): counts[j * OSLAMK_VERIFY_CLASSES + c] += points of member j in class c (zeroed by the
+ * caller); tap (class_out != NULL): class_out[i] = the class of member 0's point i */
+int oslamk_verify(const oslamk_view *v, const oslamk_verify_member *d_mem, uint32_t n_mem, uint32_t max_blocks,
+                  int window, uint32_t *counts, uint8_t *class_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,251 @@
+/*
+ * oslam_verify.c -- verification against a depth image (include/oslam.h at oslam_verify): the host side of the kernels
+ * in oslam_verify.hip.  A view is the image as float z on the device; a call checks its arguments, uploads one
+ * descriptor per member (its pose, its tolerance and the model's device cloud), zeroes the counters, runs k_verify
+ * once for every member and reads the counters back with one host wait.
+ */
+#include <math.h>
+
+#include "oslam_internal.h"
+
+struct oslam_view {
+    int dev;
+    oslamk_view k;
+    float *d_z;
+};
+
+int oslam_view_create(const void *depth, int depth_is_u16, int width, int height, const oslam_camera *cam, int dev,
+                      oslam_view **out)
+{
+    int rc = OSLAM_OK, devsel;
+    const size_t n_pix = (size_t)width * (size_t)height, px_bytes = depth_is_u16 ? 2 : 4;
+    void *d_raw = NULL;
+    oslam_view *v = NULL;
+    if (out) *out = NULL;
+    if (!depth || !cam || !out || width < 1 || height < 1 || width > 16384 || height > 16384 || !isfinite(cam->fx) ||
+        !isfinite(cam->fy) || !isfinite(cam->cx) || !isfinite(cam->cy) || !(cam->fx > 0.0f) || !(cam->fy > 0.0f) ||
+        !(cam->depth_scale > 0.0f) || !isfinite(cam->depth_scale) || !(cam->z_max >= cam->z_min) ||
+        !(cam->z_min > 0.0f) || !isfinite(cam->z_max))
+        return fail(OSLAM_E_INVALID, "bad view arguments");
+    rc = oslam_pick_device(dev, &devsel);
+    if (rc != OSLAM_OK) return rc;
+    v = (oslam_view *)calloc(1, sizeof *v);
+    if (!v) return fail(OSLAM_E_NOMEM, "host allocation failed");
+    v->dev = devsel;
+    /* the z image lives as long as the view: its own block, not one of the kept scratch blocks */
+    HIPCHK(hipMalloc((void **)&v->d_z, sizeof(float) * n_pix));
+    HIPCHK((hipError_t)oslam_dev_alloc(&d_raw, n_pix * px_bytes));
+    HIPCHK(hipMemcpyAsync(d_raw, depth, n_pix * px_bytes, hipMemcpyHostToDevice, (hipStream_t)oslam_stream()));
+    KCHK(oslamk_view_z(d_raw, depth_is_u16 != 0, width, height, cam->depth_scale, cam->z_min, cam->z_max, v->d_z,
+                       oslam_stream()));
+    HIPCHK(hipStreamSynchronize((hipStream_t)oslam_stream()));
+    v->k.z = v->d_z;
+    v->k.w = width;
+    v->k.h = height;
+    v->k.fx = cam->fx;
+    v->k.fy = cam->fy;
+    v->k.cx = cam->cx;
+    v->k.cy = cam->cy;
+    v->k.z_min = cam->z_min;
+    v->k.z_max = cam->z_max;
+done:
+    if (rc != OSLAM_OK) (void)hipStreamSynchronize((hipStream_t)oslam_stream());
+    oslam_dev_free(d_raw);
+    if (rc != OSLAM_OK) {
+        if (v->d_z) (void)hipFree(v->d_z);
+        free(v);
+        return rc;
+    }
+    *out = v;
+    return OSLAM_OK;
+}
+
+int oslam_view_destroy(oslam_view *v)
+{
+    if (!v) return fail(OSLAM_E_INVALID, "view is NULL");
+    /* every call that read the image ended with a synchronisation of its stream */
+    if (hipSetDevice(v->dev) == hipSuccess) (void)hipFree(v->d_z);
+    free(v);
+    return OSLAM_OK;
+}
+
+int oslam_verify_params_default(oslam_verify_params *p)
+{
+    if (!p) return fail(OSLAM_E_INVALID, "params is NULL");
+    memset(p, 0, sizeof *p);
+    p->depth_tol = 1.0f;
+    p->window = 1;
+    p->min_view_fitness = 0.92f;
+    p->min_coverage = 0.5f;
+    p->min_supported = 50;
+    return OSLAM_OK;
+}
+
+static int check_params(const oslam_verify_params *vp, oslam_verify_params *out)
+{
+    if (vp) *out = *vp;
+    else oslam_verify_params_default(out);
+    if (!isfinite(out->depth_tol) || !isfinite(out->min_view_fitness) || !isfinite(out->min_coverage))
+        return fail(OSLAM_E_INVALID, "verify parameters must be finite");
+    if (!(out->depth_tol > 0.0f)) return fail(OSLAM_E_INVALID, "depth_tol must be > 0");
+    if (out->window > 3) return fail(OSLAM_E_INVALID, "window above 3");
+    if (out->min_view_fitness < 0.0f || out->min_view_fitness > 1.0f || out->min_coverage < 0.0f || out->min_coverage > 1.0f)
+        return fail(OSLAM_E_INVALID, "min_view_fitness and min_coverage must lie in [0, 1]");
+    return OSLAM_OK;
+}
+
+static int is_zero_pose(const float T[16])
+{
+    int k;
+    for (k = 0; k < 16; k++)
+        if (T[k] != 0.0f) return 0;
+    return 1;
+}
+
+static int check_pair(const oslam_model *m, const oslam_view *v)
+{
+    if (m->unusable) return fail(OSLAM_E_INVALID, "this model lost its key tables with its database: it can only be destroyed");
+    if (m->dev != v->dev) return fail(OSLAM_E_INVALID, "model and view live on different devices");
+    return OSLAM_OK;
+}
+
+static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+static void set_member(oslamk_verify_member *d, const oslam_model *m, const float T[16], const oslam_verify_params *p)
+{
+    int a;
+    d->m = m->c.k;
+    for (a = 0; a < 12; a++) d->T[a] = T[a];
+    d->tol = (float)((double)p->depth_tol * (double)m->d_dist);
+    d->n_blocks = (uint32_t)(((size_t)m->c.n + OSLAMK_VERIFY_THREADS - 1) / OSLAMK_VERIFY_THREADS);
+}
+
+/* members ms[0 .. n) with T [n][16] (all-zero = skipped) against view v: one memset, one kernel, one copy back */
+static int verify_members(oslam_model *const *ms, size_t n, const oslam_view *v, const float *T, const oslam_verify_params *p,
+                          oslam_verify_result *res)
+{
+    int rc = OSLAM_OK;
+    const double t0 = now_ms();
+    size_t j, max_blocks = 0, off_cnt, bytes;
+    oslamk_verify_member *h = NULL;
+    uint32_t *cnt = NULL, launches = 0;
+    char *dev = NULL;
+    void *stream = oslam_stream();
+
+    memset(res, 0, sizeof *res * n);
+    if (n > 65535) return fail(OSLAM_E_LIMIT, "more than 65535 members in one verification");
+    off_cnt = align256(sizeof *h * (n ? n : 1));
+    bytes = off_cnt + sizeof(uint32_t) * OSLAMK_VERIFY_CLASSES * (n ? n : 1);
+    h = (oslamk_verify_member *)calloc(n ? n : 1, sizeof *h);
+    cnt = (uint32_t *)calloc((n ? n : 1) * OSLAMK_VERIFY_CLASSES, sizeof *cnt);
+    if (!h || !cnt) { free(h); free(cnt); return fail(OSLAM_E_NOMEM, "host allocation failed"); }
+    for (j = 0; j < n; j++)
+        if (!is_zero_pose(T + 16 * j)) {
+            set_member(&h[j], ms[j], T + 16 * j, p);
+            if (h[j].n_blocks > max_blocks) max_blocks = h[j].n_blocks;
+        }
+    if (max_blocks == 0) goto done;             /* every member skipped: no device work */
+    if (hipSetDevice(v->dev) != hipSuccess) { rc = fail(OSLAM_E_DEVICE, "hipSetDevice failed"); goto done; }
+    KCHK(oslam_dev_alloc((void **)&dev, bytes));
+    HIPCHK(hipMemcpyAsync(dev, h, sizeof *h * n, hipMemcpyHostToDevice, (hipStream_t)stream));
+    HIPCHK(hipMemsetAsync(dev + off_cnt, 0, sizeof(uint32_t) * OSLAMK_VERIFY_CLASSES * n, (hipStream_t)stream));
+    KCHK(oslamk_verify(&v->k, (const oslamk_verify_member *)dev, (uint32_t)n, (uint32_t)max_blocks, (int)p->window,
+                       (uint32_t *)(dev + off_cnt), NULL, stream));
+    launches++;
+    HIPCHK(hipMemcpyAsync(cnt, dev + off_cnt, sizeof(uint32_t) * OSLAMK_VERIFY_CLASSES * n, hipMemcpyDeviceToHost,
+                          (hipStream_t)stream));
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    for (j = 0; j < n; j++) {
+        oslam_verify_result *r = &res[j];
+        const uint32_t *c = cnt + OSLAMK_VERIFY_CLASSES * j;
+        uint32_t sx, sox;
+        if (h[j].n_blocks == 0) continue;
+        r->back = c[0];
+        r->out = c[1];
+        r->supported = c[2];
+        r->occluded = c[3];
+        r->conflict = c[4];
+        r->unknown = c[5];
+        sx = r->supported + r->conflict;
+        sox = sx + r->occluded;
+        r->view_fitness = sx ? (float)r->supported / (float)sx : 0.0f;
+        r->coverage = sox ? (float)r->supported / (float)sox : 0.0f;
+        r->found = r->supported >= p->min_supported && r->view_fitness >= p->min_view_fitness &&
+                   r->coverage >= p->min_coverage;
+    }
+done:
+    if (rc != OSLAM_OK) (void)hipStreamSynchronize((hipStream_t)stream);    /* nothing may still use the block */
+    if (dev) oslam_dev_free(dev);
+    if (rc == OSLAM_OK) {
+        const float ms_total = (float)(now_ms() - t0);
+        for (j = 0; j < n; j++) {
+            res[j].launches = launches;
+            res[j].ms_total = ms_total;
+        }
+    }
+    free(h);
+    free(cnt);
+    return rc;
+}
+
+int oslam_verify(oslam_model *m, const oslam_view *v, const float T[16], const oslam_verify_params *vp,
+                 oslam_verify_result *res)
+{
+    oslam_verify_params p;
+    int rc;
+    if (!m || !v || !T || !res) return fail(OSLAM_E_INVALID, "NULL argument");
+    rc = check_params(vp, &p);
+    if (rc == OSLAM_OK) rc = oslam_refine_check_rigid(T);
+    if (rc == OSLAM_OK) rc = check_pair(m, v);
+    if (rc != OSLAM_OK) return rc;
+    return verify_members(&m, 1, v, T, &p, res);
+}
+
+int oslam_db_verify(oslam_db *db, const oslam_view *v, const float *T, const oslam_verify_params *vp,
+                    oslam_verify_result *res)
+{
+    oslam_verify_params p;
+    size_t j;
+    int rc;
+    if (!db || !v || !T || !res) return fail(OSLAM_E_INVALID, "NULL argument");
+    rc = check_params(vp, &p);
+    if (rc != OSLAM_OK) return rc;
+    for (j = 0; j < db->n; j++) {
+        if (is_zero_pose(T + 16 * j)) continue;
+        rc = oslam_refine_check_rigid(T + 16 * j);
+        if (rc == OSLAM_OK) rc = check_pair(db->models[j], v);
+        if (rc != OSLAM_OK) return rc;
+    }
+    return verify_members(db->models, db->n, v, T, &p, res);
+}
+
+int oslam_verify_classes(oslam_model *m, const oslam_view *v, const float T[16], const oslam_verify_params *vp,
+                         uint8_t *class_out)
+{
+    oslam_verify_params p;
+    oslamk_verify_member h;
+    char *dev = NULL;
+    void *stream = oslam_stream();
+    size_t M, off_cls;
+    int rc;
+    if (!m || !v || !T || !class_out) return fail(OSLAM_E_INVALID, "NULL argument");
+    rc = check_params(vp, &p);
+    if (rc == OSLAM_OK) rc = oslam_refine_check_rigid(T);
+    if (rc == OSLAM_OK) rc = check_pair(m, v);
+    if (rc != OSLAM_OK) return rc;
+    if (hipSetDevice(v->dev) != hipSuccess) return fail(OSLAM_E_DEVICE, "hipSetDevice failed");
+    M = (size_t)m->c.n;
+    memset(&h, 0, sizeof h);
+    set_member(&h, m, T, &p);
+    off_cls = align256(sizeof h);
+    KCHK(oslam_dev_alloc((void **)&dev, off_cls + M));
+    HIPCHK(hipMemcpyAsync(dev, &h, sizeof h, hipMemcpyHostToDevice, (hipStream_t)stream));
+    KCHK(oslamk_verify(&v->k, (const oslamk_verify_member *)dev, 1, h.n_blocks, (int)p.window, NULL,
+                       (uint8_t *)(dev + off_cls), stream));
+    HIPCHK(hipMemcpyAsync(class_out, dev + off_cls, M, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+done:
+    if (rc != OSLAM_OK) (void)hipStreamSynchronize((hipStream_t)stream);
+    if (dev) oslam_dev_free(dev);
+    return rc;
+}

@@ -66,6 +66,23 @@ class RefineResult(C.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class VerifyParams(C.Structure):
+    _fields_ = [("depth_tol", C.c_float), ("window", C.c_uint), ("min_view_fitness", C.c_float),
+                ("min_coverage", C.c_float), ("min_supported", C.c_uint), ("reserved", C.c_int * 4)]
+
+
+class VerifyResult(C.Structure):
+    _fields_ = [("back", C.c_uint32), ("out", C.c_uint32), ("supported", C.c_uint32), ("occluded", C.c_uint32),
+                ("conflict", C.c_uint32), ("unknown", C.c_uint32), ("view_fitness", C.c_float), ("coverage", C.c_float),
+                ("found", C.c_int32), ("launches", C.c_uint32), ("ms_total", C.c_float)]
+
+    def asdict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+VERIFY_BACK, VERIFY_OUT, VERIFY_SUPPORTED, VERIFY_OCCLUDED, VERIFY_CONFLICT, VERIFY_UNKNOWN = range(6)
+
+
 class InstanceParams(C.Structure):
     _fields_ = [("max_instances", C.c_uint), ("min_separation", C.c_float), ("max_angle", C.c_float),
                 ("min_score_ratio", C.c_float), ("keep_not_found", C.c_int), ("reserved", C.c_int * 4)]
@@ -136,6 +153,12 @@ _SIGNATURES = {
     "oslam_refine": (_i, [_vp, _vp, _vp, C.POINTER(RefineParams), _vp, C.POINTER(RefineResult)]),
     "oslam_db_refine": (_i, [_vp, _vp, _vp, C.POINTER(RefineParams), _vp, _vp]),
     "oslam_refine_correspondences": (_i, [_vp, _vp, _vp, _f, _f, _vp]),
+    "oslam_view_create": (_i, [_vp, _i, _i, _i, _vp, _i, C.POINTER(_vp)]),
+    "oslam_view_destroy": (_i, [_vp]),
+    "oslam_verify_params_default": (_i, [C.POINTER(VerifyParams)]),
+    "oslam_verify": (_i, [_vp, _vp, _vp, C.POINTER(VerifyParams), C.POINTER(VerifyResult)]),
+    "oslam_db_verify": (_i, [_vp, _vp, _vp, C.POINTER(VerifyParams), _vp]),
+    "oslam_verify_classes": (_i, [_vp, _vp, _vp, C.POINTER(VerifyParams), _vp]),
     "oslam_instance_params_default": (_i, [C.POINTER(InstanceParams)]),
     "oslam_align_instances": (_i, [_vp, _vp, C.POINTER(InstanceParams), C.POINTER(RefineParams), _vp, _sz, C.POINTER(_sz),
                                    _vp]),
@@ -201,6 +224,17 @@ def default_refine_params(**kw):
     for k, v in kw.items():
         if not hasattr(p, k) or k == "reserved":
             raise TypeError("unknown refine parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def default_verify_params(**kw):
+    """oslam_verify_params_default, then the fields given as keywords."""
+    p = VerifyParams()
+    _check(lib().oslam_verify_params_default(C.byref(p)))
+    for k, v in kw.items():
+        if not hasattr(p, k) or k == "reserved":
+            raise TypeError("unknown verify parameter %r" % k)
         setattr(p, k, v)
     return p
 
@@ -409,6 +443,14 @@ class Model:
         _check(lib().oslam_refine(self._h, scene._h, _p(Ti), C.byref(p), _p(To), C.byref(r)))
         return To.reshape(4, 4), r.asdict()
 
+    def verify(self, view, T, params=None):
+        """The pose T checked against the depth image of `view` (oslam_verify): -> result dict (the six class counts,
+        view_fitness, coverage, found, launches, ms_total)."""
+        r = VerifyResult()
+        p = params if params is not None else default_verify_params()
+        _check(lib().oslam_verify(self._h, view._h, _p(_pose16(T)), C.byref(p), C.byref(r)))
+        return r.asdict()
+
     def find_instances(self, scene, refine=True, params=None, refine_params=None):
         """Every instance of the model in the scene (oslam_align_instances): -> list of (T 4x4, info dict) in
         acceptance order; info: T_vote, score, candidate, refine (zeros without refinement).  Instance 0's T_vote is
@@ -574,6 +616,17 @@ class Database:
         out = [r.asdict() for r in res]
         return To, out, np.array([bool(r["found"]) for r in out])
 
+    def verify(self, view, T, params=None):
+        """Every member's pose T[j] checked against the depth image of `view` in one set of launches (oslam_db_verify);
+        members whose T[j] is all zeros are skipped.  -> (list of result dicts, found bool [n])."""
+        n = len(self.models)
+        Ti = np.ascontiguousarray(np.asarray(T, np.float32).reshape(n, 16))
+        res = (VerifyResult * max(n, 1))()
+        p = params if params is not None else default_verify_params()
+        _check(lib().oslam_db_verify(self._h, view._h, _p(Ti), C.byref(p), res))
+        out = [res[j].asdict() for j in range(n)]
+        return out, np.array([bool(r["found"]) for r in out], dtype=bool)
+
     def find_instances(self, scene, refine=True, params=None, refine_params=None):
         """Every instance of every member in one frame (oslam_db_align_instances): -> one list per member, as
         Model.find_instances returns it."""
@@ -680,6 +733,15 @@ def refine_correspondences(model, scene, T, radius, min_normal_dot):
     return out
 
 
+def verify_classes(model, view, T, params=None):
+    """Class of every model point under T against the view (uint8 [M], VERIFY_BACK .. VERIFY_UNKNOWN): the rule of
+    oslam_verify as a test tap (oslam_verify_classes)."""
+    out = np.zeros(model.n, np.uint8)
+    p = params if params is not None else default_verify_params()
+    _check(lib().oslam_verify_classes(model._h, view._h, _p(_pose16(T)), C.byref(p), _p(out)))
+    return out
+
+
 def kernel_source_hash():
     """One hash over every file the device code is built from (kernels, their headers, the Makefile with its
     flags).  bench.py quotes PMC passes on file only for exactly this source; tools/make_pmc_traffic.py records it."""
@@ -779,6 +841,32 @@ def depth_to_cloud(depth, fx, fy, cx, cy, depth_scale=0.001, z_min=0.1, z_max=10
     _check(lib().oslam_depth_to_cloud(_p(d), int(d.dtype == np.uint16), d.shape[1], d.shape[0], C.byref(cam), int(dev),
                                       _p(po), _p(no), n, C.byref(k)))
     return po[: k.value].copy(), no[: k.value].copy()
+
+
+class View:
+    """A depth image on the device as float z, for verification (oslam_view): the camera and depth conventions of
+    depth_to_cloud (z = raw * depth_scale, valid in [z_min, z_max]; max_jump is accepted and not used)."""
+
+    def __init__(self, depth, fx, fy, cx, cy, depth_scale=0.001, z_min=0.1, z_max=10.0, max_jump=0.05, dev=0):
+        self._h = C.c_void_p(0)
+        d = np.ascontiguousarray(depth)
+        if d.dtype not in (np.uint16, np.float32) or d.ndim != 2:
+            raise ValueError("depth must be a 2-D uint16 or float32 image")
+        cam = Camera(fx, fy, cx, cy, depth_scale, z_min, z_max, max_jump)
+        self.width, self.height = d.shape[1], d.shape[0]
+        _check(lib().oslam_view_create(_p(d), int(d.dtype == np.uint16), self.width, self.height, C.byref(cam), int(dev),
+                                       C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            lib().oslam_view_destroy(self._h)
+            self._h = C.c_void_p(0)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def ht_dist(A, B):

@@ -9,6 +9,8 @@ configuration; these are not bench lines).  Needs a HIP device.
                                          -> registration against a resident model database; frames/s
   python tools/bench_configs.py refine   the refinement stage: oslam_refine on the bench registration (5k model, 100k
                                          scene) from its voting pose, and the db50 stream with db.align + db.refine
+  python tools/bench_configs.py verify   the db50 stream with db.align + db.refine + db.verify per frame: frames/s, verify
+                                         ms per frame, and the found sets of refine and of verify on every frame
   python tools/bench_configs.py instances  oslam_align_instances next to oslam_align (bench registration, a scene
                                          with 3 copies: recall and false detections) and db.find_instances on db50
 One JSON line each."""
@@ -308,6 +310,64 @@ def refine(calls=20, frames=10):
     return out
 
 
+def verify(frames=10):
+    """Verification against the depth image (oslam_db_verify) on the db50 stream: db.align + db.refine + db.verify per
+    frame (the view is built from the frame's image inside the timed loop), the found sets of refine and of verify
+    against the truth (model 0 is the only object in every frame)."""
+    n_models = 50
+    raw = [synth.make_model(k, 1500) for k in range(n_models)]
+    d = synth.d_dist_for(raw[0][0], 0.05)
+    grids = [ppf.voxel_grid(c[0], c[1], leaf=d) for c in raw]
+    dense, _ = synth.make_model(0, 300000)
+    rng = synth.SplitMix64(93)
+    imgs = []
+    for f in range(frames):
+        T = np.eye(4, dtype=np.float32)
+        T[:3, :3] = synth.random_rotation(rng)
+        T[:3, 3] = [0.5 * np.cos(0.7 * f), 0.3 * np.sin(0.7 * f), 5.5 + 0.1 * f]
+        imgs.append(synth.render_depth(dense @ T[:3, :3].T + T[:3, 3], background_z=9.0, splat=1))
+    models = [ppf.Model(g[0], g[1], d_dist=d) for g in grids]
+    db = ppf.Database(models)
+
+    def frame(img):
+        sc = ppf.Scene.from_depth(img, 525.0, 525.0, 319.5, 239.5, leaf=d, d_dist=0.0, ref_point_downsample_factor=4,
+                                  z_min=0.5, z_max=12.0, max_jump=0.08)
+        Ta, _ = db.align(sc)
+        Tr, _, found_r = db.refine(sc, Ta)
+        t = time.perf_counter()
+        view = ppf.View(img, 525.0, 525.0, 319.5, 239.5, z_min=0.5, z_max=12.0)
+        t_view = time.perf_counter()
+        res, found_v = db.verify(view, Tr)
+        t_end = time.perf_counter()
+        _, found_tight = db.verify(view, Tr, ppf.default_verify_params(depth_tol=0.5))
+        view.close()
+        sc.close()
+        return found_r, found_v, res, 1e3 * (t_end - t), 1e3 * (t_end - t_view), found_tight
+    frame(imgs[0])
+    t = time.perf_counter(); rs = [frame(im) for im in imgs]; el = time.perf_counter() - t
+    out = {"config": "verification (oslam_db_verify) on the db50 stream", "frames": frames, "models": n_models,
+           "frames_per_s_align_refine_verify": frames / el,
+           "ms_verify_per_frame_with_view": float(np.mean([r[3] for r in rs])),
+           "ms_verify_per_frame_call_only": float(np.mean([r[4] for r in rs])),
+           "ms_verify_in_library": float(np.mean([r[2][0]["ms_total"] for r in rs])),
+           "launches_per_call": [r[2][0]["launches"] for r in rs],
+           "found_refine": [[int(j) for j in np.flatnonzero(r[0])] for r in rs],
+           "found_verify": [[int(j) for j in np.flatnonzero(r[1])] for r in rs],
+           "found_verify_depth_tol_0.5": [[int(j) for j in np.flatnonzero(r[5])] for r in rs],
+           "view_fitness_model0": [round(r[2][0]["view_fitness"], 3) for r in rs],
+           "coverage_model0": [round(r[2][0]["coverage"], 3) for r in rs],
+           "max_view_fitness_absent": [round(max(x["view_fitness"] for x in r[2][1:]), 3) for r in rs],
+           "max_coverage_absent": [round(max(x["coverage"] for x in r[2][1:]), 3) for r in rs]}
+    out["frames_model0_found_refine"] = sum(0 in f for f in out["found_refine"])
+    out["frames_model0_found_verify"] = sum(0 in f for f in out["found_verify"])
+    out["false_detections_refine"] = sum(len([j for j in f if j]) for f in out["found_refine"])
+    out["false_detections_verify"] = sum(len([j for j in f if j]) for f in out["found_verify"])
+    db.close()
+    for m in models:
+        m.close()
+    return out
+
+
 def instances(calls=10, frames=10):
     """Every instance of a model (oslam_align_instances): ms without and with refinement next to oslam_align on the
     bench registration and on a 100k scene with 3 copies of the bench model (plus recall and false detections there,
@@ -378,4 +438,4 @@ def instances(calls=10, frames=10):
 if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "cfg3"
     print(json.dumps({"cfg2": cfg2, "cfg3": cfg3, "cfg3db": cfg3db, "cfg4": cfg4, "cfg5": cfg5, "planes": planes, "db50": db50,
-                      "refine": refine, "instances": instances}[which]()), flush=True)
+                      "refine": refine, "verify": verify, "instances": instances}[which]()), flush=True)

@@ -3,7 +3,7 @@
 #   tools/kernel_resources.sh > profiles/rNN_kernel_resources.txt
 # Each translation unit with the flags the Makefile builds it with.
 cd "$(dirname "$0")/../objective-slam_amd/csrc"
-for f in oslam_kernels oslam_vote_wide oslam_sort oslam_posegpu oslam_voxel oslam_depth; do
+for f in oslam_kernels oslam_vote_wide oslam_sort oslam_posegpu oslam_voxel oslam_depth oslam_refine oslam_verify; do
   fl=""; [ $f = oslam_vote_wide ] && fl="-mllvm -disable-machine-licm"
   echo "== $f.hip $fl"
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -ffp-contract=off -fno-fast-math -I../../include -I. $fl \
