@@ -547,6 +547,113 @@ int oslam_db_align_instances(oslam_db *db, oslam_scene *s, const oslam_instance_
 int oslam_select_instances(const float *T, const float *scores, size_t n, const float centroid[3], float extent,
                            const oslam_instance_params *ip, uint32_t *idx_out, size_t cap, size_t *n_out);
 
+/* ---- arbitration: hypotheses that claim the same pixels of the depth image (after oslam_verify).  oslam_verify judges
+ * every hypothesis on its own, so two database members whose facing sides coincide within the tolerance are both found
+ * at one place.  No per-hypothesis threshold separates them; a comparison does: where both explain the image, which
+ * one explains it better?
+ *
+ * Input: a view and H hypotheses (model, T), any mix of models and of several poses of one model, 1 <= H <=
+ * OSLAM_ARBITRATE_MAX_HYPOTHESES.  A T of all zeros is a skipped hypothesis.  A caller that wants only verified
+ * hypotheses to compete passes the others as zeros (oslam_db_detect does).
+ * Claims.  Every model point of hypothesis h gets the class of oslam_verify (the same float sequence, window and
+ *   tol = (float)((double)depth_tol * d_dist) with its model's d_dist).  A SUPPORTED point claims the tile of its pixel,
+ *   t = (fv / tile) * tiles_x + fu / tile (integers, tiles_x = ceil(width / tile)), with its residual r = the smallest
+ *   fabsf(z_o - p'z) over the valid pixels of its window (r <= tol), quantised to x = r * (65535.0f / tol) in float,
+ *   q = x < 65535.0f ? (uint32_t)x : 65535.  Per (h, t): cnt = the claiming points, sum = the sum of their q.
+ *   Integers: the table does not depend on the order of the points.  A model of 2^24 points or more is OSLAM_E_LIMIT.
+ * Tile.  params.tile in pixels, 4..128; 0 (the default) chooses one for the call: with d_max = the largest d_dist of
+ *   the hypotheses that are not skipped, c = the model centroid of the instance rule (oslam_align_instances),
+ *   z_c = ((R20*cx + R21*cy) + R22*cz) + t2 in float and z_near = the smallest z_c > 0 of them,
+ *   tile = ceil((((double)tile_spacing * d_max) * fx) / z_near), clamped to [4, 128]; 128 when no z_c is positive.
+ *   About two point spacings in the image: with sparser tiles two hypotheses of the same surface hardly ever meet.
+ * Ownership.  Among the live claimants of a tile (cnt >= 1) the owner has the smallest mean residual, compared exactly
+ *   as sum_a * cnt_b < sum_b * cnt_a in 64-bit integers; ties go to the lower hypothesis index.  claimed(h) = tiles with
+ *   cnt_h >= 1, owned(h) = those it owns, share(h) = (float)owned / (float)claimed.
+ * Elimination.  Live at the start: every hypothesis that is not skipped and has claimed >= max(min_tiles, 1).  Repeat:
+ *   ownership among the live ones; the loser is the live hypothesis with the smallest share (ties: the larger index);
+ *   when share(loser) < min_owned_share it is suppressed -- suppressed_by = the other live hypothesis that owns most of
+ *   the loser's claimed tiles (ties: the lower index) -- and no longer live; otherwise stop.  At most H rounds.
+ *   A hypothesis that was never live has kept 0, suppressed_by -1, owned 0, share 0.
+ * Result per hypothesis: claimed; owned and share at its elimination (kept ones: at the last round); mean_residual =
+ *   (float)((((double)sum of its q / (double)its SUPPORTED points) / 65535.0) * (double)tol), 0 without claims; kept;
+ *   suppressed_by (-1: not suppressed).  Per call: tile (as used), rounds (ownership computations), launches, ms_total.
+ *   Only SUPPORTED points claim: the hidden part of an object behind another is OCCLUDED and claims nothing, so two
+ *   real objects side by side or one behind the other both keep their own tiles but for a seam.
+ * Arguments are checked before any handle is read or any device call is made: NULL pointers, H == 0 or above the
+ *   maximum, parameters that are not finite, depth_tol <= 0, window > 3, tile not 0 and outside 4..128, tile_spacing
+ *   <= 0, min_owned_share outside [0, 1] and a T that is neither all zeros nor rigid (the test of oslam_refine) are
+ *   OSLAM_E_INVALID; so are a model and a view on different devices.  A claims table above 256 MiB (H * tiles * 8 B)
+ *   is OSLAM_E_LIMIT before anything is launched.
+ * Cost: one memset, two kernels (k_claim: every hypothesis in one grid; k_arbitrate: one workgroup, the whole
+ *   elimination) and one copy back of a 32-byte record per hypothesis, one host wait: launches == 2 for 2 hypotheses
+ *   and for 400.  Integer counters only: the results are deterministic.
+ * Defaults (calibration table: tests/test_arbitrate_host.py): tile 0, tile_spacing 2, min_tiles 4 (a floor against a
+ *   handful of chance agreements, not calibrated), min_owned_share 0.52: the middle of the gap between the present
+ *   model (>= 0.629) and its suppressed near twin (<= 0.421) on the frames where the rule separates them.  On one
+ *   calibration frame in six it does not: the twin's pose fits better there and the present model is suppressed. */
+#define OSLAM_ARBITRATE_MAX_HYPOTHESES 1024
+typedef struct oslam_arbitrate_params {
+    float depth_tol;           /* as oslam_verify_params, default 1.0 */
+    unsigned window;           /* as oslam_verify_params, default 1 */
+    unsigned tile;             /* pixels, 4..128; 0 (default): chosen from tile_spacing */
+    float tile_spacing;        /* tile width in point spacings (d_dist) at the nearest hypothesis, default 2.0 */
+    unsigned min_tiles;        /* a hypothesis with fewer claimed tiles does not take part, default 4 */
+    float min_owned_share;     /* [0, 1]: the loser is suppressed below this share, default 0.52 */
+    int reserved[4];
+} oslam_arbitrate_params;
+
+typedef struct oslam_arbitrate_result {
+    uint32_t claimed, owned;
+    float share, mean_residual;
+    int32_t kept, suppressed_by;
+    uint32_t tile, rounds;     /* the whole call, shared by all hypotheses */
+    uint32_t launches;         /* kernels this call enqueued */
+    float ms_total;            /* whole call, host clock */
+} oslam_arbitrate_result;
+
+int oslam_arbitrate_params_default(oslam_arbitrate_params *p);
+/* models [H], T [H][16], res [H]; ap may be NULL (defaults).  When every hypothesis is skipped nothing is launched. */
+int oslam_arbitrate(oslam_model *const *models, const float *T, size_t H, const oslam_view *v,
+                    const oslam_arbitrate_params *ap, oslam_arbitrate_result *res);
+/* hypothesis j = member j of the database with T[j] (zeros: skipped); equals oslam_arbitrate on the same list */
+int oslam_db_arbitrate(oslam_db *db, const oslam_view *v, const float *T, const oslam_arbitrate_params *ap,
+                       oslam_arbitrate_result *res);
+/* test tap: the table after k_claim, cnt_out [H][n_tiles] and sum_out [H][n_tiles] with n_tiles = ceil(width / tile) *
+ * ceil(height / tile) of the tile in force (*tile_out); cap = the entries each array holds (OSLAM_E_INVALID when
+ * H * n_tiles > cap; *n_tiles_out is set either way) */
+int oslam_arbitrate_claims(oslam_model *const *models, const float *T, size_t H, const oslam_view *v,
+                           const oslam_arbitrate_params *ap, uint32_t *cnt_out, uint64_t *sum_out, size_t cap,
+                           uint32_t *tile_out, size_t *n_tiles_out);
+
+/* ---- the whole chain for a database frame in one call: oslam_db_align_instances (with refinement) -> the
+ * verification of every instance (oslam_verify semantics, one set of launches) -> arbitration over all instances, those
+ * that verification did not find passed as skipped -> the detections that are found and kept, ordered by (model,
+ * instance).  It composes the stages: a detection's T, verify and arbitrate equal what the three calls return for the
+ * same lists bit for bit (launches and ms fields aside).  The scene and the view are the same frame: the view in the
+ * camera frame of the scene's cloud (oslam_scene_from_depth and oslam_view_create of one image).
+ * dp may be NULL: the defaults of every stage, except that instances.keep_not_found is 1 -- a depth frame shows one side
+ * of an object, refine's fitness stays below its threshold there and verification is the judge of
+ * presence.  out [cap]; when more than cap detections are kept the call returns
+ * OSLAM_E_LIMIT with *n_out = their number and out untouched. */
+typedef struct oslam_detect_params {
+    oslam_instance_params instances;
+    oslam_refine_params refine;
+    oslam_verify_params verify;
+    oslam_arbitrate_params arbitrate;
+    int reserved[4];
+} oslam_detect_params;
+
+typedef struct oslam_detection {
+    uint32_t model, instance;  /* database member, and its index in the member's oslam_db_align_instances list */
+    float T[16];               /* the refined pose */
+    oslam_verify_result verify;
+    oslam_arbitrate_result arbitrate;
+} oslam_detection;
+
+int oslam_detect_params_default(oslam_detect_params *p);
+int oslam_db_detect(oslam_db *db, oslam_scene *s, const oslam_view *v, const oslam_detect_params *dp,
+                    oslam_detection *out, size_t cap, size_t *n_out);
+
 /* ---- parity taps (tests): values the reference materialises as arrays.
  * Scene::getHashKeys row r (scene.cu:49-54): keys_out[n] of reference point r,
  * computed by the GPU key kernel with this d_dist (key 0 on the diagonal). */

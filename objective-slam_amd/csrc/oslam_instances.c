@@ -18,7 +18,7 @@ static int check_args(const oslam_instance_params *ip, const oslam_refine_params
 }
 
 /* centroid (mean in double, rounded to float) and extent (largest bounding-box side, oslam_d_dist_from_cloud) */
-static void model_shape(oslam_model *m)
+void oslam_model_shape(oslam_model *m)
 {
     double cm[3] = {0.0, 0.0, 0.0};
     float lo[3], hi[3], ext;
@@ -44,7 +44,7 @@ static void model_shape(oslam_model *m)
 static void make_req(oslam_model *m, const oslam_instance_params *ip, oslam_inst_req *req)
 {
     int rot_on = 0;
-    model_shape(m);
+    oslam_model_shape(m);
     memset(req, 0, sizeof *req);
     req->ip = ip;
     req->extent = m->inst_extent;

@@ -77,6 +77,12 @@ struct oslam_scene {
     struct oslam_scene_grid *grids;   /* uniform grids of the refinement stage (oslam_refine.c), NULL until the first */
 };
 
+struct oslam_view {
+    int dev;
+    oslamk_view k;
+    float *d_z;
+};
+
 typedef struct db_group {
     int n;
     size_t *members;                  /* indices into db->models */
@@ -187,5 +193,24 @@ int oslam_refine_check_rigid(const float T[16]);
  * oslam_refine's for it alone */
 int oslam_refine_members(oslam_model *const *ms, size_t n, oslam_scene *s, const float *T_in, const oslam_refine_params *p,
                          float *T_out, oslam_refine_result *res);
+
+/* centroid and extent of the instance rule into m->inst_c / m->inst_extent, made once (oslam_instances.c) */
+void oslam_model_shape(oslam_model *m);
+
+/* ---- verification (oslam_verify.c) ---- */
+/* vp NULL = defaults; checks them as oslam_verify does, *out = the parameters in force */
+int oslam_verify_check_params(const oslam_verify_params *vp, oslam_verify_params *out);
+int oslam_is_zero_pose(const float T[16]);
+/* the model is usable and lives on the view's device */
+int oslam_view_check_pair(const oslam_model *m, const oslam_view *v);
+/* the descriptor of one member: its cloud, the rows of T, tol = (float)((double)depth_tol * d_dist), its blocks */
+void oslam_verify_set_member(oslamk_verify_member *d, const oslam_model *m, const float T[16], float depth_tol);
+/* members ms[0 .. n) with T [n][16] (all-zero = skipped) against v, one set of launches; member j's result is
+ * oslam_verify's for it alone */
+int oslam_verify_members(oslam_model *const *ms, size_t n, const oslam_view *v, const float *T, const oslam_verify_params *p,
+                         oslam_verify_result *res);
+
+/* gives back the pinned record of the arbitration stage (oslam_arbitrate.c); called by oslam_release_scratch */
+void oslam_arbitrate_release(void);
 
 #endif /* OSLAM_INTERNAL_H */

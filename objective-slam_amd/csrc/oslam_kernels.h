@@ -405,6 +405,34 @@ int oslamk_view_z(const void *d_raw, int is_u16, int w, int h, float scale, floa
 int oslamk_verify(const oslamk_view *v, const oslamk_verify_member *d_mem, uint32_t n_mem, uint32_t max_blocks,
                   int window, uint32_t *counts, uint8_t *class_out, void *stream);
 
+/* ---- arbitration stage (oslam_arbitrate.hip; semantics in include/oslam.h at oslam_arbitrate) ---- */
+#define OSLAMK_ARB_MAX_HYP 1024       /* hypotheses of one call: k_arbitrate keeps four words of each in LDS */
+#define OSLAMK_ARB_THREADS 256        /* the one workgroup of k_arbitrate */
+#define OSLAMK_ARB_LDS_BYTES 40960    /* a claims table up to this size is copied into LDS for the elimination */
+#define OSLAMK_ARB_CNT_SHIFT 40       /* a claims word: count in the upper 24 bits, sum of q in the lower 40 */
+
+/* the tiling of a call: tile x tile pixels, tiles_x = ceil(w / tile), n_tiles = tiles_x * ceil(h / tile) */
+typedef struct oslamk_arb_grid {
+    int tile, tiles_x;
+    uint32_t n_tiles;
+} oslamk_arb_grid;
+
+/* what k_arbitrate leaves for hypothesis h (rec[1 + h]); rec[0].claimed = the rounds of the call */
+typedef struct oslamk_arb_rec {
+    uint32_t claimed, owned;
+    float share;
+    int32_t kept, suppressed_by;
+    uint32_t cnt_total;        /* its SUPPORTED points */
+    uint64_t sum_total;        /* the sum of their q */
+} oslamk_arb_rec;
+
+/* claims[h * n_tiles + t] += (1 << 40) + q for every SUPPORTED point of member h in tile t (zeroed by the caller) */
+int oslamk_claim(const oslamk_view *v, const oslamk_verify_member *d_mem, uint32_t n_mem, uint32_t max_blocks, int window,
+                 oslamk_arb_grid g, unsigned long long *claims, void *stream);
+/* the elimination over the claims of n_mem members (n_blocks == 0: skipped) -> rec[1 + n_mem] */
+int oslamk_arbitrate(const oslamk_verify_member *d_mem, uint32_t n_mem, uint32_t n_tiles, const unsigned long long *claims,
+                     uint32_t min_tiles, float min_owned_share, oslamk_arb_rec *rec, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,12 +8,6 @@
 
 #include "oslam_internal.h"
 
-struct oslam_view {
-    int dev;
-    oslamk_view k;
-    float *d_z;
-};
-
 int oslam_view_create(const void *depth, int depth_is_u16, int width, int height, const oslam_camera *cam, int dev,
                       oslam_view **out)
 {
@@ -81,7 +75,7 @@ int oslam_verify_params_default(oslam_verify_params *p)
     return OSLAM_OK;
 }
 
-static int check_params(const oslam_verify_params *vp, oslam_verify_params *out)
+int oslam_verify_check_params(const oslam_verify_params *vp, oslam_verify_params *out)
 {
     if (vp) *out = *vp;
     else oslam_verify_params_default(out);
@@ -94,7 +88,7 @@ static int check_params(const oslam_verify_params *vp, oslam_verify_params *out)
     return OSLAM_OK;
 }
 
-static int is_zero_pose(const float T[16])
+int oslam_is_zero_pose(const float T[16])
 {
     int k;
     for (k = 0; k < 16; k++)
@@ -102,7 +96,7 @@ static int is_zero_pose(const float T[16])
     return 1;
 }
 
-static int check_pair(const oslam_model *m, const oslam_view *v)
+int oslam_view_check_pair(const oslam_model *m, const oslam_view *v)
 {
     if (m->unusable) return fail(OSLAM_E_INVALID, "this model lost its key tables with its database: it can only be destroyed");
     if (m->dev != v->dev) return fail(OSLAM_E_INVALID, "model and view live on different devices");
@@ -111,18 +105,18 @@ static int check_pair(const oslam_model *m, const oslam_view *v)
 
 static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
-static void set_member(oslamk_verify_member *d, const oslam_model *m, const float T[16], const oslam_verify_params *p)
+void oslam_verify_set_member(oslamk_verify_member *d, const oslam_model *m, const float T[16], float depth_tol)
 {
     int a;
     d->m = m->c.k;
     for (a = 0; a < 12; a++) d->T[a] = T[a];
-    d->tol = (float)((double)p->depth_tol * (double)m->d_dist);
+    d->tol = (float)((double)depth_tol * (double)m->d_dist);
     d->n_blocks = (uint32_t)(((size_t)m->c.n + OSLAMK_VERIFY_THREADS - 1) / OSLAMK_VERIFY_THREADS);
 }
 
 /* members ms[0 .. n) with T [n][16] (all-zero = skipped) against view v: one memset, one kernel, one copy back */
-static int verify_members(oslam_model *const *ms, size_t n, const oslam_view *v, const float *T, const oslam_verify_params *p,
-                          oslam_verify_result *res)
+int oslam_verify_members(oslam_model *const *ms, size_t n, const oslam_view *v, const float *T, const oslam_verify_params *p,
+                         oslam_verify_result *res)
 {
     int rc = OSLAM_OK;
     const double t0 = now_ms();
@@ -140,8 +134,8 @@ static int verify_members(oslam_model *const *ms, size_t n, const oslam_view *v,
     cnt = (uint32_t *)calloc((n ? n : 1) * OSLAMK_VERIFY_CLASSES, sizeof *cnt);
     if (!h || !cnt) { free(h); free(cnt); return fail(OSLAM_E_NOMEM, "host allocation failed"); }
     for (j = 0; j < n; j++)
-        if (!is_zero_pose(T + 16 * j)) {
-            set_member(&h[j], ms[j], T + 16 * j, p);
+        if (!oslam_is_zero_pose(T + 16 * j)) {
+            oslam_verify_set_member(&h[j], ms[j], T + 16 * j, p->depth_tol);
             if (h[j].n_blocks > max_blocks) max_blocks = h[j].n_blocks;
         }
     if (max_blocks == 0) goto done;             /* every member skipped: no device work */
@@ -194,11 +188,11 @@ int oslam_verify(oslam_model *m, const oslam_view *v, const float T[16], const o
     oslam_verify_params p;
     int rc;
     if (!m || !v || !T || !res) return fail(OSLAM_E_INVALID, "NULL argument");
-    rc = check_params(vp, &p);
+    rc = oslam_verify_check_params(vp, &p);
     if (rc == OSLAM_OK) rc = oslam_refine_check_rigid(T);
-    if (rc == OSLAM_OK) rc = check_pair(m, v);
+    if (rc == OSLAM_OK) rc = oslam_view_check_pair(m, v);
     if (rc != OSLAM_OK) return rc;
-    return verify_members(&m, 1, v, T, &p, res);
+    return oslam_verify_members(&m, 1, v, T, &p, res);
 }
 
 int oslam_db_verify(oslam_db *db, const oslam_view *v, const float *T, const oslam_verify_params *vp,
@@ -208,15 +202,15 @@ int oslam_db_verify(oslam_db *db, const oslam_view *v, const float *T, const osl
     size_t j;
     int rc;
     if (!db || !v || !T || !res) return fail(OSLAM_E_INVALID, "NULL argument");
-    rc = check_params(vp, &p);
+    rc = oslam_verify_check_params(vp, &p);
     if (rc != OSLAM_OK) return rc;
     for (j = 0; j < db->n; j++) {
-        if (is_zero_pose(T + 16 * j)) continue;
+        if (oslam_is_zero_pose(T + 16 * j)) continue;
         rc = oslam_refine_check_rigid(T + 16 * j);
-        if (rc == OSLAM_OK) rc = check_pair(db->models[j], v);
+        if (rc == OSLAM_OK) rc = oslam_view_check_pair(db->models[j], v);
         if (rc != OSLAM_OK) return rc;
     }
-    return verify_members(db->models, db->n, v, T, &p, res);
+    return oslam_verify_members(db->models, db->n, v, T, &p, res);
 }
 
 int oslam_verify_classes(oslam_model *m, const oslam_view *v, const float T[16], const oslam_verify_params *vp,
@@ -229,14 +223,14 @@ int oslam_verify_classes(oslam_model *m, const oslam_view *v, const float T[16],
     size_t M, off_cls;
     int rc;
     if (!m || !v || !T || !class_out) return fail(OSLAM_E_INVALID, "NULL argument");
-    rc = check_params(vp, &p);
+    rc = oslam_verify_check_params(vp, &p);
     if (rc == OSLAM_OK) rc = oslam_refine_check_rigid(T);
-    if (rc == OSLAM_OK) rc = check_pair(m, v);
+    if (rc == OSLAM_OK) rc = oslam_view_check_pair(m, v);
     if (rc != OSLAM_OK) return rc;
     if (hipSetDevice(v->dev) != hipSuccess) return fail(OSLAM_E_DEVICE, "hipSetDevice failed");
     M = (size_t)m->c.n;
     memset(&h, 0, sizeof h);
-    set_member(&h, m, T, &p);
+    oslam_verify_set_member(&h, m, T, p.depth_tol);
     off_cls = align256(sizeof h);
     KCHK(oslam_dev_alloc((void **)&dev, off_cls + M));
     HIPCHK(hipMemcpyAsync(dev, &h, sizeof h, hipMemcpyHostToDevice, (hipStream_t)stream));

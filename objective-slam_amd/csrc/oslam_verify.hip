@@ -9,8 +9,7 @@
  *              points): transform, class, then per class a wave ballot + popcount, the four waves summed in LDS and
  *              one integer atomicAdd per class and workgroup into the member's counters.  Integer sums do not depend
  *              on their order: the counts are deterministic.  The tap variant writes each point's class instead.
- * Bounds: a point reads at most (2 window + 1)^2 <= 49 floats of the z image, all inside it (the window is clipped);
- * the pixel is range-checked in float before it becomes an int.
+ *              The class itself is oslam_verify_class (oslam_verify_class.h), shared with the arbitration stage.
  */
 #include <hip/hip_runtime.h>
 
@@ -18,6 +17,7 @@
 #include <stdint.h>
 
 #include "oslam_kernels.h"
+#include "oslam_verify_class.h"
 
 __global__ __launch_bounds__(256) void k_view_z(const void *raw, int is_u16, int w, int h, float scale, float z_min,
                                                 float z_max, float *z_out)
@@ -40,52 +40,7 @@ __global__ __launch_bounds__(OSLAMK_VERIFY_THREADS) void k_verify(const oslamk_v
     if (blockIdx.x >= d->n_blocks) return;     /* the whole workgroup leaves together */
     const int i = (int)(blockIdx.x * OSLAMK_VERIFY_THREADS + threadIdx.x);
 
-    int cls = -1;
-    if (i < d->m.n) {
-        float T[12];
-#pragma unroll
-        for (int k = 0; k < 12; k++) T[k] = d->T[k];
-        const float px = d->m.px[i], py = d->m.py[i], pz = d->m.pz[i];
-        const float nx = d->m.nx[i], ny = d->m.ny[i], nz = d->m.nz[i];
-        const float qx = ((T[0] * px + T[1] * py) + T[2] * pz) + T[3];
-        const float qy = ((T[4] * px + T[5] * py) + T[6] * pz) + T[7];
-        const float qz = ((T[8] * px + T[9] * py) + T[10] * pz) + T[11];
-        const float mx = (T[0] * nx + T[1] * ny) + T[2] * nz;
-        const float my = (T[4] * nx + T[5] * ny) + T[6] * nz;
-        const float mz = (T[8] * nx + T[9] * ny) + T[10] * nz;
-        if ((mx * qx + my * qy) + mz * qz >= 0.0f) {
-            cls = 0;                                               /* BACK */
-        } else {
-            bool in = qz >= v.z_min && qz <= v.z_max;
-            float fu = 0.0f, fv = 0.0f;
-            if (in) {
-                fu = floorf(((qx * v.fx) / qz + v.cx) + 0.5f);
-                fv = floorf(((qy * v.fy) / qz + v.cy) + 0.5f);
-                in = fu >= 0.0f && fu < (float)v.w && fv >= 0.0f && fv < (float)v.h;
-            }
-            if (!in) {
-                cls = 1;                                           /* OUT */
-            } else {
-                const int u = (int)fu, vv = (int)fv;
-                const int u0 = max(u - window, 0), u1 = min(u + window, v.w - 1);
-                const int v0 = max(vv - window, 0), v1 = min(vv + window, v.h - 1);
-                const float tol = d->tol, lim = qz - tol;
-                bool sup = false, near = false, any = false;
-                for (int y = v0; y <= v1; y++) {
-                    const float *row = v.z + (size_t)y * v.w;
-                    for (int x = u0; x <= u1; x++) {
-                        const float zo = row[x];
-                        if (zo > 0.0f) {
-                            any = true;
-                            if (fabsf(zo - qz) <= tol) sup = true;
-                            if (zo < lim) near = true;
-                        }
-                    }
-                }
-                cls = sup ? 2 : near ? 3 : any ? 4 : 5;            /* SUPPORTED, OCCLUDED, CONFLICT, UNKNOWN */
-            }
-        }
-    }
+    const int cls = i < d->m.n ? oslam_verify_class<false>(v, d, i, window, NULL, NULL, NULL) : -1;
     if (TAP) {
         if (cls >= 0) class_out[i] = (uint8_t)cls;
         return;

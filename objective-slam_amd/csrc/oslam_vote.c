@@ -99,6 +99,7 @@ int oslam_release_scratch(int dev)
             for (i = 0; i < 4 + 3 * MAX_BATCH_EVENTS; i++) (void)hipEventDestroy(p->ev[i]);
     }
     if (hipSetDevice(dev) == hipSuccess) oslam_dev_cache_release(dev);   /* the kept blocks of the scene path */
+    oslam_arbitrate_release();
     free(p->h_counts);
     p->buf = NULL;
     p->bytes = 0;

@@ -100,6 +100,37 @@ class Instance(C.Structure):
 
 
 MAX_INSTANCES = 64
+
+
+class ArbitrateParams(C.Structure):
+    _fields_ = [("depth_tol", C.c_float), ("window", C.c_uint), ("tile", C.c_uint), ("tile_spacing", C.c_float),
+                ("min_tiles", C.c_uint), ("min_owned_share", C.c_float), ("reserved", C.c_int * 4)]
+
+
+class ArbitrateResult(C.Structure):
+    _fields_ = [("claimed", C.c_uint32), ("owned", C.c_uint32), ("share", C.c_float), ("mean_residual", C.c_float),
+                ("kept", C.c_int32), ("suppressed_by", C.c_int32), ("tile", C.c_uint32), ("rounds", C.c_uint32),
+                ("launches", C.c_uint32), ("ms_total", C.c_float)]
+
+    def asdict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+class DetectParams(C.Structure):
+    _fields_ = [("instances", InstanceParams), ("refine", RefineParams), ("verify", VerifyParams),
+                ("arbitrate", ArbitrateParams), ("reserved", C.c_int * 4)]
+
+
+class Detection(C.Structure):
+    _fields_ = [("model", C.c_uint32), ("instance", C.c_uint32), ("T", C.c_float * 16), ("verify", VerifyResult),
+                ("arbitrate", ArbitrateResult)]
+
+    def asdict(self):
+        return {"model": int(self.model), "instance": int(self.instance), "T": np.array(self.T, np.float32).reshape(4, 4),
+                "verify": self.verify.asdict(), "arbitrate": self.arbitrate.asdict()}
+
+
+ARBITRATE_MAX_HYPOTHESES = 1024
 CELL_DTYPE = np.dtype([("code", "<u8"), ("count", "<u4"), ("pad", "<u4")])
 
 # every function include/oslam.h declares: (name, restype, argtypes)
@@ -164,6 +195,13 @@ _SIGNATURES = {
                                    _vp]),
     "oslam_db_align_instances": (_i, [_vp, _vp, C.POINTER(InstanceParams), C.POINTER(RefineParams), _vp, _sz, _vp, _vp]),
     "oslam_select_instances": (_i, [_vp, _vp, _sz, _vp, _f, C.POINTER(InstanceParams), _vp, _sz, C.POINTER(_sz)]),
+    "oslam_arbitrate_params_default": (_i, [C.POINTER(ArbitrateParams)]),
+    "oslam_arbitrate": (_i, [_vp, _vp, _sz, _vp, C.POINTER(ArbitrateParams), _vp]),
+    "oslam_db_arbitrate": (_i, [_vp, _vp, _vp, C.POINTER(ArbitrateParams), _vp]),
+    "oslam_arbitrate_claims": (_i, [_vp, _vp, _sz, _vp, C.POINTER(ArbitrateParams), _vp, _vp, _sz, C.POINTER(C.c_uint32),
+                                    C.POINTER(_sz)]),
+    "oslam_detect_params_default": (_i, [C.POINTER(DetectParams)]),
+    "oslam_db_detect": (_i, [_vp, _vp, _vp, C.POINTER(DetectParams), _vp, _sz, C.POINTER(_sz)]),
     "oslam_scene_keys": (_i, [_vp, _sz, _vp]),
     "oslam_model_keys": (_i, [_vp, _sz, _vp]),
     "oslam_model_bucket": (_i, [_vp, C.c_uint32, _vp, _sz, C.POINTER(_sz)]),
@@ -248,6 +286,58 @@ def default_instance_params(**kw):
             raise TypeError("unknown instance parameter %r" % k)
         setattr(p, k, v)
     return p
+
+
+def default_arbitrate_params(**kw):
+    """oslam_arbitrate_params_default, then the fields given as keywords."""
+    p = ArbitrateParams()
+    _check(lib().oslam_arbitrate_params_default(C.byref(p)))
+    for k, v in kw.items():
+        if not hasattr(p, k) or k == "reserved":
+            raise TypeError("unknown arbitrate parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def default_detect_params():
+    """oslam_detect_params_default: the defaults of every stage, as .instances / .refine / .verify / .arbitrate."""
+    p = DetectParams()
+    _check(lib().oslam_detect_params_default(C.byref(p)))
+    return p
+
+
+def _hypotheses(models, T):
+    """-> (array of model handles, T [H,16] float32, H)"""
+    models = list(models)
+    H = len(models)
+    Ti = np.ascontiguousarray(np.asarray(T, np.float32).reshape(H, 16))
+    return (C.c_void_p * max(H, 1))(*[m._h for m in models]), Ti, H
+
+
+def arbitrate(models, view, T, params=None):
+    """Arbitration between the hypotheses (models[h], T[h]) that claim the same pixels of the view's depth image
+    (oslam_arbitrate); an all-zero T[h] is skipped.  -> (list of result dicts, kept bool [H])."""
+    arr, Ti, H = _hypotheses(models, T)
+    res = (ArbitrateResult * max(H, 1))()
+    p = params if params is not None else default_arbitrate_params()
+    _check(lib().oslam_arbitrate(arr, _p(Ti), H, view._h, C.byref(p), res))
+    out = [res[h].asdict() for h in range(H)]
+    return out, np.array([bool(r["kept"]) for r in out], dtype=bool)
+
+
+def arbitrate_claims(models, view, T, params=None):
+    """The claims table after k_claim as a test tap (oslam_arbitrate_claims): -> (cnt uint32 [H, n_tiles], sum uint64
+    [H, n_tiles], tile in pixels)."""
+    arr, Ti, H = _hypotheses(models, T)
+    p = params if params is not None else default_arbitrate_params()
+    n_tiles = ((view.width + 3) // 4) * ((view.height + 3) // 4)       # the smallest tile: the largest table
+    cnt = np.zeros(max(H * n_tiles, 1), np.uint32)
+    sm = np.zeros(max(H * n_tiles, 1), np.uint64)
+    tile, nt = C.c_uint32(0), C.c_size_t(0)
+    _check(lib().oslam_arbitrate_claims(arr, _p(Ti), H, view._h, C.byref(p), _p(cnt), _p(sm), len(cnt), C.byref(tile),
+                                        C.byref(nt)))
+    n = H * nt.value
+    return cnt[:n].reshape(H, nt.value).copy(), sm[:n].reshape(H, nt.value).copy(), int(tile.value)
 
 
 def _instance_args(refine, params, refine_params):
@@ -626,6 +716,28 @@ class Database:
         _check(lib().oslam_db_verify(self._h, view._h, _p(Ti), C.byref(p), res))
         out = [res[j].asdict() for j in range(n)]
         return out, np.array([bool(r["found"]) for r in out], dtype=bool)
+
+    def arbitrate(self, view, T, params=None):
+        """Arbitration between the members' poses T[j] (oslam_db_arbitrate; all-zero = skipped, e.g. the members that
+        verify did not find).  -> (list of result dicts, kept bool [n])."""
+        n = len(self.models)
+        Ti = np.ascontiguousarray(np.asarray(T, np.float32).reshape(n, 16))
+        res = (ArbitrateResult * max(n, 1))()
+        p = params if params is not None else default_arbitrate_params()
+        _check(lib().oslam_db_arbitrate(self._h, view._h, _p(Ti), C.byref(p), res))
+        out = [res[j].asdict() for j in range(n)]
+        return out, np.array([bool(r["kept"]) for r in out], dtype=bool)
+
+    def detect(self, scene, view, params=None):
+        """The whole chain for one frame (oslam_db_detect): every instance of every member, refined, verified against
+        the view and arbitrated.  -> list of dicts (model, instance, T 4x4, verify, arbitrate) ordered by (model,
+        instance).  params: a DetectParams (default_detect_params())."""
+        p = params if params is not None else default_detect_params()
+        cap = max(1, len(self.models) * int(p.instances.max_instances))
+        out = (Detection * cap)()
+        n = C.c_size_t(0)
+        _check(lib().oslam_db_detect(self._h, scene._h, view._h, C.byref(p), out, cap, C.byref(n)))
+        return [out[k].asdict() for k in range(n.value)]
 
     def find_instances(self, scene, refine=True, params=None, refine_params=None):
         """Every instance of every member in one frame (oslam_db_align_instances): -> one list per member, as

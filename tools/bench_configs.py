@@ -9,6 +9,8 @@ configuration; these are not bench lines).  Needs a HIP device.
                                          -> registration against a resident model database; frames/s
   python tools/bench_configs.py refine   the refinement stage: oslam_refine on the bench registration (5k model, 100k
                                          scene) from its voting pose, and the db50 stream with db.align + db.refine
+  python tools/bench_configs.py arbitrate   the db50 stream with db.align + db.refine + db.verify + db.arbitrate per frame and
+                                         with db.detect: frames/s, arbitrate ms per frame, the found sets before and after
   python tools/bench_configs.py verify   the db50 stream with db.align + db.refine + db.verify per frame: frames/s, verify
                                          ms per frame, and the found sets of refine and of verify on every frame
   python tools/bench_configs.py instances  oslam_align_instances next to oslam_align (bench registration, a scene
@@ -435,7 +437,72 @@ def instances(calls=10, frames=10):
     return out
 
 
+def arbitrate(frames=10):
+    """Arbitration (oslam_db_arbitrate) on the db50 stream: db.align + db.refine + db.verify + db.arbitrate per frame
+    (the members verification did not find are passed as skipped), the found sets before and after arbitration, and
+    the same frames through the one call (db.detect).  Member 36 is the near twin of the rendered model 0."""
+    n_models = 50
+    raw = [synth.make_model(k, 1500) for k in range(n_models)]
+    d = synth.d_dist_for(raw[0][0], 0.05)
+    grids = [ppf.voxel_grid(c[0], c[1], leaf=d) for c in raw]
+    dense, _ = synth.make_model(0, 300000)
+    rng = synth.SplitMix64(93)
+    imgs = []
+    for f in range(frames):
+        T = np.eye(4, dtype=np.float32)
+        T[:3, :3] = synth.random_rotation(rng)
+        T[:3, 3] = [0.5 * np.cos(0.7 * f), 0.3 * np.sin(0.7 * f), 5.5 + 0.1 * f]
+        imgs.append(synth.render_depth(dense @ T[:3, :3].T + T[:3, 3], background_z=9.0, splat=1))
+    models = [ppf.Model(g[0], g[1], d_dist=d) for g in grids]
+    db = ppf.Database(models)
+
+    def scene_of(img):
+        return ppf.Scene.from_depth(img, 525.0, 525.0, 319.5, 239.5, leaf=d, d_dist=0.0, ref_point_downsample_factor=4,
+                                    z_min=0.5, z_max=12.0, max_jump=0.08)
+
+    def frame(img):
+        sc = scene_of(img)
+        Ta, _ = db.align(sc)
+        Tr, _, _ = db.refine(sc, Ta)
+        view = ppf.View(img, 525.0, 525.0, 319.5, 239.5, z_min=0.5, z_max=12.0)
+        _, found = db.verify(view, Tr)
+        t = time.perf_counter()
+        res, kept = db.arbitrate(view, np.where(found[:, None, None], Tr, np.float32(0)))
+        ms = 1e3 * (time.perf_counter() - t)
+        view.close()
+        sc.close()
+        return found, kept, res, ms
+
+    def detect(img):
+        sc = scene_of(img)
+        view = ppf.View(img, 525.0, 525.0, 319.5, 239.5, z_min=0.5, z_max=12.0)
+        det = db.detect(sc, view)
+        view.close()
+        sc.close()
+        return det
+    frame(imgs[0])
+    t = time.perf_counter(); rs = [frame(im) for im in imgs]; el = time.perf_counter() - t
+    detect(imgs[0])
+    t = time.perf_counter(); ds = [detect(im) for im in imgs]; el_d = time.perf_counter() - t
+    out = {"config": "arbitration (oslam_db_arbitrate) on the db50 stream", "frames": frames, "models": n_models,
+           "frames_per_s_align_refine_verify_arbitrate": frames / el,
+           "frames_per_s_detect": frames / el_d,
+           "ms_arbitrate_per_frame_median": float(np.median([r[3] for r in rs])),
+           "ms_arbitrate_in_library_median": float(np.median([r[2][0]["ms_total"] for r in rs])),
+           "launches_per_call": [r[2][0]["launches"] for r in rs],
+           "tile": [r[2][0]["tile"] for r in rs], "rounds": [r[2][0]["rounds"] for r in rs],
+           "found_verify": [[int(j) for j in np.flatnonzero(r[0])] for r in rs],
+           "kept_arbitrate": [[int(j) for j in np.flatnonzero(r[1])] for r in rs],
+           "share_model0": [round(r[2][0]["share"], 3) for r in rs],
+           "share_model36": [round(r[2][36]["share"], 3) for r in rs],
+           "detect": [[(g["model"], g["instance"]) for g in det] for det in ds]}
+    db.close()
+    for m in models:
+        m.close()
+    return out
+
+
 if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "cfg3"
     print(json.dumps({"cfg2": cfg2, "cfg3": cfg3, "cfg3db": cfg3db, "cfg4": cfg4, "cfg5": cfg5, "planes": planes, "db50": db50,
-                      "refine": refine, "verify": verify, "instances": instances}[which]()), flush=True)
+                      "refine": refine, "verify": verify, "instances": instances, "arbitrate": arbitrate}[which]()), flush=True)

@@ -1,9 +1,12 @@
 #!/bin/bash
 # Registers, scratch and LDS of every kernel, as the compiler reports them (no GPU needed):
 #   tools/kernel_resources.sh > profiles/rNN_kernel_resources.txt
+#   tools/kernel_resources.sh oslam_arbitrate > profiles/rNN_kernel_resources_arbitrate.txt   (the named units only)
 # Each translation unit with the flags the Makefile builds it with.
 cd "$(dirname "$0")/../objective-slam_amd/csrc"
-for f in oslam_kernels oslam_vote_wide oslam_sort oslam_posegpu oslam_voxel oslam_depth oslam_refine oslam_verify; do
+units="$*"
+[ -z "$units" ] && units="oslam_kernels oslam_vote_wide oslam_sort oslam_posegpu oslam_voxel oslam_depth oslam_refine oslam_verify oslam_arbitrate"
+for f in $units; do
   fl=""; [ $f = oslam_vote_wide ] && fl="-mllvm -disable-machine-licm"
   echo "== $f.hip $fl"
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -ffp-contract=off -fno-fast-math -I../../include -I. $fl \
