@@ -404,8 +404,8 @@ int oslam_refine_correspondences(oslam_model *m, oslam_scene *s, const float T[1
  *
  * A view holds the depth image on the device as float z.  It shares the camera frame of oslam_depth_to_cloud (the
  * camera at the origin looking along +z, so the clouds of oslam_scene_from_depth are in the same coordinates), with
- * the same conventions: z = raw * depth_scale in float, valid in [z_min, z_max]; max_jump is not used.  A view is
- * independent of any scene: a point-cloud scene with a known sensor can be verified as well.
+ * the same conventions: z = raw * depth_scale in float, valid in [z_min, z_max]; max_jump is remembered for the normal
+ * map of the tracking stage (oslam_track) and not used by verification.  A view is independent of any scene: a point-cloud scene with a known sensor can be verified as well.
  *
  * Rule.  Model point i is (p, n); T is a float32 row-major model -> scene (camera) pose.  p' and n' are computed
  * exactly as oslam_refine does: p'x = ((R00*px + R01*py) + R02*pz) + t0, likewise y and z; n' the same without t.
@@ -653,6 +653,133 @@ typedef struct oslam_detection {
 int oslam_detect_params_default(oslam_detect_params *p);
 int oslam_db_detect(oslam_db *db, oslam_scene *s, const oslam_view *v, const oslam_detect_params *dp,
                     oslam_detection *out, size_t cap, size_t *n_out);
+
+/* ---- tracking across depth frames: projective ICP against the image itself (after oslam_db_detect; KinFu's data
+ * association).  A detection's pose is carried from frame to frame at a cost that does not depend on the database: no
+ * scene cloud, no voxel grid, no neighbour grid and no votes.  Each model point looks at one pixel.
+ *
+ * Normals on the view.  A view gains a per-pixel vertex and normal map on the device, built on first use by one kernel
+ * (k_view_normals) and kept with the view; a view that is never tracked on costs what it did.  The point and the normal
+ * of a pixel are exactly what oslam_depth_to_cloud produces for it with the view's camera (max_jump included): the
+ * back-projection, the four axis neighbours valid and within max_jump, the cross product normalised and turned to face
+ * the camera, no normal for a zero or non-finite cross product -- bit for bit, so the clouds of oslam_scene_from_depth
+ * and the tracker see one geometry.
+ * Correspondence of model point i (p, n) under the float32 pose T: p' and n' exactly as oslam_refine and oslam_verify
+ *   compute them.  The point takes part only when it is neither BACK nor OUT by oslam_verify's tests; its pixel is
+ *   oslam_verify's (fu, fv); q and nq are that pixel's vertex and normal.  The correspondence exists when the pixel has
+ *   a normal, (dx*dx + dy*dy) + dz*dz <= r*r with d = q - p' and r = max_corr_dist * d_dist (float, r*r rounded to
+ *   float), and (n'x*nqx + n'y*nqy) + n'z*nqz >= min_normal_dot.  One candidate pixel per point, no search: the image
+ *   is dense where the model cloud is sparse.
+ * Step, convergence and pose bookkeeping are oslam_refine's with these correspondences: the same residual and Jacobian
+ *   about the transformed centroid, the same 29 sums (float per block of 256 consecutive model points through the fixed
+ *   tree, double across blocks in index order), the same damped Cholesky in double, Rodrigues step and Gram-Schmidt,
+ *   "fewer than 6 correspondences (or a failed factorisation) stop the hypothesis with its pose kept", stop_rot and
+ *   stop_trans.
+ * Judgement.  At the final pose every hypothesis is classed and scored exactly as oslam_verify would be with
+ *   params.verify: res->verify equals oslam_verify(model, view, T_out) bit for bit (launches and ms_total aside, which
+ *   are this call's), res->found = res->verify.found.
+ * Input: H hypotheses (model, T_prev) as in oslam_arbitrate, several instances of one model being several entries,
+ *   1 <= H <= OSLAM_ARBITRATE_MAX_HYPOTHESES.  An all-zero T_prev is skipped: T_out zeros, result zeros, found 0.
+ * Arguments are checked before any handle is read or any device call is made: NULL pointers, H == 0 or above the
+ *   maximum, parameters that are not finite, max_corr_dist <= 0, max_iterations > 1000, a negative stop criterion, the
+ *   verify parameters as oslam_verify checks them and a T_prev that is neither all zeros nor rigid (the test of
+ *   oslam_refine) are OSLAM_E_INVALID; so are a model and a view on different devices.
+ * Cost: one kernel (k_track) and one host wait for the whole call, at any iteration count: one workgroup per hypothesis
+ *   runs every iteration itself (per iteration: its model's blocks of 256 points, each with the transform, the
+ *   projection and one gather of vertex and normal; the block sums in the fixed order, no float atomics; the blocks in
+ *   double in index order; one thread solves the 6x6 system and publishes the new float32 pose through LDS), then
+ *   classes and counts for the judgement and writes one record per hypothesis, which is copied to pinned memory.
+ *   res->launches == 1 for 1 hypothesis and for 50; 2 on the first call on a view (k_view_normals).  The results are
+ *   deterministic. */
+typedef struct oslam_track_params {
+    unsigned max_iterations;   /* default 10 */
+    float max_corr_dist;       /* correspondence radius in units of the model's d_dist, default 2.0 */
+    float min_normal_dot;      /* gate on (R n_model) . n_pixel, default 0.8 */
+    float stop_rot;            /* as oslam_refine_params, default 1e-5 */
+    float stop_trans;          /* as oslam_refine_params, default 1e-4 */
+    oslam_verify_params verify;   /* the judgement at the final pose, defaults of oslam_verify */
+    int reserved[4];
+} oslam_track_params;
+
+typedef struct oslam_track_result {
+    oslam_verify_result verify;   /* oslam_verify at T_out */
+    uint32_t iterations, correspondences;   /* correspondences: of the last step */
+    int32_t converged, found;  /* found = verify.found */
+    uint32_t launches;         /* kernels this call enqueued (the whole call, shared by all hypotheses) */
+    float ms_total;            /* whole call, host clock */
+} oslam_track_result;
+
+int oslam_track_params_default(oslam_track_params *p);
+/* models [H], T_prev / T_out [H][16], res [H] (may be NULL); tp may be NULL (defaults) */
+int oslam_track(oslam_model *const *models, const float *T_prev, size_t H, const oslam_view *v,
+                const oslam_track_params *tp, float *T_out, oslam_track_result *res);
+/* hypothesis h = member member[h] of the database (an index below its size) with T_prev[h]; equals oslam_track on the
+ * same list */
+int oslam_db_track(oslam_db *db, const uint32_t *member, const float *T_prev, size_t H, const oslam_view *v,
+                   const oslam_track_params *tp, float *T_out, oslam_track_result *res);
+/* test taps.  The maps of a view (built when they do not exist yet), width * height entries in row-major pixel order:
+ * nrm_out [h*w][3] / vtx_out [h*w][3] (zeros where the pixel has no normal), has_normal_out [h*w] 0 or 1 */
+int oslam_view_normals(oslam_view *v, float *nrm_out, uint8_t *has_normal_out);
+int oslam_view_vertices(oslam_view *v, float *vtx_out);
+/* pixel_out[M] = v * width + u of each model point's correspondence under T, -1 = none */
+int oslam_track_correspondences(oslam_model *m, const oslam_view *v, const float T[16], float max_corr_dist,
+                                float min_normal_dot, int32_t *pixel_out);
+
+/* ---- a tracker over the stages: identity across frames.  A host-side object with no kernel of its own.
+ * One oslam_tracker_step does, in this order:
+ *   1. oslam_db_track once over all live tracks from their last poses;
+ *   2. arbitration (oslam_arbitrate, params.arbitrate) over the tracks that were found, the others passed as skipped:
+ *      two tracks that slid onto one object must not both live; a suppressed track counts as not found;
+ *   3. a track that was found: its pose becomes T_out, hits + 1, misses = 0;
+ *   4. a track that was not found: its pose is kept, misses + 1, and it is deleted once misses > max_misses;
+ *   5. the search, when scene != NULL and either no track lives or frame % detect_every == 0 (frame counts the steps of
+ *      this tracker from 0): oslam_db_detect on the scene and view (params.detect), then oslam_tracker_update.
+ *   Every live track's age goes up by 1 per step after its birth.  Output: the live tracks ordered by id (tracks born in
+ *   this step included, with age 0 and the detection's pose); when more than cap live, OSLAM_E_LIMIT with *n_out = their
+ *   number.  *searched (may be NULL) says whether this frame voted.
+ * oslam_tracker_update associates and gives birth, on the host alone: a detection belongs to a live track of the same
+ *   model when the two are the same instance by the test of oslam_select_instances (the transformed centroids within
+ *   assoc_min_separation * extent and, unless assoc_max_angle == (float)pi, the rotation test); the nearest such track
+ *   (smallest d2 of the centroids, in float) wins, ties to the lower id.  A matched detection changes nothing: the
+ *   tracked pose is the fresher one.  An unmatched detection starts a track with the next id (hits 1, misses 0, found 1);
+ *   ids are never reused.  Detections are handled in list order, so a second detection can match a track the first one
+ *   started.
+ * A tracker borrows its database.  oslam_tracker_create_shapes makes one from the models' shapes alone (centroid [n][3]
+ *   and extent [n] of the instance rule) for hosts without a device: oslam_tracker_update and oslam_tracker_tracks work,
+ *   oslam_tracker_step is OSLAM_E_INVALID. */
+typedef struct oslam_tracker oslam_tracker;
+typedef struct oslam_tracker_params {
+    oslam_track_params track;
+    oslam_detect_params detect;
+    oslam_arbitrate_params arbitrate;   /* over the tracked poses (step 2) */
+    unsigned max_misses;       /* default 2 */
+    unsigned detect_every;     /* frames between two searches, >= 1, default 10 */
+    float assoc_min_separation;   /* as oslam_instance_params.min_separation, default 0.5 */
+    float assoc_max_angle;     /* as oslam_instance_params.max_angle, default pi (translation only) */
+    int reserved[4];
+} oslam_tracker_params;
+
+typedef struct oslam_track_state {
+    uint32_t id, model;        /* model: database member */
+    float T[16];
+    uint32_t age, hits, misses;
+    int32_t found;             /* in the last step (a birth counts as found) */
+    oslam_track_result track;  /* of the last step; zeros for a track born in it */
+} oslam_track_state;
+
+int oslam_tracker_params_default(oslam_tracker_params *p);
+/* p may be NULL (defaults) */
+int oslam_tracker_create(oslam_db *db, const oslam_tracker_params *p, oslam_tracker **out);
+int oslam_tracker_create_shapes(const float *centroid /* [n][3] */, const float *extent /* [n] */, size_t n,
+                                const oslam_tracker_params *p, oslam_tracker **out);
+void oslam_tracker_destroy(oslam_tracker *t);
+/* host only: fold a detection list into the tracks (association + birth); used by _step, exported for tests */
+int oslam_tracker_update(oslam_tracker *t, const oslam_detection *det, size_t n);
+/* the live tracks ordered by id; OSLAM_E_LIMIT with *n_out = their number when cap is too small */
+int oslam_tracker_tracks(const oslam_tracker *t, oslam_track_state *out, size_t cap, size_t *n_out);
+/* one frame: scene may be NULL (no search this frame) */
+int oslam_tracker_step(oslam_tracker *t, oslam_scene *scene, const oslam_view *v, oslam_track_state *out, size_t cap,
+                       size_t *n_out, int *searched);
 
 /* ---- parity taps (tests): values the reference materialises as arrays.
  * Scene::getHashKeys row r (scene.cu:49-54): keys_out[n] of reference point r,

@@ -38,7 +38,7 @@ int oslam_arbitrate_params_default(oslam_arbitrate_params *p)
     return OSLAM_OK;
 }
 
-static int check_params(const oslam_arbitrate_params *ap, oslam_arbitrate_params *out)
+int oslam_arbitrate_check_params(const oslam_arbitrate_params *ap, oslam_arbitrate_params *out)
 {
     if (ap) *out = *ap;
     else oslam_arbitrate_params_default(out);
@@ -209,7 +209,7 @@ int oslam_arbitrate(oslam_model *const *models, const float *T, size_t H, const 
     oslam_arbitrate_params p;
     int rc;
     if (!models || !T || !v || !res) return fail(OSLAM_E_INVALID, "NULL argument");
-    rc = check_params(ap, &p);
+    rc = oslam_arbitrate_check_params(ap, &p);
     if (rc == OSLAM_OK) rc = check_list(models, T, H, v);
     if (rc != OSLAM_OK) return rc;
     return arbitrate_members(models, H, v, T, &p, res, NULL, NULL, 0, NULL, NULL);
@@ -221,7 +221,7 @@ int oslam_db_arbitrate(oslam_db *db, const oslam_view *v, const float *T, const 
     oslam_arbitrate_params p;
     int rc;
     if (!db || !v || !T || !res) return fail(OSLAM_E_INVALID, "NULL argument");
-    rc = check_params(ap, &p);
+    rc = oslam_arbitrate_check_params(ap, &p);
     if (rc != OSLAM_OK) return rc;
     if (db->n && !db->models) return fail(OSLAM_E_INVALID, "the database holds no models");
     rc = check_list(db->models, T, db->n, v);
@@ -236,7 +236,7 @@ int oslam_arbitrate_claims(oslam_model *const *models, const float *T, size_t H,
     oslam_arbitrate_params p;
     int rc;
     if (!models || !T || !v || !cnt_out || !sum_out) return fail(OSLAM_E_INVALID, "NULL argument");
-    rc = check_params(ap, &p);
+    rc = oslam_arbitrate_check_params(ap, &p);
     if (rc == OSLAM_OK) rc = check_list(models, T, H, v);
     if (rc != OSLAM_OK) return rc;
     return arbitrate_members(models, H, v, T, &p, NULL, cnt_out, sum_out, cap, tile_out, n_tiles_out);
@@ -278,7 +278,7 @@ int oslam_db_detect(oslam_db *db, oslam_scene *s, const oslam_view *v, const osl
         return fail(OSLAM_E_INVALID, "instance parameters out of range");
     rc = oslam_refine_check_params(&p.refine, &rp);
     if (rc == OSLAM_OK) rc = oslam_verify_check_params(&p.verify, &vp);
-    if (rc == OSLAM_OK) rc = check_params(&p.arbitrate, &ap);
+    if (rc == OSLAM_OK) rc = oslam_arbitrate_check_params(&p.arbitrate, &ap);
     if (rc != OSLAM_OK) return rc;
     if (db->n == 0) return OSLAM_OK;
     for (j = 0; j < db->n; j++) {

@@ -20,25 +20,15 @@
 
 #include <stdint.h>
 
+#include "oslam_depth_normal.h"
 #include "oslam_kernels.h"
 #include "ppf_math.h"
-
-struct depth_cam {
-    float fx, fy, cx, cy, scale, z_min, z_max, max_jump;
-};
 
 __device__ __forceinline__ float depth_at(const void *img, int is_u16, int w, int u, int v, float scale)
 {
     const size_t i = (size_t)v * w + u;
     return is_u16 ? (float)reinterpret_cast<const uint16_t *>(img)[i] * scale
                   : reinterpret_cast<const float *>(img)[i] * scale;
-}
-__device__ __forceinline__ bool depth_ok(float z, const depth_cam &c) { return z >= c.z_min && z <= c.z_max; }
-__device__ __forceinline__ void back_project(int u, int v, float z, const depth_cam &c, float p[3])
-{
-    p[0] = (((float)u - c.cx) * z) / c.fx;
-    p[1] = (((float)v - c.cy) * z) / c.fy;
-    p[2] = z;
 }
 
 /* one thread per pixel: out6[pixel] = x y z nx ny nz and flags[pixel] = 1 where the pixel has a normal */
@@ -53,33 +43,13 @@ __global__ __launch_bounds__(256) void k_depth_points(const void *img, int is_u1
     if (depth_ok(z, c) && u > 0 && v > 0 && u + 1 < w && v + 1 < h) {
         const float zl = depth_at(img, is_u16, w, u - 1, v, c.scale), zr = depth_at(img, is_u16, w, u + 1, v, c.scale);
         const float zu = depth_at(img, is_u16, w, u, v - 1, c.scale), zd = depth_at(img, is_u16, w, u, v + 1, c.scale);
+        float p[3], n[3];
         if (depth_ok(zl, c) && depth_ok(zr, c) && depth_ok(zu, c) && depth_ok(zd, c) &&
-            pm_fabsf(zl - z) <= c.max_jump && pm_fabsf(zr - z) <= c.max_jump && pm_fabsf(zu - z) <= c.max_jump &&
-            pm_fabsf(zd - z) <= c.max_jump) {
-            float p[3], pl[3], pr[3], pu[3], pd[3];
-            back_project(u, v, z, c, p);
-            back_project(u - 1, v, zl, c, pl);
-            back_project(u + 1, v, zr, c, pr);
-            back_project(u, v - 1, zu, c, pu);
-            back_project(u, v + 1, zd, c, pd);
-            const float ax = pr[0] - pl[0], ay = pr[1] - pl[1], az = pr[2] - pl[2];
-            const float bx = pd[0] - pu[0], by = pd[1] - pu[1], bz = pd[2] - pu[2];
-            float nx = ay * bz - az * by, ny = az * bx - ax * bz, nz = ax * by - ay * bx;
-            const float len = pm_sqrtf(nx * nx + ny * ny + nz * nz);
-            if (len > 0.0f && len <= 3.0e38f) {
-                nx = nx / len;
-                ny = ny / len;
-                nz = nz / len;
-                if (nx * p[0] + ny * p[1] + nz * p[2] > 0.0f) {
-                    nx = -nx;
-                    ny = -ny;
-                    nz = -nz;
-                }
-                float *o = out6 + 6 * i;
-                o[0] = p[0]; o[1] = p[1]; o[2] = p[2];
-                o[3] = nx; o[4] = ny; o[5] = nz;
-                ok = 1;
-            }
+            depth_point_normal(u, v, z, zl, zr, zu, zd, c, p, n)) {
+            float *o = out6 + 6 * i;
+            o[0] = p[0]; o[1] = p[1]; o[2] = p[2];
+            o[3] = n[0]; o[4] = n[1]; o[5] = n[2];
+            ok = 1;
         }
     }
     flags[i] = ok;

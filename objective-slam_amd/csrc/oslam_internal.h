@@ -81,6 +81,8 @@ struct oslam_view {
     int dev;
     oslamk_view k;
     float *d_z;
+    float max_jump;                   /* of the camera: the normal map's depth-step limit */
+    float *d_maps;                    /* vertex and normal map of the tracking stage (oslam_track.c), NULL until the first */
 };
 
 typedef struct db_group {
@@ -209,6 +211,16 @@ void oslam_verify_set_member(oslamk_verify_member *d, const oslam_model *m, cons
  * oslam_verify's for it alone */
 int oslam_verify_members(oslam_model *const *ms, size_t n, const oslam_view *v, const float *T, const oslam_verify_params *p,
                          oslam_verify_result *res);
+
+/* ---- tracking (oslam_track.c) ---- */
+/* tp NULL = defaults; checks them as oslam_track does, *out = the parameters in force */
+int oslam_track_check_params(const oslam_track_params *tp, oslam_track_params *out);
+/* gives back the view's maps; called by oslam_view_destroy with the view's device bound */
+void oslam_track_release_maps(oslam_view *v);
+/* gives back the pinned record of the tracking stage; called by oslam_release_scratch */
+void oslam_track_release(void);
+/* the arbitration's parameter check (oslam_arbitrate.c) */
+int oslam_arbitrate_check_params(const oslam_arbitrate_params *ap, oslam_arbitrate_params *out);
 
 /* gives back the pinned record of the arbitration stage (oslam_arbitrate.c); called by oslam_release_scratch */
 void oslam_arbitrate_release(void);

@@ -433,6 +433,40 @@ int oslamk_claim(const oslamk_view *v, const oslamk_verify_member *d_mem, uint32
 int oslamk_arbitrate(const oslamk_verify_member *d_mem, uint32_t n_mem, uint32_t n_tiles, const unsigned long long *claims,
                      uint32_t min_tiles, float min_owned_share, oslamk_arb_rec *rec, void *stream);
 
+/* ---- tracking stage (oslam_track.hip; semantics in include/oslam.h at oslam_track) ---- */
+#define OSLAMK_TRACK_THREADS 256      /* the one workgroup of a hypothesis; a block of the sums is 256 model points */
+
+/* one hypothesis of a tracking call; the host fills everything */
+typedef struct oslamk_track_member {
+    double T[12];              /* rows of [R | t]: the input pose (float32 values) */
+    double cm[3];              /* model centroid (double mean of the points) */
+    oslamk_cloud m;            /* the model's points and normals (SoA in HBM) */
+    float c[3];                /* float32 rounding of T * cm */
+    float r2_corr, min_dot;
+    float stop_rot, stop_trans;   /* stop_trans in scene units */
+    float tol;                 /* of the judgement: (float)((double)depth_tol * d_dist) */
+    uint32_t max_iter;
+    uint32_t n_blocks;         /* ceil(m.n / OSLAMK_TRACK_THREADS); 0 = skipped */
+} oslamk_track_member;
+
+/* what k_track leaves for a hypothesis that is not skipped */
+typedef struct oslamk_track_rec {
+    float T[12];               /* the final float32 pose */
+    uint32_t counts[OSLAMK_VERIFY_CLASSES];   /* the classes of oslam_verify at that pose */
+    uint32_t n_corr, iterations;
+    int32_t converged, pad;
+} oslamk_track_rec;
+
+/* maps[(v * w + u) * 8 ..]: x y z has | nx ny nz 0 of pixel (u, v), has = 1.0f where the pixel has a normal (zeros
+ * elsewhere); from the z image of the view */
+int oslamk_view_normals(const oslamk_view *v, float max_jump, float *maps, void *stream);
+/* one workgroup per member: every iteration, then the judgement -> rec[n_mem] */
+int oslamk_track(const oslamk_view *v, const float *maps, const oslamk_track_member *d_mem, uint32_t n_mem, int window,
+                 oslamk_track_rec *rec, void *stream);
+/* tap: pixel_out[i] = pixel of the correspondence of member 0's point i, -1 = none */
+int oslamk_track_corr(const oslamk_view *v, const float *maps, const oslamk_track_member *d_mem, uint32_t n_blocks,
+                      int32_t *pixel_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,7 @@
 #include <stdint.h>
 
 #include "oslam_kernels.h"
+#include "oslam_refine_step.h"
 
 /* ---------------------------------------------------------------- scene grid */
 __device__ __forceinline__ int grid_axis(float x, double lo, double inv, int dim)
@@ -192,38 +193,14 @@ __global__ __launch_bounds__(OSLAMK_REFINE_THREADS) void k_refine_corr(const osl
         } else if (found) {
             const float4 a = pts[2 * (size_t)best_pos];
             const float4 b = pts[2 * (size_t)best_pos + 1];
-            const float ex = qx - a.x, ey = qy - a.y, ez = qz - a.z;
-            const float r = (b.x * ex + b.y * ey) + b.z * ez;
-            const float ux = qx - d->c[0], uy = qy - d->c[1], uz = qz - d->c[2];
-            float J[6];
-            J[0] = uy * b.z - uz * b.y;
-            J[1] = uz * b.x - ux * b.z;
-            J[2] = ux * b.y - uy * b.x;
-            J[3] = b.x;
-            J[4] = b.y;
-            J[5] = b.z;
-            int k = 0;
-#pragma unroll
-            for (int u = 0; u < 6; u++)
-#pragma unroll
-                for (int v = u; v < 6; v++) s[k++] = J[u] * J[v];
-#pragma unroll
-            for (int u = 0; u < 6; u++) s[21 + u] = J[u] * r;
-            s[27] = 1.0f;
-            s[28] = r * r;
+            oslam_refine_point_sums(qx, qy, qz, a, b, d->c, s);
         }
     }
     if (MODE == OSLAMK_REFINE_TAP) return;
 
     /* fixed-order reduction: shuffle tree inside each wave, then the waves in index order */
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < NS; k++) {
-        float v = s[k];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-        s[k] = v;
-    }
+    oslam_refine_wave_sums<NS>(s);
     if (lane == 0) {
 #pragma unroll
         for (int k = 0; k < NS; k++) sh[w][k] = s[k];
@@ -238,11 +215,6 @@ __global__ __launch_bounds__(OSLAMK_REFINE_THREADS) void k_refine_corr(const osl
 }
 
 /* ---------------------------------------------------------------- solve */
-__device__ void rot_apply(const double R[9], const double x[3], double y[3])
-{
-    for (int a = 0; a < 3; a++) y[a] = (R[3 * a] * x[0] + R[3 * a + 1] * x[1]) + R[3 * a + 2] * x[2];
-}
-
 __device__ void member_stop(oslamk_refine_member *d, uint32_t *n_done)
 {
     d->done = 1;
@@ -265,86 +237,10 @@ __global__ __launch_bounds__(64) void k_refine_solve(oslamk_refine_member *mem, 
     __syncthreads();
     if (lane != 0) return;
 
-    const double count = S[27];
-    d->n_corr = (int32_t)count;
-    if (count < 6.0) { member_stop(d, n_done); return; }
-    double A[36], x[6], L[36];
-    int k = 0;
-    for (int u = 0; u < 6; u++)
-        for (int v = u; v < 6; v++) {
-            A[6 * u + v] = S[k];
-            A[6 * v + u] = S[k];
-            k++;
-        }
-    const double mu = 1e-6 * (((((A[0] + A[7]) + A[14]) + A[21]) + A[28]) + A[35]) / 6.0;
-    for (int u = 0; u < 6; u++) A[7 * u] += mu;
-    /* Cholesky A = L L^T */
-    for (int u = 0; u < 6; u++) {
-        for (int v = 0; v <= u; v++) {
-            double t = A[6 * u + v];
-            for (int q = 0; q < v; q++) t -= L[6 * u + q] * L[6 * v + q];
-            if (u == v) {
-                if (!(t > 0.0)) { member_stop(d, n_done); return; }
-                L[7 * u] = sqrt(t);
-            } else {
-                L[6 * u + v] = t / L[7 * v];
-            }
-        }
-    }
-    double y[6];
-    for (int u = 0; u < 6; u++) {
-        double t = -S[21 + u];                      /* b = -sum J^T r */
-        for (int q = 0; q < u; q++) t -= L[6 * u + q] * y[q];
-        y[u] = t / L[7 * u];
-    }
-    for (int u = 5; u >= 0; u--) {
-        double t = y[u];
-        for (int q = u + 1; q < 6; q++) t -= L[6 * q + u] * x[q];
-        x[u] = t / L[7 * u];
-    }
-
-    /* dR = Rodrigues(omega) */
-    const double th = sqrt((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2]);
-    double dR[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-    if (th > 0.0) {
-        const double kx = x[0] / th, ky = x[1] / th, kz = x[2] / th;
-        const double cs = cos(th), sn = sin(th), vc = 1.0 - cs;
-        dR[0] = cs + kx * kx * vc;      dR[1] = kx * ky * vc - kz * sn; dR[2] = kx * kz * vc + ky * sn;
-        dR[3] = ky * kx * vc + kz * sn; dR[4] = cs + ky * ky * vc;      dR[5] = ky * kz * vc - kx * sn;
-        dR[6] = kz * kx * vc - ky * sn; dR[7] = kz * ky * vc + kx * sn; dR[8] = cs + kz * kz * vc;
-    }
-    double R[9], t[3], c[3], Rn[9], tn[3], dRc[3], dRt[3];
-    for (int a = 0; a < 3; a++) {
-        R[3 * a] = d->T[4 * a]; R[3 * a + 1] = d->T[4 * a + 1]; R[3 * a + 2] = d->T[4 * a + 2];
-        t[a] = d->T[4 * a + 3];
-    }
-    rot_apply(R, d->cm, c);
-    for (int a = 0; a < 3; a++) c[a] += t[a];
-    rot_apply(dR, c, dRc);
-    rot_apply(dR, t, dRt);
-    for (int a = 0; a < 3; a++) {
-        for (int b = 0; b < 3; b++)
-            Rn[3 * a + b] = (dR[3 * a] * R[b] + dR[3 * a + 1] * R[3 + b]) + dR[3 * a + 2] * R[6 + b];
-        tn[a] = dRt[a] + ((c[a] - dRc[a]) + x[3 + a]);
-    }
-    /* Gram-Schmidt over the columns x, y, z */
-    for (int col = 0; col < 3; col++) {
-        for (int prev = 0; prev < col; prev++) {
-            const double p = (Rn[prev] * Rn[col] + Rn[3 + prev] * Rn[3 + col]) + Rn[6 + prev] * Rn[6 + col];
-            for (int a = 0; a < 3; a++) Rn[3 * a + col] -= p * Rn[3 * a + prev];
-        }
-        const double nrm = sqrt((Rn[col] * Rn[col] + Rn[3 + col] * Rn[3 + col]) + Rn[6 + col] * Rn[6 + col]);
-        for (int a = 0; a < 3; a++) Rn[3 * a + col] /= nrm;
-    }
-    for (int a = 0; a < 3; a++) {
-        d->T[4 * a] = Rn[3 * a]; d->T[4 * a + 1] = Rn[3 * a + 1]; d->T[4 * a + 2] = Rn[3 * a + 2];
-        d->T[4 * a + 3] = tn[a];
-    }
-    for (int q = 0; q < 12; q++) d->Tf[q] = (float)d->T[q];
-    rot_apply(Rn, d->cm, c);
-    for (int a = 0; a < 3; a++) d->c[a] = (float)(c[a] + tn[a]);
+    d->n_corr = (int32_t)S[27];
+    double th, vn;
+    if (!oslam_refine_step(S, d->T, d->cm, d->Tf, d->c, &th, &vn)) { member_stop(d, n_done); return; }
     d->iterations += 1;
-    const double vn = sqrt((x[3] * x[3] + x[4] * x[4]) + x[5] * x[5]);
     if (th < (double)d->stop_rot && vn < (double)d->stop_trans) {
         d->converged = 1;
         member_stop(d, n_done);

@@ -42,6 +42,7 @@ int oslam_view_create(const void *depth, int depth_is_u16, int width, int height
     v->k.cy = cam->cy;
     v->k.z_min = cam->z_min;
     v->k.z_max = cam->z_max;
+    v->max_jump = cam->max_jump;
 done:
     if (rc != OSLAM_OK) (void)hipStreamSynchronize((hipStream_t)oslam_stream());
     oslam_dev_free(d_raw);
@@ -58,7 +59,10 @@ int oslam_view_destroy(oslam_view *v)
 {
     if (!v) return fail(OSLAM_E_INVALID, "view is NULL");
     /* every call that read the image ended with a synchronisation of its stream */
-    if (hipSetDevice(v->dev) == hipSuccess) (void)hipFree(v->d_z);
+    if (hipSetDevice(v->dev) == hipSuccess) {
+        oslam_track_release_maps(v);
+        (void)hipFree(v->d_z);
+    }
     free(v);
     return OSLAM_OK;
 }

@@ -130,6 +130,37 @@ class Detection(C.Structure):
                 "verify": self.verify.asdict(), "arbitrate": self.arbitrate.asdict()}
 
 
+class TrackParams(C.Structure):
+    _fields_ = [("max_iterations", C.c_uint), ("max_corr_dist", C.c_float), ("min_normal_dot", C.c_float),
+                ("stop_rot", C.c_float), ("stop_trans", C.c_float), ("verify", VerifyParams), ("reserved", C.c_int * 4)]
+
+
+class TrackResult(C.Structure):
+    _fields_ = [("verify", VerifyResult), ("iterations", C.c_uint32), ("correspondences", C.c_uint32),
+                ("converged", C.c_int32), ("found", C.c_int32), ("launches", C.c_uint32), ("ms_total", C.c_float)]
+
+    def asdict(self):
+        return {"verify": self.verify.asdict(), "iterations": int(self.iterations),
+                "correspondences": int(self.correspondences), "converged": int(self.converged), "found": int(self.found),
+                "launches": int(self.launches), "ms_total": float(self.ms_total)}
+
+
+class TrackerParams(C.Structure):
+    _fields_ = [("track", TrackParams), ("detect", DetectParams), ("arbitrate", ArbitrateParams), ("max_misses", C.c_uint),
+                ("detect_every", C.c_uint), ("assoc_min_separation", C.c_float), ("assoc_max_angle", C.c_float),
+                ("reserved", C.c_int * 4)]
+
+
+class TrackState(C.Structure):
+    _fields_ = [("id", C.c_uint32), ("model", C.c_uint32), ("T", C.c_float * 16), ("age", C.c_uint32), ("hits", C.c_uint32),
+                ("misses", C.c_uint32), ("found", C.c_int32), ("track", TrackResult)]
+
+    def asdict(self):
+        return {"id": int(self.id), "model": int(self.model), "T": np.array(self.T, np.float32).reshape(4, 4),
+                "age": int(self.age), "hits": int(self.hits), "misses": int(self.misses), "found": int(self.found),
+                "track": self.track.asdict()}
+
+
 ARBITRATE_MAX_HYPOTHESES = 1024
 CELL_DTYPE = np.dtype([("code", "<u8"), ("count", "<u4"), ("pad", "<u4")])
 
@@ -202,6 +233,19 @@ _SIGNATURES = {
                                     C.POINTER(_sz)]),
     "oslam_detect_params_default": (_i, [C.POINTER(DetectParams)]),
     "oslam_db_detect": (_i, [_vp, _vp, _vp, C.POINTER(DetectParams), _vp, _sz, C.POINTER(_sz)]),
+    "oslam_track_params_default": (_i, [C.POINTER(TrackParams)]),
+    "oslam_track": (_i, [_vp, _vp, _sz, _vp, C.POINTER(TrackParams), _vp, _vp]),
+    "oslam_db_track": (_i, [_vp, _vp, _vp, _sz, _vp, C.POINTER(TrackParams), _vp, _vp]),
+    "oslam_view_normals": (_i, [_vp, _vp, _vp]),
+    "oslam_view_vertices": (_i, [_vp, _vp]),
+    "oslam_track_correspondences": (_i, [_vp, _vp, _vp, _f, _f, _vp]),
+    "oslam_tracker_params_default": (_i, [C.POINTER(TrackerParams)]),
+    "oslam_tracker_create": (_i, [_vp, C.POINTER(TrackerParams), C.POINTER(_vp)]),
+    "oslam_tracker_create_shapes": (_i, [_vp, _vp, _sz, C.POINTER(TrackerParams), C.POINTER(_vp)]),
+    "oslam_tracker_destroy": (None, [_vp]),
+    "oslam_tracker_update": (_i, [_vp, _vp, _sz]),
+    "oslam_tracker_tracks": (_i, [_vp, _vp, _sz, C.POINTER(_sz)]),
+    "oslam_tracker_step": (_i, [_vp, _vp, _vp, _vp, _sz, C.POINTER(_sz), C.POINTER(_i)]),
     "oslam_scene_keys": (_i, [_vp, _sz, _vp]),
     "oslam_model_keys": (_i, [_vp, _sz, _vp]),
     "oslam_model_bucket": (_i, [_vp, C.c_uint32, _vp, _sz, C.POINTER(_sz)]),
@@ -306,6 +350,28 @@ def default_detect_params():
     return p
 
 
+def default_track_params(**kw):
+    """oslam_track_params_default, then the fields given as keywords (verify: a VerifyParams)."""
+    p = TrackParams()
+    _check(lib().oslam_track_params_default(C.byref(p)))
+    for k, v in kw.items():
+        if not hasattr(p, k) or k == "reserved":
+            raise TypeError("unknown track parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def default_tracker_params(**kw):
+    """oslam_tracker_params_default, then the fields given as keywords (track / detect / arbitrate: their structures)."""
+    p = TrackerParams()
+    _check(lib().oslam_tracker_params_default(C.byref(p)))
+    for k, v in kw.items():
+        if not hasattr(p, k) or k == "reserved":
+            raise TypeError("unknown tracker parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
 def _hypotheses(models, T):
     """-> (array of model handles, T [H,16] float32, H)"""
     models = list(models)
@@ -323,6 +389,107 @@ def arbitrate(models, view, T, params=None):
     _check(lib().oslam_arbitrate(arr, _p(Ti), H, view._h, C.byref(p), res))
     out = [res[h].asdict() for h in range(H)]
     return out, np.array([bool(r["kept"]) for r in out], dtype=bool)
+
+
+def _track_out(To, res, H):
+    out = [res[h].asdict() for h in range(H)]
+    return To.reshape(H, 4, 4), out, np.array([bool(r["found"]) for r in out], dtype=bool)
+
+
+def track(models, view, T, params=None):
+    """The hypotheses (models[h], T[h]) followed into the view's depth image by projective ICP and judged there
+    (oslam_track); an all-zero T[h] is skipped.  -> (T [H,4,4], list of result dicts, found bool [H])."""
+    arr, Ti, H = _hypotheses(models, T)
+    To = np.zeros((max(H, 1), 16), np.float32)
+    res = (TrackResult * max(H, 1))()
+    p = params if params is not None else default_track_params()
+    _check(lib().oslam_track(arr, _p(Ti), H, view._h, C.byref(p), _p(To), res))
+    return _track_out(To[:H], res, H)
+
+
+def track_correspondences(model, view, T, max_corr_dist=2.0, min_normal_dot=0.8):
+    """Pixel v * width + u of every model point's correspondence under T, -1 = none (oslam_track_correspondences: the
+    rule of oslam_track, as a test tap)."""
+    out = np.zeros(model.n, np.int32)
+    _check(lib().oslam_track_correspondences(model._h, view._h, _p(_pose16(T)), float(max_corr_dist), float(min_normal_dot),
+                                             _p(out)))
+    return out
+
+
+def view_normals(view):
+    """The view's vertex and normal maps as a test tap (oslam_view_vertices / oslam_view_normals): -> (vertices [h,w,3],
+    normals [h,w,3], has_normal bool [h,w])."""
+    n = view.width * view.height
+    vtx, nrm, has = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32), np.zeros(n, np.uint8)
+    _check(lib().oslam_view_normals(view._h, _p(nrm), _p(has)))
+    _check(lib().oslam_view_vertices(view._h, _p(vtx)))
+    shape = (view.height, view.width)
+    return vtx.reshape(shape + (3,)), nrm.reshape(shape + (3,)), has.reshape(shape).astype(bool)
+
+
+class Tracker:
+    """Identity across depth frames (oslam_tracker): Tracker(db, params).step(view, scene=None) follows every live track
+    into the frame and, when a scene is given and a search is due, runs db.detect and folds its detections in;
+    .update(detections) is that last step alone (host only).  Tracker.from_shapes(centroids, extents) makes one without
+    a database, for update() on a machine without a device."""
+
+    def __init__(self, db, params=None, _shapes=None):
+        self._h = C.c_void_p(0)
+        self.db = db
+        self.params = params if params is not None else default_tracker_params()
+        if _shapes is None:
+            _check(lib().oslam_tracker_create(db._h, C.byref(self.params), C.byref(self._h)))
+        else:
+            c, e = _shapes
+            _check(lib().oslam_tracker_create_shapes(_p(c), _p(e), len(e), C.byref(self.params), C.byref(self._h)))
+
+    @classmethod
+    def from_shapes(cls, centroids, extents, params=None):
+        c = np.ascontiguousarray(np.asarray(centroids, np.float32).reshape(-1, 3))
+        e = np.ascontiguousarray(extents, np.float32).reshape(-1)
+        if len(c) != len(e):
+            raise ValueError("centroids and extents differ in length")
+        return cls(None, params, _shapes=(c, e))
+
+    def tracks(self):
+        """The live tracks ordered by id, as dicts (id, model, T 4x4, age, hits, misses, found, track)."""
+        n = C.c_size_t(0)
+        rc = lib().oslam_tracker_tracks(self._h, None, 0, C.byref(n))
+        if rc not in (OSLAM_OK, OSLAM_E_LIMIT):
+            _check(rc)
+        out = (TrackState * max(n.value, 1))()
+        _check(lib().oslam_tracker_tracks(self._h, out, max(n.value, 1), C.byref(n)))
+        return [out[k].asdict() for k in range(n.value)]
+
+    def update(self, detections):
+        """Fold a detection list (dicts with model and T, as Database.detect returns them) into the tracks."""
+        det = (Detection * max(len(detections), 1))()
+        for k, d in enumerate(detections):
+            det[k].model = int(d["model"])
+            det[k].instance = int(d.get("instance", 0))
+            det[k].T[:] = [float(x) for x in np.asarray(d["T"], np.float32).reshape(16)]
+        _check(lib().oslam_tracker_update(self._h, det, len(detections)))
+        return self.tracks()
+
+    def step(self, view, scene=None):
+        """One frame.  -> (live tracks as dicts, searched bool)."""
+        cap = ARBITRATE_MAX_HYPOTHESES + max(1, len(self.db.models)) * MAX_INSTANCES
+        out = (TrackState * cap)()
+        n, searched = C.c_size_t(0), C.c_int(0)
+        _check(lib().oslam_tracker_step(self._h, scene._h if scene is not None else None, view._h, out, cap, C.byref(n),
+                                        C.byref(searched)))
+        return [out[k].asdict() for k in range(n.value)], bool(searched.value)
+
+    def close(self):
+        if self._h:
+            lib().oslam_tracker_destroy(self._h)
+            self._h = C.c_void_p(0)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def arbitrate_claims(models, view, T, params=None):
@@ -739,6 +906,18 @@ class Database:
         _check(lib().oslam_db_detect(self._h, scene._h, view._h, C.byref(p), out, cap, C.byref(n)))
         return [out[k].asdict() for k in range(n.value)]
 
+    def track(self, view, members, T, params=None):
+        """The hypotheses (member members[h], T[h]) followed into the view's depth image (oslam_db_track; all-zero =
+        skipped).  -> (T [H,4,4], list of result dicts, found bool [H])."""
+        mem = np.ascontiguousarray(members, np.uint32).reshape(-1)
+        H = len(mem)
+        Ti = np.ascontiguousarray(np.asarray(T, np.float32).reshape(H, 16))
+        To = np.zeros((max(H, 1), 16), np.float32)
+        res = (TrackResult * max(H, 1))()
+        p = params if params is not None else default_track_params()
+        _check(lib().oslam_db_track(self._h, _p(mem), _p(Ti), H, view._h, C.byref(p), _p(To), res))
+        return _track_out(To[:H], res, H)
+
     def find_instances(self, scene, refine=True, params=None, refine_params=None):
         """Every instance of every member in one frame (oslam_db_align_instances): -> one list per member, as
         Model.find_instances returns it."""
@@ -957,7 +1136,7 @@ def depth_to_cloud(depth, fx, fy, cx, cy, depth_scale=0.001, z_min=0.1, z_max=10
 
 class View:
     """A depth image on the device as float z, for verification (oslam_view): the camera and depth conventions of
-    depth_to_cloud (z = raw * depth_scale, valid in [z_min, z_max]; max_jump is accepted and not used)."""
+    depth_to_cloud (z = raw * depth_scale, valid in [z_min, z_max]; max_jump limits the normal map of the tracking stage)."""
 
     def __init__(self, depth, fx, fy, cx, cy, depth_scale=0.001, z_min=0.1, z_max=10.0, max_jump=0.05, dev=0):
         self._h = C.c_void_p(0)

@@ -204,3 +204,24 @@ def render_depth(points, width=640, height=480, fx=525.0, fy=525.0, cx=319.5, cy
     bg = 0 if background_z is None else int(round(background_z / depth_scale))
     img[img == 65536] = bg
     return img.reshape(height, width).astype(np.uint16)
+
+
+def smooth_motion_poses(d_dist, frames=10, seed=93, deg=3.0, step=0.5, axis=(1.0, 2.0, 0.5)):
+    """Ground-truth poses (float32 4x4, model -> camera) of an object that moves smoothly before the camera: a seeded
+    start rotation, then per frame `deg` degrees about `axis` (applied on the left) and `step` d_dist along x, z from
+    5.5 m receding 5 cm per frame.  For the tracking tests and bench; render each with render_depth."""
+    rng = SplitMix64(seed)
+    R = random_rotation(rng)
+    k = np.asarray(axis, np.float64)
+    k = k / np.linalg.norm(k)
+    th = np.radians(deg)
+    K = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+    dR = np.cos(th) * np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * np.outer(k, k)
+    out = []
+    for f in range(frames):
+        T = np.eye(4)
+        T[:3, :3] = R
+        T[:3, 3] = [-0.4 + step * float(d_dist) * f, 0.1, 5.5 + 0.05 * f]
+        out.append(T.astype(np.float32))
+        R = dR @ R
+    return out

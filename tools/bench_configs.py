@@ -15,6 +15,9 @@ configuration; these are not bench lines).  Needs a HIP device.
                                          ms per frame, and the found sets of refine and of verify on every frame
   python tools/bench_configs.py instances  oslam_align_instances next to oslam_align (bench registration, a scene
                                          with 3 copies: recall and false detections) and db.find_instances on db50
+  python tools/bench_configs.py track    the db50 stream with smooth motion over 30 frames: db.detect on every frame next
+                                         to Tracker.step (detect_every 10, the scene built on search frames only), and
+                                         db.track per call for 1 and 50 hypotheses next to db.refine + db.verify
 One JSON line each."""
 import importlib, json, os, sys, time
 
@@ -502,7 +505,111 @@ def arbitrate(frames=10):
     return out
 
 
+def track(frames=30, calls=20):
+    """Tracking (oslam_db_track, oslam_tracker_step) on the db50 stream with smooth motion (synth.smooth_motion_poses: 3
+    degrees and 0.5 d_dist per frame): (a) db.detect on every frame, (b) Tracker.step with detect_every 10, building the
+    scene only on search frames, (c) db.track alone per call, inside the library and from Python, for 1 and for 50
+    hypotheses, next to db.refine + db.verify on the same poses."""
+    n_models = 50
+    raw = [synth.make_model(k, 1500) for k in range(n_models)]
+    d = synth.d_dist_for(raw[0][0], 0.05)
+    grids = [ppf.voxel_grid(c[0], c[1], leaf=d) for c in raw]
+    dense, _ = synth.make_model(0, 300000)
+    poses = synth.smooth_motion_poses(d, frames=frames)
+    imgs = [synth.render_depth(dense @ T[:3, :3].T.astype(np.float64) + T[:3, 3], background_z=9.0, splat=1) for T in poses]
+    models = [ppf.Model(g[0], g[1], d_dist=d) for g in grids]
+    db = ppf.Database(models)
+
+    def scene_of(img):
+        return ppf.Scene.from_depth(img, 525.0, 525.0, 319.5, 239.5, leaf=d, d_dist=0.0, ref_point_downsample_factor=4,
+                                    z_min=0.5, z_max=12.0, max_jump=0.08)
+
+    def view_of(img):
+        return ppf.View(img, 525.0, 525.0, 319.5, 239.5, z_min=0.5, z_max=12.0, max_jump=0.08)
+
+    def detect(img):
+        sc, view = scene_of(img), view_of(img)
+        det = db.detect(sc, view)
+        view.close()
+        sc.close()
+        return det
+
+    def tracked():
+        tracker = ppf.Tracker(db, ppf.default_tracker_params(detect_every=10))
+        rows = []
+        for f, img in enumerate(imgs):
+            view = view_of(img)
+            sc = scene_of(img) if f % 10 == 0 or not rows or not rows[-1][0] else None
+            tr, searched = tracker.step(view, sc)
+            rows.append((tr, searched))
+            if sc is not None:
+                sc.close()
+            view.close()
+        tracker.close()
+        return rows
+
+    def err(T, f):
+        Rd = T[:3, :3].astype(np.float64) @ poses[f][:3, :3].astype(np.float64).T
+        s = np.linalg.norm([Rd[2, 1] - Rd[1, 2], Rd[0, 2] - Rd[2, 0], Rd[1, 0] - Rd[0, 1]]) / 2
+        return (float(np.degrees(np.arctan2(s, (np.trace(Rd) - 1) / 2))), float(np.linalg.norm(T[:3, 3] - poses[f][:3, 3]) / d))
+    detect(imgs[0])
+    t = time.perf_counter(); ds = [detect(im) for im in imgs]; el_a = time.perf_counter() - t
+    tracked()
+    t = time.perf_counter(); rows = tracked(); el_b = time.perf_counter() - t
+    errs = [max([err(x["T"], f) for x in tr if x["model"] == 0 and x["found"]] or [(None, None)]) for f, (tr, _) in enumerate(rows)]
+
+    # (c) one call: frame 1 from the poses of frame 0 (every member at the rendered object's pose), 1 and 50 hypotheses
+    view, sc = view_of(imgs[1]), scene_of(imgs[1])
+    per_call = {}
+    for H in (1, n_models):
+        T0 = np.repeat(poses[0][None], H, axis=0)
+        members = np.arange(H)
+        sub = db if H == n_models else None
+        db.track(view, members, T0)
+        py, lib_ms, launches = [], [], 0
+        for _ in range(calls):
+            t = time.perf_counter()
+            _, res, _ = db.track(view, members, T0)
+            py.append(1e3 * (time.perf_counter() - t))
+            lib_ms.append(res[0]["ms_total"])
+            launches = res[0]["launches"]
+        per_call["track_%d" % H] = {"ms_python_median": float(np.median(py)), "ms_library_median": float(np.median(lib_ms)),
+                                    "launches": launches, "iterations": [r["iterations"] for r in res][:4]}
+        if sub is not None:
+            Tr, rr, _ = db.refine(sc, T0)
+            py_r, lib_r, py_v, lib_v = [], [], [], []
+            for _ in range(calls):
+                t = time.perf_counter(); Tr, rr, _ = db.refine(sc, T0); py_r.append(1e3 * (time.perf_counter() - t))
+                lib_r.append(rr[0]["ms_total"])
+                t = time.perf_counter(); vr, _ = db.verify(view, Tr); py_v.append(1e3 * (time.perf_counter() - t))
+                lib_v.append(vr[0]["ms_total"])
+            per_call["refine_%d" % H] = {"ms_python_median": float(np.median(py_r)), "ms_library_median": float(np.median(lib_r)),
+                                         "launches": rr[0]["launches"]}
+            per_call["verify_%d" % H] = {"ms_python_median": float(np.median(py_v)), "ms_library_median": float(np.median(lib_v)),
+                                         "launches": vr[0]["launches"]}
+    m0 = models[0]
+    Tr, rr = m0.refine(sc, poses[0]); m0.verify(view, Tr)
+    py_r, lib_r, py_v, lib_v = [], [], [], []
+    for _ in range(calls):
+        t = time.perf_counter(); Tr, rr = m0.refine(sc, poses[0]); py_r.append(1e3 * (time.perf_counter() - t)); lib_r.append(rr["ms_total"])
+        t = time.perf_counter(); vr = m0.verify(view, Tr); py_v.append(1e3 * (time.perf_counter() - t)); lib_v.append(vr["ms_total"])
+    per_call["refine_1"] = {"ms_python_median": float(np.median(py_r)), "ms_library_median": float(np.median(lib_r)), "launches": rr["launches"]}
+    per_call["verify_1"] = {"ms_python_median": float(np.median(py_v)), "ms_library_median": float(np.median(lib_v)), "launches": vr["launches"]}
+    view.close()
+    sc.close()
+    out = {"config": "tracking (oslam_db_track, oslam_tracker_step) on the db50 stream with smooth motion", "frames": frames,
+           "models": n_models, "frames_per_s_detect_every_frame": frames / el_a, "frames_per_s_tracker_detect_every_10": frames / el_b,
+           "searched_frames": [f for f, (_, s) in enumerate(rows) if s],
+           "tracks_per_frame": [[(x["id"], x["model"], x["found"]) for x in tr] for tr, _ in rows],
+           "model0_rot_deg_trans_d_dist": [(None if e[0] is None else round(e[0], 3), None if e[1] is None else round(e[1], 3)) for e in errs],
+           "detect": [[(g["model"], g["instance"]) for g in det] for det in ds], "per_call": per_call}
+    db.close()
+    for m in models:
+        m.close()
+    return out
+
+
 if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "cfg3"
     print(json.dumps({"cfg2": cfg2, "cfg3": cfg3, "cfg3db": cfg3db, "cfg4": cfg4, "cfg5": cfg5, "planes": planes, "db50": db50,
-                      "refine": refine, "verify": verify, "instances": instances, "arbitrate": arbitrate}[which]()), flush=True)
+                      "refine": refine, "verify": verify, "instances": instances, "arbitrate": arbitrate, "track": track}[which]()), flush=True)
