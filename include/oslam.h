@@ -624,6 +624,15 @@ int oslam_db_arbitrate(oslam_db *db, const oslam_view *v, const float *T, const 
 int oslam_arbitrate_claims(oslam_model *const *models, const float *T, size_t H, const oslam_view *v,
                            const oslam_arbitrate_params *ap, uint32_t *cnt_out, uint64_t *sum_out, size_t cap,
                            uint32_t *tile_out, size_t *n_tiles_out);
+/* test tap: the elimination (k_arbitrate) alone over a table the caller gives, so that exact ties and large counts can
+ * be put before it: cnt [H][n_tiles] (each below 2^24), sum [H][n_tiles] (each below 2^40), skipped [H] (non-zero: a
+ * skipped hypothesis), packed into the words k_claim writes, on device 0.  res [H] as oslam_arbitrate fills it with
+ * tol = 1 (mean_residual = (sum of q / points) / 65535) and tile 0; *rounds_out = rounds.  The checks of
+ * oslam_arbitrate: NULL pointers, H == 0 or above the maximum, n_tiles == 0, min_owned_share not finite or outside
+ * [0, 1] and an entry that does not fit its field are OSLAM_E_INVALID, a table above 256 MiB is OSLAM_E_LIMIT, before
+ * any device call; when every hypothesis is skipped nothing is launched. */
+int oslam_arbitrate_table(const uint32_t *cnt, const uint64_t *sum, const uint8_t *skipped, size_t H, size_t n_tiles,
+                          unsigned min_tiles, float min_owned_share, oslam_arbitrate_result *res, uint32_t *rounds_out);
 
 /* ---- the whole chain for a database frame in one call: oslam_db_align_instances (with refinement) -> the
  * verification of every instance (oslam_verify semantics, one set of launches) -> arbitration over all instances, those

@@ -97,6 +97,52 @@ static int choose_tile(oslam_model *const *ms, const float *T, size_t H, const o
     return !(t >= 4.0) ? 4 : t > 128.0 ? 128 : (int)t;
 }
 
+/* The elimination of a call whose block `dev` holds the descriptors at 0, the claims table at off_tbl and room for
+ * 1 + H records at off_rec: k_arbitrate, the records back through the pinned g_rec (made on first use) with one host
+ * wait, res[h] filled for every hypothesis that is not skipped.  The caller holds g_rec_mu. */
+static int run_elimination(char *dev, size_t off_tbl, size_t off_rec, const oslamk_verify_member *hm, size_t H,
+                           uint32_t n_tiles, uint32_t min_tiles, float min_owned_share, void *stream,
+                           oslam_arbitrate_result *res, uint32_t *rounds)
+{
+    int rc = OSLAM_OK;
+    size_t h;
+    if (!g_rec)
+        HIPCHK(hipHostMalloc((void **)&g_rec, sizeof *g_rec * (1 + OSLAMK_ARB_MAX_HYP), hipHostMallocPortable));
+    KCHK(oslamk_arbitrate((const oslamk_verify_member *)dev, (uint32_t)H, n_tiles, (const unsigned long long *)(dev + off_tbl),
+                          min_tiles, min_owned_share, (oslamk_arb_rec *)(dev + off_rec), stream));
+    HIPCHK(hipMemcpyAsync(g_rec, dev + off_rec, sizeof *g_rec * (1 + H), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    *rounds = g_rec[0].claimed;
+    for (h = 0; h < H; h++) {
+        const oslamk_arb_rec *k = &g_rec[1 + h];
+        oslam_arbitrate_result *r = &res[h];
+        if (hm[h].n_blocks == 0) continue;
+        r->claimed = k->claimed;
+        r->owned = k->owned;
+        r->share = k->share;
+        r->kept = k->kept;
+        r->suppressed_by = k->suppressed_by;
+        r->mean_residual = k->cnt_total ? (float)((((double)k->sum_total / (double)k->cnt_total) / 65535.0) * (double)hm[h].tol)
+                                        : 0.0f;
+    }
+done:
+    return rc;
+}
+
+/* the fields of a call that every hypothesis shares, and suppressed_by -1 for the skipped ones */
+static void finish_results(oslam_arbitrate_result *res, const oslamk_verify_member *hm, size_t H, uint32_t rounds,
+                           uint32_t launches, double t0)
+{
+    const float ms_total = (float)(now_ms() - t0);
+    size_t h;
+    for (h = 0; h < H; h++) {
+        if (hm[h].n_blocks == 0) res[h].suppressed_by = -1;
+        res[h].rounds = rounds;
+        res[h].launches = launches;
+        res[h].ms_total = ms_total;
+    }
+}
+
 /* Hypotheses ms[0 .. H) with T [H][16] (all-zero = skipped) against v.  res != NULL: the whole arbitration.
  * cnt_out / sum_out != NULL (the tap): the table after k_claim, H * n_tiles entries each (cap: what they hold). */
 static int arbitrate_members(oslam_model *const *ms, size_t H, const oslam_view *v, const float *T,
@@ -146,8 +192,6 @@ static int arbitrate_members(oslam_model *const *ms, size_t H, const oslam_view 
     if (hipSetDevice(v->dev) != hipSuccess) { rc = fail(OSLAM_E_DEVICE, "hipSetDevice failed"); goto done; }
     pthread_mutex_lock(&g_rec_mu);
     locked = 1;
-    if (res && !g_rec)
-        HIPCHK(hipHostMalloc((void **)&g_rec, sizeof *g_rec * (1 + OSLAMK_ARB_MAX_HYP), hipHostMallocPortable));
     off_tbl = align256(sizeof *hm * H);
     off_rec = off_tbl + align256(tbl_bytes);
     bytes = off_rec + sizeof(oslamk_arb_rec) * (1 + H);
@@ -166,38 +210,14 @@ static int arbitrate_members(oslam_model *const *ms, size_t H, const oslam_view 
         }
         goto done;
     }
-    KCHK(oslamk_arbitrate((const oslamk_verify_member *)dev, (uint32_t)H, g.n_tiles,
-                          (const unsigned long long *)(dev + off_tbl), p->min_tiles, p->min_owned_share,
-                          (oslamk_arb_rec *)(dev + off_rec), stream));
+    rc = run_elimination(dev, off_tbl, off_rec, hm, H, g.n_tiles, p->min_tiles, p->min_owned_share, stream, res, &rounds);
+    if (rc != OSLAM_OK) goto done;
     launches++;
-    HIPCHK(hipMemcpyAsync(g_rec, dev + off_rec, sizeof *g_rec * (1 + H), hipMemcpyDeviceToHost, (hipStream_t)stream));
-    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-    rounds = g_rec[0].claimed;
-    for (h = 0; h < H; h++) {
-        const oslamk_arb_rec *k = &g_rec[1 + h];
-        oslam_arbitrate_result *r = &res[h];
-        if (hm[h].n_blocks == 0) continue;
-        r->claimed = k->claimed;
-        r->owned = k->owned;
-        r->share = k->share;
-        r->kept = k->kept;
-        r->suppressed_by = k->suppressed_by;
-        r->mean_residual = k->cnt_total ? (float)((((double)k->sum_total / (double)k->cnt_total) / 65535.0) * (double)hm[h].tol)
-                                        : 0.0f;
-    }
 done:
     if (rc != OSLAM_OK) (void)hipStreamSynchronize((hipStream_t)stream);    /* nothing may still use the block */
     if (locked) pthread_mutex_unlock(&g_rec_mu);
     if (dev) oslam_dev_free(dev);
-    if (rc == OSLAM_OK && res) {
-        const float ms_total = (float)(now_ms() - t0);
-        for (h = 0; h < H; h++) {
-            if (hm[h].n_blocks == 0) res[h].suppressed_by = -1;
-            res[h].rounds = rounds;
-            res[h].launches = launches;
-            res[h].ms_total = ms_total;
-        }
-    }
+    if (rc == OSLAM_OK && res) finish_results(res, hm, H, rounds, launches, t0);
     free(hm);
     free(h_tbl);
     return rc;
@@ -240,6 +260,68 @@ int oslam_arbitrate_claims(oslam_model *const *models, const float *T, size_t H,
     if (rc == OSLAM_OK) rc = check_list(models, T, H, v);
     if (rc != OSLAM_OK) return rc;
     return arbitrate_members(models, H, v, T, &p, NULL, cnt_out, sum_out, cap, tile_out, n_tiles_out);
+}
+
+/* test tap: k_arbitrate alone over a table given by the caller (include/oslam.h) */
+int oslam_arbitrate_table(const uint32_t *cnt, const uint64_t *sum, const uint8_t *skipped, size_t H, size_t n_tiles,
+                          unsigned min_tiles, float min_owned_share, oslam_arbitrate_result *res, uint32_t *rounds_out)
+{
+    int rc = OSLAM_OK, locked = 0, devsel = 0;
+    const double t0 = now_ms();
+    size_t h, e, n_ent, tbl_bytes, off_tbl, off_rec, live = 0;
+    oslamk_verify_member *hm = NULL;
+    uint64_t *h_tbl = NULL;
+    uint32_t launches = 0, rounds = 0;
+    char *dev = NULL;
+    void *stream = oslam_stream();
+
+    if (!cnt || !sum || !skipped || !res || !rounds_out) return fail(OSLAM_E_INVALID, "NULL argument");
+    *rounds_out = 0;
+    if (!isfinite(min_owned_share)) return fail(OSLAM_E_INVALID, "arbitrate parameters must be finite");
+    if (min_owned_share < 0.0f || min_owned_share > 1.0f) return fail(OSLAM_E_INVALID, "min_owned_share must lie in [0, 1]");
+    if (H == 0 || H > OSLAM_ARBITRATE_MAX_HYPOTHESES)
+        return fail(OSLAM_E_INVALID, "the number of hypotheses must lie in 1..OSLAM_ARBITRATE_MAX_HYPOTHESES");
+    if (n_tiles == 0 || n_tiles > ARB_MAX_TABLE_BYTES / sizeof(uint64_t)) return fail(OSLAM_E_INVALID, "n_tiles must lie in 1..2^25");
+    n_ent = H * n_tiles;
+    tbl_bytes = n_ent * sizeof(uint64_t);
+    if (tbl_bytes > ARB_MAX_TABLE_BYTES) return fail(OSLAM_E_LIMIT, "the claims table (hypotheses x tiles x 8 B) exceeds 256 MiB");
+    for (e = 0; e < n_ent; e++)
+        if (cnt[e] >> (64 - OSLAMK_ARB_CNT_SHIFT) || sum[e] >> OSLAMK_ARB_CNT_SHIFT)
+            return fail(OSLAM_E_INVALID, "a count of 2^24 or a sum of 2^40 or more does not fit a claims word");
+    memset(res, 0, sizeof *res * H);
+    hm = (oslamk_verify_member *)calloc(H, sizeof *hm);
+    h_tbl = (uint64_t *)malloc(tbl_bytes);
+    if (!hm || !h_tbl) { free(hm); free(h_tbl); return fail(OSLAM_E_NOMEM, "host allocation failed"); }
+    for (h = 0; h < H; h++) {
+        hm[h].n_blocks = skipped[h] ? 0u : 1u;   /* k_arbitrate reads nothing else of a member */
+        hm[h].tol = 1.0f;
+        live += !skipped[h];
+    }
+    for (e = 0; e < n_ent; e++) h_tbl[e] = ((uint64_t)cnt[e] << OSLAMK_ARB_CNT_SHIFT) | sum[e];
+    if (live == 0) goto done;                   /* every hypothesis skipped: no device work, as oslam_arbitrate */
+    rc = oslam_pick_device(0, &devsel);
+    if (rc != OSLAM_OK) goto done;
+    pthread_mutex_lock(&g_rec_mu);
+    locked = 1;
+    off_tbl = align256(sizeof *hm * H);
+    off_rec = off_tbl + align256(tbl_bytes);
+    KCHK(oslam_dev_alloc((void **)&dev, off_rec + sizeof(oslamk_arb_rec) * (1 + H)));
+    HIPCHK(hipMemcpyAsync(dev, hm, sizeof *hm * H, hipMemcpyHostToDevice, (hipStream_t)stream));
+    HIPCHK(hipMemcpyAsync(dev + off_tbl, h_tbl, tbl_bytes, hipMemcpyHostToDevice, (hipStream_t)stream));
+    rc = run_elimination(dev, off_tbl, off_rec, hm, H, (uint32_t)n_tiles, min_tiles, min_owned_share, stream, res, &rounds);
+    if (rc != OSLAM_OK) goto done;
+    launches++;
+done:
+    if (rc != OSLAM_OK && dev) (void)hipStreamSynchronize((hipStream_t)stream);
+    if (locked) pthread_mutex_unlock(&g_rec_mu);
+    if (dev) oslam_dev_free(dev);
+    if (rc == OSLAM_OK) {
+        finish_results(res, hm, H, rounds, launches, t0);
+        *rounds_out = rounds;
+    }
+    free(hm);
+    free(h_tbl);
+    return rc;
 }
 
 /* ---- the whole chain ---- */

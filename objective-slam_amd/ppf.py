@@ -231,6 +231,7 @@ _SIGNATURES = {
     "oslam_db_arbitrate": (_i, [_vp, _vp, _vp, C.POINTER(ArbitrateParams), _vp]),
     "oslam_arbitrate_claims": (_i, [_vp, _vp, _sz, _vp, C.POINTER(ArbitrateParams), _vp, _vp, _sz, C.POINTER(C.c_uint32),
                                     C.POINTER(_sz)]),
+    "oslam_arbitrate_table": (_i, [_vp, _vp, _vp, _sz, _sz, C.c_uint, _f, _vp, C.POINTER(C.c_uint32)]),
     "oslam_detect_params_default": (_i, [C.POINTER(DetectParams)]),
     "oslam_db_detect": (_i, [_vp, _vp, _vp, C.POINTER(DetectParams), _vp, _sz, C.POINTER(_sz)]),
     "oslam_track_params_default": (_i, [C.POINTER(TrackParams)]),
@@ -505,6 +506,24 @@ def arbitrate_claims(models, view, T, params=None):
                                         C.byref(nt)))
     n = H * nt.value
     return cnt[:n].reshape(H, nt.value).copy(), sm[:n].reshape(H, nt.value).copy(), int(tile.value)
+
+
+def arbitrate_table(cnt, sm, skipped=None, min_tiles=4, min_owned_share=0.52):
+    """The elimination alone over a given claims table as a test tap (oslam_arbitrate_table): cnt [H, n_tiles] (below
+    2^24), sm [H, n_tiles] (below 2^40), skipped bool [H].  -> (list of result dicts, rounds)."""
+    c = np.ascontiguousarray(cnt, np.uint32)
+    s = np.ascontiguousarray(sm, np.uint64)
+    if c.ndim != 2 or s.shape != c.shape:
+        raise ValueError("cnt and sm must both be [H, n_tiles]")
+    H, n_tiles = c.shape
+    k = np.zeros(max(H, 1), np.uint8) if skipped is None else np.ascontiguousarray(np.asarray(skipped, bool), np.uint8)
+    if skipped is not None and k.shape != (H,):
+        raise ValueError("skipped must be [H]")
+    res = (ArbitrateResult * max(H, 1))()
+    rounds = C.c_uint32(0)
+    _check(lib().oslam_arbitrate_table(_p(c) if c.size else None, _p(s) if s.size else None, _p(k), H, n_tiles, int(min_tiles),
+                                       float(min_owned_share), res, C.byref(rounds)))
+    return [res[h].asdict() for h in range(H)], int(rounds.value)
 
 
 def _instance_args(refine, params, refine_params):

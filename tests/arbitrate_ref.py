@@ -112,8 +112,9 @@ def owners(cnt, sm, live):
     return own
 
 
-def eliminate(cnt, sm, skipped, tols, min_tiles=4, min_owned_share=0.52):
-    """The elimination over a claims table -> (list of result dicts, rounds)."""
+def eliminate(cnt, sm, skipped, tols, min_tiles=4, min_owned_share=0.52, order=None):
+    """The elimination over a claims table -> (list of result dicts, rounds).  order: a list that receives the
+    suppressed hypotheses in the order they leave."""
     H = cnt.shape[0]
     claimed = (cnt > 0).sum(axis=1)
     live = [bool(not skipped[h] and claimed[h] >= 1 and claimed[h] >= min_tiles) for h in range(H)]
@@ -148,6 +149,8 @@ def eliminate(cnt, sm, skipped, tols, min_tiles=4, min_owned_share=0.52):
                 by, bb = h, b
         res[loser]["suppressed_by"] = by
         live[loser] = False
+        if order is not None:
+            order.append(loser)
     for h in range(H):
         res[h]["kept"] = live[h]
     return res, rounds

@@ -92,9 +92,13 @@ def correspondences(mp, mn, T, maps, cam, radius, min_dot):
     return np.where(good, v * w + u, -1).astype(np.int32), q, m
 
 
-def track(mp, mn, T_prev, depth, cam, d_dist, max_jump, maps=None, **kw):
+def track(mp, mn, T_prev, depth, cam, d_dist, max_jump, maps=None, sums="f64", **kw):
     """One hypothesis followed into the image -> (T_out float32 4x4, dict verify iterations correspondences converged
-    found).  The loop is refine_ref.refine's with the correspondences above."""
+    found, cond: the condition number of the last damped 6x6 system).  The loop is refine_ref.refine's with the
+    correspondences above.  sums: the precision and order of the step's sums -- "f64" (float64 products of the float32
+    terms), or "f32" (float32 products summed in float32 in index order, the device's terms in another order); the
+    spread between the two is the step's own sensitivity to the summation."""
+    assert sums in ("f64", "f32")
     p = default_params()
     p.update(kw)
     mp = np.asarray(mp, np.float32)
@@ -108,7 +112,7 @@ def track(mp, mn, T_prev, depth, cam, d_dist, max_jump, maps=None, **kw):
     cm = mp.astype(np.float64).mean(axis=0)
     T = np.asarray(T_prev, np.float32).reshape(4, 4).astype(np.float64)
     Tf = np.asarray(T_prev, np.float32).reshape(4, 4).copy()
-    it, converged, n_corr = 0, False, 0
+    it, converged, n_corr, A_last = 0, False, 0, None
     while it < p["max_iterations"]:
         pix, q, _ = correspondences(mp, mn, Tf, maps, cam, rc, p["min_normal_dot"])
         ok = pix >= 0
@@ -119,10 +123,19 @@ def track(mp, mn, T_prev, depth, cam, d_dist, max_jump, maps=None, **kw):
         c = (T[:3, :3] @ cm + T[:3, 3]).astype(np.float32)
         e = P - Q
         r = (Nq[:, 0] * e[:, 0] + Nq[:, 1] * e[:, 1]) + Nq[:, 2] * e[:, 2]
-        J = np.concatenate([np.cross(P - c, Nq), Nq], axis=1).astype(np.float64)
-        A = J.T @ J
-        g = J.T @ r.astype(np.float64)
+        Jf = np.concatenate([np.cross(P - c, Nq), Nq], axis=1).astype(np.float32)
+        if sums == "f32":
+            A, g = np.zeros((6, 6)), np.zeros(6)
+            for a in range(6):
+                for b in range(a, 6):
+                    A[a, b] = A[b, a] = np.cumsum(Jf[:, a] * Jf[:, b], dtype=np.float32)[-1]
+                g[a] = np.cumsum(Jf[:, a] * r, dtype=np.float32)[-1]
+        else:
+            J = Jf.astype(np.float64)
+            A = J.T @ J
+            g = J.T @ r.astype(np.float64)
         A = A + 1e-6 * np.trace(A) / 6.0 * np.eye(6)
+        A_last = A
         try:
             L = np.linalg.cholesky(A)
         except np.linalg.LinAlgError:
@@ -143,7 +156,8 @@ def track(mp, mn, T_prev, depth, cam, d_dist, max_jump, maps=None, **kw):
             break
     vp = dict(p["verify"])
     ver, _ = view_ref.verify(mp, mn, Tf, depth, cam, d_dist, depth_tol=vp.pop("depth_tol"), window=vp.pop("window"), **vp)
-    return Tf, dict(verify=ver, iterations=it, correspondences=n_corr, converged=converged, found=ver["found"])
+    cond = float(np.linalg.cond(A_last)) if A_last is not None else 0.0
+    return Tf, dict(verify=ver, iterations=it, correspondences=n_corr, converged=converged, found=ver["found"], cond=cond)
 
 
 # ---------------------------------------------------------------- part 3: the tracker
