@@ -790,6 +790,120 @@ int oslam_tracker_tracks(const oslam_tracker *t, oslam_track_state *out, size_t 
 int oslam_tracker_step(oslam_tracker *t, oslam_scene *scene, const oslam_view *v, oslam_track_state *out, size_t cap,
                        size_t *n_out, int *searched);
 
+/* ---- camera motion between two depth views: dense projective ICP of one whole image against another (KinFu's camera
+ * tracking, frame to frame).  It gives the camera's motion once per frame, independent of the database; the stages
+ * above assume a camera that stands still.
+ *
+ * T_out is the float32 row-major rigid transform that takes a point in the source camera's coordinates to the
+ * destination camera's.  With src = the previous frame and dst = the current one a static world point keeps its
+ * identity, and a static object's pose in the new frame is T_out * T_old.
+ * Levels.  Up to OSLAM_EGOMOTION_MAX_LEVELS levels {stride, max_iterations}, run in order (a level with max_iterations
+ *   0 is passed over); the default is KinFu's coarse-to-fine schedule, strides 4, 2, 1 with 4, 5 and 10 iterations.  A
+ *   level selects the source pixels with u % stride == 0 && v % stride == 0, numbered row-major over that lattice:
+ *   index i is the pixel (u, v) = ((i % lw) * stride, (i / lw) * stride) with lw = ceil(width / stride) and
+ *   n = lw * ceil(height / stride) indices.  Levels subsample the source only; the destination is always the
+ *   full-resolution map.  A coarse level buys time, not a wider convergence basin: every level looks at the one pixel a
+ *   source point projects to, and the gates are the same at every level.  Image pyramids are out of scope.
+ * Correspondence of a selected source pixel.  Its record in the source's map (the maps of oslam_track, built on first
+ *   use) is (p, n); it takes part only when it has a normal.  p' and n' under the float32 pose T exactly as
+ *   oslam_refine, oslam_verify and oslam_track compute them: p'x = ((T0*px + T1*py) + T2*pz) + T3 and so on, n' without
+ *   the translation.  p'z must lie within [z_min, z_max] of dst; the pixel in dst is oslam_verify's (fu, fv) with the
+ *   destination's intrinsics, fu = floorf(((p'x * fx) / p'z + cx) + 0.5f), range-checked in float.  q, nq are that
+ *   pixel's record in the destination's map.  The correspondence exists when the pixel has a normal,
+ *   (dx*dx + dy*dy) + dz*dz <= r*r with d = q - p' and r = max_corr_dist in metres (a view has no d_dist; r*r rounded
+ *   to float), and (n'x*nqx + n'y*nqy) + n'z*nqz >= min_normal_dot.  One candidate pixel, no search and no BACK test.
+ * Step.  oslam_refine's Gauss-Newton step with these correspondences and the model centroid cm = (0, 0, 0), so that
+ *   the pivot is the source camera's centre in the destination frame: the residual nq . (p' - q), the same 29 sums, the
+ *   same damped Cholesky in double, Rodrigues step and Gram-Schmidt.  The sums: float over each block of 256
+ *   consecutive lattice indices through the fixed tree (per 64 indices v[l] += v[l + off] for off = 32, 16, 8, 4, 2, 1,
+ *   an index without a correspondence adds 0; then the four 64s as ((s0 + s1) + s2) + s3), then double.  The grouping of
+ *   the double additions depends on the level and the image size only, never on which workgroup finished first: with
+ *   nb = ceil(n / 256) blocks, chunk = ceil(nb / 256) and G = ceil(nb / chunk) slots, slot g is the sum of its blocks
+ *   g * chunk .. min((g + 1) * chunk, nb) - 1 added in ascending order to 0.0; strand j (0..7) is the sum of the slots
+ *   j, j + 8, j + 16, ... added in ascending order to 0.0; the sum is ((((((s0 + s1) + s2) + s3) + s4) + s5) + s6) + s7.
+ *   The convergence test, |omega| < stop_rot (radians) and |v| < stop_trans (metres), ends a level, not the call: the
+ *   next level starts from the float32 pose it left (inside a level the pose is carried in double), so a call with the
+ *   levels A then B equals a call with A followed by a call with B from its T_out, bit for bit.  Fewer than 6 correspondences or a failed factorisation end the call with
+ *   the pose as it then stands.
+ * Result: iterations per level (steps taken); correspondences and rmse = sqrtf((float)(S[28] / S[27])) of the last step
+ *   of the call (0 without a correspondence); overlap = (float)c / (float)s of the last step of the level with the
+ *   smallest stride that evaluated a step (the later of equal strides), c = its correspondences and s = its selected
+ *   source pixels that have a normal (0 when s is 0); converged = the last level that ran ended by its convergence
+ *   test; ok = overlap >= min_overlap; launches, ms_total.
+ * src == dst (the same handle) returns the identity at once: no device call, iterations 0, converged 1, overlap 1,
+ *   ok = 1 >= min_overlap, whatever T_init is.
+ * Arguments are checked before any handle is read or any device call is made: NULL src, dst or T_out, parameters that
+ *   are not finite, n_levels outside 1..3, a stride outside 1..16, an iteration count above 1000, max_corr_dist <= 0, a
+ *   negative stop criterion, min_overlap outside [0, 1] and a T_init that is not rigid (the test of oslam_refine) are
+ *   OSLAM_E_INVALID; so are two views on different devices.
+ * Cost: one kernel launch per scheduled iteration (k_ego_step, at most 256 workgroups of 256 threads; the last
+ *   workgroup to arrive adds the partial sums in the order above, solves and leaves the pose for the next launch; no
+ *   workgroup waits for another, no float atomics), all enqueued back to back, a launch whose level is over or whose
+ *   call is done returning at once; one memset, one host wait and one copy of the result record into pinned memory.
+ *   res->launches == the scheduled iterations (19 by default), plus 1 for each view whose maps did not exist yet.  Two
+ *   calls give the same bits.  Egomotion calls of one process take turns, on every device: they share one pinned
+ *   state, and its lock is held from the upload to the end of the host wait.  The lock of the views' maps (the tracking
+ *   stage's) is taken inside it, never the other way round.
+ * Defaults (calibration table: tests/test_camera_host.py, a camera that turns 3 degrees and moves 3 cm per frame
+ *   before a room 5.4 m away, three seeds).  min_normal_dot is KinFu's cos(20 degrees).  max_corr_dist is 0.30 m and
+ *   NOT KinFu's 0.10 m: at that motion a point moves 0.28 m between frames, 0.10 m shuts out the surfaces that tell a
+ *   turn from a step sideways and the result slides by 0.22 .. 0.29 m; 0.20, 0.30 and 0.50 m all follow the camera to
+ *   0.012 degrees and 0.8 mm per frame.  Without an image pyramid the gate has to admit the motion itself.  stop_rot
+ *   1e-5, stop_trans 1e-5 m.  min_overlap 0.75: consecutive frames reach an overlap of 0.832 .. 0.935, a jump of 7 .. 9
+ *   frames (21 .. 27 degrees) 0.000 .. 0.672.  The overlap measures shared surface, not identity: frames of a similar
+ *   room (the same floor, a wall 0.4 m further) reach 0.274 .. 0.875 and are not told apart. */
+#define OSLAM_EGOMOTION_MAX_LEVELS 3
+typedef struct oslam_egomotion_level {
+    unsigned stride;           /* 1..16 */
+    unsigned max_iterations;   /* 0..1000 */
+} oslam_egomotion_level;
+
+typedef struct oslam_egomotion_params {
+    unsigned n_levels;         /* 1..3, default 3 */
+    oslam_egomotion_level level[OSLAM_EGOMOTION_MAX_LEVELS];   /* default {4, 4}, {2, 5}, {1, 10} */
+    float max_corr_dist;       /* metres, default 0.30 */
+    float min_normal_dot;      /* default 0.93969262 (cos 20 degrees) */
+    float stop_rot;            /* radians, default 1e-5 */
+    float stop_trans;          /* metres, default 1e-5 */
+    float min_overlap;         /* [0, 1], default 0.75 */
+    int reserved[4];
+} oslam_egomotion_params;
+
+typedef struct oslam_egomotion_result {
+    uint32_t iterations[OSLAM_EGOMOTION_MAX_LEVELS];
+    uint32_t correspondences;  /* of the last step */
+    float rmse;                /* of the last step, metres */
+    float overlap;
+    int32_t converged, ok;
+    uint32_t launches;         /* kernels this call enqueued */
+    float ms_total;            /* whole call, host clock */
+} oslam_egomotion_result;
+
+int oslam_egomotion_params_default(oslam_egomotion_params *p);
+/* T_init may be NULL (identity), ep may be NULL (defaults), res may be NULL */
+int oslam_view_egomotion(oslam_view *src, oslam_view *dst, const float T_init[16], const oslam_egomotion_params *ep,
+                         float T_out[16], oslam_egomotion_result *res);
+/* test tap: pixel_out[w*h of src] = v*width+u in dst of each source pixel's correspondence under T at stride 1, -1 = none */
+int oslam_view_egomotion_correspondences(oslam_view *src, oslam_view *dst, const float T[16],
+                                         const oslam_egomotion_params *ep, int32_t *pixel_out);
+
+/* ---- the tracker under a moving camera.  oslam_tracker_step_cam is oslam_tracker_step with a step 0 before the
+ * tracking call: when T_cam != NULL (the camera's motion from the previous frame to this one, source camera to
+ * destination camera: oslam_view_egomotion(previous view, this view)) every live track's pose T becomes
+ * float32(double(T_cam) * double(T)), each element as ((a0*b0 + a1*b1) + a2*b2) (+ a3 for the translation) in double; an
+ * element whose value does not change keeps its bits, so T_cam = identity gives oslam_tracker_step bit for bit, as
+ * T_cam == NULL does.  The tracker also accumulates the camera's pose in the frame of its first step's camera (the
+ * world): T_world_cam <- T_world_cam * T_cam^-1 in double, the inverse as [R^T | -(R^T t)]; a track's world pose is
+ * T_world_cam * T.  oslam_tracker_camera returns its float32 rounding.  The tracker does not own views: the caller
+ * computes T_cam and passes NULL when the result's ok is 0 (the prediction is then "where it was").  NULL t, v or n_out
+ * and a T_cam that is not rigid (the test of oslam_refine) are OSLAM_E_INVALID before anything changes.
+ * oslam_tracker_predict is step 0 alone, on the host (exported for tests; it also works on a tracker made from
+ * shapes). */
+int oslam_tracker_step_cam(oslam_tracker *t, oslam_scene *scene, const oslam_view *v, const float T_cam[16],
+                           oslam_track_state *out, size_t cap, size_t *n_out, int *searched);
+int oslam_tracker_predict(oslam_tracker *t, const float T_cam[16]);
+int oslam_tracker_camera(const oslam_tracker *t, float T_world_cam[16]);
+
 /* ---- parity taps (tests): values the reference materialises as arrays.
  * Scene::getHashKeys row r (scene.cu:49-54): keys_out[n] of reference point r,
  * computed by the GPU key kernel with this d_dist (key 0 on the diagonal). */

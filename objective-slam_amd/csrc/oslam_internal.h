@@ -78,7 +78,8 @@ struct oslam_scene {
 };
 
 struct oslam_view {
-    int dev;
+    int dev;                          /* stays the first field: the argument tests (tests/test_*_host.py) hand the entry
+                                         points zeroed stand-in handles and write the device number at offset 0 */
     oslamk_view k;
     float *d_z;
     float max_jump;                   /* of the camera: the normal map's depth-step limit */
@@ -219,6 +220,11 @@ int oslam_track_check_params(const oslam_track_params *tp, oslam_track_params *o
 void oslam_track_release_maps(oslam_view *v);
 /* gives back the pinned record of the tracking stage; called by oslam_release_scratch */
 void oslam_track_release(void);
+/* the view's maps for another stage: built when they do not exist yet (enqueued on the stream, *built = 1), with the
+ * view's device bound */
+int oslam_track_view_maps(oslam_view *v, int *built);
+/* gives back the pinned state of the camera motion stage (oslam_ego.c); called by oslam_release_scratch */
+void oslam_ego_release(void);
 /* the arbitration's parameter check (oslam_arbitrate.c) */
 int oslam_arbitrate_check_params(const oslam_arbitrate_params *ap, oslam_arbitrate_params *out);
 

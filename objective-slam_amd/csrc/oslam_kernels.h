@@ -467,6 +467,48 @@ int oslamk_track(const oslamk_view *v, const float *maps, const oslamk_track_mem
 int oslamk_track_corr(const oslamk_view *v, const float *maps, const oslamk_track_member *d_mem, uint32_t n_blocks,
                       int32_t *pixel_out, void *stream);
 
+/* ---- camera motion stage (oslam_ego.hip; semantics in include/oslam.h at oslam_view_egomotion) ---- */
+#define OSLAMK_EGO_THREADS 256        /* a block of the sums is 256 consecutive selected pixels */
+#define OSLAMK_EGO_MAX_LEVELS 3
+#define OSLAMK_EGO_MAX_SLOTS 256      /* workgroups of one launch at most: one slot of the partials buffer each */
+#define OSLAMK_EGO_STRANDS 8          /* the slots are added in 8 interleaved strands */
+#define OSLAMK_EGO_SLOT 32            /* doubles per slot: the 29 sums, [29] = selected source pixels with a normal */
+
+/* the selected pixels of one level: the lattice u % stride == 0 && v % stride == 0 of the source image, row-major */
+typedef struct oslamk_ego_level {
+    int stride, lw;            /* lw = ceil(w / stride) lattice columns */
+    uint32_t n;                /* lattice points: lw * ceil(h / stride) */
+    uint32_t n_blocks;         /* ceil(n / OSLAMK_EGO_THREADS) */
+    uint32_t chunk;            /* consecutive blocks per workgroup: ceil(n_blocks / OSLAMK_EGO_MAX_SLOTS) */
+    uint32_t n_slots;          /* workgroups: ceil(n_blocks / chunk) */
+    uint32_t max_iter;
+    int32_t level, next_level; /* this level's index; the next level that has iterations (or the number of levels) */
+} oslamk_ego_level;
+
+/* the state of a call: the host fills the pose and the gates, every step updates the rest */
+typedef struct oslamk_ego_state {
+    double T[12];              /* rows of [R | t] in double: the pose between iterations */
+    float Tf[12];              /* float32 rounding of T: what the correspondences use */
+    float c[3];                /* float32 rounding of t: the pivot (the model centroid is the origin) */
+    float r2_corr, min_dot, stop_rot, stop_trans;
+    int32_t level, iter;       /* the level in force and the steps taken in it */
+    int32_t done, converged;
+    int32_t n_levels, pad;
+    uint32_t iterations[OSLAMK_EGO_MAX_LEVELS];
+    uint32_t corr[OSLAMK_EGO_MAX_LEVELS], n_src[OSLAMK_EGO_MAX_LEVELS];   /* of the level's last step */
+    uint32_t last_corr;        /* correspondences of the last step of the call */
+    float rmse;                /* of that step */
+} oslamk_ego_state;
+
+/* one scheduled iteration: returns at once when the call is done or lv->level is not the level in force; otherwise
+ * every workgroup leaves its sums in slots[blockIdx.x] and the last one to arrive at *arrive (zero before the launch,
+ * used by this launch alone) adds them, steps and writes *st */
+int oslamk_ego_step(const oslamk_view *src, const float *src_maps, const oslamk_view *dst, const float *dst_maps,
+                    const oslamk_ego_level *lv, oslamk_ego_state *st, double *slots, uint32_t *arrive, void *stream);
+/* tap: pixel_out[i] = pixel in dst of the correspondence of source pixel i under T (float32 rows), -1 = none */
+int oslamk_ego_corr(const oslamk_view *src, const float *src_maps, const oslamk_view *dst, const float *dst_maps,
+                    const float *T12, float r2_corr, float min_dot, int32_t *pixel_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -100,6 +100,15 @@ done:
     return rc;
 }
 
+int oslam_track_view_maps(oslam_view *v, int *built)
+{
+    int rc;
+    pthread_mutex_lock(&g_track_mu);
+    rc = view_maps(v, built);
+    pthread_mutex_unlock(&g_track_mu);
+    return rc;
+}
+
 /* the descriptor of one hypothesis: the pose bookkeeping of oslam_refine (oslam_refine.c, set_pose and centroid) */
 static void set_member(oslamk_track_member *d, const oslam_model *m, const float T[16], const oslam_track_params *p)
 {

@@ -2,7 +2,8 @@
  * oslam_tracker.c -- identity across depth frames (include/oslam.h at oslam_tracker_step): a host-side object over the
  * stages, with no kernel of its own.  A step tracks every live track from its last pose (oslam_db_track), arbitrates
  * the ones that were found, ages and deletes, and now and then runs the search (oslam_db_detect) and folds its
- * detections into the tracks (oslam_tracker_update: association by the same-instance test, birth).
+ * detections into the tracks (oslam_tracker_update: association by the same-instance test, birth).  Under a moving
+ * camera oslam_tracker_step_cam first moves every live pose by the camera's motion (predict) and accumulates the camera.
  */
 #include <math.h>
 
@@ -18,6 +19,7 @@ struct oslam_tracker {
     size_t n, cap;
     uint32_t next_id;
     uint64_t frame;
+    double T_world_cam[16];           /* the camera in the frame of the first step's camera (oslam_tracker_predict) */
 };
 
 int oslam_tracker_params_default(oslam_tracker_params *p)
@@ -74,6 +76,7 @@ static int tracker_new(size_t n, const oslam_tracker_params *p, oslam_tracker **
     }
     t->n_models = n;
     t->p = *p;
+    t->T_world_cam[0] = t->T_world_cam[5] = t->T_world_cam[10] = t->T_world_cam[15] = 1.0;
     *out = t;
     return OSLAM_OK;
 }
@@ -199,8 +202,61 @@ int oslam_tracker_tracks(const oslam_tracker *t, oslam_track_state *out, size_t 
     return OSLAM_OK;
 }
 
+/* step 0 of oslam_tracker_step_cam: T <- float32(T_cam * T) of every live track, T_world_cam <- T_world_cam * T_cam^-1 */
+static void predict(oslam_tracker *t, const float C[16])
+{
+    double W[16], inv[12];
+    size_t k;
+    int a, b;
+    for (k = 0; k < t->n; k++) {
+        float *T = t->tracks[k].T, N[12];
+        for (a = 0; a < 3; a++)
+            for (b = 0; b < 4; b++) {
+                double x = ((double)C[4 * a] * (double)T[b] + (double)C[4 * a + 1] * (double)T[4 + b]) +
+                           (double)C[4 * a + 2] * (double)T[8 + b];
+                if (b == 3) x += (double)C[4 * a + 3];
+                N[4 * a + b] = (float)x;
+            }
+        for (a = 0; a < 12; a++)
+            if (N[a] != T[a]) T[a] = N[a];      /* an element whose value does not change keeps its bits */
+    }
+    for (a = 0; a < 3; a++) {
+        for (b = 0; b < 3; b++) inv[4 * a + b] = (double)C[4 * b + a];
+        inv[4 * a + 3] = -(((double)C[a] * (double)C[3] + (double)C[4 + a] * (double)C[7]) + (double)C[8 + a] * (double)C[11]);
+    }
+    memcpy(W, t->T_world_cam, sizeof W);
+    for (a = 0; a < 3; a++)
+        for (b = 0; b < 4; b++) {
+            double x = (W[4 * a] * inv[b] + W[4 * a + 1] * inv[4 + b]) + W[4 * a + 2] * inv[8 + b];
+            if (b == 3) x += W[4 * a + 3];
+            t->T_world_cam[4 * a + b] = x;
+        }
+}
+
+int oslam_tracker_predict(oslam_tracker *t, const float T_cam[16])
+{
+    if (!t || !T_cam) return fail(OSLAM_E_INVALID, "NULL argument");
+    if (oslam_refine_check_rigid(T_cam) != OSLAM_OK) return OSLAM_E_INVALID;
+    predict(t, T_cam);
+    return OSLAM_OK;
+}
+
+int oslam_tracker_camera(const oslam_tracker *t, float T_world_cam[16])
+{
+    int a;
+    if (!t || !T_world_cam) return fail(OSLAM_E_INVALID, "NULL argument");
+    for (a = 0; a < 16; a++) T_world_cam[a] = (float)t->T_world_cam[a];
+    return OSLAM_OK;
+}
+
 int oslam_tracker_step(oslam_tracker *t, oslam_scene *scene, const oslam_view *v, oslam_track_state *out, size_t cap,
                        size_t *n_out, int *searched)
+{
+    return oslam_tracker_step_cam(t, scene, v, NULL, out, cap, n_out, searched);
+}
+
+int oslam_tracker_step_cam(oslam_tracker *t, oslam_scene *scene, const oslam_view *v, const float T_cam[16],
+                           oslam_track_state *out, size_t cap, size_t *n_out, int *searched)
 {
     int rc = OSLAM_OK, any = 0;
     size_t k, H, kept = 0;
@@ -213,9 +269,11 @@ int oslam_tracker_step(oslam_tracker *t, oslam_scene *scene, const oslam_view *v
     if (searched) *searched = 0;
     if (!t || !v || !n_out || (cap && !out)) return fail(OSLAM_E_INVALID, "NULL argument");
     *n_out = 0;
+    if (T_cam && oslam_refine_check_rigid(T_cam) != OSLAM_OK) return OSLAM_E_INVALID;
     if (!t->db) return fail(OSLAM_E_INVALID, "a tracker made from shapes has no database to step with");
     H = t->n;
     if (H > OSLAM_ARBITRATE_MAX_HYPOTHESES) return fail(OSLAM_E_LIMIT, "more live tracks than one tracking call takes");
+    if (T_cam) predict(t, T_cam);
     if (H) {
         member = (uint32_t *)malloc(sizeof *member * H);
         ms = (oslam_model **)malloc(sizeof *ms * H);

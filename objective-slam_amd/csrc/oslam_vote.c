@@ -101,6 +101,7 @@ int oslam_release_scratch(int dev)
     if (hipSetDevice(dev) == hipSuccess) oslam_dev_cache_release(dev);   /* the kept blocks of the scene path */
     oslam_arbitrate_release();
     oslam_track_release();
+    oslam_ego_release();
     free(p->h_counts);
     p->buf = NULL;
     p->bytes = 0;

@@ -161,6 +161,26 @@ class TrackState(C.Structure):
                 "track": self.track.asdict()}
 
 
+class EgomotionLevel(C.Structure):
+    _fields_ = [("stride", C.c_uint), ("max_iterations", C.c_uint)]
+
+
+class EgomotionParams(C.Structure):
+    _fields_ = [("n_levels", C.c_uint), ("level", EgomotionLevel * 3), ("max_corr_dist", C.c_float),
+                ("min_normal_dot", C.c_float), ("stop_rot", C.c_float), ("stop_trans", C.c_float), ("min_overlap", C.c_float),
+                ("reserved", C.c_int * 4)]
+
+
+class EgomotionResult(C.Structure):
+    _fields_ = [("iterations", C.c_uint32 * 3), ("correspondences", C.c_uint32), ("rmse", C.c_float), ("overlap", C.c_float),
+                ("converged", C.c_int32), ("ok", C.c_int32), ("launches", C.c_uint32), ("ms_total", C.c_float)]
+
+    def asdict(self):
+        return {"iterations": [int(x) for x in self.iterations], "correspondences": int(self.correspondences),
+                "rmse": float(self.rmse), "overlap": float(self.overlap), "converged": int(self.converged), "ok": int(self.ok),
+                "launches": int(self.launches), "ms_total": float(self.ms_total)}
+
+
 ARBITRATE_MAX_HYPOTHESES = 1024
 CELL_DTYPE = np.dtype([("code", "<u8"), ("count", "<u4"), ("pad", "<u4")])
 
@@ -247,6 +267,12 @@ _SIGNATURES = {
     "oslam_tracker_update": (_i, [_vp, _vp, _sz]),
     "oslam_tracker_tracks": (_i, [_vp, _vp, _sz, C.POINTER(_sz)]),
     "oslam_tracker_step": (_i, [_vp, _vp, _vp, _vp, _sz, C.POINTER(_sz), C.POINTER(_i)]),
+    "oslam_egomotion_params_default": (_i, [C.POINTER(EgomotionParams)]),
+    "oslam_view_egomotion": (_i, [_vp, _vp, _vp, C.POINTER(EgomotionParams), _vp, C.POINTER(EgomotionResult)]),
+    "oslam_view_egomotion_correspondences": (_i, [_vp, _vp, _vp, C.POINTER(EgomotionParams), _vp]),
+    "oslam_tracker_step_cam": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(_sz), C.POINTER(_i)]),
+    "oslam_tracker_predict": (_i, [_vp, _vp]),
+    "oslam_tracker_camera": (_i, [_vp, _vp]),
     "oslam_scene_keys": (_i, [_vp, _sz, _vp]),
     "oslam_model_keys": (_i, [_vp, _sz, _vp]),
     "oslam_model_bucket": (_i, [_vp, C.c_uint32, _vp, _sz, C.POINTER(_sz)]),
@@ -373,6 +399,47 @@ def default_tracker_params(**kw):
     return p
 
 
+def default_egomotion_params(**kw):
+    """oslam_egomotion_params_default, then the fields given as keywords; levels=[(stride, max_iterations), ...] sets
+    n_levels and level together."""
+    p = EgomotionParams()
+    _check(lib().oslam_egomotion_params_default(C.byref(p)))
+    levels = kw.pop("levels", None)
+    if levels is not None:
+        levels = list(levels)
+        if len(levels) > 3:
+            raise ValueError("at most 3 levels")
+        p.n_levels = len(levels)
+        for k in range(3):
+            p.level[k].stride, p.level[k].max_iterations = levels[k] if k < len(levels) else (0, 0)
+    for k, v in kw.items():
+        if not hasattr(p, k) or k in ("reserved", "level"):
+            raise TypeError("unknown egomotion parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def egomotion(src_view, dst_view, T_init=None, params=None):
+    """The camera's motion between two depth views by dense projective ICP (oslam_view_egomotion): -> (T float32 4x4,
+    source camera coordinates -> destination camera coordinates; result dict).  T_init None: the identity."""
+    p = params if params is not None else default_egomotion_params()
+    To = np.zeros(16, np.float32)
+    res = EgomotionResult()
+    Ti = _pose16(T_init) if T_init is not None else None
+    _check(lib().oslam_view_egomotion(src_view._h, dst_view._h, _p(Ti) if Ti is not None else None, C.byref(p), _p(To),
+                                      C.byref(res)))
+    return To.reshape(4, 4), res.asdict()
+
+
+def egomotion_correspondences(src_view, dst_view, T, params=None):
+    """Pixel v * width + u in dst of every source pixel's correspondence under T at stride 1, -1 = none
+    (oslam_view_egomotion_correspondences: the rule of oslam_view_egomotion, as a test tap).  -> int32 [h, w] of src."""
+    p = params if params is not None else default_egomotion_params()
+    out = np.zeros(src_view.width * src_view.height, np.int32)
+    _check(lib().oslam_view_egomotion_correspondences(src_view._h, dst_view._h, _p(_pose16(T)), C.byref(p), _p(out)))
+    return out.reshape(src_view.height, src_view.width)
+
+
 def _hypotheses(models, T):
     """-> (array of model handles, T [H,16] float32, H)"""
     models = list(models)
@@ -472,14 +539,30 @@ class Tracker:
         _check(lib().oslam_tracker_update(self._h, det, len(detections)))
         return self.tracks()
 
-    def step(self, view, scene=None):
-        """One frame.  -> (live tracks as dicts, searched bool)."""
+    def step(self, view, scene=None, T_cam=None):
+        """One frame.  T_cam: the camera's motion from the previous frame to this one (egomotion(previous, view)), moved
+        into every live track before it is followed; None: none.  -> (live tracks as dicts, searched bool)."""
         cap = ARBITRATE_MAX_HYPOTHESES + max(1, len(self.db.models)) * MAX_INSTANCES
         out = (TrackState * cap)()
         n, searched = C.c_size_t(0), C.c_int(0)
-        _check(lib().oslam_tracker_step(self._h, scene._h if scene is not None else None, view._h, out, cap, C.byref(n),
-                                        C.byref(searched)))
+        sc = scene._h if scene is not None else None
+        if T_cam is None:
+            _check(lib().oslam_tracker_step(self._h, sc, view._h, out, cap, C.byref(n), C.byref(searched)))
+        else:
+            _check(lib().oslam_tracker_step_cam(self._h, sc, view._h, _p(_pose16(T_cam)), out, cap, C.byref(n),
+                                                C.byref(searched)))
         return [out[k].asdict() for k in range(n.value)], bool(searched.value)
+
+    def predict(self, T_cam):
+        """Step 0 of step(T_cam=...) alone, on the host (oslam_tracker_predict).  -> the live tracks."""
+        _check(lib().oslam_tracker_predict(self._h, _p(_pose16(T_cam))))
+        return self.tracks()
+
+    def camera(self):
+        """The camera's accumulated pose in the frame of the first step's camera (oslam_tracker_camera), float32 4x4."""
+        T = np.zeros(16, np.float32)
+        _check(lib().oslam_tracker_camera(self._h, _p(T)))
+        return T.reshape(4, 4)
 
     def close(self):
         if self._h:

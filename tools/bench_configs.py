@@ -18,6 +18,9 @@ configuration; these are not bench lines).  Needs a HIP device.
   python tools/bench_configs.py track    the db50 stream with smooth motion over 30 frames: db.detect on every frame next
                                          to Tracker.step (detect_every 10, the scene built on search frames only), and
                                          db.track per call for 1 and 50 hypotheses next to db.refine + db.verify
+  python tools/bench_configs.py camera   a static world seen from a moving camera (3 degrees and 3 cm per frame, 30 frames
+                                         at 640x480): oslam_view_egomotion per call, and Tracker.step on one object
+                                         with and without the camera's motion
 One JSON line each."""
 import importlib, json, os, sys, time
 
@@ -609,7 +612,80 @@ def track(frames=30, calls=20):
     return out
 
 
+def camera(frames=30, calls=20):
+    """Camera motion (oslam_view_egomotion, oslam_tracker_step_cam) on the static world of tests/camera_ref.py: the camera
+    sweeps 9 frames of 3 degrees and 3 cm out and back again, 30 frames in all.  (a) egomotion per call on one pair, inside
+    the library and from Python, with the launches; (b) the stream: egomotion on every pair and its chained error;
+    (c) Tracker.step on one object of a 3-model database with T_cam from (b) and without."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import camera_ref as E
+    import refine_ref
+    world = E.make_world(synth, 0)
+    sweep = E.trajectory(synth, 0, frames=10)
+    order = [abs((f + 9) % 18 - 9) for f in range(frames)]          # 0 1 .. 9 8 .. 0 1 ..
+    rendered = [E.render(synth, world, T) for T in sweep]
+    traj, imgs = [sweep[k] for k in order], [rendered[k] for k in order]
+    cam = E.CAM
+
+    def view_of(img):
+        return ppf.View(img, cam["fx"], cam["fy"], cam["cx"], cam["cy"], z_min=cam["z_min"], z_max=cam["z_max"],
+                        max_jump=E.MAX_JUMP)
+    views = [view_of(im) for im in imgs]
+    ppf.egomotion(views[0], views[1])
+    py, lib_ms = [], []
+    for _ in range(calls):
+        t = time.perf_counter(); _, r = ppf.egomotion(views[0], views[1]); py.append(1e3 * (time.perf_counter() - t))
+        lib_ms.append(r["ms_total"])
+    per_call = {"ms_python_median": float(np.median(py)), "ms_library_median": float(np.median(lib_ms)),
+                "launches": r["launches"], "iterations": r["iterations"]}
+    t = time.perf_counter()
+    motions = [ppf.egomotion(views[f - 1], views[f]) for f in range(1, frames)]
+    el = time.perf_counter() - t
+    chain, errs = np.eye(4), []
+    for f, (T, r) in enumerate(motions, 1):
+        chain = T.astype(np.float64) @ chain
+        e = refine_ref.pose_error(T, E.truth(traj[f - 1], traj[f])) + refine_ref.pose_error(chain, E.truth(traj[0], traj[f]))
+        errs.append([round(x, 5) for x in e] + [round(r["overlap"], 3), r["ok"]])
+
+    clouds = [synth.make_model(k, 1500) for k in range(3)]
+    clouds = [(np.ascontiguousarray(p * np.float32(E.OBJECT_SCALE)), n) for p, n in clouds]
+    d = synth.d_dist_for(clouds[0][0], 0.05)
+    models = [ppf.Model(p, n, d_dist=d) for p, n in clouds]
+    db = ppf.Database(models)
+    k = 1                                                           # the object nearest the camera
+    poses = [(np.linalg.inv(Twc) @ E.object_pose(synth, 0, k)).astype(np.float32) for Twc in traj]
+    streams = {}
+    for name in ("with_T_cam", "without"):
+        tracker = ppf.Tracker(db)
+        tracker.update([dict(model=k, T=poses[0])])
+        rows = []
+        t = time.perf_counter()
+        for f in range(1, frames):
+            T, r = motions[f - 1]
+            tr, _ = tracker.step(views[f], T_cam=T if name == "with_T_cam" and r["ok"] else None)
+            rows.append(tr)
+        el_t = time.perf_counter() - t
+        streams[name] = {"frames_per_s_tracker_step": (frames - 1) / el_t,
+                         "found_frames": sum(bool(tr and tr[0]["found"]) for tr in rows),
+                         "rot_deg_trans_d_dist": [None if not (tr and tr[0]["found"]) else
+                                                  [round(refine_ref.pose_error(tr[0]["T"], poses[f])[0], 3),
+                                                   round(refine_ref.pose_error(tr[0]["T"], poses[f])[1] / d, 3)]
+                                                  for f, tr in enumerate(rows, 1)]}
+        if name == "with_T_cam":
+            streams[name]["camera_rot_deg_trans_m"] = [round(x, 5) for x in refine_ref.pose_error(tracker.camera(), traj[-1])]
+        tracker.close()
+    out = {"config": "camera motion (oslam_view_egomotion, oslam_tracker_step_cam): static world, 3 degrees and 3 cm per frame",
+           "frames": frames, "egomotion_per_call": per_call, "egomotion_pairs_per_s": (frames - 1) / el,
+           "pair_rot_deg_trans_m_chained_rot_trans_overlap_ok": errs, "tracked_object": k, "tracker": streams}
+    for v in views:
+        v.close()
+    db.close()
+    for m in models:
+        m.close()
+    return out
+
+
 if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "cfg3"
     print(json.dumps({"cfg2": cfg2, "cfg3": cfg3, "cfg3db": cfg3db, "cfg4": cfg4, "cfg5": cfg5, "planes": planes, "db50": db50,
-                      "refine": refine, "verify": verify, "instances": instances, "arbitrate": arbitrate, "track": track}[which]()), flush=True)
+                      "refine": refine, "verify": verify, "instances": instances, "arbitrate": arbitrate, "track": track, "camera": camera}[which]()), flush=True)
