@@ -904,6 +904,110 @@ int oslam_tracker_step_cam(oslam_tracker *t, oslam_scene *scene, const oslam_vie
 int oslam_tracker_predict(oslam_tracker *t, const float T_cam[16]);
 int oslam_tracker_camera(const oslam_tracker *t, float T_world_cam[16]);
 
+/* ---- fusion: depth views into a TSDF volume, and the volume ray-cast back into a view (KinFu's map).  A ray-cast view
+ * is a genuine oslam_view: oslam_view_egomotion, oslam_track, oslam_verify and oslam_arbitrate take it as they take a
+ * depth view, which gives frame-to-model camera tracking (oslam_volume_track) and clouds of the fused surface
+ * (oslam_view_to_cloud).  The restatement in numpy is tests/volume_ref.py; device and restatement agree bit for bit.
+ *
+ * T_vol_cam is everywhere the camera's pose in the volume frame: float32 row-major, camera coordinates -> volume
+ * coordinates, rigid by the test of oslam_refine.  Its inverse T is formed on the host in double as [R^T | -(R^T t)],
+ * -(R^T t)_a = -((R0a*t0 + R1a*t1) + R2a*t2), and rounded to float.
+ * Storage.  One 32-bit word per voxel, int16 q | uint16 w << 16, x fastest, then y, then z; F = (float)q / 32767.0f; a
+ *   new value is stored as q = (int)rintf(F * 32767.0f) (round to nearest even).  A fresh or reset volume is all zero:
+ *   w = 0 reads as "never seen".
+ * Integration of view V at T_vol_cam, for voxel (i, j, k): the centre g_x = origin_x + ((float)i + 0.5f) * voxel (y, z
+ *   alike); p' = T g as oslam_refine computes it, p'x = ((T0*gx + T1*gy) + T2*gz) + T3; skipped unless p'z > 0 (a NaN
+ *   fails); the pixel is oslam_verify's, fu = floorf(((p'x * fx) / p'z + cx) + 0.5f) with V's intrinsics, range-checked
+ *   in float; z_o = V's z there, skipped unless z_o > 0; sdf = z_o - p'z; skipped unless sdf >= -mu;
+ *   f = fminf(1.0f, sdf / mu); F' = ((F * (float)w) + f) / (float)(w + 1); w' = min(w + 1, max_weight).  sdf is the
+ *   projective distance along the optical axis, the residual oslam_verify uses, NOT KinFu's distance along the ray: the
+ *   zero crossing is the same, the band is thinner by the cosine towards the image's corners.  A skipped voxel is
+ *   neither read nor written; a voxel belongs to one thread; no float atomics; two calls give the same bits.
+ * Ray cast at T_vol_cam = M (rows M0..M11) with camera cam and size width x height, for pixel (u, v):
+ *   d = (((float)u - cx) / fx, ((float)v - cy) / fy, 1), not normalised: the ray parameter t is the camera-frame z and a
+ *   vertex is (dx * t, dy * t, t).  In the volume frame o = (M3, M7, M11) and Dx = (M0*dx + M1*dy) + M2 (y, z alike); the
+ *   point at t is Px = ox + Dx * t.  Interval: [tn, tf] starts as [z_min, z_max]; per axis a with lo = origin_a + voxel
+ *   and hi = origin_a + (float)(n_a - 1) * voxel (the box shrunk by one voxel): D_a == 0 misses unless lo <= o_a <= hi,
+ *   otherwise ta = (lo - o_a) / D_a, tb = (hi - o_a) / D_a, tn = fmaxf(tn, fminf(ta, tb)), tf = fminf(tf, fmaxf(ta, tb));
+ *   no hit unless tn <= tf.  Samples t_k = tn + (float)k * step, k = 0, 1, ... while t_k <= tf, step = 0.5f * mu in t (t
+ *   is z and the truncation is along z, so no 1 / |d|).  A sample is the word of the voxel floorf((P_a - origin_a) *
+ *   inv_voxel) per axis, inv_voxel = 1.0f / voxel; a coordinate outside the volume reads as w = 0.  A sample with w = 0
+ *   forgets the previous sample; (F_prev > 0, F < 0) is a front-face crossing between t_prev and t_k;
+ *   (F_prev < 0, F > 0) ends the ray without a hit.
+ *   Trilinear F at a volume-frame point: c_a = (P_a - origin_a) * inv_voxel - 0.5f, b_a = floorf(c_a), f_a = c_a - b_a;
+ *   all of 0 <= b_a <= n_a - 2 and all 8 corners with w > 0, or there is no value; lerp(p, q, f) = p * (1.0f - f) + q * f
+ *   along x, then y, then z.  At a crossing Ft, Ftdt = the trilinear F at t_prev and t_k (no value: no hit);
+ *   t* = t_prev - (step * Ft) / (Ftdt - Ft); no hit unless Ftdt - Ft < 0, t_prev <= t* <= t_k and z_min <= t* <= z_max.
+ *   The pixel's z is t*.  Normal: g_a = F(P* + voxel e_a) - F(P* - voxel e_a) with P* the point at t*, six trilinear
+ *   reads that all need a value; len = sqrtf((gx*gx + gy*gy) + gz*gz) must satisfy 0 < len <= 3.0e38f (the test of
+ *   oslam_depth_to_cloud); n = g / len; into the camera frame by R^T, n'x = (M0*nx + M4*ny) + M8*nz; the pixel has a
+ *   normal only when (n'x * vx + n'y * vy) + n'z * t* < 0: the gradient of a front crossing faces the camera, one that
+ *   does not is a defect of the data and is not flipped.
+ *   The result is an oslam_view the caller owns (oslam_view_destroy): its z image holds t* (0 without a hit), its maps
+ *   exist from the start (x y z 1 | nx ny nz 0 where the pixel has a normal, zeros elsewhere), max_jump is cam's,
+ *   depth_scale is ignored.
+ * oslam_volume_track is host glue: ray-cast at T_vol_cam_prev with the frame's own camera and size,
+ *   oslam_view_egomotion(src = the frame, dst = the ray-cast view, identity, ep), T_vol_cam_out =
+ *   float32(double(T_vol_cam_prev) * double(T)) with the element order of oslam_tracker_step_cam; the egomotion result
+ *   comes back as it is (launches + 1 for the ray cast).  It does not integrate: the caller does when ok is 1.
+ * oslam_view_to_cloud compacts the pixels of a view that have a normal, in row-major order, through the flag, scan and
+ *   compact path of oslam_depth_to_cloud: for a depth view it returns what oslam_depth_to_cloud returns for the same
+ *   image and camera bit for bit, for a ray-cast view the fused surface seen from that pose.  OSLAM_E_LIMIT with
+ *   *n_out = the number of points when cap is too small.
+ * Arguments are checked before any handle is read or any device call is made: NULL pointers, parameters that are not
+ *   finite or lie outside the ranges below, a T_vol_cam that is not rigid, a camera oslam_view_create would refuse and a
+ *   size outside 1..16384 are OSLAM_E_INVALID; so are a volume and a view on different devices.  The allocation is
+ *   computed in size_t (512^3 voxels are 512 MiB).
+ * Cost: integrate = one memset of the counter, k_tsdf_integrate, one copy back, one host wait; raycast = the same with
+ *   k_tsdf_raycast.  Calls on volumes take turns (one lock, held to the end of the host wait).
+ * Out of scope: a moving or shifting volume, colour, the along-ray distance, marching cubes and mesh export, masking
+ *   tracked objects out of the integration, image pyramids, several GPUs; oslam_tracker keeps taking T_cam from the
+ *   caller. */
+typedef struct oslam_volume oslam_volume;
+typedef struct oslam_volume_params {
+    unsigned nx, ny, nz;      /* voxels per side, each 16..512 and a multiple of 8; default 256^3 */
+    float voxel;              /* metres, > 0; default 0.02 */
+    float origin[3];          /* volume-frame position of the corner of voxel (0,0,0); default the volume centred before
+                                 the camera: (-nx/2, -ny/2, 0) voxels */
+    float mu;                 /* truncation distance in metres, >= 2 voxels; default 4 voxels (KinFu's order).  Across
+                                 surfaces seen at a grazing angle the projective band is thinner than mu, and a trilinear
+                                 read needs all 8 corners seen: in the calibration room 4 voxels leave the
+                                 frame-to-model overlap at 0.65, below oslam_view_egomotion's min_overlap of 0.75; 8
+                                 voxels track there.  Choose mu for the scene */
+    unsigned max_weight;      /* 1..65535, default 128 (KinFu's) */
+    int reserved[4];
+} oslam_volume_params;
+
+typedef struct oslam_integrate_result {
+    uint32_t updated;          /* voxels the call updated */
+    uint32_t launches;
+    float ms_total;            /* whole call, host clock */
+} oslam_integrate_result;
+
+typedef struct oslam_raycast_result {
+    uint32_t hits;             /* pixels with a hit */
+    uint32_t normals;          /* pixels with a normal */
+    uint32_t launches;
+    float ms_total;
+} oslam_raycast_result;
+
+int oslam_volume_params_default(oslam_volume_params *p);
+int oslam_volume_create(const oslam_volume_params *p, int dev, oslam_volume **out);
+int oslam_volume_destroy(oslam_volume *vol);
+int oslam_volume_reset(oslam_volume *vol);
+/* res may be NULL */
+int oslam_volume_integrate(oslam_volume *vol, const oslam_view *v, const float T_vol_cam[16], oslam_integrate_result *res);
+int oslam_volume_raycast(oslam_volume *vol, const float T_vol_cam[16], const oslam_camera *cam, int width, int height,
+                         oslam_view **view_out, oslam_raycast_result *res);
+/* ep may be NULL (defaults), ego_res may be NULL */
+int oslam_volume_track(oslam_volume *vol, oslam_view *v, const float T_vol_cam_prev[16], const oslam_egomotion_params *ep,
+                       float T_vol_cam_out[16], oslam_egomotion_result *ego_res);
+int oslam_view_to_cloud(oslam_view *v, float *xyz_out, float *nrm_out, size_t cap, size_t *n_out);
+/* test taps: the whole volume, tsdf_q_out and weight_out [nz][ny][nx]; the view's maps [h][w][8] and z [h][w] (z_out may
+ * be NULL) */
+int oslam_volume_voxels(oslam_volume *vol, int16_t *tsdf_q_out, uint16_t *weight_out);
+int oslam_view_maps(oslam_view *v, float *maps_out, float *z_out);
+
 /* ---- parity taps (tests): values the reference materialises as arrays.
  * Scene::getHashKeys row r (scene.cu:49-54): keys_out[n] of reference point r,
  * computed by the GPU key kernel with this d_dist (key 0 on the diagonal). */

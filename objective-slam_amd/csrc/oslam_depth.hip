@@ -88,16 +88,29 @@ extern "C" int oslamk_aos6_to_soa(const float *d_in6, size_t n, float *d_soa, vo
         }                            \
     } while (0)
 
-/* d_img: the depth image in HBM (uint16 or float, row-major w x h).  d_out6: device [w*h][6].
- * Returns a hipError_t as int. */
-extern "C" int oslamk_depth_to_cloud(const void *d_img, int is_u16, int w, int h, float fx, float fy, float cx,
-                                     float cy, float scale, float z_min, float z_max, float max_jump, float *d_out6,
-                                     uint32_t *n_out, void *stream_)
+/* one thread per pixel of a view's maps (x y z has | nx ny nz 0): out6[pixel] and flags[pixel] as k_depth_points
+ * leaves them */
+__global__ __launch_bounds__(256) void k_maps_points(const float *maps, size_t n, float *out6, uint32_t *flags)
 {
-    hipStream_t stream = (hipStream_t)stream_;
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float4 a = reinterpret_cast<const float4 *>(maps)[2 * i], b = reinterpret_cast<const float4 *>(maps)[2 * i + 1];
+    const uint32_t ok = a.w != 0.0f;
+    if (ok) {
+        float *o = out6 + 6 * i;
+        o[0] = a.x; o[1] = a.y; o[2] = a.z;
+        o[3] = b.x; o[4] = b.y; o[5] = b.z;
+    }
+    flags[i] = ok;
+}
+
+/* The front end's stable compaction: the per-pixel records come from k_depth_points (maps == NULL: the depth image
+ * d_img with camera c) or from a view's maps (k_maps_points); flags -> rocPRIM exclusive scan -> scatter.  d_out6:
+ * device [n][6].  Returns a hipError_t as int. */
+static int points_to_cloud(const void *d_img, int is_u16, int w, int h, const depth_cam &c, const float *maps, size_t n,
+                           float *d_out6, uint32_t *n_out, hipStream_t stream)
+{
     int rc = 0;
-    const size_t n = (size_t)w * h;
-    depth_cam c = {fx, fy, cx, cy, scale, z_min, z_max, max_jump};
     float *d_tmp6 = NULL;
     uint32_t *d_u = NULL;          /* flags, ord */
     void *d_scan = NULL;
@@ -107,8 +120,11 @@ extern "C" int oslamk_depth_to_cloud(const void *d_img, int is_u16, int w, int h
     if (n == 0) return 0;
     DCHK((hipError_t)oslam_dev_alloc((void **)&d_tmp6, sizeof(float) * 6 * n));
     DCHK((hipError_t)oslam_dev_alloc((void **)&d_u, sizeof(uint32_t) * 2 * n));
-    hipLaunchKernelGGL(k_depth_points, dim3((w + 31) / 32, (h + 7) / 8), dim3(256), 0, stream, d_img, is_u16, w, h, c,
-                       d_tmp6, d_u);
+    if (maps)
+        hipLaunchKernelGGL(k_maps_points, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, maps, n, d_tmp6, d_u);
+    else
+        hipLaunchKernelGGL(k_depth_points, dim3((w + 31) / 32, (h + 7) / 8), dim3(256), 0, stream, d_img, is_u16, w, h, c,
+                           d_tmp6, d_u);
     DCHK(rocprim::exclusive_scan(nullptr, scan_bytes, d_u, d_u + n, 0u, n, rocprim::plus<uint32_t>(), stream));
     DCHK((hipError_t)oslam_dev_alloc(&d_scan, scan_bytes ? scan_bytes : 16));
     DCHK(rocprim::exclusive_scan(d_scan, scan_bytes, d_u, d_u + n, 0u, n, rocprim::plus<uint32_t>(), stream));
@@ -124,4 +140,21 @@ done:
     oslam_dev_free(d_u);
     oslam_dev_free(d_scan);
     return rc;
+}
+
+/* d_img: the depth image in HBM (uint16 or float, row-major w x h).  d_out6: device [w*h][6].
+ * Returns a hipError_t as int. */
+extern "C" int oslamk_depth_to_cloud(const void *d_img, int is_u16, int w, int h, float fx, float fy, float cx,
+                                     float cy, float scale, float z_min, float z_max, float max_jump, float *d_out6,
+                                     uint32_t *n_out, void *stream)
+{
+    const depth_cam c = {fx, fy, cx, cy, scale, z_min, z_max, max_jump};
+    return points_to_cloud(d_img, is_u16, w, h, c, NULL, (size_t)w * h, d_out6, n_out, (hipStream_t)stream);
+}
+
+extern "C" int oslamk_maps_to_cloud(const float *maps, size_t n_pix, float *d_out6, uint32_t *n_out, void *stream)
+{
+    const depth_cam c = {};
+    if (!maps) return (int)hipErrorInvalidValue;
+    return points_to_cloud(NULL, 0, 0, 0, c, maps, n_pix, d_out6, n_out, (hipStream_t)stream);
 }

@@ -61,6 +61,8 @@ static int check_params(const oslam_egomotion_params *ep, oslam_egomotion_params
     return OSLAM_OK;
 }
 
+int oslam_ego_check_params(const oslam_egomotion_params *ep, oslam_egomotion_params *out) { return check_params(ep, out); }
+
 static const float k_identity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
 
 static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }

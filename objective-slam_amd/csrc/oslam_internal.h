@@ -225,6 +225,8 @@ void oslam_track_release(void);
 int oslam_track_view_maps(oslam_view *v, int *built);
 /* gives back the pinned state of the camera motion stage (oslam_ego.c); called by oslam_release_scratch */
 void oslam_ego_release(void);
+/* ep NULL = defaults; checks them as oslam_view_egomotion does, *out = the parameters in force (oslam_ego.c) */
+int oslam_ego_check_params(const oslam_egomotion_params *ep, oslam_egomotion_params *out);
 /* the arbitration's parameter check (oslam_arbitrate.c) */
 int oslam_arbitrate_check_params(const oslam_arbitrate_params *ap, oslam_arbitrate_params *out);
 

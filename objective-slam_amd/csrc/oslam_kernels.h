@@ -509,6 +509,36 @@ int oslamk_ego_step(const oslamk_view *src, const float *src_maps, const oslamk_
 int oslamk_ego_corr(const oslamk_view *src, const float *src_maps, const oslamk_view *dst, const float *dst_maps,
                     const float *T12, float r2_corr, float min_dot, int32_t *pixel_out, void *stream);
 
+/* ---- fusion stage (oslam_volume.hip; semantics in include/oslam.h at oslam_volume_integrate / oslam_volume_raycast) ---- */
+#define OSLAMK_VOL_ZRUN 8             /* consecutive z a thread of k_tsdf_integrate walks; nz is a multiple of it */
+#define OSLAMK_VOL_MAX_STEPS 1024     /* samples of one ray at most: step >= one voxel and the box's diagonal is below
+                                         887 voxels, so the march never reaches it */
+
+/* the volume: one word per voxel, int16 q | uint16 w << 16, x fastest, then y, then z */
+typedef struct oslamk_volume {
+    uint32_t *words;
+    int nx, ny, nz;
+    float voxel, inv_voxel;    /* inv_voxel = 1.0f / voxel */
+    float origin[3];
+    float mu;
+    uint32_t max_weight;
+} oslamk_volume;
+
+/* rows of [R | t], float32 */
+typedef struct oslamk_pose {
+    float T[12];
+} oslamk_pose;
+
+/* one frame into the volume; T12 = rows of the inverse of T_vol_cam; *count (zeroed by the caller) += voxels updated */
+int oslamk_tsdf_integrate(const oslamk_volume *vol, const oslamk_view *v, const float *T12, uint32_t *count, void *stream);
+/* the volume seen from T12 = rows of T_vol_cam with the camera and size of *v (v->z is not read): z_out [w*h], maps
+ * [w*h][8]; count[0] += pixels with a hit, count[1] += pixels with a normal (zeroed by the caller) */
+int oslamk_tsdf_raycast(const oslamk_volume *vol, const oslamk_view *v, const float *T12, float *z_out, float *maps,
+                        uint32_t *count, void *stream);
+/* the records of a view's maps that have a normal, in row-major order, as device [n][6] (oslam_depth.hip: the flag,
+ * scan and compact path of oslamk_depth_to_cloud); d_out6 = device [n_pix][6]; returns a hipError_t */
+int oslamk_maps_to_cloud(const float *maps, size_t n_pix, float *d_out6, uint32_t *n_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -181,6 +181,26 @@ class EgomotionResult(C.Structure):
                 "launches": int(self.launches), "ms_total": float(self.ms_total)}
 
 
+class VolumeParams(C.Structure):
+    _fields_ = [("nx", C.c_uint), ("ny", C.c_uint), ("nz", C.c_uint), ("voxel", C.c_float), ("origin", C.c_float * 3),
+                ("mu", C.c_float), ("max_weight", C.c_uint), ("reserved", C.c_int * 4)]
+
+
+class IntegrateResult(C.Structure):
+    _fields_ = [("updated", C.c_uint32), ("launches", C.c_uint32), ("ms_total", C.c_float)]
+
+    def asdict(self):
+        return {"updated": int(self.updated), "launches": int(self.launches), "ms_total": float(self.ms_total)}
+
+
+class RaycastResult(C.Structure):
+    _fields_ = [("hits", C.c_uint32), ("normals", C.c_uint32), ("launches", C.c_uint32), ("ms_total", C.c_float)]
+
+    def asdict(self):
+        return {"hits": int(self.hits), "normals": int(self.normals), "launches": int(self.launches),
+                "ms_total": float(self.ms_total)}
+
+
 ARBITRATE_MAX_HYPOTHESES = 1024
 CELL_DTYPE = np.dtype([("code", "<u8"), ("count", "<u4"), ("pad", "<u4")])
 
@@ -273,6 +293,16 @@ _SIGNATURES = {
     "oslam_tracker_step_cam": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(_sz), C.POINTER(_i)]),
     "oslam_tracker_predict": (_i, [_vp, _vp]),
     "oslam_tracker_camera": (_i, [_vp, _vp]),
+    "oslam_volume_params_default": (_i, [C.POINTER(VolumeParams)]),
+    "oslam_volume_create": (_i, [C.POINTER(VolumeParams), _i, C.POINTER(_vp)]),
+    "oslam_volume_destroy": (_i, [_vp]),
+    "oslam_volume_reset": (_i, [_vp]),
+    "oslam_volume_integrate": (_i, [_vp, _vp, _vp, C.POINTER(IntegrateResult)]),
+    "oslam_volume_raycast": (_i, [_vp, _vp, _vp, _i, _i, C.POINTER(_vp), C.POINTER(RaycastResult)]),
+    "oslam_volume_track": (_i, [_vp, _vp, _vp, C.POINTER(EgomotionParams), _vp, C.POINTER(EgomotionResult)]),
+    "oslam_view_to_cloud": (_i, [_vp, _vp, _vp, _sz, C.POINTER(_sz)]),
+    "oslam_volume_voxels": (_i, [_vp, _vp, _vp]),
+    "oslam_view_maps": (_i, [_vp, _vp, _vp]),
     "oslam_scene_keys": (_i, [_vp, _sz, _vp]),
     "oslam_model_keys": (_i, [_vp, _sz, _vp]),
     "oslam_model_bucket": (_i, [_vp, C.c_uint32, _vp, _sz, C.POINTER(_sz)]),
@@ -1253,6 +1283,115 @@ class View:
     def close(self):
         if self._h:
             lib().oslam_view_destroy(self._h)
+            self._h = C.c_void_p(0)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def view_to_cloud(view):
+    """The pixels of a view that have a normal, in row-major order (oslam_view_to_cloud): -> (points, normals) in the
+    view's camera coordinates.  For a depth view what depth_to_cloud returns for its image, for a ray-cast view the fused
+    surface seen from its pose."""
+    n = view.width * view.height
+    po, no = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32)
+    k = C.c_size_t(0)
+    _check(lib().oslam_view_to_cloud(view._h, _p(po), _p(no), n, C.byref(k)))
+    return po[: k.value].copy(), no[: k.value].copy()
+
+
+def view_maps(view):
+    """The view's maps and z image as a test tap (oslam_view_maps): -> (maps float32 [h,w,8]: x y z has | nx ny nz 0,
+    z float32 [h,w])."""
+    n = view.width * view.height
+    maps, z = np.zeros((n, 8), np.float32), np.zeros(n, np.float32)
+    _check(lib().oslam_view_maps(view._h, _p(maps), _p(z)))
+    return maps.reshape(view.height, view.width, 8), z.reshape(view.height, view.width)
+
+
+def default_volume_params(**kw):
+    """oslam_volume_params_default, then the fields given as keywords (origin: three floats)."""
+    p = VolumeParams()
+    _check(lib().oslam_volume_params_default(C.byref(p)))
+    for k, v in kw.items():
+        if not hasattr(p, k) or k == "reserved":
+            raise TypeError("unknown volume parameter %r" % k)
+        if k == "origin":
+            p.origin[:] = [float(x) for x in v]
+        else:
+            setattr(p, k, v)
+    return p
+
+
+class Volume:
+    """A TSDF volume on the device (oslam_volume): integrate(view, T_vol_cam) fuses a depth view, raycast(...) returns
+    the fused surface as a View, track(view, T_prev) follows the camera against it.  T_vol_cam: the camera's pose in the
+    volume frame, float32 4x4.  mu None: 4 voxels."""
+
+    def __init__(self, nx, ny, nz, voxel, origin, mu=None, max_weight=128, dev=0):
+        self._h = C.c_void_p(0)
+        p = default_volume_params(nx=nx, ny=ny, nz=nz, voxel=voxel, origin=origin,
+                                  mu=float(np.float32(4.0) * np.float32(voxel)) if mu is None else mu, max_weight=max_weight)
+        self.params = p
+        self.T, self._started = np.eye(4, dtype=np.float32), False      # the pose step() keeps
+        _check(lib().oslam_volume_create(C.byref(p), int(dev), C.byref(self._h)))
+
+    def integrate(self, view, T_vol_cam):
+        res = IntegrateResult()
+        _check(lib().oslam_volume_integrate(self._h, view._h, _p(_pose16(T_vol_cam)), C.byref(res)))
+        return res.asdict()
+
+    def raycast(self, T_vol_cam, fx, fy, cx, cy, width, height, z_min=0.1, z_max=10.0, max_jump=0.05):
+        """-> (View, result dict)"""
+        cam = Camera(fx, fy, cx, cy, 1.0, z_min, z_max, max_jump)
+        res = RaycastResult()
+        v = View.__new__(View)
+        v._h = C.c_void_p(0)
+        v.width, v.height = int(width), int(height)
+        _check(lib().oslam_volume_raycast(self._h, _p(_pose16(T_vol_cam)), C.byref(cam), int(width), int(height),
+                                          C.byref(v._h), C.byref(res)))
+        return v, res.asdict()
+
+    def track(self, view, T_prev, params=None):
+        """Frame-to-model camera tracking (oslam_volume_track): -> (T_vol_cam float32 4x4, egomotion result dict)."""
+        p = params if params is not None else default_egomotion_params()
+        To = np.zeros(16, np.float32)
+        res = EgomotionResult()
+        _check(lib().oslam_volume_track(self._h, view._h, _p(_pose16(T_prev)), C.byref(p), _p(To), C.byref(res)))
+        return To.reshape(4, 4), res.asdict()
+
+    def step(self, view, params=None):
+        """One frame with the pose kept here: the first call integrates at the initial pose (the identity: the
+        volume frame is the first camera's);
+        a later call tracks from the kept pose and integrates when the result is ok.  -> (T_vol_cam, egomotion result
+        dict, None on the first call)."""
+        if not self._started:
+            self.integrate(view, self.T)
+            self._started = True
+            return self.T.copy(), None
+        T, res = self.track(view, self.T, params)
+        if res["ok"]:
+            self.T = T
+            self.integrate(view, T)
+        return self.T.copy(), res
+
+    def voxels(self):
+        """The whole volume as a test tap: -> (q int16 [nz,ny,nx], w uint16 [nz,ny,nx])."""
+        shape = (self.params.nz, self.params.ny, self.params.nx)
+        q, w = np.zeros(shape, np.int16), np.zeros(shape, np.uint16)
+        _check(lib().oslam_volume_voxels(self._h, _p(q), _p(w)))
+        return q, w
+
+    def reset(self):
+        _check(lib().oslam_volume_reset(self._h))
+        self.T, self._started = np.eye(4, dtype=np.float32), False
+
+    def close(self):
+        if self._h:
+            lib().oslam_volume_destroy(self._h)
             self._h = C.c_void_p(0)
 
     def __del__(self):

@@ -21,6 +21,9 @@ configuration; these are not bench lines).  Needs a HIP device.
   python tools/bench_configs.py camera   a static world seen from a moving camera (3 degrees and 3 cm per frame, 30 frames
                                          at 640x480): oslam_view_egomotion per call, and Tracker.step on one object
                                          with and without the camera's motion
+  python tools/bench_configs.py fusion   a 256^3 TSDF volume over the room of the camera configuration and its 640x480
+                                         stream: integrate, raycast, track per call, Volume.step in frames/s, and the
+                                         bytes per second the integration rule loads and stores
 One JSON line each."""
 import importlib, json, os, sys, time
 
@@ -685,7 +688,62 @@ def camera(frames=30, calls=20):
     return out
 
 
+def fusion(calls=20):
+    """The fusion stage (oslam_volume_integrate / _raycast / _track) on the static world of tests/camera_ref.py: a 256^3
+    volume of 3.6 cm voxels over the room, the 640x480 stream out and back.  The integration figure counts the words the
+    rule loads and stores (8 bytes per updated voxel); once the 64 MiB volume is resident it is a cache figure."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import camera_ref as E
+    import refine_ref
+    world = E.make_world(synth, 0)
+    sweep = E.trajectory(synth, 0, frames=10)
+    order = list(range(10)) + list(range(8, -1, -1))
+    cam = E.CAM
+    rendered = [ppf.View(E.render(synth, world, T), cam["fx"], cam["fy"], cam["cx"], cam["cy"], z_min=cam["z_min"],
+                         z_max=cam["z_max"], max_jump=E.MAX_JUMP) for T in sweep]
+    spec = dict(nx=256, ny=256, nz=256, voxel=0.036, origin=[-2.9, -4.3, 0.3], mu=0.288)
+    vol = ppf.Volume(**spec)
+    eye = np.eye(4, dtype=np.float32)
+
+    def raycast(T):
+        return vol.raycast(T, cam["fx"], cam["fy"], cam["cx"], cam["cy"], 640, 480, z_min=cam["z_min"], z_max=cam["z_max"],
+                           max_jump=E.MAX_JUMP)
+    vol.integrate(rendered[0], eye)
+    integ, upd = [], 0
+    for _ in range(calls):
+        r = vol.integrate(rendered[0], eye)
+        integ.append(r["ms_total"])
+        upd = r["updated"]
+    rays = []
+    for _ in range(calls + 1):
+        v, r = raycast(eye)
+        rays.append(r["ms_total"])
+        hits = (r["hits"], r["normals"])
+        v.close()
+    trk = [vol.track(rendered[1], eye)[1] for _ in range(calls + 1)]
+    vol.reset()
+    t = time.perf_counter()
+    steps = [vol.step(rendered[k]) for k in order]
+    el = time.perf_counter() - t
+    end = refine_ref.pose_error(steps[-1][0], sweep[0])
+    ms_i = float(np.median(integ))
+    out = {"config": "fusion (oslam_volume): 256^3 volume of 3.6 cm voxels, 640x480 stream, 3 degrees and 3 cm per frame",
+           "volume": spec, "integrate_ms_median": ms_i, "integrate_voxels_updated": upd,
+           "integrate_rule_bytes_per_s": 8.0 * upd / (ms_i * 1e-3), "hbm_peak_bytes_per_s": 8e12,
+           "raycast_ms_median": float(np.median(rays[1:])), "raycast_hits_normals": hits,
+           "track_ms_median": float(np.median([r["ms_total"] for r in trk[1:]])), "track_launches": trk[-1]["launches"],
+           "track_iterations": trk[-1]["iterations"], "step_frames_per_s": len(order) / el,
+           "step_ok": [None if r is None else r["ok"] for _, r in steps],
+           "step_overlap": [None if r is None else round(r["overlap"], 3) for _, r in steps],
+           "end_pose_rot_deg_trans_m": [round(x, 5) for x in end]}
+    for v in rendered:
+        v.close()
+    vol.close()
+    return out
+
+
 if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "cfg3"
     print(json.dumps({"cfg2": cfg2, "cfg3": cfg3, "cfg3db": cfg3db, "cfg4": cfg4, "cfg5": cfg5, "planes": planes, "db50": db50,
-                      "refine": refine, "verify": verify, "instances": instances, "arbitrate": arbitrate, "track": track, "camera": camera}[which]()), flush=True)
+                      "refine": refine, "verify": verify, "instances": instances, "arbitrate": arbitrate, "track": track, "camera": camera,
+                      "fusion": fusion}[which]()), flush=True)
