@@ -65,8 +65,10 @@ class Volume:
         self.w = np.zeros((nz, ny, nx), np.uint16)
 
     # ------------------------------------------------------------ integration
-    def integrate(self, z, cam, T_vol_cam):
-        """z: the view's z image (view_ref.view_z), float32 [h, w], 0 = not valid.  -> voxels updated."""
+    def integrate(self, z, cam, T_vol_cam, trace=None):
+        """z: the view's z image (view_ref.view_z), float32 [h, w], 0 = not valid.  -> voxels updated.
+        trace: a dict that receives the number of voxels per skip reason and per kind of update (added to what it
+        holds); the volume and the return value do not depend on it."""
         T = invert_pose(T_vol_cam)
         h, w = z.shape
         nx, ny, nz = self.n
@@ -93,6 +95,22 @@ class Volume:
             qn = np.rint(np.where(ok, Fn, 0) * F(32767.0)).astype(np.int16)
         wn = np.minimum(self.w.astype(np.int32) + 1, self.max_weight).astype(np.uint16)
         assert px.dtype == np.float32 and Fn.dtype == np.float32
+        if trace is not None:
+            with np.errstate(all="ignore"):
+                front = pz > F(0)
+                in_u, in_v = (fu >= F(0)) & (fu < F(w)), (fv >= F(0)) & (fv < F(h))
+                inside = front & in_u & in_v
+                seen = inside & (zo > F(0))
+                near = seen & (sdf >= -self.mu)
+                counts = dict(behind=~front, outside=front & ~(in_u & in_v), off_left=front & (fu == F(-1)) & in_v,
+                              off_right=front & (fu == F(w)) & in_v, off_top=front & (fv == F(-1)) & in_u,
+                              off_bottom=front & (fv == F(h)) & in_u, hole=inside & ~seen, far=seen & ~near,
+                              at_minus_mu=near & (sdf == -self.mu), clamped=near & (sdf / self.mu > F(1.0)),
+                              band=near & (f > F(-1.0)) & (f < F(1.0)), updated=ok, w_max=ok & (wn == self.max_weight),
+                              w_256=ok & (self.w == 255) & (wn == 256), q_max=ok & (qn == 32767), q_neg=ok & (qn < 0),
+                              q_min=ok & (qn == -32767))
+            for key, m in counts.items():
+                trace[key] = trace.get(key, 0) + int(m.sum())
         self.q[ok] = qn[ok]
         self.w[ok] = wn[ok]
         return int(ok.sum())
@@ -137,8 +155,13 @@ class Volume:
         return val, ok
 
     # ------------------------------------------------------------ ray cast
-    def raycast(self, T_vol_cam, cam, width, height):
-        """-> (z float32 [h, w], (V, N, has) as track_ref.view_maps, dict hits normals)."""
+    def raycast(self, T_vol_cam, cam, width, height, trace=None):
+        """-> (z float32 [h, w], (V, N, has) as track_ref.view_maps, dict hits normals).
+        trace: a dict that receives the number of rays per exit reason (added to what it holds); "zero_then_negative",
+        the samples F < 0 that follow a sample F == 0 (no crossing: F_prev > 0 fails), and "zero_then_negative_live", those
+        of them where a rule with F_prev >= 0 would have returned a hit (both trilinear reads have a value, Ftdt - Ft < 0
+        and t* lies in its bracket and in [z_min, z_max]); "max_step", the largest step index a ray used; "exit", the
+        reason of every pixel ([h, w] of str).  The result does not depend on it."""
         M = np.asarray(T_vol_cam, np.float32).reshape(4, 4)
         fx, fy, cx, cy = F(cam["fx"]), F(cam["fy"]), F(cam["cx"]), F(cam["cy"])
         z_min, z_max = F(cam["z_min"]), F(cam["z_max"])
@@ -161,6 +184,15 @@ class Volume:
                 tn = np.where(zero, tn, np.maximum(tn, np.minimum(ta, tb)))
                 tf = np.where(zero, tf, np.minimum(tf, np.maximum(ta, tb)))
             active = ~miss & (tn <= tf)
+        why = np.full(n, "exhausted", dtype="U16") if trace is not None else None      # marched to tf without a crossing
+        if trace is not None:
+            any_zero = (D[0] == F(0)) | (D[1] == F(0)) | (D[2] == F(0))
+            why[miss] = "zero_miss"
+            why[~miss & ~active] = "empty"
+            gap = np.zeros(n, bool)                       # the ray forgot a sample it had: an unseen gap
+            tr = dict(zero_inside=int((any_zero & ~miss).sum()), zero_marched=int((any_zero & active).sum()),
+                      tn_is_z_min=int((active & (tn == z_min)).sum()), tf_is_z_max=int((active & (tf == z_max)).sum()),
+                      zero_then_negative=0, zero_then_negative_live=0, max_step=-1)
         step = F(0.5) * self.mu
         have = np.zeros(n, bool)
         Fp, tp, ts = np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.float32)
@@ -172,14 +204,30 @@ class Volume:
             alive = t <= tf[idx]
             active[idx[~alive]] = False
             idx, t = idx[alive], t[alive]
+            if trace is not None and idx.size:
+                tr["max_step"] = k
             x, y, zz = (o[a] + D[a][idx] * t for a in range(3))
             Fc, w = self._nearest(x, y, zz)
             seen = w > 0
+            if trace is not None:
+                gap[idx[~seen & have[idx]]] = True
+                zn = seen & have[idx] & (Fp[idx] == F(0)) & (Fc < F(0))
+                tr["zero_then_negative"] += int(zn.sum())
+                if zn.any():
+                    iz = idx[zn]
+                    Fa, oka = self._trilinear(*(o[a] + D[a][iz] * tp[iz] for a in range(3)))
+                    Fb, okb = self._trilinear(x[zn], y[zn], zz[zn])
+                    with np.errstate(all="ignore"):
+                        tz = tp[iz] - (step * Fa) / (Fb - Fa)
+                        live = oka & okb & (Fb - Fa < F(0)) & (tz >= tp[iz]) & (tz <= t[zn]) & (tz >= z_min) & (tz <= z_max)
+                    tr["zero_then_negative_live"] += int(live.sum())
             have[idx[~seen]] = False
             cross = seen & have[idx] & (Fp[idx] > F(0)) & (Fc < F(0))
             back = seen & ~cross & have[idx] & (Fp[idx] < F(0)) & (Fc > F(0))
             rest = seen & ~cross & ~back
             active[idx[cross | back]] = False
+            if trace is not None:
+                why[idx[back]] = "back_face"
             ic = idx[cross]
             if ic.size:
                 tpc, tc = tp[ic], t[cross]
@@ -190,6 +238,12 @@ class Volume:
                     tstar = tpc - (step * Ft) / den
                     good = ok0 & ok1 & (den < F(0)) & (tstar >= tpc) & (tstar <= tc) & (tstar >= z_min) & (tstar <= z_max)
                 ts[ic[good]] = tstar[good]
+                if trace is not None:
+                    with np.errstate(all="ignore"):
+                        for name, m in (("z_cut", ~((tstar >= z_min) & (tstar <= z_max))),
+                                        ("off_bracket", ~((tstar >= tpc) & (tstar <= tc))), ("den", ~(den < F(0))),
+                                        ("trilinear", ~(ok0 & ok1)), ("hit", good)):       # the first that fails names it
+                            why[ic[m]] = name
             ir = idx[rest]
             have[ir] = True
             Fp[ir] = Fc[rest]
@@ -220,6 +274,15 @@ class Volume:
             V[sel] = np.stack([vx[ok], vy[ok], t[ok]], axis=1)
             N[sel] = np.stack([nc[0][ok], nc[1][ok], nc[2][ok]], axis=1)
         shape = (height, width)
+        if trace is not None:
+            why[hit & ~has] = "no_normal"
+            tr["gap_then_hit"] = int((gap & hit).sum())
+            for name in ("zero_miss", "empty", "exhausted", "back_face", "trilinear", "den", "off_bracket", "z_cut", "no_normal",
+                         "hit"):
+                tr[name] = int((why == name).sum())
+            for key, val in tr.items():
+                trace[key] = max(trace.get(key, -1), val) if key == "max_step" else trace.get(key, 0) + val
+            trace["exit"] = why.reshape(shape)
         return ts.reshape(shape), (V.reshape(shape + (3,)), N.reshape(shape + (3,)), has.reshape(shape)), \
             dict(hits=int(hit.sum()), normals=int(has.sum()))
 
