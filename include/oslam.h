@@ -906,8 +906,8 @@ int oslam_tracker_camera(const oslam_tracker *t, float T_world_cam[16]);
 
 /* ---- fusion: depth views into a TSDF volume, and the volume ray-cast back into a view (KinFu's map).  A ray-cast view
  * is a genuine oslam_view: oslam_view_egomotion, oslam_track, oslam_verify and oslam_arbitrate take it as they take a
- * depth view, which gives frame-to-model camera tracking (oslam_volume_track) and clouds of the fused surface
- * (oslam_view_to_cloud).  The restatement in numpy is tests/volume_ref.py; device and restatement agree bit for bit.
+ * depth view, which gives frame-to-model camera tracking (oslam_volume_track) and clouds of the fused surface as one
+ * pose sees it (oslam_view_to_cloud); oslam_volume_surface below gives the whole of it.  The restatement in numpy is tests/volume_ref.py; device and restatement agree bit for bit.
  *
  * T_vol_cam is everywhere the camera's pose in the volume frame: float32 row-major, camera coordinates -> volume
  * coordinates, rigid by the test of oslam_refine.  Its inverse T is formed on the host in double as [R^T | -(R^T t)],
@@ -1007,6 +1007,61 @@ int oslam_view_to_cloud(oslam_view *v, float *xyz_out, float *nrm_out, size_t ca
  * be NULL) */
 int oslam_volume_voxels(oslam_volume *vol, int16_t *tsdf_q_out, uint16_t *weight_out);
 int oslam_view_maps(oslam_view *v, float *maps_out, float *z_out);
+
+/* ---- the fused surface of a whole volume as a cloud and as a scene (KinFu's fetchCloud plus fetchNormals): every zero
+ * crossing of the TSDF along a voxel edge becomes a point with a normal, in the volume frame.  The restatement in numpy
+ * is tests/surface_ref.py; device and restatement agree bit for bit, order included.
+ *
+ * Storage and F = (float)q / 32767.0f are oslam_volume_integrate's.  All arithmetic is float32, grouped as written.
+ * Seen.  A voxel is seen iff w >= min_weight.
+ * Crossings.  For voxel (i, j, k) and axis a in the order x, y, z the neighbour is (i+1, j, k), (i, j+1, k) or
+ *   (i, j, k+1).  The edge exists only if the neighbour's index is below n_a: the last voxel of a row has no +x edge
+ *   and does not read the first voxel of the next row.  With q0, q1 the two stored int16 and both voxels seen, the edge
+ *   is a crossing iff (q0 < 0) != (q1 < 0): an integer test in which zero counts as positive, so a surface that passes
+ *   exactly through a voxel centre is found once, on the edge whose other end is negative.
+ * Point.  F0 = (float)q0 / 32767.0f, F1 alike; t = F0 / (F0 - F1) (the denominator is not 0 when the signs differ);
+ *   the voxel centre is g_b = origin_b + ((float)idx_b + 0.5f) * voxel; P_a = g_a + t * voxel and P_b = g_b on the two
+ *   other axes.
+ * Normal.  g_b = F(P + voxel e_b) - F(P - voxel e_b) with the trilinear read of oslam_volume_raycast unchanged: all
+ *   eight corners need w > 0 (min_weight does not enter it) and 0 <= b_a <= n_a - 2.  All six reads must have a value;
+ *   len = sqrtf((gx*gx + gy*gy) + gz*gz) must satisfy 0 < len <= 3.0e38f; n = g / len.  The TSDF grows towards free
+ *   space, so n is the outward normal; there is no camera and hence no facing test.  A crossing without a normal is
+ *   counted (result.crossings) and dropped.
+ * Order.  Ascending 3 * (i + nx * (j + ny * k)) + a.  Two calls give the same bits; there are no float atomics.
+ * oslam_volume_surface: xyz_out and nrm_out [cap][3] are both given or both NULL; both NULL needs cap == 0 and only
+ *   counts.  *n_out = the number of points in every case that reached the device; OSLAM_E_LIMIT when outputs are given
+ *   and cap is below it (nothing is written, the result is filled).  sp NULL = defaults, res may be NULL.
+ * oslam_scene_from_volume: extraction -> voxel grid (leaf > 0; 0 skips) -> scene, the cloud never leaving HBM; leaf,
+ *   d_dist, ref_point_downsample_factor, params and n_points_out as in oslam_scene_from_depth, except that the scene
+ *   lives on the volume's device (params->dev is not read).  It equals oslam_scene_create over oslam_voxel_grid over
+ *   oslam_volume_surface.
+ * oslam_volume_set_voxels is the inverse of oslam_volume_voxels, tsdf_q and weight [nz][ny][nx]: it restores a saved
+ *   map and is the tests' way to any volume.
+ * Arguments are checked before any handle is read or any device call is made: NULL vol, n_out or out, a min_weight
+ *   outside 1..65535, one output without the other, NULL outputs with cap > 0, leaf or d_dist below 0 (or NaN) and a
+ *   factor of 0 are OSLAM_E_INVALID.
+ * Cost: one memset of the totals, k_surface_count and k_surface_scan, one copy back and host wait for the number of
+ *   points, then k_surface_emit into a block of exactly that size and one more wait.  Device memory besides the output:
+ *   one counter per workgroup of 1024 voxels.  Calls take turns with the other calls on volumes. */
+typedef struct oslam_surface_params {
+    unsigned min_weight;      /* 1..65535, default 1: a voxel is seen from this weight on */
+    int reserved[7];
+} oslam_surface_params;
+
+typedef struct oslam_surface_result {
+    uint32_t crossings;        /* sign changes along edges between seen voxels */
+    uint32_t points;           /* crossings that have a normal: what the call returns */
+    uint32_t launches;
+    float ms_total;            /* whole call, host clock */
+} oslam_surface_result;
+
+int oslam_surface_params_default(oslam_surface_params *p);
+int oslam_volume_surface(oslam_volume *vol, const oslam_surface_params *sp, float *xyz_out, float *nrm_out, size_t cap,
+                         size_t *n_out, oslam_surface_result *res);
+int oslam_scene_from_volume(oslam_volume *vol, const oslam_surface_params *sp, float leaf, float d_dist,
+                            unsigned ref_point_downsample_factor, const oslam_params *params, oslam_scene **out,
+                            size_t *n_points_out);
+int oslam_volume_set_voxels(oslam_volume *vol, const int16_t *tsdf_q, const uint16_t *weight);
 
 /* ---- parity taps (tests): values the reference materialises as arrays.
  * Scene::getHashKeys row r (scene.cu:49-54): keys_out[n] of reference point r,

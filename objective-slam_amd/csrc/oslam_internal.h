@@ -227,6 +227,12 @@ int oslam_track_view_maps(oslam_view *v, int *built);
 void oslam_ego_release(void);
 /* ep NULL = defaults; checks them as oslam_view_egomotion does, *out = the parameters in force (oslam_ego.c) */
 int oslam_ego_check_params(const oslam_egomotion_params *ep, oslam_egomotion_params *out);
+/* ---- surface extraction (oslam_volume.c) ---- */
+/* sp NULL = defaults; checks them as oslam_volume_surface does, *out = the parameters in force */
+int oslam_surface_check_params(const oslam_surface_params *sp, oslam_surface_params *out);
+/* the volume's surface in HBM as [*np][6] (NULL without points) on device *dev; the caller frees the block
+ * (oslam_dev_free).  Takes the volume lock for the extraction */
+int oslam_volume_surface_cloud(oslam_volume *vol, unsigned min_weight, int *dev, float **d_pts6, uint32_t *np);
 /* the arbitration's parameter check (oslam_arbitrate.c) */
 int oslam_arbitrate_check_params(const oslam_arbitrate_params *ap, oslam_arbitrate_params *out);
 

@@ -539,6 +539,21 @@ int oslamk_tsdf_raycast(const oslamk_volume *vol, const oslamk_view *v, const fl
  * scan and compact path of oslamk_depth_to_cloud); d_out6 = device [n_pix][6]; returns a hipError_t */
 int oslamk_maps_to_cloud(const float *maps, size_t n_pix, float *d_out6, uint32_t *n_out, void *stream);
 
+/* ---- surface extraction (oslam_surface.hip; semantics in include/oslam.h at oslam_volume_surface) ---- */
+#define OSLAMK_SURF_THREADS 256
+#define OSLAMK_SURF_ITEMS 4           /* chunks of 256 consecutive voxels per workgroup */
+#define OSLAMK_SURF_RUN (OSLAMK_SURF_THREADS * OSLAMK_SURF_ITEMS)   /* consecutive linear voxel indices a workgroup owns */
+
+/* workgroups of the two passes: ceil(nx * ny * nz / OSLAMK_SURF_RUN), at most 2^17 */
+uint32_t oslamk_surface_groups(const oslamk_volume *vol);
+/* first pass and scan: counts [n_groups] leaves as the exclusive offsets of the workgroups' points; totals[0] +=
+ * crossings (zeroed by the caller), totals[1] = points */
+int oslamk_surface_count(const oslamk_volume *vol, uint32_t min_weight, uint32_t n_groups, uint32_t *counts, uint32_t *totals,
+                         void *stream);
+/* second pass: out6 = device [n_points][6] (x y z nx ny nz), offsets and n_points as oslamk_surface_count left them */
+int oslamk_surface_emit(const oslamk_volume *vol, uint32_t min_weight, uint32_t n_groups, const uint32_t *offsets,
+                        uint32_t n_points, float *out6, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,6 @@
 /*
- * oslam_scene.c -- a scene: from host buffers or from a depth image, with its reference points and their
- * frames (scene.cu:24-55).
+ * oslam_scene.c -- a scene: from host buffers, from a depth image or from a volume's surface, with its reference
+ * points and their frames (scene.cu:24-55).
  */
 
 #include "oslam_internal.h"
@@ -79,26 +79,16 @@ int oslam_scene_create(const float *xyz, const float *nrm, size_t n, size_t stri
     return scene_create_any(xyz, nrm, stride_bytes, NULL, n, d_dist, df, params, out);
 }
 
-int oslam_scene_from_depth(const void *depth, int depth_is_u16, int width, int height, const oslam_camera *cam,
-                           float leaf, float d_dist, unsigned df, const oslam_params *params, oslam_scene **out,
-                           size_t *n_points_out)
+/* a cloud that lies in HBM as [np][6] -> voxel grid (leaf > 0) -> scene; `few` names the source when fewer than 2 points
+ * are left */
+static int scene_from_points6(const float *d_pts6, uint32_t np, float leaf, float d_dist, unsigned df, const oslam_params *p,
+                              const char *few, oslam_scene **out, size_t *n_points_out)
 {
     int rc = OSLAM_OK, k;
-    oslam_params p;
-    void *d_img = NULL;
-    float *d_pts6 = NULL, *d_soa = NULL, *d_vox6 = NULL;
-    const float *d_final;
-    uint32_t np = 0, nv = 0;
-    size_t n_final;
-    if (!out) return fail(OSLAM_E_INVALID, "out is NULL");
-    *out = NULL;
-    if (n_points_out) *n_points_out = 0;
-    if (!(leaf >= 0.0f)) return fail(OSLAM_E_INVALID, "bad depth image arguments");
-    if (params) p = *params; else oslam_params_default(&p);
-    rc = oslam_depth_points(depth, depth_is_u16, width, height, cam, p.dev, &d_img, &d_pts6, &np);
-    if (rc != OSLAM_OK) goto done;
-    d_final = d_pts6;
-    n_final = np;
+    float *d_soa = NULL, *d_vox6 = NULL;
+    const float *d_final = d_pts6;
+    uint32_t nv = 0;
+    size_t n_final = np;
     if (leaf > 0.0f && np > 0) {
         HIPCHK((hipError_t)oslam_dev_alloc((void **)&d_soa, sizeof(float) * 6 * (size_t)np));
         HIPCHK((hipError_t)oslam_dev_alloc((void **)&d_vox6, sizeof(float) * 6 * (size_t)np));
@@ -109,14 +99,60 @@ int oslam_scene_from_depth(const void *depth, int depth_is_u16, int width, int h
         d_final = d_vox6;
         n_final = nv;
     }
-    if (n_final < 2) { rc = fail(OSLAM_E_INVALID, "the depth image leaves fewer than 2 scene points"); goto done; }
+    if (n_final < 2) { rc = fail(OSLAM_E_INVALID, few); goto done; }
     /* the scene's arrays are made from the cloud where it lies; one copy comes back for the host's reference frames */
-    rc = scene_create_any(NULL, NULL, 0, d_final, n_final, d_dist, df, &p, out);
+    rc = scene_create_any(NULL, NULL, 0, d_final, n_final, d_dist, df, p, out);
     if (rc == OSLAM_OK && n_points_out) *n_points_out = n_final;
 done:
-    oslam_dev_free(d_img);
-    oslam_dev_free(d_pts6);
     oslam_dev_free(d_soa);
     oslam_dev_free(d_vox6);
+    return rc;
+}
+
+int oslam_scene_from_depth(const void *depth, int depth_is_u16, int width, int height, const oslam_camera *cam,
+                           float leaf, float d_dist, unsigned df, const oslam_params *params, oslam_scene **out,
+                           size_t *n_points_out)
+{
+    int rc;
+    oslam_params p;
+    void *d_img = NULL;
+    float *d_pts6 = NULL;
+    uint32_t np = 0;
+    if (!out) return fail(OSLAM_E_INVALID, "out is NULL");
+    *out = NULL;
+    if (n_points_out) *n_points_out = 0;
+    if (!(leaf >= 0.0f)) return fail(OSLAM_E_INVALID, "bad depth image arguments");
+    if (params) p = *params; else oslam_params_default(&p);
+    rc = oslam_depth_points(depth, depth_is_u16, width, height, cam, p.dev, &d_img, &d_pts6, &np);
+    if (rc == OSLAM_OK)
+        rc = scene_from_points6(d_pts6, np, leaf, d_dist, df, &p, "the depth image leaves fewer than 2 scene points", out,
+                                n_points_out);
+    oslam_dev_free(d_img);
+    oslam_dev_free(d_pts6);
+    return rc;
+}
+
+int oslam_scene_from_volume(oslam_volume *vol, const oslam_surface_params *sp, float leaf, float d_dist, unsigned df,
+                            const oslam_params *params, oslam_scene **out, size_t *n_points_out)
+{
+    int rc;
+    oslam_params p;
+    oslam_surface_params s;
+    float *d_pts6 = NULL;
+    uint32_t np = 0;
+    if (!out) return fail(OSLAM_E_INVALID, "out is NULL");
+    *out = NULL;
+    if (n_points_out) *n_points_out = 0;
+    if (!vol) return fail(OSLAM_E_INVALID, "volume is NULL");
+    if (!(leaf >= 0.0f) || !(d_dist >= 0.0f) || df == 0) return fail(OSLAM_E_INVALID, "bad scene arguments");
+    rc = oslam_surface_check_params(sp, &s);
+    if (rc != OSLAM_OK) return rc;
+    if (params) p = *params; else oslam_params_default(&p);
+    /* the scene lives where the volume does */
+    rc = oslam_volume_surface_cloud(vol, s.min_weight, &p.dev, &d_pts6, &np);
+    if (rc == OSLAM_OK)
+        rc = scene_from_points6(d_pts6, np, leaf, d_dist, df, &p, "the volume's surface leaves fewer than 2 scene points", out,
+                                n_points_out);
+    oslam_dev_free(d_pts6);
     return rc;
 }

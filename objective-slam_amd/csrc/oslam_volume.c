@@ -3,6 +3,8 @@
  * oslam_volume_integrate): the host side of the kernels in oslam_volume.hip.  A call checks its arguments, zeroes a
  * counter block, runs one kernel and reads the counters back with one host wait.  oslam_volume_track is glue over the
  * ray cast and oslam_view_egomotion; oslam_view_to_cloud runs the depth front end's compaction over a view's maps.
+ * oslam_volume_surface (kernels: oslam_surface.hip) counts, waits for the number of points, allocates exactly that and
+ * emits.
  */
 #include <math.h>
 #include <pthread.h>
@@ -348,5 +350,130 @@ int oslam_view_maps(oslam_view *v, float *maps_out, float *z_out)
 done:
     if (hipStreamSynchronize((hipStream_t)oslam_stream()) != hipSuccess && rc == OSLAM_OK) rc = fail(OSLAM_E_DEVICE, "synchronisation failed");
     pthread_mutex_unlock(&g_vol_mu);
+    return rc;
+}
+
+/* ---- the fused surface as a cloud (include/oslam.h at oslam_volume_surface; kernels: oslam_surface.hip) ---- */
+int oslam_surface_params_default(oslam_surface_params *p)
+{
+    if (!p) return fail(OSLAM_E_INVALID, "params is NULL");
+    memset(p, 0, sizeof *p);
+    p->min_weight = 1;
+    return OSLAM_OK;
+}
+
+int oslam_surface_check_params(const oslam_surface_params *sp, oslam_surface_params *out)
+{
+    if (sp) *out = *sp; else oslam_surface_params_default(out);
+    if (out->min_weight < 1 || out->min_weight > 65535) return fail(OSLAM_E_INVALID, "min_weight must lie in 1..65535");
+    return OSLAM_OK;
+}
+
+/* the two passes, with g_vol_mu held and the volume's device bound.  cap: the most points the caller takes (the second
+ * pass is skipped above it, and with d_out6 == NULL); *d_out6 = device [points][6] from oslam_dev_alloc, NULL without points */
+static int surface_passes(oslam_volume *vol, unsigned min_weight, size_t cap, float **d_out6, uint32_t tot[2], uint32_t *launches)
+{
+    int rc = OSLAM_OK;
+    const uint32_t n_groups = oslamk_surface_groups(&vol->k);
+    uint32_t *d_cnt = NULL;                       /* totals in the first 256 bytes, then one counter per workgroup */
+    void *stream = oslam_stream();
+    tot[0] = tot[1] = 0;
+    *launches = 0;
+    KCHK(oslam_dev_alloc((void **)&d_cnt, 256 + sizeof(uint32_t) * (size_t)n_groups));
+    HIPCHK(hipMemsetAsync(d_cnt, 0, 256, (hipStream_t)stream));
+    KCHK(oslamk_surface_count(&vol->k, min_weight, n_groups, d_cnt + 64, d_cnt, stream));
+    HIPCHK(hipMemcpyAsync(tot, d_cnt, sizeof(uint32_t) * 2, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    *launches = 2;
+    if (d_out6 && tot[1] > 0 && (size_t)tot[1] <= cap) {
+        KCHK(oslam_dev_alloc((void **)d_out6, sizeof(float) * 6 * (size_t)tot[1]));
+        KCHK(oslamk_surface_emit(&vol->k, min_weight, n_groups, d_cnt + 64, tot[1], *d_out6, stream));
+        HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+        *launches = 3;
+    }
+done:
+    if (rc != OSLAM_OK) {
+        (void)hipStreamSynchronize((hipStream_t)stream);
+        if (d_out6 && *d_out6) { oslam_dev_free(*d_out6); *d_out6 = NULL; }
+    }
+    if (d_cnt) oslam_dev_free(d_cnt);
+    return rc;
+}
+
+int oslam_volume_surface(oslam_volume *vol, const oslam_surface_params *sp, float *xyz_out, float *nrm_out, size_t cap,
+                         size_t *n_out, oslam_surface_result *res)
+{
+    int rc;
+    const double t0 = now_ms();
+    oslam_surface_params p;
+    float *d_out = NULL, *h_out = NULL;
+    uint32_t tot[2] = {0, 0}, launches = 0;
+    size_t i;
+    if (!vol || !n_out) return fail(OSLAM_E_INVALID, "NULL argument");
+    if (!xyz_out != !nrm_out) return fail(OSLAM_E_INVALID, "xyz_out and nrm_out must both be given or both be NULL");
+    if (!xyz_out && cap != 0) return fail(OSLAM_E_INVALID, "cap must be 0 without outputs");
+    rc = oslam_surface_check_params(sp, &p);
+    if (rc != OSLAM_OK) return rc;
+    *n_out = 0;
+    if (res) memset(res, 0, sizeof *res);
+    if (hipSetDevice(vol->dev) != hipSuccess) return fail(OSLAM_E_DEVICE, "hipSetDevice failed");
+    pthread_mutex_lock(&g_vol_mu);
+    rc = surface_passes(vol, p.min_weight, cap, xyz_out ? &d_out : NULL, tot, &launches);
+    if (rc != OSLAM_OK) goto done;
+    *n_out = tot[1];
+    if (xyz_out && (size_t)tot[1] > cap) { rc = fail(OSLAM_E_LIMIT, "output capacity too small"); goto done; }
+    if (d_out) {
+        h_out = (float *)malloc(sizeof(float) * 6 * (size_t)tot[1]);
+        if (!h_out) { rc = fail(OSLAM_E_NOMEM, "host allocation failed"); goto done; }
+        HIPCHK(hipMemcpy(h_out, d_out, sizeof(float) * 6 * (size_t)tot[1], hipMemcpyDeviceToHost));
+        for (i = 0; i < tot[1]; i++) {
+            memcpy(xyz_out + 3 * i, h_out + 6 * i, 3 * sizeof(float));
+            memcpy(nrm_out + 3 * i, h_out + 6 * i + 3, 3 * sizeof(float));
+        }
+    }
+done:
+    pthread_mutex_unlock(&g_vol_mu);
+    free(h_out);
+    if (d_out) oslam_dev_free(d_out);
+    if ((rc == OSLAM_OK || rc == OSLAM_E_LIMIT) && res) {
+        res->crossings = tot[0];
+        res->points = tot[1];
+        res->launches = launches;
+        res->ms_total = (float)(now_ms() - t0);
+    }
+    return rc;
+}
+
+int oslam_volume_surface_cloud(oslam_volume *vol, unsigned min_weight, int *dev, float **d_pts6, uint32_t *np)
+{
+    int rc;
+    uint32_t tot[2], launches;
+    *d_pts6 = NULL;
+    *np = 0;
+    *dev = vol->dev;
+    if (hipSetDevice(vol->dev) != hipSuccess) return fail(OSLAM_E_DEVICE, "hipSetDevice failed");
+    pthread_mutex_lock(&g_vol_mu);
+    rc = surface_passes(vol, min_weight, (size_t)-1, d_pts6, tot, &launches);
+    pthread_mutex_unlock(&g_vol_mu);
+    if (rc == OSLAM_OK) *np = tot[1];
+    return rc;
+}
+
+int oslam_volume_set_voxels(oslam_volume *vol, const int16_t *tsdf_q, const uint16_t *weight)
+{
+    int rc = OSLAM_OK;
+    size_t i, n;
+    uint32_t *h = NULL;
+    if (!vol || !tsdf_q || !weight) return fail(OSLAM_E_INVALID, "NULL argument");
+    n = (size_t)vol->p.nx * (size_t)vol->p.ny * (size_t)vol->p.nz;
+    if (hipSetDevice(vol->dev) != hipSuccess) return fail(OSLAM_E_DEVICE, "hipSetDevice failed");
+    h = (uint32_t *)malloc(n * sizeof *h);
+    if (!h) return fail(OSLAM_E_NOMEM, "host allocation failed");
+    for (i = 0; i < n; i++) h[i] = (uint32_t)(uint16_t)tsdf_q[i] | (uint32_t)weight[i] << 16;
+    pthread_mutex_lock(&g_vol_mu);
+    HIPCHK(hipMemcpy(vol->k.words, h, n * sizeof *h, hipMemcpyHostToDevice));
+done:
+    pthread_mutex_unlock(&g_vol_mu);
+    free(h);
     return rc;
 }

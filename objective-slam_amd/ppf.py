@@ -201,6 +201,18 @@ class RaycastResult(C.Structure):
                 "ms_total": float(self.ms_total)}
 
 
+class SurfaceParams(C.Structure):
+    _fields_ = [("min_weight", C.c_uint), ("reserved", C.c_int * 7)]
+
+
+class SurfaceResult(C.Structure):
+    _fields_ = [("crossings", C.c_uint32), ("points", C.c_uint32), ("launches", C.c_uint32), ("ms_total", C.c_float)]
+
+    def asdict(self):
+        return {"crossings": int(self.crossings), "points": int(self.points), "launches": int(self.launches),
+                "ms_total": float(self.ms_total)}
+
+
 ARBITRATE_MAX_HYPOTHESES = 1024
 CELL_DTYPE = np.dtype([("code", "<u8"), ("count", "<u4"), ("pad", "<u4")])
 
@@ -303,6 +315,11 @@ _SIGNATURES = {
     "oslam_view_to_cloud": (_i, [_vp, _vp, _vp, _sz, C.POINTER(_sz)]),
     "oslam_volume_voxels": (_i, [_vp, _vp, _vp]),
     "oslam_view_maps": (_i, [_vp, _vp, _vp]),
+    "oslam_surface_params_default": (_i, [C.POINTER(SurfaceParams)]),
+    "oslam_volume_surface": (_i, [_vp, C.POINTER(SurfaceParams), _vp, _vp, _sz, C.POINTER(_sz), C.POINTER(SurfaceResult)]),
+    "oslam_scene_from_volume": (_i, [_vp, C.POINTER(SurfaceParams), _f, _f, _u, C.POINTER(Params), C.POINTER(_vp),
+                                     C.POINTER(_sz)]),
+    "oslam_volume_set_voxels": (_i, [_vp, _vp, _vp]),
     "oslam_scene_keys": (_i, [_vp, _sz, _vp]),
     "oslam_model_keys": (_i, [_vp, _sz, _vp]),
     "oslam_model_bucket": (_i, [_vp, C.c_uint32, _vp, _sz, C.POINTER(_sz)]),
@@ -725,6 +742,21 @@ class Scene:
         _check(lib().oslam_scene_from_depth(_p(d), int(d.dtype == np.uint16), d.shape[1], d.shape[0], C.byref(cam),
                                             float(leaf), self.d_dist, self.df, C.byref(self.params), C.byref(self._h),
                                             C.byref(n)))
+        self.n = n.value
+        return self
+
+    @classmethod
+    def from_volume(cls, vol, leaf, d_dist=0.0, ref_point_downsample_factor=1, min_weight=1, params=None):
+        """The fused surface of a Volume -> voxel grid (leaf > 0) -> Scene in one call, the extracted cloud staying in
+        HBM (oslam_scene_from_volume).  The scene is in the volume frame and on the volume's device."""
+        self = cls.__new__(cls)
+        self._h = C.c_void_p(0)
+        self.params = params if params is not None else default_params()
+        self.d_dist, self.df = float(d_dist), int(ref_point_downsample_factor)
+        sp = default_surface_params(min_weight=min_weight)
+        n = C.c_size_t(0)
+        _check(lib().oslam_scene_from_volume(vol._h, C.byref(sp), float(leaf), self.d_dist, self.df, C.byref(self.params),
+                                             C.byref(self._h), C.byref(n)))
         self.n = n.value
         return self
 
@@ -1326,6 +1358,17 @@ def default_volume_params(**kw):
     return p
 
 
+def default_surface_params(**kw):
+    """oslam_surface_params_default, then the fields given as keywords."""
+    p = SurfaceParams()
+    _check(lib().oslam_surface_params_default(C.byref(p)))
+    for k, v in kw.items():
+        if not hasattr(p, k) or k == "reserved":
+            raise TypeError("unknown surface parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
 class Volume:
     """A TSDF volume on the device (oslam_volume): integrate(view, T_vol_cam) fuses a depth view, raycast(...) returns
     the fused surface as a View, track(view, T_prev) follows the camera against it.  T_vol_cam: the camera's pose in the
@@ -1384,6 +1427,25 @@ class Volume:
         q, w = np.zeros(shape, np.int16), np.zeros(shape, np.uint16)
         _check(lib().oslam_volume_voxels(self._h, _p(q), _p(w)))
         return q, w
+
+    def set_voxels(self, q, w):
+        """The inverse of voxels(): q int16 and w uint16, [nz,ny,nx] each (oslam_volume_set_voxels)."""
+        shape = (self.params.nz, self.params.ny, self.params.nx)
+        q, w = np.ascontiguousarray(q, np.int16), np.ascontiguousarray(w, np.uint16)
+        if q.shape != shape or w.shape != shape:
+            raise ValueError("q and w must both be [nz,ny,nx] = %r" % (shape,))
+        _check(lib().oslam_volume_set_voxels(self._h, _p(q), _p(w)))
+
+    def surface(self, min_weight=1):
+        """Every zero crossing of the fused TSDF along a voxel edge as a point with its outward normal, in the volume
+        frame and in voxel order (oslam_volume_surface): -> (points [n,3], normals [n,3], result dict)."""
+        sp = default_surface_params(min_weight=min_weight)
+        n, res = C.c_size_t(0), SurfaceResult()
+        _check(lib().oslam_volume_surface(self._h, C.byref(sp), None, None, 0, C.byref(n), C.byref(res)))
+        po, no = np.zeros((n.value, 3), np.float32), np.zeros((n.value, 3), np.float32)
+        if n.value:
+            _check(lib().oslam_volume_surface(self._h, C.byref(sp), _p(po), _p(no), n.value, C.byref(n), C.byref(res)))
+        return po, no, res.asdict()
 
     def reset(self):
         _check(lib().oslam_volume_reset(self._h))

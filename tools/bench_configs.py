@@ -24,6 +24,8 @@ configuration; these are not bench lines).  Needs a HIP device.
   python tools/bench_configs.py fusion   a 256^3 TSDF volume over the room of the camera configuration and its 640x480
                                          stream: integrate, raycast, track per call, Volume.step in frames/s, and the
                                          bytes per second the integration rule loads and stores
+  python tools/bench_configs.py surface  the fusion configuration's 256^3 volume after its stream: Volume.surface and
+                                         Scene.from_volume per call next to one integrate (all three stream the volume)
 One JSON line each."""
 import importlib, json, os, sys, time
 
@@ -742,8 +744,48 @@ def fusion(calls=20):
     return out
 
 
+def surface(calls=20):
+    """Whole-volume surface extraction (oslam_volume_surface / oslam_scene_from_volume) on the fusion configuration's
+    256^3 volume after its out-and-back stream.  The yardstick is one integrate on the same volume: both stream the
+    64 MiB of words, the extraction twice (count and emit)."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import camera_ref as E
+    world = E.make_world(synth, 0)
+    sweep = E.trajectory(synth, 0, frames=10)
+    cam = E.CAM
+    rendered = [ppf.View(E.render(synth, world, T), cam["fx"], cam["fy"], cam["cx"], cam["cy"], z_min=cam["z_min"],
+                         z_max=cam["z_max"], max_jump=E.MAX_JUMP) for T in sweep]
+    spec = dict(nx=256, ny=256, nz=256, voxel=0.036, origin=[-2.9, -4.3, 0.3], mu=0.288)
+    vol = ppf.Volume(**spec)
+    steps = [vol.step(rendered[k]) for k in list(range(10)) + list(range(8, -1, -1))]
+    integ = [vol.integrate(rendered[0], vol.T)["ms_total"] for _ in range(calls + 1)]
+    leaf = 0.1
+    vol.surface()
+    ppf.Scene.from_volume(vol, leaf).close()
+    surf, scene, n_scene = [], [], 0
+    for _ in range(calls):
+        t = time.perf_counter()
+        xyz, nrm, res = vol.surface()
+        surf.append((time.perf_counter() - t) * 1e3)
+        t = time.perf_counter()
+        sc = ppf.Scene.from_volume(vol, leaf)
+        scene.append((time.perf_counter() - t) * 1e3)
+        n_scene = sc.numPoints()
+        sc.close()
+    out = {"config": "surface (oslam_volume_surface): the fusion configuration's 256^3 volume after its 19-frame stream",
+           "volume": spec, "step_ok": [None if r is None else r["ok"] for _, r in steps],
+           "crossings": res["crossings"], "points": res["points"], "launches": res["launches"],
+           "surface_ms_median": float(np.median(surf)), "surface_ms_median_library": res["ms_total"],
+           "scene_from_volume_ms_median": float(np.median(scene)), "scene_leaf": leaf, "scene_points": n_scene,
+           "integrate_ms_median": float(np.median(integ[1:])), "volume_bytes": 4 * 256 ** 3}
+    for v in rendered:
+        v.close()
+    vol.close()
+    return out
+
+
 if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "cfg3"
     print(json.dumps({"cfg2": cfg2, "cfg3": cfg3, "cfg3db": cfg3db, "cfg4": cfg4, "cfg5": cfg5, "planes": planes, "db50": db50,
                       "refine": refine, "verify": verify, "instances": instances, "arbitrate": arbitrate, "track": track, "camera": camera,
-                      "fusion": fusion}[which]()), flush=True)
+                      "fusion": fusion, "surface": surface}[which]()), flush=True)
