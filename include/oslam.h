@@ -803,7 +803,8 @@ int oslam_tracker_step(oslam_tracker *t, oslam_scene *scene, const oslam_view *v
  *   index i is the pixel (u, v) = ((i % lw) * stride, (i / lw) * stride) with lw = ceil(width / stride) and
  *   n = lw * ceil(height / stride) indices.  Levels subsample the source only; the destination is always the
  *   full-resolution map.  A coarse level buys time, not a wider convergence basin: every level looks at the one pixel a
- *   source point projects to, and the gates are the same at every level.  Image pyramids are out of scope.
+ *   source point projects to, and the gates are the same at every level.  Image pyramids are oslam_pyramid_egomotion's
+ *   (below): there a level halves both images.
  * Correspondence of a selected source pixel.  Its record in the source's map (the maps of oslam_track, built on first
  *   use) is (p, n); it takes part only when it has a normal.  p' and n' under the float32 pose T exactly as
  *   oslam_refine, oslam_verify and oslam_track compute them: p'x = ((T0*px + T1*py) + T2*pz) + T3 and so on, n' without
@@ -848,7 +849,7 @@ int oslam_tracker_step(oslam_tracker *t, oslam_scene *scene, const oslam_view *v
  *   before a room 5.4 m away, three seeds).  min_normal_dot is KinFu's cos(20 degrees).  max_corr_dist is 0.30 m and
  *   NOT KinFu's 0.10 m: at that motion a point moves 0.28 m between frames, 0.10 m shuts out the surfaces that tell a
  *   turn from a step sideways and the result slides by 0.22 .. 0.29 m; 0.20, 0.30 and 0.50 m all follow the camera to
- *   0.012 degrees and 0.8 mm per frame.  Without an image pyramid the gate has to admit the motion itself.  stop_rot
+ *   0.012 degrees and 0.8 mm per frame.  On one image pair the gate has to admit the motion itself (the pyramid's calibration: DESIGN.md 7j).  stop_rot
  *   1e-5, stop_trans 1e-5 m.  min_overlap 0.75: consecutive frames reach an overlap of 0.832 .. 0.935, a jump of 7 .. 9
  *   frames (21 .. 27 degrees) 0.000 .. 0.672.  The overlap measures shared surface, not identity: frames of a similar
  *   room (the same floor, a wall 0.4 m further) reach 0.274 .. 0.875 and are not told apart. */
@@ -961,8 +962,7 @@ int oslam_tracker_camera(const oslam_tracker *t, float T_world_cam[16]);
  * Cost: integrate = one memset of the counter, k_tsdf_integrate, one copy back, one host wait; raycast = the same with
  *   k_tsdf_raycast.  Calls on volumes take turns (one lock, held to the end of the host wait).
  * Out of scope: a moving or shifting volume, colour, the along-ray distance, marching cubes and mesh export, masking
- *   tracked objects out of the integration, image pyramids, several GPUs; oslam_tracker keeps taking T_cam from the
- *   caller. */
+ *   tracked objects out of the integration, several GPUs; oslam_tracker keeps taking T_cam from the caller. */
 typedef struct oslam_volume oslam_volume;
 typedef struct oslam_volume_params {
     unsigned nx, ny, nz;      /* voxels per side, each 16..512 and a multiple of 8; default 256^3 */
@@ -1007,6 +1007,72 @@ int oslam_view_to_cloud(oslam_view *v, float *xyz_out, float *nrm_out, size_t ca
  * be NULL) */
 int oslam_volume_voxels(oslam_volume *vol, int16_t *tsdf_q_out, uint16_t *weight_out);
 int oslam_view_maps(oslam_view *v, float *maps_out, float *z_out);
+
+/* ---- depth image pyramids and coarse-to-fine camera tracking over them (KinFu's pyrDown and its three-level ICP).  A
+ * pyramid is up to three views of one image: level 0 is the caller's view, level k + 1 is level k at half the
+ * resolution.  A coarser level is a genuine oslam_view: oslam_verify, oslam_track, oslam_arbitrate, oslam_view_egomotion
+ * and oslam_volume_integrate take it unchanged.  At half resolution the same motion is half as many pixels and the one
+ * pixel a source point projects to stands for four, which is what widens the convergence basin of the projective
+ * correspondence.  The restatement in numpy is tests/pyramid_ref.py; device and restatement agree bit for bit.
+ *
+ * Size and camera.  Level k is w x h with camera (fx, fy, cx, cy, z_min, z_max, max_jump).  Level k + 1 is
+ *   w' = (w + 1) / 2 by h' = (h + 1) / 2; its pixel (u, v) is centred on pixel (2u, 2v) of level k, which always exists.
+ *   Its camera is fx * 0.5f, fy * 0.5f, cx * 0.5f, cy * 0.5f (all exact in float), z_min and z_max unchanged, and
+ *   max_jump * 2.0f: the pixel spacing doubles, so the same slope gives twice the depth step between neighbours.
+ * Depth (KinFu's pyrDown).  c = z[2v][2u]; c == 0 (invalid) gives 0.  Otherwise the 5 x 5 window dy = -2..2 (outer),
+ *   dx = -2..2 (inner), clipped to the image, is walked from sum = 0.0f, cnt = 0: a pixel takes part iff z > 0 and
+ *   fabsf(z - c) <= depth_band, and then does sum += z in float, in that row-major order, and cnt++ (the centre always
+ *   takes part).  The output is fminf(fmaxf(sum / (float)cnt, z_min), z_max).  No fused multiply-add anywhere; the
+ *   division is the correctly rounded one.  depth_band is in metres; the default 0.09 is KinFu's 3 x 30 mm.
+ * Maps.  A coarser level starts without maps; it gets its vertex and normal map on first use as every depth view does,
+ *   from its own z image, its camera and its max_jump.  That holds for the pyramid of a ray-cast view too: level 0
+ *   keeps the normals of the TSDF gradient, the coarser levels take theirs from z differences of the down-sampled t*.
+ * oslam_pyramid_create borrows base as level 0 (the caller keeps it alive and destroys it after the pyramid) and owns
+ *   the rest: n_levels - 1 launches of k_pyr_down back to back, one host wait.  oslam_pyramid_level returns a borrowed
+ *   view, level 0 is base itself.  oslam_pyramid_destroy does not destroy base.
+ * oslam_pyramid_egomotion is oslam_view_egomotion with a pair of views per schedule level.  ep->level[i].stride must be
+ *   1, 2 or 4 and names pyramid level log2(stride) of both pyramids (a level either lacks is OSLAM_E_INVALID); that level
+ *   of the schedule runs oslam_view_egomotion's step with the level-k views as source and destination over the stride-1
+ *   lattice of the level-k source, so the default schedule {4, 4}, {2, 5}, {1, 10} is KinFu's: levels 2, 1, 0.
+ *   Everything else is oslam_view_egomotion's, under the same lock: the gates in metres (the same at every level), the
+ *   sums, the solve, the convergence test that ends a level, the float32 hand-over of the pose between levels, the
+ *   result fields (overlap from the level with the smallest stride that evaluated a step), one memset, one host wait,
+ *   one pinned copy; launches == the scheduled iterations plus 1 for every level view whose maps did not exist yet (a
+ *   level with max_iterations 0 builds none).  src == dst returns the identity at once.  The call equals the chain of
+ *   oslam_view_egomotion(level k of src, level k of dst, T, {n_levels 1, {1, its iterations}}) calls in schedule order,
+ *   each from the previous T_out, bit for bit in T_out and iterations; correspondences, rmse and overlap are those of
+ *   the chain's last call that evaluated a step.
+ * oslam_volume_track_pyramid is host glue as oslam_volume_track is: ray-cast at T_vol_cam_prev with the camera and size
+ *   of the frame's level 0, a pyramid of the ray-cast view with pp (NULL: the defaults),
+ *   oslam_pyramid_egomotion(src = frame, dst = that pyramid, identity, ep), the pose product of oslam_volume_track; the
+ *   ray-cast view and its pyramid are freed.  launches counts the ray cast and the down-sampling launches too.  It does
+ *   not integrate.
+ * Arguments are checked before any handle is read or any device call is made: NULL pointers, n_levels outside 1..3, a
+ *   depth_band that is not finite or <= 0, a k beyond the pyramid, the parameter checks of oslam_view_egomotion, a stride
+ *   other than 1, 2, 4 and a T that is not rigid are OSLAM_E_INVALID; so are pyramids (or a volume and a pyramid) on
+ *   different devices.
+ * Out of scope: a bilateral filter of the raw depth, resizing the ray cast's TSDF normals instead of recomputing them
+ *   from z, per-level gates, feeding oslam_tracker or a volume's own stepping from the pyramid (callers opt in through
+ *   these calls), several GPUs. */
+typedef struct oslam_pyramid oslam_pyramid;
+typedef struct oslam_pyramid_params {
+    unsigned n_levels;         /* 1..3 including the base, default 3 */
+    float depth_band;          /* metres, > 0, default 0.09 */
+    int reserved[4];
+} oslam_pyramid_params;
+
+int oslam_pyramid_params_default(oslam_pyramid_params *p);
+/* pp may be NULL (defaults) */
+int oslam_pyramid_create(oslam_view *base, const oslam_pyramid_params *pp, oslam_pyramid **out);
+int oslam_pyramid_destroy(oslam_pyramid *pyr);
+int oslam_pyramid_level(oslam_pyramid *pyr, unsigned k, oslam_view **view_out);
+/* T_init may be NULL (identity), ep may be NULL (defaults), res may be NULL */
+int oslam_pyramid_egomotion(oslam_pyramid *src, oslam_pyramid *dst, const float T_init[16],
+                            const oslam_egomotion_params *ep, float T_out[16], oslam_egomotion_result *res);
+/* pp and ep may be NULL (defaults), ego_res may be NULL */
+int oslam_volume_track_pyramid(oslam_volume *vol, oslam_pyramid *frame, const float T_vol_cam_prev[16],
+                               const oslam_pyramid_params *pp, const oslam_egomotion_params *ep,
+                               float T_vol_cam_out[16], oslam_egomotion_result *ego_res);
 
 /* ---- the fused surface of a whole volume as a cloud and as a scene (KinFu's fetchCloud plus fetchNormals): every zero
  * crossing of the TSDF along a voxel edge becomes a point with a normal, in the volume frame.  The restatement in numpy

@@ -1,8 +1,10 @@
 /*
  * oslam_ego.c -- camera motion between two depth views by dense projective ICP (include/oslam.h at
  * oslam_view_egomotion): the host side of the kernels in oslam_ego.hip.  A call checks its arguments, builds the maps of
- * both views when they do not exist yet, uploads the state, zeroes the arrival counters, enqueues one k_ego_step per
- * scheduled iteration back to back and reads the state back into pinned memory with one host wait.
+ * its views when they do not exist yet, uploads the state, zeroes the arrival counters, enqueues one k_ego_step per
+ * scheduled iteration back to back and reads the state back into pinned memory with one host wait.  Every level of the
+ * schedule has its own source and destination view: oslam_view_egomotion runs all of them on one pair,
+ * oslam_pyramid_egomotion on the matching levels of two pyramids (oslam_pyramid.c).
  */
 #include <math.h>
 #include <pthread.h>
@@ -67,10 +69,10 @@ static const float k_identity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0
 
 static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
-/* the lattice of level l of p over the source image (include/oslam.h, "Levels" and "Step") */
-static void set_level(oslamk_ego_level *lv, const oslam_egomotion_params *p, unsigned l, const oslamk_view *src)
+/* the lattice of level l of p over its source image, every stride-th pixel (include/oslam.h, "Levels" and "Step") */
+static void set_level(oslamk_ego_level *lv, const oslam_egomotion_params *p, unsigned l, const oslamk_view *src, unsigned stride)
 {
-    const int s = (int)p->level[l].stride;
+    const int s = (int)stride;
     unsigned q;
     lv->stride = s;
     lv->lw = (src->w + s - 1) / s;
@@ -84,8 +86,8 @@ static void set_level(oslamk_ego_level *lv, const oslam_egomotion_params *p, uns
     lv->next_level = (int32_t)q;
 }
 
-static int egomotion(oslam_view *src, oslam_view *dst, const float T0[16], const oslam_egomotion_params *p, float T_out[16],
-                     oslam_egomotion_result *res)
+int oslam_ego_run(const oslam_ego_pair *pair, const float T0[16], const oslam_egomotion_params *p, float T_out[16],
+                  oslam_egomotion_result *res)
 {
     int rc = OSLAM_OK, locked = 0, built = 0, a, finest = -1;
     const double t0 = now_ms();
@@ -100,7 +102,7 @@ static int egomotion(oslam_view *src, oslam_view *dst, const float T0[16], const
     memcpy(T_out, T0, 16 * sizeof(float));
     if (res) memset(res, 0, sizeof *res);
     for (l = 0; l < p->n_levels; l++) {
-        set_level(&lv[l], p, l, &src->k);
+        set_level(&lv[l], p, l, &pair[l].src->k, pair[l].lattice);
         scheduled += lv[l].max_iter;
     }
     if (scheduled == 0) goto done;              /* nothing to run: the pose as given, overlap 0 */
@@ -118,7 +120,7 @@ static int egomotion(oslam_view *src, oslam_view *dst, const float T0[16], const
     st.level = (int32_t)first;
     st.n_levels = (int32_t)p->n_levels;
 
-    if (hipSetDevice(src->dev) != hipSuccess) { rc = fail(OSLAM_E_DEVICE, "hipSetDevice failed"); goto done; }
+    if (hipSetDevice(pair[first].src->dev) != hipSuccess) { rc = fail(OSLAM_E_DEVICE, "hipSetDevice failed"); goto done; }
     pthread_mutex_lock(&g_ego_mu);
     locked = 1;
     if (!g_state) HIPCHK(hipHostMalloc((void **)&g_state, sizeof *g_state, hipHostMallocPortable));
@@ -127,14 +129,18 @@ static int egomotion(oslam_view *src, oslam_view *dst, const float T0[16], const
     KCHK(oslam_dev_alloc((void **)&dev, off_slots + sizeof(double) * OSLAMK_EGO_SLOT * OSLAMK_EGO_MAX_SLOTS));
     HIPCHK(hipMemcpyAsync(dev, &st, sizeof st, hipMemcpyHostToDevice, (hipStream_t)stream));
     HIPCHK(hipMemsetAsync(dev + off_cnt, 0, sizeof(uint32_t) * scheduled, (hipStream_t)stream));
-    rc = oslam_track_view_maps(src, &built);
-    if (rc != OSLAM_OK) goto done;
-    launches += (uint32_t)built;
-    rc = oslam_track_view_maps(dst, &built);
-    if (rc != OSLAM_OK) goto done;
-    launches += (uint32_t)built;
+    for (l = first; l < p->n_levels; l++) {     /* the maps of every view a level runs on; a view that has them builds nothing */
+        if (lv[l].max_iter == 0) continue;
+        rc = oslam_track_view_maps(pair[l].src, &built);
+        if (rc != OSLAM_OK) goto done;
+        launches += (uint32_t)built;
+        rc = oslam_track_view_maps(pair[l].dst, &built);
+        if (rc != OSLAM_OK) goto done;
+        launches += (uint32_t)built;
+    }
     for (l = 0; l < p->n_levels; l++)
         for (it = 0; it < lv[l].max_iter; it++, k++) {
+            oslam_view *src = pair[l].src, *dst = pair[l].dst;
             KCHK(oslamk_ego_step(&src->k, src->d_maps, &dst->k, dst->d_maps, &lv[l], (oslamk_ego_state *)dev,
                                  (double *)(dev + off_slots), (uint32_t *)(dev + off_cnt) + k, stream));
             launches++;
@@ -169,7 +175,7 @@ done:
 }
 
 /* everything that can be said without reading a handle */
-static int check_call(const oslam_view *src, const oslam_view *dst, const float *T, const oslam_egomotion_params *ep,
+static int check_call(const void *src, const void *dst, const float *T, const oslam_egomotion_params *ep,
                       oslam_egomotion_params *p)
 {
     int rc;
@@ -179,26 +185,69 @@ static int check_call(const oslam_view *src, const oslam_view *dst, const float 
     return rc;
 }
 
+/* src == dst: the identity at once, without a device */
+static void same_handle(const oslam_egomotion_params *p, float T_out[16], oslam_egomotion_result *res)
+{
+    memcpy(T_out, k_identity, sizeof k_identity);
+    if (res) {
+        memset(res, 0, sizeof *res);
+        res->converged = 1;
+        res->overlap = 1.0f;
+        res->ok = 1.0f >= p->min_overlap;
+    }
+}
+
 int oslam_view_egomotion(oslam_view *src, oslam_view *dst, const float T_init[16], const oslam_egomotion_params *ep,
                          float T_out[16], oslam_egomotion_result *res)
 {
     oslam_egomotion_params p;
+    oslam_ego_pair pair[OSLAM_EGOMOTION_MAX_LEVELS];
+    unsigned l;
     int rc;
     if (!T_out) return fail(OSLAM_E_INVALID, "NULL argument");
     rc = check_call(src, dst, T_init, ep, &p);
     if (rc != OSLAM_OK) return rc;
     if (src == dst) {
-        memcpy(T_out, k_identity, sizeof k_identity);
-        if (res) {
-            memset(res, 0, sizeof *res);
-            res->converged = 1;
-            res->overlap = 1.0f;
-            res->ok = 1.0f >= p.min_overlap;
-        }
+        same_handle(&p, T_out, res);
         return OSLAM_OK;
     }
     if (src->dev != dst->dev) return fail(OSLAM_E_INVALID, "the two views live on different devices");
-    return egomotion(src, dst, T_init ? T_init : k_identity, &p, T_out, res);
+    for (l = 0; l < p.n_levels; l++) {          /* every level on the one pair, its stride over the source */
+        pair[l].src = src;
+        pair[l].dst = dst;
+        pair[l].lattice = p.level[l].stride;
+    }
+    return oslam_ego_run(pair, T_init ? T_init : k_identity, &p, T_out, res);
+}
+
+int oslam_pyramid_egomotion(oslam_pyramid *src, oslam_pyramid *dst, const float T_init[16], const oslam_egomotion_params *ep,
+                            float T_out[16], oslam_egomotion_result *res)
+{
+    oslam_egomotion_params p;
+    oslam_ego_pair pair[OSLAM_EGOMOTION_MAX_LEVELS];
+    unsigned l, k[OSLAM_EGOMOTION_MAX_LEVELS];
+    int rc;
+    if (!T_out) return fail(OSLAM_E_INVALID, "NULL argument");
+    rc = check_call(src, dst, T_init, ep, &p);
+    if (rc != OSLAM_OK) return rc;
+    for (l = 0; l < p.n_levels; l++) {
+        const unsigned s = p.level[l].stride;
+        if (s != 1 && s != 2 && s != 4) return fail(OSLAM_E_INVALID, "a stride of a pyramid schedule must be 1, 2 or 4");
+        k[l] = s >> 1;                          /* log2 of 1, 2, 4 */
+    }
+    if (src == dst) {
+        same_handle(&p, T_out, res);
+        return OSLAM_OK;
+    }
+    if (src->dev != dst->dev) return fail(OSLAM_E_INVALID, "the two pyramids live on different devices");
+    for (l = 0; l < p.n_levels; l++) {          /* level log2(stride) of both pyramids, every pixel of its source */
+        if (k[l] >= src->n_levels || k[l] >= dst->n_levels)
+            return fail(OSLAM_E_INVALID, "a stride names a level the pyramid does not have");
+        pair[l].src = src->level[k[l]];
+        pair[l].dst = dst->level[k[l]];
+        pair[l].lattice = 1;
+    }
+    return oslam_ego_run(pair, T_init ? T_init : k_identity, &p, T_out, res);
 }
 
 int oslam_view_egomotion_correspondences(oslam_view *src, oslam_view *dst, const float T[16],

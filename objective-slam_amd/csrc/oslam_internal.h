@@ -86,6 +86,12 @@ struct oslam_view {
     float *d_maps;                    /* vertex and normal map of the tracking stage (oslam_track.c), NULL until the first */
 };
 
+struct oslam_pyramid {
+    int dev;                          /* stays the first field, as in oslam_view */
+    unsigned n_levels;
+    oslam_view *level[3];             /* [0] is the caller's base (borrowed), the rest are owned */
+};
+
 typedef struct db_group {
     int n;
     size_t *members;                  /* indices into db->models */
@@ -227,6 +233,18 @@ int oslam_track_view_maps(oslam_view *v, int *built);
 void oslam_ego_release(void);
 /* ep NULL = defaults; checks them as oslam_view_egomotion does, *out = the parameters in force (oslam_ego.c) */
 int oslam_ego_check_params(const oslam_egomotion_params *ep, oslam_egomotion_params *out);
+/* one level of an egomotion schedule: its views and the stride of its lattice over the source */
+typedef struct oslam_ego_pair {
+    oslam_view *src, *dst;
+    unsigned lattice;
+} oslam_ego_pair;
+/* the schedule of p (checked) from T0 with pair[l] as level l's views, all on one device: oslam_view_egomotion's call
+ * from the upload to the result (oslam_ego.c) */
+int oslam_ego_run(const oslam_ego_pair *pair, const float T0[16], const oslam_egomotion_params *p, float T_out[16],
+                  oslam_egomotion_result *res);
+/* ---- image pyramid (oslam_pyramid.c) ---- */
+/* pp NULL = defaults; checks them as oslam_pyramid_create does, *out = the parameters in force */
+int oslam_pyramid_check_params(const oslam_pyramid_params *pp, oslam_pyramid_params *out);
 /* ---- surface extraction (oslam_volume.c) ---- */
 /* sp NULL = defaults; checks them as oslam_volume_surface does, *out = the parameters in force */
 int oslam_surface_check_params(const oslam_surface_params *sp, oslam_surface_params *out);

@@ -509,6 +509,10 @@ int oslamk_ego_step(const oslamk_view *src, const float *src_maps, const oslamk_
 int oslamk_ego_corr(const oslamk_view *src, const float *src_maps, const oslamk_view *dst, const float *dst_maps,
                     const float *T12, float r2_corr, float min_dot, int32_t *pixel_out, void *stream);
 
+/* ---- image pyramid (oslam_pyramid.hip; semantics in include/oslam.h at oslam_pyramid_create) ---- */
+/* the z image of the next coarser level of *src: z_out [(h + 1) / 2][(w + 1) / 2], clamped to src's [z_min, z_max] */
+int oslamk_pyr_down(const oslamk_view *src, float depth_band, float *z_out, void *stream);
+
 /* ---- fusion stage (oslam_volume.hip; semantics in include/oslam.h at oslam_volume_integrate / oslam_volume_raycast) ---- */
 #define OSLAMK_VOL_ZRUN 8             /* consecutive z a thread of k_tsdf_integrate walks; nz is a multiple of it */
 #define OSLAMK_VOL_MAX_STEPS 1024     /* samples of one ray at most: step >= one voxel and the box's diagonal is below

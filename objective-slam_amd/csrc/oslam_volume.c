@@ -2,7 +2,8 @@
  * oslam_volume.c -- fusion of depth views into a TSDF volume and the ray cast back into a view (include/oslam.h at
  * oslam_volume_integrate): the host side of the kernels in oslam_volume.hip.  A call checks its arguments, zeroes a
  * counter block, runs one kernel and reads the counters back with one host wait.  oslam_volume_track is glue over the
- * ray cast and oslam_view_egomotion; oslam_view_to_cloud runs the depth front end's compaction over a view's maps.
+ * ray cast and oslam_view_egomotion, oslam_volume_track_pyramid over the ray cast, a pyramid of it and
+ * oslam_pyramid_egomotion; oslam_view_to_cloud runs the depth front end's compaction over a view's maps.
  * oslam_volume_surface (kernels: oslam_surface.hip) counts, waits for the number of points, allocates exactly that and
  * emits.
  */
@@ -231,10 +232,25 @@ int oslam_volume_raycast(oslam_volume *vol, const float T_vol_cam[16], const osl
     return rc;
 }
 
+/* T_out = float32(double(T_prev) * double(T)), the element order of oslam_tracker_step_cam */
+static void pose_product(const float T_prev[16], const float T[16], float T_out[16])
+{
+    int a, b;
+    for (a = 0; a < 3; a++)
+        for (b = 0; b < 4; b++) {
+            double x = ((double)T_prev[4 * a] * (double)T[b] + (double)T_prev[4 * a + 1] * (double)T[4 + b]) +
+                       (double)T_prev[4 * a + 2] * (double)T[8 + b];
+            if (b == 3) x += (double)T_prev[4 * a + 3];
+            T_out[4 * a + b] = (float)x;
+        }
+    T_out[12] = T_out[13] = T_out[14] = 0.0f;
+    T_out[15] = 1.0f;
+}
+
 int oslam_volume_track(oslam_volume *vol, oslam_view *v, const float T_prev[16], const oslam_egomotion_params *ep,
                        float T_out[16], oslam_egomotion_result *ego_res)
 {
-    int rc, a, b;
+    int rc;
     const double t0 = now_ms();
     oslam_egomotion_params p;
     oslam_egomotion_result er;
@@ -263,18 +279,65 @@ int oslam_volume_track(oslam_volume *vol, oslam_view *v, const float T_prev[16],
     pthread_mutex_unlock(&g_vol_mu);
     if (model) oslam_view_destroy(model);
     if (rc != OSLAM_OK) return rc;
-    for (a = 0; a < 3; a++)
-        for (b = 0; b < 4; b++) {
-            double x = ((double)T_prev[4 * a] * (double)T[b] + (double)T_prev[4 * a + 1] * (double)T[4 + b]) +
-                       (double)T_prev[4 * a + 2] * (double)T[8 + b];
-            if (b == 3) x += (double)T_prev[4 * a + 3];
-            T_out[4 * a + b] = (float)x;
-        }
-    T_out[12] = T_out[13] = T_out[14] = 0.0f;
-    T_out[15] = 1.0f;
+    pose_product(T_prev, T, T_out);
     if (ego_res) {
         *ego_res = er;
         ego_res->launches += 1;
+        ego_res->ms_total = (float)(now_ms() - t0);
+    }
+    return OSLAM_OK;
+}
+
+int oslam_volume_track_pyramid(oslam_volume *vol, oslam_pyramid *frame, const float T_prev[16], const oslam_pyramid_params *pp,
+                               const oslam_egomotion_params *ep, float T_out[16], oslam_egomotion_result *ego_res)
+{
+    int rc;
+    unsigned l;
+    const double t0 = now_ms();
+    oslam_egomotion_params p;
+    oslam_pyramid_params q;
+    oslam_egomotion_result er;
+    oslam_camera cam;
+    const oslam_view *v;
+    oslam_view *model = NULL;
+    oslam_pyramid *model_pyr = NULL;
+    uint32_t cnt[2];
+    float T[16];
+    if (!vol || !frame || !T_prev || !T_out) return fail(OSLAM_E_INVALID, "NULL argument");
+    rc = oslam_ego_check_params(ep, &p);
+    if (rc == OSLAM_OK) rc = oslam_pyramid_check_params(pp, &q);
+    if (rc == OSLAM_OK) rc = oslam_refine_check_rigid(T_prev);
+    if (rc != OSLAM_OK) return rc;
+    for (l = 0; l < p.n_levels; l++) {
+        const unsigned s = p.level[l].stride;
+        if (s != 1 && s != 2 && s != 4) return fail(OSLAM_E_INVALID, "a stride of a pyramid schedule must be 1, 2 or 4");
+        if ((s >> 1) >= q.n_levels || (s >> 1) >= frame->n_levels)
+            return fail(OSLAM_E_INVALID, "a stride names a level the pyramid does not have");
+    }
+    if (vol->dev != frame->dev) return fail(OSLAM_E_INVALID, "volume and pyramid live on different devices");
+    v = frame->level[0];
+    memset(&cam, 0, sizeof cam);
+    cam.fx = v->k.fx;
+    cam.fy = v->k.fy;
+    cam.cx = v->k.cx;
+    cam.cy = v->k.cy;
+    cam.depth_scale = 1.0f;
+    cam.z_min = v->k.z_min;
+    cam.z_max = v->k.z_max;
+    cam.max_jump = v->max_jump;
+    if (hipSetDevice(vol->dev) != hipSuccess) return fail(OSLAM_E_DEVICE, "hipSetDevice failed");
+    pthread_mutex_lock(&g_vol_mu);
+    rc = raycast(vol, T_prev, &cam, v->k.w, v->k.h, &model, cnt);
+    if (rc == OSLAM_OK) rc = oslam_pyramid_create(model, &q, &model_pyr);
+    if (rc == OSLAM_OK) rc = oslam_pyramid_egomotion(frame, model_pyr, NULL, &p, T, &er);
+    pthread_mutex_unlock(&g_vol_mu);
+    if (model_pyr) oslam_pyramid_destroy(model_pyr);
+    if (model) oslam_view_destroy(model);
+    if (rc != OSLAM_OK) return rc;
+    pose_product(T_prev, T, T_out);
+    if (ego_res) {
+        *ego_res = er;
+        ego_res->launches += 1 + (q.n_levels - 1);      /* the ray cast and the down-sampling launches */
         ego_res->ms_total = (float)(now_ms() - t0);
     }
     return OSLAM_OK;

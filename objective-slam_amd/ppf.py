@@ -181,6 +181,10 @@ class EgomotionResult(C.Structure):
                 "launches": int(self.launches), "ms_total": float(self.ms_total)}
 
 
+class PyramidParams(C.Structure):
+    _fields_ = [("n_levels", C.c_uint), ("depth_band", C.c_float), ("reserved", C.c_int * 4)]
+
+
 class VolumeParams(C.Structure):
     _fields_ = [("nx", C.c_uint), ("ny", C.c_uint), ("nz", C.c_uint), ("voxel", C.c_float), ("origin", C.c_float * 3),
                 ("mu", C.c_float), ("max_weight", C.c_uint), ("reserved", C.c_int * 4)]
@@ -315,6 +319,13 @@ _SIGNATURES = {
     "oslam_view_to_cloud": (_i, [_vp, _vp, _vp, _sz, C.POINTER(_sz)]),
     "oslam_volume_voxels": (_i, [_vp, _vp, _vp]),
     "oslam_view_maps": (_i, [_vp, _vp, _vp]),
+    "oslam_pyramid_params_default": (_i, [C.POINTER(PyramidParams)]),
+    "oslam_pyramid_create": (_i, [_vp, C.POINTER(PyramidParams), C.POINTER(_vp)]),
+    "oslam_pyramid_destroy": (_i, [_vp]),
+    "oslam_pyramid_level": (_i, [_vp, _u, C.POINTER(_vp)]),
+    "oslam_pyramid_egomotion": (_i, [_vp, _vp, _vp, C.POINTER(EgomotionParams), _vp, C.POINTER(EgomotionResult)]),
+    "oslam_volume_track_pyramid": (_i, [_vp, _vp, _vp, C.POINTER(PyramidParams), C.POINTER(EgomotionParams), _vp,
+                                        C.POINTER(EgomotionResult)]),
     "oslam_surface_params_default": (_i, [C.POINTER(SurfaceParams)]),
     "oslam_volume_surface": (_i, [_vp, C.POINTER(SurfaceParams), _vp, _vp, _sz, C.POINTER(_sz), C.POINTER(SurfaceResult)]),
     "oslam_scene_from_volume": (_i, [_vp, C.POINTER(SurfaceParams), _f, _f, _u, C.POINTER(Params), C.POINTER(_vp),
@@ -1344,6 +1355,72 @@ def view_maps(view):
     return maps.reshape(view.height, view.width, 8), z.reshape(view.height, view.width)
 
 
+def default_pyramid_params(**kw):
+    """oslam_pyramid_params_default, then the fields given as keywords."""
+    p = PyramidParams()
+    _check(lib().oslam_pyramid_params_default(C.byref(p)))
+    for k, v in kw.items():
+        if not hasattr(p, k) or k == "reserved":
+            raise TypeError("unknown pyramid parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+class Pyramid:
+    """Up to three views of one depth image, each at half the resolution of the one before (oslam_pyramid): level 0 is
+    `view` itself, which the pyramid keeps alive.  level(k) is a View that does not own its handle."""
+
+    def __init__(self, view, levels=3, depth_band=0.09):
+        self._h = C.c_void_p(0)
+        self.base = view
+        self.params = default_pyramid_params(n_levels=levels, depth_band=depth_band)
+        _check(lib().oslam_pyramid_create(view._h, C.byref(self.params), C.byref(self._h)))
+        self.levels = int(levels)
+
+    def level(self, k):
+        h = C.c_void_p(0)
+        _check(lib().oslam_pyramid_level(self._h, int(k), C.byref(h)))
+        v = _BorrowedView.__new__(_BorrowedView)
+        v._h, v._owner = h, self                # the pyramid, and through it the base, live as long as the level does
+        v.width, v.height = self.base.width, self.base.height
+        for _ in range(int(k)):
+            v.width, v.height = (v.width + 1) // 2, (v.height + 1) // 2
+        return v
+
+    def close(self):
+        if self._h:
+            lib().oslam_pyramid_destroy(self._h)
+            self._h = C.c_void_p(0)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _BorrowedView(View):
+    """A View whose handle belongs to something else: closing it gives nothing back."""
+
+    def close(self):
+        self._h = C.c_void_p(0)
+
+
+def egomotion_pyramid(src_pyr, dst_pyr, T_init=None, params=None, **fields):
+    """Coarse-to-fine camera motion over two pyramids (oslam_pyramid_egomotion): stride 1, 2, 4 of a schedule level names
+    pyramid level 0, 1, 2.  params: an EgomotionParams, or none and the fields of default_egomotion_params as keywords.
+    -> what egomotion returns."""
+    if params is not None and fields:
+        raise TypeError("give params or keyword fields, not both")
+    p = params if params is not None else default_egomotion_params(**fields)
+    To = np.zeros(16, np.float32)
+    res = EgomotionResult()
+    Ti = _pose16(T_init) if T_init is not None else None
+    _check(lib().oslam_pyramid_egomotion(src_pyr._h, dst_pyr._h, _p(Ti) if Ti is not None else None, C.byref(p), _p(To),
+                                         C.byref(res)))
+    return To.reshape(4, 4), res.asdict()
+
+
 def default_volume_params(**kw):
     """oslam_volume_params_default, then the fields given as keywords (origin: three floats)."""
     p = VolumeParams()
@@ -1404,6 +1481,17 @@ class Volume:
         To = np.zeros(16, np.float32)
         res = EgomotionResult()
         _check(lib().oslam_volume_track(self._h, view._h, _p(_pose16(T_prev)), C.byref(p), _p(To), C.byref(res)))
+        return To.reshape(4, 4), res.asdict()
+
+    def track_pyramid(self, pyr, T_prev, params=None, levels=3, depth_band=0.09):
+        """Frame-to-model camera tracking over pyramids (oslam_volume_track_pyramid): the volume is ray-cast at T_prev
+        and down-sampled with (levels, depth_band).  -> (T_vol_cam float32 4x4, egomotion result dict)."""
+        p = params if params is not None else default_egomotion_params()
+        pp = default_pyramid_params(n_levels=levels, depth_band=depth_band)
+        To = np.zeros(16, np.float32)
+        res = EgomotionResult()
+        _check(lib().oslam_volume_track_pyramid(self._h, pyr._h, _p(_pose16(T_prev)), C.byref(pp), C.byref(p), _p(To),
+                                                C.byref(res)))
         return To.reshape(4, 4), res.asdict()
 
     def step(self, view, params=None):

@@ -26,6 +26,8 @@ configuration; these are not bench lines).  Needs a HIP device.
                                          bytes per second the integration rule loads and stores
   python tools/bench_configs.py surface  the fusion configuration's 256^3 volume after its stream: Volume.surface and
                                          Scene.from_volume per call next to one integrate (all three stream the volume)
+  python tools/bench_configs.py pyramid  the camera configuration's 640x480 stream: Pyramid(view), egomotion_pyramid and,
+                                         in the same run, egomotion on the same pair; median of 20 calls each
 One JSON line each."""
 import importlib, json, os, sys, time
 
@@ -784,8 +786,47 @@ def surface(calls=20):
     return out
 
 
+def pyramid(calls=20):
+    """Image pyramids (oslam_pyramid_create, oslam_pyramid_egomotion) on frames 0 and 1 of the camera configuration's
+    640x480 stream: the median of `calls` calls of Pyramid(view), of egomotion_pyramid and, in the same run, of egomotion
+    on the same pair (the yardstick).  Host clock around calls that end in a host wait; every shape is warmed up first."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import camera_ref as E
+    import refine_ref
+    world = E.make_world(synth, 0)
+    traj = E.trajectory(synth, 0, frames=2)
+    cam = E.CAM
+    views = [ppf.View(E.render(synth, world, T), cam["fx"], cam["fy"], cam["cx"], cam["cy"], z_min=cam["z_min"],
+                      z_max=cam["z_max"], max_jump=E.MAX_JUMP) for T in traj]
+    pyrs = [ppf.Pyramid(v) for v in views]
+    ppf.egomotion_pyramid(pyrs[0], pyrs[1])
+    ppf.egomotion(views[0], views[1])
+    ppf.Pyramid(views[0]).close()
+    make, ego_p, ego_p_lib, ego_v, ego_v_lib = [], [], [], [], []
+    for _ in range(calls):                                          # the three alternate, so that drift hits them alike
+        t = time.perf_counter(); q = ppf.Pyramid(views[0]); make.append(1e3 * (time.perf_counter() - t)); q.close()
+        t = time.perf_counter(); Tp, rp = ppf.egomotion_pyramid(pyrs[0], pyrs[1]); ego_p.append(1e3 * (time.perf_counter() - t))
+        t = time.perf_counter(); Tv, rv = ppf.egomotion(views[0], views[1]); ego_v.append(1e3 * (time.perf_counter() - t))
+        ego_p_lib.append(rp["ms_total"])
+        ego_v_lib.append(rv["ms_total"])
+    G = E.truth(traj[0], traj[1])
+    out = {"config": "pyramid (oslam_pyramid_create, oslam_pyramid_egomotion): 640x480, 3 levels, the camera stream's first pair",
+           "calls": calls, "pyramid_create_ms_median": float(np.median(make)),
+           "egomotion_pyramid_ms_median": float(np.median(ego_p)), "egomotion_pyramid_ms_library_median": float(np.median(ego_p_lib)),
+           "egomotion_ms_median": float(np.median(ego_v)), "egomotion_ms_library_median": float(np.median(ego_v_lib)),
+           "egomotion_pyramid": {"launches": rp["launches"], "iterations": rp["iterations"], "overlap": round(rp["overlap"], 3),
+                                 "rot_deg_trans_m": [round(x, 5) for x in refine_ref.pose_error(Tp, G)]},
+           "egomotion": {"launches": rv["launches"], "iterations": rv["iterations"], "overlap": round(rv["overlap"], 3),
+                         "rot_deg_trans_m": [round(x, 5) for x in refine_ref.pose_error(Tv, G)]}}
+    for q in pyrs:
+        q.close()
+    for v in views:
+        v.close()
+    return out
+
+
 if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "cfg3"
     print(json.dumps({"cfg2": cfg2, "cfg3": cfg3, "cfg3db": cfg3db, "cfg4": cfg4, "cfg5": cfg5, "planes": planes, "db50": db50,
                       "refine": refine, "verify": verify, "instances": instances, "arbitrate": arbitrate, "track": track, "camera": camera,
-                      "fusion": fusion, "surface": surface}[which]()), flush=True)
+                      "fusion": fusion, "surface": surface, "pyramid": pyramid}[which]()), flush=True)
