@@ -74,8 +74,6 @@ static int check_list(oslam_model *const *ms, const float *T, size_t H, const os
     return OSLAM_OK;
 }
 
-static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 /* the tile of a call (include/oslam.h, "Tile") */
 static int choose_tile(oslam_model *const *ms, const float *T, size_t H, const oslam_view *v, const oslam_arbitrate_params *p)
 {

@@ -67,8 +67,6 @@ int oslam_ego_check_params(const oslam_egomotion_params *ep, oslam_egomotion_par
 
 static const float k_identity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
 
-static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 /* the lattice of level l of p over its source image, every stride-th pixel (include/oslam.h, "Levels" and "Step") */
 static void set_level(oslamk_ego_level *lv, const oslam_egomotion_params *p, unsigned l, const oslamk_view *src, unsigned stride)
 {
@@ -197,6 +195,18 @@ static void same_handle(const oslam_egomotion_params *p, float T_out[16], oslam_
     }
 }
 
+int oslam_ego_check_pyramid_schedule(const oslam_egomotion_params *p, unsigned n_levels)
+{
+    unsigned l;
+    for (l = 0; l < p->n_levels; l++) {
+        const unsigned s = p->level[l].stride;
+        if (s != 1 && s != 2 && s != 4) return fail(OSLAM_E_INVALID, "a stride of a pyramid schedule must be 1, 2 or 4");
+        if ((s >> 1) >= n_levels)               /* s >> 1: log2 of 1, 2, 4 */
+            return fail(OSLAM_E_INVALID, "a stride names a level the pyramid does not have");
+    }
+    return OSLAM_OK;
+}
+
 int oslam_view_egomotion(oslam_view *src, oslam_view *dst, const float T_init[16], const oslam_egomotion_params *ep,
                          float T_out[16], oslam_egomotion_result *res)
 {
@@ -225,26 +235,23 @@ int oslam_pyramid_egomotion(oslam_pyramid *src, oslam_pyramid *dst, const float 
 {
     oslam_egomotion_params p;
     oslam_ego_pair pair[OSLAM_EGOMOTION_MAX_LEVELS];
-    unsigned l, k[OSLAM_EGOMOTION_MAX_LEVELS];
+    unsigned l;
     int rc;
     if (!T_out) return fail(OSLAM_E_INVALID, "NULL argument");
     rc = check_call(src, dst, T_init, ep, &p);
     if (rc != OSLAM_OK) return rc;
-    for (l = 0; l < p.n_levels; l++) {
-        const unsigned s = p.level[l].stride;
-        if (s != 1 && s != 2 && s != 4) return fail(OSLAM_E_INVALID, "a stride of a pyramid schedule must be 1, 2 or 4");
-        k[l] = s >> 1;                          /* log2 of 1, 2, 4 */
-    }
+    rc = oslam_ego_check_pyramid_schedule(&p, UINT_MAX);     /* the strides alone, before a handle is read */
+    if (rc != OSLAM_OK) return rc;
     if (src == dst) {
         same_handle(&p, T_out, res);
         return OSLAM_OK;
     }
     if (src->dev != dst->dev) return fail(OSLAM_E_INVALID, "the two pyramids live on different devices");
+    rc = oslam_ego_check_pyramid_schedule(&p, src->n_levels < dst->n_levels ? src->n_levels : dst->n_levels);
+    if (rc != OSLAM_OK) return rc;
     for (l = 0; l < p.n_levels; l++) {          /* level log2(stride) of both pyramids, every pixel of its source */
-        if (k[l] >= src->n_levels || k[l] >= dst->n_levels)
-            return fail(OSLAM_E_INVALID, "a stride names a level the pyramid does not have");
-        pair[l].src = src->level[k[l]];
-        pair[l].dst = dst->level[k[l]];
+        pair[l].src = src->level[p.level[l].stride >> 1];
+        pair[l].dst = dst->level[p.level[l].stride >> 1];
         pair[l].lattice = 1;
     }
     return oslam_ego_run(pair, T_init ? T_init : k_identity, &p, T_out, res);

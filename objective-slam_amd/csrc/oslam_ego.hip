@@ -4,11 +4,11 @@
  *
  *   k_ego_step   one launch per scheduled iteration, lv.n_slots workgroups of 256 threads.  A workgroup walks lv.chunk
  *                consecutive blocks of 256 selected source pixels: per thread one 32-byte record of the source map, the
- *                transform under the float32 pose, the projection with the destination's camera (the pixel of
- *                oslam_verify_class), one 32-byte gather from the destination map, the gates and the 29 terms of the
- *                step (oslam_refine_step.h); the block's sums through the wave64 shuffle tree and the four waves in
- *                index order through LDS (two buffers, one barrier per block), added in double in block order by the
- *                threads 0..29 ([29]: the selected source pixels that have a normal, counted by ballots).  The
+ *                transform under the float32 pose, the projection with the destination's camera, one 32-byte gather
+ *                from the destination map and the gates (oslam_icp_core.h), the 29 terms of the step
+ *                (oslam_refine_step.h); the block's sums in the fixed order of oslam_icp_block_sums (two LDS buffers
+ *                taken in turn, one barrier per block; its extra column [29]: the selected source pixels that have a
+ *                normal, counted by ballots), added in double in block order by the threads 0..29.  The
  *                workgroup's 30 doubles go to its slot of the partials buffer.  Then the hand-off: every wave drains
  *                its stores, a barrier, thread 0 releases at agent scope and draws a ticket from the launch's arrival
  *                counter; the workgroup that draws the last ticket acquires at agent scope, adds the slots in the
@@ -26,11 +26,12 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "oslam_icp_core.h"
 #include "oslam_kernels.h"
 #include "oslam_refine_step.h"
 
 /* The correspondence of the source pixel spix under the float32 pose T (rows of [R | t]): its pixel index in dst, or -1.
- * *has = the source pixel has a normal; q = p', a and b = the destination pixel's vertex and normal records. */
+ * *has = the source pixel has a normal; q = p'; with a pixel, a and b = its vertex and normal records. */
 __device__ __forceinline__ int ego_correspond(const float4 *smaps, size_t spix, const float *T, const oslamk_view &dv,
                                               const float4 *dmaps, float r2, float min_dot, bool *has, float q[3],
                                               float4 *a_out, float4 *b_out)
@@ -38,31 +39,12 @@ __device__ __forceinline__ int ego_correspond(const float4 *smaps, size_t spix, 
     const float4 p = smaps[2 * spix], n = smaps[2 * spix + 1];
     *has = p.w != 0.0f;
     if (!*has) return -1;
-    const float qx = ((T[0] * p.x + T[1] * p.y) + T[2] * p.z) + T[3];
-    const float qy = ((T[4] * p.x + T[5] * p.y) + T[6] * p.z) + T[7];
-    const float qz = ((T[8] * p.x + T[9] * p.y) + T[10] * p.z) + T[11];
-    const float mx = (T[0] * n.x + T[1] * n.y) + T[2] * n.z;
-    const float my = (T[4] * n.x + T[5] * n.y) + T[6] * n.z;
-    const float mz = (T[8] * n.x + T[9] * n.y) + T[10] * n.z;
-    if (!(qz >= dv.z_min && qz <= dv.z_max)) return -1;
-    const float fu = floorf(((qx * dv.fx) / qz + dv.cx) + 0.5f);
-    const float fv = floorf(((qy * dv.fy) / qz + dv.cy) + 0.5f);
-    if (!(fu >= 0.0f && fu < (float)dv.w && fv >= 0.0f && fv < (float)dv.h)) return -1;
-    const int pix = (int)fv * dv.w + (int)fu;
-    const float4 a = dmaps[2 * (size_t)pix];
-    if (a.w == 0.0f) return -1;                    /* the pixel has no normal */
-    const float dx = a.x - qx, dy = a.y - qy, dz = a.z - qz;
-    const float d2 = (dx * dx + dy * dy) + dz * dz;
-    if (!(d2 <= r2)) return -1;
-    const float4 b = dmaps[2 * (size_t)pix + 1];
-    const float dot = (mx * b.x + my * b.y) + mz * b.z;
-    if (!(dot >= min_dot)) return -1;
-    q[0] = qx;
-    q[1] = qy;
-    q[2] = qz;
-    *a_out = a;
-    *b_out = b;
-    return pix;
+    float m[3];
+    int u, vv;
+    oslam_icp_transform(T, p.x, p.y, p.z, n.x, n.y, n.z, q, m);
+    if (!oslam_icp_project(dv, q, &u, &vv)) return -1;
+    const int pix = vv * dv.w + u;
+    return oslam_icp_gate(dmaps, pix, q, m, r2, min_dot, a_out, b_out) ? pix : -1;
 }
 
 /* One workgroup: the slots in the pinned order, the step, the state of the next launch. */
@@ -128,7 +110,7 @@ __global__ __launch_bounds__(OSLAMK_EGO_THREADS) void k_ego_step(const oslamk_vi
     __shared__ float sT[12], sc[3];
     __shared__ int s_last;
     const float4 *smaps = reinterpret_cast<const float4 *>(smaps_), *dmaps = reinterpret_cast<const float4 *>(dmaps_);
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int tid = threadIdx.x;
     if (tid < 12) sT[tid] = st->Tf[tid];
     if (tid < 3) sc[tid] = st->c[tid];
     const float r2 = st->r2_corr, min_dot = st->min_dot;
@@ -140,7 +122,7 @@ __global__ __launch_bounds__(OSLAMK_EGO_THREADS) void k_ego_step(const oslamk_vi
     double acc = 0.0;
     const uint32_t b0 = blockIdx.x * lv.chunk;
     for (uint32_t j = 0; j < lv.chunk && b0 + j < lv.n_blocks; j++) {
-        float s[NS];
+        float s[NS + 1];
 #pragma unroll
         for (int k = 0; k < NS; k++) s[k] = 0.0f;
         const uint32_t i = (b0 + j) * OSLAMK_EGO_THREADS + (uint32_t)tid;
@@ -153,21 +135,9 @@ __global__ __launch_bounds__(OSLAMK_EGO_THREADS) void k_ego_step(const oslamk_vi
             if (ego_correspond(smaps, spix, T, dv, dmaps, r2, min_dot, &has, q, &pa, &pb) >= 0)
                 oslam_refine_point_sums(q[0], q[1], q[2], pa, pb, sc, s);
         }
-        const int n_has = __popcll(__ballot(has));
-        oslam_refine_wave_sums<NS>(s);
-        const int par = (int)(j & 1u);
-        if (lane == 0) {
-#pragma unroll
-            for (int k = 0; k < NS; k++) sh[par][w][k] = s[k];
-            sh[par][w][NS] = (float)n_has;
-        }
-        __syncthreads();
-        if (tid <= NS) {
-            float x = sh[par][0][tid];
-#pragma unroll
-            for (int ww = 1; ww < NW; ww++) x += sh[par][ww][tid];
-            acc += (double)x;
-        }
+        s[NS] = (float)__popcll(__ballot(has));    /* the extra column: the wave's count, not summed by the tree */
+        const float x = oslam_icp_block_sums<NS>(s, sh[j & 1u]);
+        if (tid <= NS) acc += (double)x;
     }
     if (tid <= NS) slots[(size_t)blockIdx.x * OSLAMK_EGO_SLOT + tid] = acc;
     /* the hand-off: drain, barrier, release, ticket; the last arriver acquires before anyone of it reads a slot */

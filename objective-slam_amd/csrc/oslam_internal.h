@@ -6,6 +6,7 @@
 #define OSLAM_INTERNAL_H
 
 #include <hip/hip_runtime_api.h>
+#include <limits.h>
 #include <stddef.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -129,6 +130,9 @@ static inline double now_ms(void)
     return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6;
 }
 
+/* offsets of the parts of one device block */
+static inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
 /* the launch stream of this thread's calls (oslam_set_stream) */
 void *oslam_stream(void);
 /* binds device dev_req (clamped to the last device, ppf.cu:45) */
@@ -210,6 +214,8 @@ void oslam_model_shape(oslam_model *m);
 /* vp NULL = defaults; checks them as oslam_verify does, *out = the parameters in force */
 int oslam_verify_check_params(const oslam_verify_params *vp, oslam_verify_params *out);
 int oslam_is_zero_pose(const float T[16]);
+/* *r's counts from the six class counts c[0 .. 6), and from them view_fitness, coverage and found under p */
+void oslam_verify_fill_result(oslam_verify_result *r, const uint32_t *c, const oslam_verify_params *p);
 /* the model is usable and lives on the view's device */
 int oslam_view_check_pair(const oslam_model *m, const oslam_view *v);
 /* the descriptor of one member: its cloud, the rows of T, tol = (float)((double)depth_tol * d_dist), its blocks */
@@ -233,6 +239,9 @@ int oslam_track_view_maps(oslam_view *v, int *built);
 void oslam_ego_release(void);
 /* ep NULL = defaults; checks them as oslam_view_egomotion does, *out = the parameters in force (oslam_ego.c) */
 int oslam_ego_check_params(const oslam_egomotion_params *ep, oslam_egomotion_params *out);
+/* a pyramid schedule: every stride of p is 1, 2 or 4 and names a level (its log2) below n_levels, the levels of the
+ * pyramids it runs on (UINT_MAX while they cannot be read yet: the strides alone) */
+int oslam_ego_check_pyramid_schedule(const oslam_egomotion_params *p, unsigned n_levels);
 /* one level of an egomotion schedule: its views and the stride of its lattice over the source */
 typedef struct oslam_ego_pair {
     oslam_view *src, *dst;

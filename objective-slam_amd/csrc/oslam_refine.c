@@ -102,8 +102,6 @@ void oslam_refine_release_grids(oslam_scene *s)
     s->grids = NULL;
 }
 
-static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 /* A grid of the scene whose cells serve `radius`: a cached one with an edge in [radius, 2 radius], or a new one
  * (enqueued on the stream; *built = 1). */
 static int scene_grid(oslam_scene *s, float radius, oslamk_grid *out, int *built)

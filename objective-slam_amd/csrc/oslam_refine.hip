@@ -6,9 +6,10 @@
  *                  k_scan_top (exclusive scan of the cell counts: 4096 cells per workgroup, then the block
  *                  totals in one workgroup), k_grid_scatter (cell starts, points in cell order)
  *   correspond     k_refine_corr: one thread per model point, every member of the call in one grid (y = member,
- *                  x = block of 256 model points); the 27-cell walk, then the 29 (step) or 2 (score) partial sums
- *                  through a fixed wave64 shuffle tree and a fixed LDS order into a (member, workgroup) slab.  No
- *                  float atomics: the sums are bitwise reproducible
+ *                  x = block of 256 model points); the transform (oslam_icp_core.h), the 27-cell walk, then the 29
+ *                  (step) or 2 (score) partial sums through the fixed wave64 shuffle tree and the fixed LDS order of
+ *                  oslam_icp_block_sums into a (member, workgroup) slab.  No float atomics: the sums are bitwise
+ *                  reproducible
  *   solve          k_refine_solve: one wave per member sums its slab in double in workgroup order, solves the 6x6
  *                  system by Cholesky and updates the double pose
  */
@@ -17,6 +18,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "oslam_icp_core.h"
 #include "oslam_kernels.h"
 #include "oslam_refine_step.h"
 
@@ -138,19 +140,11 @@ __global__ __launch_bounds__(OSLAMK_REFINE_THREADS) void k_refine_corr(const osl
     for (int k = 0; k < NS; k++) s[k] = 0.0f;
 
     if (i < d->m.n) {
-        float T[12];
-#pragma unroll
-        for (int k = 0; k < 12; k++) T[k] = d->Tf[k];
         const float r2 = MODE == OSLAMK_REFINE_SCORE ? d->r2_score : d->r2_corr;
         const float min_dot = d->min_dot;
-        const float px = d->m.px[i], py = d->m.py[i], pz = d->m.pz[i];
-        const float nx = d->m.nx[i], ny = d->m.ny[i], nz = d->m.nz[i];
-        const float qx = ((T[0] * px + T[1] * py) + T[2] * pz) + T[3];
-        const float qy = ((T[4] * px + T[5] * py) + T[6] * pz) + T[7];
-        const float qz = ((T[8] * px + T[9] * py) + T[10] * pz) + T[11];
-        const float mx = (T[0] * nx + T[1] * ny) + T[2] * nz;
-        const float my = (T[4] * nx + T[5] * ny) + T[6] * nz;
-        const float mz = (T[8] * nx + T[9] * ny) + T[10] * nz;
+        float q[3], m[3];
+        oslam_icp_transform(d->Tf, d->m.px[i], d->m.py[i], d->m.pz[i], d->m.nx[i], d->m.ny[i], d->m.nz[i], q, m);
+        const float qx = q[0], qy = q[1], qz = q[2], mx = m[0], my = m[1], mz = m[2];
 
         const int cx = grid_axis(qx, g.lo[0], g.inv_edge, g.dim[0]);
         const int cy = grid_axis(qy, g.lo[1], g.inv_edge, g.dim[1]);
@@ -199,19 +193,8 @@ __global__ __launch_bounds__(OSLAMK_REFINE_THREADS) void k_refine_corr(const osl
     if (MODE == OSLAMK_REFINE_TAP) return;
 
     /* fixed-order reduction: shuffle tree inside each wave, then the waves in index order */
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    oslam_refine_wave_sums<NS>(s);
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < NS; k++) sh[w][k] = s[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < NS) {
-        float v = sh[0][threadIdx.x];
-#pragma unroll
-        for (int ww = 1; ww < OSLAMK_REFINE_THREADS / 64; ww++) v += sh[ww][threadIdx.x];
-        slab[((size_t)j * max_blocks + blockIdx.x) * STRIDE + threadIdx.x] = v;
-    }
+    const float sum = oslam_icp_block_sums<NS>(s, sh);
+    if (threadIdx.x < NS) slab[((size_t)j * max_blocks + blockIdx.x) * STRIDE + threadIdx.x] = sum;
 }
 
 /* ---------------------------------------------------------------- solve */

@@ -1,10 +1,11 @@
 /*
  * oslam_refine_step.h -- the Gauss-Newton step of the point-to-plane ICP (include/oslam.h at oslam_refine, "Step"), the
- * one source of the refinement kernels (oslam_refine.hip: correspondences from the scene grid) and of k_track
- * (oslam_track.hip: correspondences from the depth image).  Device code only.
+ * one source of the refinement kernels (oslam_refine.hip: correspondences from the scene grid), of k_track
+ * (oslam_track.hip: correspondences from the depth image) and of k_ego_step (oslam_ego.hip: from another view's maps).
+ * What surrounds the step -- transform, projection, gates, the block's fixed-order sums -- is oslam_icp_core.h.
+ * Device code only.
  *
  *   oslam_refine_point_sums   the 29 terms of one correspondence: J^T J upper triangle (21, row-major), J^T r (6), 1, r^2
- *   oslam_refine_wave_sums    the fixed wave64 shuffle tree over every term (lane 0 holds the wave's sum)
  *   oslam_refine_step         the sums in double -> damped Cholesky, Rodrigues, the pose update about the transformed
  *                             centroid and Gram-Schmidt; one thread
  */
@@ -41,19 +42,6 @@ __device__ __forceinline__ void oslam_refine_point_sums(float qx, float qy, floa
     for (int u = 0; u < 6; u++) s[21 + u] = J[u] * r;
     s[27] = 1.0f;
     s[28] = r * r;
-}
-
-/* fixed-order reduction inside each wave: a shuffle tree, the same for every term */
-template <int NS>
-__device__ __forceinline__ void oslam_refine_wave_sums(float *s)
-{
-#pragma unroll
-    for (int k = 0; k < NS; k++) {
-        float v = s[k];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-        s[k] = v;
-    }
 }
 
 __device__ inline void oslam_rot_apply(const double R[9], const double x[3], double y[3])

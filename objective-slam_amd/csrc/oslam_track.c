@@ -77,8 +77,6 @@ static int check_list(oslam_model *const *ms, const float *T, size_t H, const os
     return OSLAM_OK;
 }
 
-static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 /* The view's maps, built on first use (enqueued on the stream; *built = 1).  Called with g_track_mu held and the view's
  * device bound.  The block lives as long as the view and goes back to the kept blocks of the scene path with it: the
  * next frame's view takes it again without a hipMalloc / hipFree pair. */
@@ -178,24 +176,11 @@ static int track_members(oslam_model *const *ms, size_t H, const oslam_view *v, 
         T[15] = 1.0f;
         if (res) {
             oslam_track_result *r = &res[h];
-            oslam_verify_result *q = &r->verify;
-            uint32_t sx, sox;
-            q->back = k->counts[0];
-            q->out = k->counts[1];
-            q->supported = k->counts[2];
-            q->occluded = k->counts[3];
-            q->conflict = k->counts[4];
-            q->unknown = k->counts[5];
-            sx = q->supported + q->conflict;
-            sox = sx + q->occluded;
-            q->view_fitness = sx ? (float)q->supported / (float)sx : 0.0f;
-            q->coverage = sox ? (float)q->supported / (float)sox : 0.0f;
-            q->found = q->supported >= p->verify.min_supported && q->view_fitness >= p->verify.min_view_fitness &&
-                       q->coverage >= p->verify.min_coverage;
+            oslam_verify_fill_result(&r->verify, k->counts, &p->verify);
             r->iterations = k->iterations;
             r->correspondences = k->n_corr;
             r->converged = k->converged;
-            r->found = q->found;
+            r->found = r->verify.found;
         }
     }
 done:

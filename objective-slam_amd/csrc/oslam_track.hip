@@ -6,18 +6,17 @@
  *                    (oslam_depth_normal.h, the code of k_depth_points) into a 32-byte record per pixel, x y z has |
  *                    nx ny nz 0, so that a correspondence is one 32-byte gather.
  *   k_track          one workgroup of 256 threads per hypothesis runs the whole call.  Per iteration it walks its
- *                    model's blocks of 256 points: transform and projection (oslam_verify_class with window 0: the
- *                    BACK / OUT tests and the pixel of k_verify), the gather, the gates, the 29 terms of the step
- *                    (oslam_refine_step.h, the code of k_refine_corr); the block's sums through the wave64 shuffle tree
- *                    and the four waves in index order through LDS (two buffers, so one barrier per block), added in
- *                    double in block order by the threads 0..28.  Thread 0 solves the 6x6 system in double
- *                    (oslam_refine_step, the code of k_refine_solve) and publishes the float32 pose and the transformed
- *                    centroid through LDS; a barrier, then the next iteration.  No float atomics: the result is bitwise
- *                    reproducible.  After the last iteration the blocks are classed with the caller's window
- *                    (oslam_verify_class, k_verify's class), counted per wave by ballots and summed as integers.
+ *                    model's blocks of 256 points: the transform, k_verify's BACK test, the pixel, the gather and the
+ *                    gates (oslam_icp_core.h; the z image is not read), the 29 terms of the step (oslam_refine_step.h);
+ *                    the block's sums in the fixed order of oslam_icp_block_sums (two LDS buffers taken in turn, so one
+ *                    barrier per block), added in double in block order by the threads 0..28.  Thread 0 solves the 6x6
+ *                    system in double (oslam_refine_step, the code of k_refine_solve) and publishes the float32 pose and
+ *                    the transformed centroid through LDS; a barrier, then the next iteration.  No float atomics: the
+ *                    result is bitwise reproducible.  After the last iteration the blocks are classed with the caller's
+ *                    window (oslam_verify_class, k_verify's class), counted per wave by ballots and summed as integers.
  *   k_track_corr     the tap: one thread per model point, the pixel of its correspondence.
  * Bounds: a model point index is checked against the model's point count before its loads; the pixel is range-checked
- * in float before it becomes an int (oslam_verify_class), so the gather reads inside the w * h records of the map.
+ * in float before it becomes an int (oslam_icp_project), so the gather reads inside the w * h records of the map.
  */
 #include <hip/hip_runtime.h>
 
@@ -25,6 +24,7 @@
 #include <stdint.h>
 
 #include "oslam_depth_normal.h"
+#include "oslam_icp_core.h"
 #include "oslam_kernels.h"
 #include "oslam_refine_step.h"
 #include "oslam_verify_class.h"
@@ -51,40 +51,18 @@ __global__ __launch_bounds__(256) void k_view_normals(const oslamk_view v, float
     dst[1] = b;
 }
 
-/* The correspondence of point i (i < d->m.n) of a hypothesis with pose d->T: its pixel index, or -1.  q = p', a and b =
- * the pixel's vertex and normal records. */
+/* The correspondence of point i (i < d->m.n) of a hypothesis with pose d->T: its pixel index, or -1.  q = p'; with a
+ * pixel, a and b = its vertex and normal records. */
 __device__ __forceinline__ int track_correspond(const oslamk_view &v, const float4 *maps, const oslamk_verify_member *d, int i,
                                                 float r2, float min_dot, float q[3], float4 *a_out, float4 *b_out)
 {
-    int u = 0, vv = 0;
-    float resid = 0.0f;
-    if (oslam_verify_class<true>(v, d, i, 0, &u, &vv, &resid) < 2) return -1;        /* BACK or OUT */
+    float m[3];
+    int u, vv;
+    oslam_icp_transform(d->T, d->m.px[i], d->m.py[i], d->m.pz[i], d->m.nx[i], d->m.ny[i], d->m.nz[i], q, m);
+    if ((m[0] * q[0] + m[1] * q[1]) + m[2] * q[2] >= 0.0f) return -1;  /* BACK, k_verify's test */
+    if (!oslam_icp_project(v, q, &u, &vv)) return -1;                  /* OUT */
     const int pix = vv * v.w + u;
-    const float4 a = maps[2 * (size_t)pix];
-    if (a.w == 0.0f) return -1;                    /* the pixel has no normal */
-    float T[12];
-#pragma unroll
-    for (int k = 0; k < 12; k++) T[k] = d->T[k];
-    const float px = d->m.px[i], py = d->m.py[i], pz = d->m.pz[i];
-    const float nx = d->m.nx[i], ny = d->m.ny[i], nz = d->m.nz[i];
-    const float qx = ((T[0] * px + T[1] * py) + T[2] * pz) + T[3];
-    const float qy = ((T[4] * px + T[5] * py) + T[6] * pz) + T[7];
-    const float qz = ((T[8] * px + T[9] * py) + T[10] * pz) + T[11];
-    const float mx = (T[0] * nx + T[1] * ny) + T[2] * nz;
-    const float my = (T[4] * nx + T[5] * ny) + T[6] * nz;
-    const float mz = (T[8] * nx + T[9] * ny) + T[10] * nz;
-    const float dx = a.x - qx, dy = a.y - qy, dz = a.z - qz;
-    const float d2 = (dx * dx + dy * dy) + dz * dz;
-    if (!(d2 <= r2)) return -1;
-    const float4 b = maps[2 * (size_t)pix + 1];
-    const float dot = (mx * b.x + my * b.y) + mz * b.z;
-    if (!(dot >= min_dot)) return -1;
-    q[0] = qx;
-    q[1] = qy;
-    q[2] = qz;
-    *a_out = a;
-    *b_out = b;
-    return pix;
+    return oslam_icp_gate(maps, pix, q, m, r2, min_dot, a_out, b_out) ? pix : -1;
 }
 
 __global__ __launch_bounds__(OSLAMK_TRACK_THREADS) void k_track(const oslamk_view v, const float *maps_,
@@ -140,19 +118,8 @@ __global__ __launch_bounds__(OSLAMK_TRACK_THREADS) void k_track(const oslamk_vie
                 if (track_correspond(v, maps, &vm, i, r2, min_dot, q, &pa, &pb) >= 0)
                     oslam_refine_point_sums(q[0], q[1], q[2], pa, pb, sc, s);
             }
-            oslam_refine_wave_sums<NS>(s);
-            const int par = (int)(b & 1u);
-            if (lane == 0) {
-#pragma unroll
-                for (int k = 0; k < NS; k++) sh[par][w][k] = s[k];
-            }
-            __syncthreads();
-            if (tid < NS) {
-                float x = sh[par][0][tid];
-#pragma unroll
-                for (int ww = 1; ww < NW; ww++) x += sh[par][ww][tid];
-                acc += (double)x;
-            }
+            const float x = oslam_icp_block_sums<NS>(s, sh[b & 1u]);
+            if (tid < NS) acc += (double)x;
         }
         if (tid < NS) S[tid] = acc;
         __syncthreads();

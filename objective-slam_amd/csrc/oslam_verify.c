@@ -107,7 +107,19 @@ int oslam_view_check_pair(const oslam_model *m, const oslam_view *v)
     return OSLAM_OK;
 }
 
-static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+void oslam_verify_fill_result(oslam_verify_result *r, const uint32_t *c, const oslam_verify_params *p)
+{
+    const uint32_t sx = c[2] + c[4], sox = sx + c[3];
+    r->back = c[0];
+    r->out = c[1];
+    r->supported = c[2];
+    r->occluded = c[3];
+    r->conflict = c[4];
+    r->unknown = c[5];
+    r->view_fitness = sx ? (float)r->supported / (float)sx : 0.0f;
+    r->coverage = sox ? (float)r->supported / (float)sox : 0.0f;
+    r->found = r->supported >= p->min_supported && r->view_fitness >= p->min_view_fitness && r->coverage >= p->min_coverage;
+}
 
 void oslam_verify_set_member(oslamk_verify_member *d, const oslam_model *m, const float T[16], float depth_tol)
 {
@@ -153,24 +165,8 @@ int oslam_verify_members(oslam_model *const *ms, size_t n, const oslam_view *v, 
     HIPCHK(hipMemcpyAsync(cnt, dev + off_cnt, sizeof(uint32_t) * OSLAMK_VERIFY_CLASSES * n, hipMemcpyDeviceToHost,
                           (hipStream_t)stream));
     HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-    for (j = 0; j < n; j++) {
-        oslam_verify_result *r = &res[j];
-        const uint32_t *c = cnt + OSLAMK_VERIFY_CLASSES * j;
-        uint32_t sx, sox;
-        if (h[j].n_blocks == 0) continue;
-        r->back = c[0];
-        r->out = c[1];
-        r->supported = c[2];
-        r->occluded = c[3];
-        r->conflict = c[4];
-        r->unknown = c[5];
-        sx = r->supported + r->conflict;
-        sox = sx + r->occluded;
-        r->view_fitness = sx ? (float)r->supported / (float)sx : 0.0f;
-        r->coverage = sox ? (float)r->supported / (float)sox : 0.0f;
-        r->found = r->supported >= p->min_supported && r->view_fitness >= p->min_view_fitness &&
-                   r->coverage >= p->min_coverage;
-    }
+    for (j = 0; j < n; j++)
+        if (h[j].n_blocks) oslam_verify_fill_result(&res[j], cnt + OSLAMK_VERIFY_CLASSES * j, p);
 done:
     if (rc != OSLAM_OK) (void)hipStreamSynchronize((hipStream_t)stream);    /* nothing may still use the block */
     if (dev) oslam_dev_free(dev);

@@ -3,9 +3,9 @@
  * oslam_volume_integrate): the host side of the kernels in oslam_volume.hip.  A call checks its arguments, zeroes a
  * counter block, runs one kernel and reads the counters back with one host wait.  oslam_volume_track is glue over the
  * ray cast and oslam_view_egomotion, oslam_volume_track_pyramid over the ray cast, a pyramid of it and
- * oslam_pyramid_egomotion; oslam_view_to_cloud runs the depth front end's compaction over a view's maps.
- * oslam_volume_surface (kernels: oslam_surface.hip) counts, waits for the number of points, allocates exactly that and
- * emits.
+ * oslam_pyramid_egomotion (one body, track_from_raycast); oslam_view_to_cloud runs the depth front end's compaction
+ * over a view's maps.  oslam_volume_surface (kernels: oslam_surface.hip) counts, waits for the number of points,
+ * allocates exactly that and emits.
  */
 #include <math.h>
 #include <pthread.h>
@@ -247,89 +247,43 @@ static void pose_product(const float T_prev[16], const float T[16], float T_out[
     T_out[15] = 1.0f;
 }
 
-int oslam_volume_track(oslam_volume *vol, oslam_view *v, const float T_prev[16], const oslam_egomotion_params *ep,
-                       float T_out[16], oslam_egomotion_result *ego_res)
+/* the camera that renders a view like v */
+static void camera_of_view(const oslam_view *v, oslam_camera *cam)
 {
-    int rc;
-    const double t0 = now_ms();
-    oslam_egomotion_params p;
-    oslam_egomotion_result er;
-    oslam_camera cam;
-    oslam_view *model = NULL;
-    uint32_t cnt[2];
-    float T[16];
-    if (!vol || !v || !T_prev || !T_out) return fail(OSLAM_E_INVALID, "NULL argument");
-    rc = oslam_ego_check_params(ep, &p);
-    if (rc == OSLAM_OK) rc = oslam_refine_check_rigid(T_prev);
-    if (rc != OSLAM_OK) return rc;
-    if (vol->dev != v->dev) return fail(OSLAM_E_INVALID, "volume and view live on different devices");
-    memset(&cam, 0, sizeof cam);
-    cam.fx = v->k.fx;
-    cam.fy = v->k.fy;
-    cam.cx = v->k.cx;
-    cam.cy = v->k.cy;
-    cam.depth_scale = 1.0f;
-    cam.z_min = v->k.z_min;
-    cam.z_max = v->k.z_max;
-    cam.max_jump = v->max_jump;
-    if (hipSetDevice(vol->dev) != hipSuccess) return fail(OSLAM_E_DEVICE, "hipSetDevice failed");
-    pthread_mutex_lock(&g_vol_mu);
-    rc = raycast(vol, T_prev, &cam, v->k.w, v->k.h, &model, cnt);
-    if (rc == OSLAM_OK) rc = oslam_view_egomotion(v, model, NULL, &p, T, &er);
-    pthread_mutex_unlock(&g_vol_mu);
-    if (model) oslam_view_destroy(model);
-    if (rc != OSLAM_OK) return rc;
-    pose_product(T_prev, T, T_out);
-    if (ego_res) {
-        *ego_res = er;
-        ego_res->launches += 1;
-        ego_res->ms_total = (float)(now_ms() - t0);
-    }
-    return OSLAM_OK;
+    memset(cam, 0, sizeof *cam);
+    cam->fx = v->k.fx;
+    cam->fy = v->k.fy;
+    cam->cx = v->k.cx;
+    cam->cy = v->k.cy;
+    cam->depth_scale = 1.0f;
+    cam->z_min = v->k.z_min;
+    cam->z_max = v->k.z_max;
+    cam->max_jump = v->max_jump;
 }
 
-int oslam_volume_track_pyramid(oslam_volume *vol, oslam_pyramid *frame, const float T_prev[16], const oslam_pyramid_params *pp,
-                               const oslam_egomotion_params *ep, float T_out[16], oslam_egomotion_result *ego_res)
+/* The body of oslam_volume_track (frame and q both NULL: v against the ray cast from T_prev) and of
+ * oslam_volume_track_pyramid (frame and q both given, v = the base of frame: frame against a pyramid of the ray cast
+ * made with q), after their argument checks; p and q are the parameters in force, t0 the start of the call.  frame is
+ * NULL exactly when q is: q is read only under frame. */
+static int track_from_raycast(oslam_volume *vol, oslam_view *v, oslam_pyramid *frame, const oslam_pyramid_params *q,
+                              const float T_prev[16], const oslam_egomotion_params *p, double t0, float T_out[16],
+                              oslam_egomotion_result *ego_res)
 {
     int rc;
-    unsigned l;
-    const double t0 = now_ms();
-    oslam_egomotion_params p;
-    oslam_pyramid_params q;
     oslam_egomotion_result er;
     oslam_camera cam;
-    const oslam_view *v;
     oslam_view *model = NULL;
     oslam_pyramid *model_pyr = NULL;
     uint32_t cnt[2];
     float T[16];
-    if (!vol || !frame || !T_prev || !T_out) return fail(OSLAM_E_INVALID, "NULL argument");
-    rc = oslam_ego_check_params(ep, &p);
-    if (rc == OSLAM_OK) rc = oslam_pyramid_check_params(pp, &q);
-    if (rc == OSLAM_OK) rc = oslam_refine_check_rigid(T_prev);
-    if (rc != OSLAM_OK) return rc;
-    for (l = 0; l < p.n_levels; l++) {
-        const unsigned s = p.level[l].stride;
-        if (s != 1 && s != 2 && s != 4) return fail(OSLAM_E_INVALID, "a stride of a pyramid schedule must be 1, 2 or 4");
-        if ((s >> 1) >= q.n_levels || (s >> 1) >= frame->n_levels)
-            return fail(OSLAM_E_INVALID, "a stride names a level the pyramid does not have");
-    }
-    if (vol->dev != frame->dev) return fail(OSLAM_E_INVALID, "volume and pyramid live on different devices");
-    v = frame->level[0];
-    memset(&cam, 0, sizeof cam);
-    cam.fx = v->k.fx;
-    cam.fy = v->k.fy;
-    cam.cx = v->k.cx;
-    cam.cy = v->k.cy;
-    cam.depth_scale = 1.0f;
-    cam.z_min = v->k.z_min;
-    cam.z_max = v->k.z_max;
-    cam.max_jump = v->max_jump;
+    camera_of_view(v, &cam);
     if (hipSetDevice(vol->dev) != hipSuccess) return fail(OSLAM_E_DEVICE, "hipSetDevice failed");
     pthread_mutex_lock(&g_vol_mu);
     rc = raycast(vol, T_prev, &cam, v->k.w, v->k.h, &model, cnt);
-    if (rc == OSLAM_OK) rc = oslam_pyramid_create(model, &q, &model_pyr);
-    if (rc == OSLAM_OK) rc = oslam_pyramid_egomotion(frame, model_pyr, NULL, &p, T, &er);
+    if (rc == OSLAM_OK && frame) rc = oslam_pyramid_create(model, q, &model_pyr);
+    if (rc == OSLAM_OK)
+        rc = frame ? oslam_pyramid_egomotion(frame, model_pyr, NULL, p, T, &er)
+                   : oslam_view_egomotion(v, model, NULL, p, T, &er);
     pthread_mutex_unlock(&g_vol_mu);
     if (model_pyr) oslam_pyramid_destroy(model_pyr);
     if (model) oslam_view_destroy(model);
@@ -337,10 +291,52 @@ int oslam_volume_track_pyramid(oslam_volume *vol, oslam_pyramid *frame, const fl
     pose_product(T_prev, T, T_out);
     if (ego_res) {
         *ego_res = er;
-        ego_res->launches += 1 + (q.n_levels - 1);      /* the ray cast and the down-sampling launches */
+        ego_res->launches += 1 + (frame ? q->n_levels - 1 : 0);     /* the ray cast and the down-sampling launches */
         ego_res->ms_total = (float)(now_ms() - t0);
     }
     return OSLAM_OK;
+}
+
+int oslam_volume_track(oslam_volume *vol, oslam_view *v, const float T_prev[16], const oslam_egomotion_params *ep,
+                       float T_out[16], oslam_egomotion_result *ego_res)
+{
+    int rc;
+    const double t0 = now_ms();
+    oslam_egomotion_params p;
+    if (!vol || !v || !T_prev || !T_out) return fail(OSLAM_E_INVALID, "NULL argument");
+    rc = oslam_ego_check_params(ep, &p);
+    if (rc == OSLAM_OK) rc = oslam_refine_check_rigid(T_prev);
+    if (rc != OSLAM_OK) return rc;
+    if (vol->dev != v->dev) return fail(OSLAM_E_INVALID, "volume and view live on different devices");
+    return track_from_raycast(vol, v, NULL, NULL, T_prev, &p, t0, T_out, ego_res);
+}
+
+int oslam_volume_track_pyramid(oslam_volume *vol, oslam_pyramid *frame, const float T_prev[16], const oslam_pyramid_params *pp,
+                               const oslam_egomotion_params *ep, float T_out[16], oslam_egomotion_result *ego_res)
+{
+    int rc;
+    const double t0 = now_ms();
+    oslam_egomotion_params p;
+    oslam_pyramid_params q;
+    if (!vol || !frame || !T_prev || !T_out) return fail(OSLAM_E_INVALID, "NULL argument");
+    rc = oslam_ego_check_params(ep, &p);
+    if (rc == OSLAM_OK) rc = oslam_pyramid_check_params(pp, &q);
+    if (rc == OSLAM_OK) rc = oslam_refine_check_rigid(T_prev);
+    if (rc == OSLAM_OK)
+        rc = oslam_ego_check_pyramid_schedule(&p, q.n_levels < frame->n_levels ? q.n_levels : frame->n_levels);
+    if (rc != OSLAM_OK) return rc;
+    if (vol->dev != frame->dev) return fail(OSLAM_E_INVALID, "volume and pyramid live on different devices");
+    return track_from_raycast(vol, frame->level[0], frame, &q, T_prev, &p, t0, T_out, ego_res);
+}
+
+/* interleaved [n][6] points (x y z nx ny nz) into xyz [n][3] and normals [n][3] */
+static void split_points(const float *pts6, size_t n, float *xyz_out, float *nrm_out)
+{
+    size_t i;
+    for (i = 0; i < n; i++) {
+        memcpy(xyz_out + 3 * i, pts6 + 6 * i, 3 * sizeof(float));
+        memcpy(nrm_out + 3 * i, pts6 + 6 * i + 3, 3 * sizeof(float));
+    }
 }
 
 int oslam_view_to_cloud(oslam_view *v, float *xyz_out, float *nrm_out, size_t cap, size_t *n_out)
@@ -348,7 +344,7 @@ int oslam_view_to_cloud(oslam_view *v, float *xyz_out, float *nrm_out, size_t ca
     int rc, built = 0, k;
     float *d_out = NULL, *h_out = NULL;
     uint32_t np = 0;
-    size_t i, n_pix;
+    size_t n_pix;
     if (!v || !xyz_out || !nrm_out || !n_out) return fail(OSLAM_E_INVALID, "NULL argument");
     *n_out = 0;
     n_pix = (size_t)v->k.w * (size_t)v->k.h;
@@ -365,10 +361,7 @@ int oslam_view_to_cloud(oslam_view *v, float *xyz_out, float *nrm_out, size_t ca
     h_out = (float *)malloc(sizeof(float) * 6 * (np ? np : 1));
     if (!h_out) { rc = fail(OSLAM_E_NOMEM, "host allocation failed"); goto done; }
     if (np) HIPCHK(hipMemcpy(h_out, d_out, sizeof(float) * 6 * np, hipMemcpyDeviceToHost));
-    for (i = 0; i < np; i++) {
-        memcpy(xyz_out + 3 * i, h_out + 6 * i, 3 * sizeof(float));
-        memcpy(nrm_out + 3 * i, h_out + 6 * i + 3, 3 * sizeof(float));
-    }
+    split_points(h_out, np, xyz_out, nrm_out);
 done:
     pthread_mutex_unlock(&g_vol_mu);
     free(h_out);
@@ -471,7 +464,6 @@ int oslam_volume_surface(oslam_volume *vol, const oslam_surface_params *sp, floa
     oslam_surface_params p;
     float *d_out = NULL, *h_out = NULL;
     uint32_t tot[2] = {0, 0}, launches = 0;
-    size_t i;
     if (!vol || !n_out) return fail(OSLAM_E_INVALID, "NULL argument");
     if (!xyz_out != !nrm_out) return fail(OSLAM_E_INVALID, "xyz_out and nrm_out must both be given or both be NULL");
     if (!xyz_out && cap != 0) return fail(OSLAM_E_INVALID, "cap must be 0 without outputs");
@@ -489,10 +481,7 @@ int oslam_volume_surface(oslam_volume *vol, const oslam_surface_params *sp, floa
         h_out = (float *)malloc(sizeof(float) * 6 * (size_t)tot[1]);
         if (!h_out) { rc = fail(OSLAM_E_NOMEM, "host allocation failed"); goto done; }
         HIPCHK(hipMemcpy(h_out, d_out, sizeof(float) * 6 * (size_t)tot[1], hipMemcpyDeviceToHost));
-        for (i = 0; i < tot[1]; i++) {
-            memcpy(xyz_out + 3 * i, h_out + 6 * i, 3 * sizeof(float));
-            memcpy(nrm_out + 3 * i, h_out + 6 * i + 3, 3 * sizeof(float));
-        }
+        split_points(h_out, tot[1], xyz_out, nrm_out);
     }
 done:
     pthread_mutex_unlock(&g_vol_mu);
