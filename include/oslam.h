@@ -961,8 +961,8 @@ int oslam_tracker_camera(const oslam_tracker *t, float T_world_cam[16]);
  *   computed in size_t (512^3 voxels are 512 MiB).
  * Cost: integrate = one memset of the counter, k_tsdf_integrate, one copy back, one host wait; raycast = the same with
  *   k_tsdf_raycast.  Calls on volumes take turns (one lock, held to the end of the host wait).
- * Out of scope: a moving or shifting volume, colour, the along-ray distance, marching cubes and mesh export, masking
- *   tracked objects out of the integration, several GPUs; oslam_tracker keeps taking T_cam from the caller. */
+ * Out of scope: a moving or shifting volume, colour, the along-ray distance, masking tracked objects out of the
+ *   integration, several GPUs; oslam_tracker keeps taking T_cam from the caller. */
 typedef struct oslam_volume oslam_volume;
 typedef struct oslam_volume_params {
     unsigned nx, ny, nz;      /* voxels per side, each 16..512 and a multiple of 8; default 256^3 */
@@ -1128,6 +1128,81 @@ int oslam_scene_from_volume(oslam_volume *vol, const oslam_surface_params *sp, f
                             unsigned ref_point_downsample_factor, const oslam_params *params, oslam_scene **out,
                             size_t *n_points_out);
 int oslam_volume_set_voxels(oslam_volume *vol, const int16_t *tsdf_q, const uint16_t *weight);
+
+/* ---- the fused surface of a whole volume as a triangle mesh by marching cubes (KinFu's marching cubes).  The
+ * restatement in numpy is tests/mesh_ref.py; device and restatement agree bit for bit, order included.
+ *
+ * Storage, F and "seen iff w >= min_weight" are oslam_volume_surface's.  All arithmetic is float32, grouped as written
+ * there.
+ * Vertices.  Vertex v is the v-th crossing of oslam_volume_surface's rule in its order: every edge between two seen
+ *   voxels with (q0 < 0) != (q1 < 0), ascending 3 * voxel + axis, whether or not it has a normal.  Its position is that
+ *   rule's P, bit for bit; its normal comes from the same six trilinear reads, and a crossing without a normal keeps
+ *   its vertex and gets (0, 0, 0).  So the number of vertices equals oslam_surface_result.crossings, and the vertices
+ *   with a non-zero normal, in order, are exactly oslam_volume_surface's points and normals.  With nrm_out == NULL the
+ *   normals are not computed at all.
+ * Cubes.  Cube (i, j, k) exists for i <= nx-2, j <= ny-2, k <= nz-2 and is full iff all eight corners are seen.  Corner
+ *   c = dx + 2*dy + 4*dz is voxel (i+dx, j+dy, k+dz); case = sum((q_c < 0) << c), the integer test, so zero counts as
+ *   positive.  Cubes that are not full emit nothing.  Every edge of a full cube joins two seen voxels, so every vertex
+ *   a triangle needs exists.  A vertex next to unseen voxels or on the volume's border may be referenced by no
+ *   triangle: that is legal, and the unreferenced vertices are not dropped.
+ * Cube edges.  e = 4*a + m runs along axis a; m holds the two other offsets in axis order (x: dy + 2*dz, y: dx + 2*dz,
+ *   z: dx + 2*dy).  Its global id is 3 * lin(start voxel) + a, oslam_volume_surface's key; 512^3 voxels keep it inside
+ *   uint32.
+ * Table.  tools/gen_mc_table.py derives csrc/oslam_mc_table.h: for each case and each of the six faces it counts the
+ *   sign changes round the face.  Two changes give one segment between the two crossing edges; four changes (the
+ *   ambiguous face) give two segments, each joining the two face edges that meet at a NEGATIVE corner.  The rule reads
+ *   only the face's four signs, so both cubes at a face agree and the mesh is closed wherever the cubes are full.
+ *   Every crossing edge lies on two faces, so the segments close into disjoint loops.  A segment is walked from A to
+ *   B so that (B - A) x f, f the face's outward normal, points from the segment towards the negative ends of the two
+ *   edges it joins: the single negative corner 0 gives x-edge -> y-edge -> z-edge, and triangle normals point towards
+ *   growing F, outwards, like the vertex normals.  A loop is rotated to start at its smallest cube-edge number from
+ *   which no fan diagonal lies in a face of the cube, and fanned, (v0, v_i, v_i+1); loops are ordered by their smallest
+ *   edge number.  (A diagonal inside an ambiguous face could be laid by the cube behind the face as well, which gives an
+ *   edge of four triangles; such an apex exists for every loop, and 18 loops of the table do not start at their smallest
+ *   edge because of it.)  At most OSLAM_MC_MAX_TRI = 5 triangles per case.
+ * Triangles.  Ascending linear index of the cube's corner voxel, then the row's order; a triangle is three uint32
+ *   vertex indices in the row's order.  A corner value of exactly 0 gives t = 0 and hence zero-area triangles: they are
+ *   kept, the topology matters more than the area.
+ * Determinism.  Two calls give the same bytes; there are no float atomics.
+ * oslam_volume_mesh: xyz_out [v_cap][3] and tri_out [t_cap][3] are both given or both NULL; both NULL needs both caps 0
+ *   and only counts; nrm_out [v_cap][3] is optional alongside xyz_out.  *nv_out and *nt_out = the numbers of vertices
+ *   and triangles in every case that reached the device; OSLAM_E_LIMIT when outputs are given and either cap is below
+ *   its count (nothing is written, the result is filled).  A triangle corner whose edge has no vertex (it cannot happen
+ *   under the rule above; the kernel checks it like the index checks of the other stages) fails the call with
+ *   OSLAM_E_DEVICE and nothing is written.  mp NULL = defaults, res may be NULL.
+ * Arguments are checked before any handle is read or any device call is made: NULL vol, nv_out or nt_out, one of
+ *   xyz_out and tri_out without the other, nrm_out without xyz_out, NULL outputs with a cap > 0 and a min_weight outside
+ *   1..65535 are OSLAM_E_INVALID.
+ * Cost: one memset of the totals, k_mesh_count and two runs of k_surface_scan, one copy back and host wait for the two
+ *   counts, then k_mesh_vertices and k_mesh_triangles into blocks of exactly those sizes and one more wait.  Device
+ *   memory besides the outputs: two counters per workgroup of 1024 voxels and one uint32 edge id per vertex.  Calls
+ *   take turns with the other calls on volumes.
+ * oslam_ply_write_mesh writes the vertex element as oslam_ply_write writes it (nrm is needed: pass zeros where there are
+ *   no normals), then `element face nt` with `property list uchar int vertex_indices`; an index >= nv is
+ *   OSLAM_E_INVALID.  oslam_ply_read reads such a file's vertices back and skips the faces.
+ * oslam_mc_table_row is a host-only tap on the compiled-in table for the tests: edges_out [15] gets 3 * *n_tri_out
+ *   cube-edge numbers.
+ * Out of scope: colour, merging or decimating triangles, dropping unreferenced vertices on the device, smoothing, a
+ *   min_weight for the normal's corners, meshing across a shifting volume, several GPUs. */
+typedef struct oslam_mesh_params {
+    unsigned min_weight;      /* 1..65535, default 1: a voxel is seen from this weight on */
+    int reserved[7];
+} oslam_mesh_params;
+
+typedef struct oslam_mesh_result {
+    uint32_t vertices;         /* crossings: equals oslam_surface_result.crossings */
+    uint32_t triangles;
+    uint32_t cubes;            /* full cubes with a case other than 0 and 255 */
+    uint32_t launches;
+    float ms_total;            /* whole call, host clock */
+} oslam_mesh_result;
+
+int oslam_mesh_params_default(oslam_mesh_params *p);
+int oslam_volume_mesh(oslam_volume *vol, const oslam_mesh_params *mp, float *xyz_out, float *nrm_out, size_t v_cap,
+                      uint32_t *tri_out, size_t t_cap, size_t *nv_out, size_t *nt_out, oslam_mesh_result *res);
+int oslam_ply_write_mesh(const char *path, const float *xyz, const float *nrm, size_t nv, const uint32_t *tri, size_t nt,
+                         int binary);
+int oslam_mc_table_row(unsigned mc_case, uint8_t *edges_out, unsigned *n_tri_out);
 
 /* ---- parity taps (tests): values the reference materialises as arrays.
  * Scene::getHashKeys row r (scene.cu:49-54): keys_out[n] of reference point r,

@@ -557,6 +557,27 @@ int oslamk_surface_count(const oslamk_volume *vol, uint32_t min_weight, uint32_t
 /* second pass: out6 = device [n_points][6] (x y z nx ny nz), offsets and n_points as oslamk_surface_count left them */
 int oslamk_surface_emit(const oslamk_volume *vol, uint32_t min_weight, uint32_t n_groups, const uint32_t *offsets,
                         uint32_t n_points, float *out6, void *stream);
+/* the scan alone: counts [n] (n <= 2^17) becomes its exclusive prefix sums in place, totals[1] = the sum */
+int oslamk_surface_scan(uint32_t *counts, uint32_t n, uint32_t *totals, void *stream);
+
+/* ---- mesh extraction (oslam_mesh.hip; semantics in include/oslam.h at oslam_volume_mesh); workgroups and runs are the
+ * surface extraction's, n_groups = oslamk_surface_groups(vol) ---- */
+#define OSLAMK_MESH_T_CUBES 0         /* totals: full cubes with a case other than 0 and 255 (zeroed by the caller) */
+#define OSLAMK_MESH_T_VERTS 1         /*         vertices */
+#define OSLAMK_MESH_T_TRIS 2          /*         triangles */
+#define OSLAMK_MESH_T_MISS 3          /*         triangle corners whose edge has no vertex (zeroed by the caller; stays 0) */
+/* first pass and scans: vcounts and tcounts [n_groups] leave as the exclusive offsets of the workgroups' vertices and
+ * triangles; totals [4] as above */
+int oslamk_mesh_count(const oslamk_volume *vol, uint32_t min_weight, uint32_t n_groups, uint32_t *vcounts, uint32_t *tcounts,
+                      uint32_t *totals, void *stream);
+/* second pass: xyz [n_verts][3], nrm [n_verts][3] or NULL (the normals are then not computed), edge_id [n_verts] =
+ * 3 * voxel + axis of each vertex, ascending */
+int oslamk_mesh_vertices(const oslamk_volume *vol, uint32_t min_weight, uint32_t n_groups, const uint32_t *voffsets,
+                         uint32_t n_verts, float *xyz, float *nrm, uint32_t *edge_id, void *stream);
+/* third pass: tri [n_tris][3] vertex indices, found by binary search in edge_id; totals[OSLAMK_MESH_T_MISS] += misses */
+int oslamk_mesh_triangles(const oslamk_volume *vol, uint32_t min_weight, uint32_t n_groups, const uint32_t *toffsets,
+                          uint32_t n_tris, const uint32_t *edge_id, uint32_t n_verts, uint32_t *tri, uint32_t *totals,
+                          void *stream);
 
 #ifdef __cplusplus
 }

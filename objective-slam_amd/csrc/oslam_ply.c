@@ -4,9 +4,11 @@
  * with pcl::PLYWriter (pcl/voxel_grid/voxel_grid.cpp:27-29) or matlab/write_ply_cloud.m.
  * Host-only.  Reads `format ascii 1.0` and `format binary_little_endian 1.0`; the vertex
  * element must come first; it needs x, y, z and normals named nx ny nz or
- * normal_x normal_y normal_z (any scalar type, any other properties are skipped).
+ * normal_x normal_y normal_z (any scalar type, any other properties are skipped).  Elements after the
+ * vertices (the faces that oslam_ply_write_mesh writes) are skipped.
  */
 #include <ctype.h>
+#include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -121,17 +123,20 @@ done:
     return rc;
 }
 
-int oslam_ply_write(const char *path, const float *xyz, const float *nrm, size_t n, int binary)
+/* the header up to the vertex properties, then (n_faces != (size_t)-1) the face element, then end_header */
+static void ply_header(FILE *f, int binary, size_t n, size_t n_faces)
 {
-    FILE *f;
-    size_t v;
-    if (!path || !xyz || !nrm) return OSLAM_E_INVALID;
-    f = fopen(path, "wb");
-    if (!f) return OSLAM_E_INVALID;
     fprintf(f, "ply\nformat %s 1.0\ncomment written by liboslam_hip\nelement vertex %zu\n"
                "property float x\nproperty float y\nproperty float z\n"
-               "property float normal_x\nproperty float normal_y\nproperty float normal_z\nend_header\n",
+               "property float normal_x\nproperty float normal_y\nproperty float normal_z\n",
             binary ? "binary_little_endian" : "ascii", n);
+    if (n_faces != (size_t)-1) fprintf(f, "element face %zu\nproperty list uchar int vertex_indices\n", n_faces);
+    fprintf(f, "end_header\n");
+}
+
+static void ply_vertices(FILE *f, int binary, const float *xyz, const float *nrm, size_t n)
+{
+    size_t v;
     for (v = 0; v < n; v++) {
         if (binary) {
             fwrite(xyz + 3 * v, sizeof(float), 3, f);
@@ -139,6 +144,42 @@ int oslam_ply_write(const char *path, const float *xyz, const float *nrm, size_t
         } else {
             fprintf(f, "%.9g %.9g %.9g %.9g %.9g %.9g\n", xyz[3 * v], xyz[3 * v + 1], xyz[3 * v + 2], nrm[3 * v],
                     nrm[3 * v + 1], nrm[3 * v + 2]);
+        }
+    }
+}
+
+int oslam_ply_write(const char *path, const float *xyz, const float *nrm, size_t n, int binary)
+{
+    FILE *f;
+    if (!path || !xyz || !nrm) return OSLAM_E_INVALID;
+    f = fopen(path, "wb");
+    if (!f) return OSLAM_E_INVALID;
+    ply_header(f, binary, n, (size_t)-1);
+    ply_vertices(f, binary, xyz, nrm, n);
+    return fclose(f) ? OSLAM_E_INVALID : OSLAM_OK;
+}
+
+int oslam_ply_write_mesh(const char *path, const float *xyz, const float *nrm, size_t nv, const uint32_t *tri, size_t nt, int binary)
+{
+    FILE *f;
+    size_t t;
+    int k;
+    if (!path || (nv && (!xyz || !nrm)) || (nt && !tri)) return OSLAM_E_INVALID;
+    for (t = 0; t < 3 * nt; t++)
+        if (tri[t] >= nv || tri[t] > 0x7fffffffu) return OSLAM_E_INVALID;      /* the list's entries are int */
+    f = fopen(path, "wb");
+    if (!f) return OSLAM_E_INVALID;
+    ply_header(f, binary, nv, nt);
+    ply_vertices(f, binary, xyz, nrm, nv);
+    for (t = 0; t < nt; t++) {
+        if (binary) {
+            const unsigned char three = 3;
+            int32_t idx[3];
+            for (k = 0; k < 3; k++) idx[k] = (int32_t)tri[3 * t + k];
+            fwrite(&three, 1, 1, f);
+            fwrite(idx, sizeof(int32_t), 3, f);
+        } else {
+            fprintf(f, "3 %u %u %u\n", tri[3 * t], tri[3 * t + 1], tri[3 * t + 2]);
         }
     }
     return fclose(f) ? OSLAM_E_INVALID : OSLAM_OK;

@@ -5,12 +5,13 @@
  * ray cast and oslam_view_egomotion, oslam_volume_track_pyramid over the ray cast, a pyramid of it and
  * oslam_pyramid_egomotion (one body, track_from_raycast); oslam_view_to_cloud runs the depth front end's compaction
  * over a view's maps.  oslam_volume_surface (kernels: oslam_surface.hip) counts, waits for the number of points,
- * allocates exactly that and emits.
+ * allocates exactly that and emits; oslam_volume_mesh (kernels: oslam_mesh.hip) does the same for vertices and triangles.
  */
 #include <math.h>
 #include <pthread.h>
 
 #include "oslam_internal.h"
+#include "oslam_mc_table.h"
 
 struct oslam_volume {
     int dev;                          /* stays the first field, as in oslam_view (the argument tests write it) */
@@ -508,6 +509,92 @@ int oslam_volume_surface_cloud(oslam_volume *vol, unsigned min_weight, int *dev,
     rc = surface_passes(vol, min_weight, (size_t)-1, d_pts6, tot, &launches);
     pthread_mutex_unlock(&g_vol_mu);
     if (rc == OSLAM_OK) *np = tot[1];
+    return rc;
+}
+
+/* ---- the fused surface as a triangle mesh (include/oslam.h at oslam_volume_mesh; kernels: oslam_mesh.hip) ---- */
+int oslam_mesh_params_default(oslam_mesh_params *p)
+{
+    if (!p) return fail(OSLAM_E_INVALID, "params is NULL");
+    memset(p, 0, sizeof *p);
+    p->min_weight = 1;
+    return OSLAM_OK;
+}
+
+int oslam_mc_table_row(unsigned mc_case, uint8_t *edges_out, unsigned *n_tri_out)
+{
+    static const uint8_t ntri[256] = {OSLAM_MC_NTRI_FLAT};
+    static const uint8_t edges[256 * OSLAM_MC_ROW] = {OSLAM_MC_EDGES_FLAT};
+    if (mc_case > 255u || !edges_out || !n_tri_out) return fail(OSLAM_E_INVALID, "case must lie in 0..255 and the outputs must be given");
+    *n_tri_out = ntri[mc_case];
+    memcpy(edges_out, edges + (size_t)mc_case * OSLAM_MC_ROW, 3 * (size_t)ntri[mc_case]);
+    return OSLAM_OK;
+}
+
+int oslam_volume_mesh(oslam_volume *vol, const oslam_mesh_params *mp, float *xyz_out, float *nrm_out, size_t v_cap,
+                      uint32_t *tri_out, size_t t_cap, size_t *nv_out, size_t *nt_out, oslam_mesh_result *res)
+{
+    int rc = OSLAM_OK;
+    const double t0 = now_ms();
+    oslam_mesh_params p;
+    uint32_t *d_cnt = NULL, *d_eid = NULL, *d_tri = NULL;       /* totals in the first 256 bytes, then two counters per workgroup */
+    float *d_xyz = NULL, *d_nrm = NULL;
+    uint32_t tot[4] = {0, 0, 0, 0}, launches = 0, n_groups, miss = 0;
+    void *stream = oslam_stream();
+    if (!vol || !nv_out || !nt_out) return fail(OSLAM_E_INVALID, "NULL argument");
+    if (!xyz_out != !tri_out) return fail(OSLAM_E_INVALID, "xyz_out and tri_out must both be given or both be NULL");
+    if (!xyz_out && nrm_out) return fail(OSLAM_E_INVALID, "nrm_out needs xyz_out");
+    if (!xyz_out && (v_cap != 0 || t_cap != 0)) return fail(OSLAM_E_INVALID, "v_cap and t_cap must be 0 without outputs");
+    if (mp) p = *mp; else oslam_mesh_params_default(&p);
+    if (p.min_weight < 1 || p.min_weight > 65535) return fail(OSLAM_E_INVALID, "min_weight must lie in 1..65535");
+    *nv_out = *nt_out = 0;
+    if (res) memset(res, 0, sizeof *res);
+    if (hipSetDevice(vol->dev) != hipSuccess) return fail(OSLAM_E_DEVICE, "hipSetDevice failed");
+    pthread_mutex_lock(&g_vol_mu);
+    n_groups = oslamk_surface_groups(&vol->k);
+    KCHK(oslam_dev_alloc((void **)&d_cnt, 256 + sizeof(uint32_t) * 2 * (size_t)n_groups));
+    HIPCHK(hipMemsetAsync(d_cnt, 0, 256, (hipStream_t)stream));
+    KCHK(oslamk_mesh_count(&vol->k, p.min_weight, n_groups, d_cnt + 64, d_cnt + 64 + n_groups, d_cnt, stream));
+    HIPCHK(hipMemcpyAsync(tot, d_cnt, sizeof tot, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    launches = 3;
+    *nv_out = tot[OSLAMK_MESH_T_VERTS];
+    *nt_out = tot[OSLAMK_MESH_T_TRIS];
+    if (xyz_out && (*nv_out > v_cap || *nt_out > t_cap)) { rc = fail(OSLAM_E_LIMIT, "output capacity too small"); goto done; }
+    if (xyz_out && *nv_out > 0) {
+        const uint32_t nv = tot[OSLAMK_MESH_T_VERTS], nt = tot[OSLAMK_MESH_T_TRIS];
+        KCHK(oslam_dev_alloc((void **)&d_xyz, sizeof(float) * 3 * (size_t)nv));
+        if (nrm_out) KCHK(oslam_dev_alloc((void **)&d_nrm, sizeof(float) * 3 * (size_t)nv));
+        KCHK(oslam_dev_alloc((void **)&d_eid, sizeof(uint32_t) * (size_t)nv));
+        KCHK(oslamk_mesh_vertices(&vol->k, p.min_weight, n_groups, d_cnt + 64, nv, d_xyz, d_nrm, d_eid, stream));
+        launches++;
+        if (nt > 0) {
+            KCHK(oslam_dev_alloc((void **)&d_tri, sizeof(uint32_t) * 3 * (size_t)nt));
+            KCHK(oslamk_mesh_triangles(&vol->k, p.min_weight, n_groups, d_cnt + 64 + n_groups, nt, d_eid, nv, d_tri, d_cnt, stream));
+            launches++;
+        }
+        HIPCHK(hipMemcpyAsync(&miss, d_cnt + OSLAMK_MESH_T_MISS, sizeof miss, hipMemcpyDeviceToHost, (hipStream_t)stream));
+        HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+        if (miss) { rc = fail(OSLAM_E_DEVICE, "a triangle corner found no vertex on its edge: the mesh was not written"); goto done; }
+        HIPCHK(hipMemcpy(xyz_out, d_xyz, sizeof(float) * 3 * (size_t)nv, hipMemcpyDeviceToHost));
+        if (nrm_out) HIPCHK(hipMemcpy(nrm_out, d_nrm, sizeof(float) * 3 * (size_t)nv, hipMemcpyDeviceToHost));
+        if (nt > 0) HIPCHK(hipMemcpy(tri_out, d_tri, sizeof(uint32_t) * 3 * (size_t)nt, hipMemcpyDeviceToHost));
+    }
+done:
+    if (rc != OSLAM_OK && rc != OSLAM_E_LIMIT) (void)hipStreamSynchronize((hipStream_t)stream);
+    pthread_mutex_unlock(&g_vol_mu);
+    if (d_tri) oslam_dev_free(d_tri);
+    if (d_eid) oslam_dev_free(d_eid);
+    if (d_nrm) oslam_dev_free(d_nrm);
+    if (d_xyz) oslam_dev_free(d_xyz);
+    if (d_cnt) oslam_dev_free(d_cnt);
+    if ((rc == OSLAM_OK || rc == OSLAM_E_LIMIT) && res) {
+        res->vertices = tot[OSLAMK_MESH_T_VERTS];
+        res->triangles = tot[OSLAMK_MESH_T_TRIS];
+        res->cubes = tot[OSLAMK_MESH_T_CUBES];
+        res->launches = launches;
+        res->ms_total = (float)(now_ms() - t0);
+    }
     return rc;
 }
 

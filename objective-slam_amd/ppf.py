@@ -217,6 +217,19 @@ class SurfaceResult(C.Structure):
                 "ms_total": float(self.ms_total)}
 
 
+class MeshParams(C.Structure):
+    _fields_ = [("min_weight", C.c_uint), ("reserved", C.c_int * 7)]
+
+
+class MeshResult(C.Structure):
+    _fields_ = [("vertices", C.c_uint32), ("triangles", C.c_uint32), ("cubes", C.c_uint32), ("launches", C.c_uint32),
+                ("ms_total", C.c_float)]
+
+    def asdict(self):
+        return {"vertices": int(self.vertices), "triangles": int(self.triangles), "cubes": int(self.cubes),
+                "launches": int(self.launches), "ms_total": float(self.ms_total)}
+
+
 ARBITRATE_MAX_HYPOTHESES = 1024
 CELL_DTYPE = np.dtype([("code", "<u8"), ("count", "<u4"), ("pad", "<u4")])
 
@@ -331,6 +344,11 @@ _SIGNATURES = {
     "oslam_scene_from_volume": (_i, [_vp, C.POINTER(SurfaceParams), _f, _f, _u, C.POINTER(Params), C.POINTER(_vp),
                                      C.POINTER(_sz)]),
     "oslam_volume_set_voxels": (_i, [_vp, _vp, _vp]),
+    "oslam_mesh_params_default": (_i, [C.POINTER(MeshParams)]),
+    "oslam_volume_mesh": (_i, [_vp, C.POINTER(MeshParams), _vp, _vp, _sz, _vp, _sz, C.POINTER(_sz), C.POINTER(_sz),
+                               C.POINTER(MeshResult)]),
+    "oslam_ply_write_mesh": (_i, [C.c_char_p, _vp, _vp, _sz, _vp, _sz, _i]),
+    "oslam_mc_table_row": (_i, [_u, _vp, C.POINTER(_u)]),
     "oslam_scene_keys": (_i, [_vp, _sz, _vp]),
     "oslam_model_keys": (_i, [_vp, _sz, _vp]),
     "oslam_model_bucket": (_i, [_vp, C.c_uint32, _vp, _sz, C.POINTER(_sz)]),
@@ -1280,6 +1298,26 @@ def ply_write(path, points, normals, binary=True):
         raise OslamError(rc, "cannot write PLY file %s" % path)
 
 
+def ply_write_mesh(path, points, normals, triangles, binary=True):
+    """A triangle mesh as a PLY file (oslam_ply_write_mesh): points [nv,3], normals [nv,3] or None (zeros are written),
+    triangles [nt,3] vertex indices."""
+    p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    q = np.zeros_like(p) if normals is None else np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    t = np.ascontiguousarray(triangles, np.uint32).reshape(-1, 3)
+    if q.shape != p.shape:
+        raise ValueError("points and normals must have the same shape")
+    rc = lib().oslam_ply_write_mesh(os.fsencode(path), _p(p), _p(q), len(p), _p(t), len(t), int(binary))
+    if rc != OSLAM_OK:
+        raise OslamError(rc, "cannot write PLY file %s" % path)
+
+
+def mc_table_row(case):
+    """Row `case` of the library's marching-cubes table (oslam_mc_table_row): a list of (e0, e1, e2) cube-edge numbers."""
+    edges, n = np.zeros(15, np.uint8), C.c_uint(0)
+    _check(lib().oslam_mc_table_row(int(case), _p(edges), C.byref(n)))
+    return [tuple(int(e) for e in edges[3 * t:3 * t + 3]) for t in range(n.value)]
+
+
 def voxel_grid(points, normals=None, leaf=None, dev=0):
     """voxelGridDownsample (alignment.cpp:79-87): (points, normals) of the occupied voxels."""
     xyz, nrm, n, stride, keep = _cloud_args(points, normals)
@@ -1446,6 +1484,17 @@ def default_surface_params(**kw):
     return p
 
 
+def default_mesh_params(**kw):
+    """oslam_mesh_params_default, then the fields given as keywords."""
+    p = MeshParams()
+    _check(lib().oslam_mesh_params_default(C.byref(p)))
+    for k, v in kw.items():
+        if not hasattr(p, k) or k == "reserved":
+            raise TypeError("unknown mesh parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
 class Volume:
     """A TSDF volume on the device (oslam_volume): integrate(view, T_vol_cam) fuses a depth view, raycast(...) returns
     the fused surface as a View, track(view, T_prev) follows the camera against it.  T_vol_cam: the camera's pose in the
@@ -1534,6 +1583,20 @@ class Volume:
         if n.value:
             _check(lib().oslam_volume_surface(self._h, C.byref(sp), _p(po), _p(no), n.value, C.byref(n), C.byref(res)))
         return po, no, res.asdict()
+
+    def mesh(self, min_weight=1, normals=True):
+        """The fused surface as a triangle mesh by marching cubes, in the volume frame (oslam_volume_mesh): -> (vertices
+        [nv,3], normals [nv,3] with (0, 0, 0) where a vertex has none, or None with normals=False, triangles uint32
+        [nt,3], result dict).  The vertices are surface()'s crossings, in its order."""
+        mp = default_mesh_params(min_weight=min_weight)
+        nv, nt, res = C.c_size_t(0), C.c_size_t(0), MeshResult()
+        _check(lib().oslam_volume_mesh(self._h, C.byref(mp), None, None, 0, None, 0, C.byref(nv), C.byref(nt), C.byref(res)))
+        xyz, tri = np.zeros((nv.value, 3), np.float32), np.zeros((nt.value, 3), np.uint32)
+        nrm = np.zeros((nv.value, 3), np.float32) if normals else None
+        if nv.value:
+            _check(lib().oslam_volume_mesh(self._h, C.byref(mp), _p(xyz), _p(nrm) if normals else None, nv.value, _p(tri),
+                                           nt.value, C.byref(nv), C.byref(nt), C.byref(res)))
+        return xyz, nrm, tri, res.asdict()
 
     def reset(self):
         _check(lib().oslam_volume_reset(self._h))

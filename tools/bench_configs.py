@@ -26,6 +26,8 @@ configuration; these are not bench lines).  Needs a HIP device.
                                          bytes per second the integration rule loads and stores
   python tools/bench_configs.py surface  the fusion configuration's 256^3 volume after its stream: Volume.surface and
                                          Scene.from_volume per call next to one integrate (all three stream the volume)
+  python tools/bench_configs.py mesh     the same volume: Volume.mesh with and without normals and, in the same run,
+                                         Volume.surface and one integrate; median of 20 calls each
   python tools/bench_configs.py pyramid  the camera configuration's 640x480 stream: Pyramid(view), egomotion_pyramid and,
                                          in the same run, egomotion on the same pair; median of 20 calls each
 One JSON line each."""
@@ -786,6 +788,48 @@ def surface(calls=20):
     return out
 
 
+def mesh(calls=20):
+    """Whole-volume mesh extraction (oslam_volume_mesh) on the fusion configuration's 256^3 volume after its out-and-back
+    stream: the median of `calls` calls of Volume.mesh with and without normals and, in the same run, of Volume.surface
+    and of one integrate (the yardsticks).  Each Volume call is the two library calls it makes (count, then fill); the
+    four alternate, so that drift hits them alike."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import camera_ref as E
+    world = E.make_world(synth, 0)
+    sweep = E.trajectory(synth, 0, frames=10)
+    cam = E.CAM
+    rendered = [ppf.View(E.render(synth, world, T), cam["fx"], cam["fy"], cam["cx"], cam["cy"], z_min=cam["z_min"],
+                         z_max=cam["z_max"], max_jump=E.MAX_JUMP) for T in sweep]
+    spec = dict(nx=256, ny=256, nz=256, voxel=0.036, origin=[-2.9, -4.3, 0.3], mu=0.288)
+    vol = ppf.Volume(**spec)
+    steps = [vol.step(rendered[k]) for k in list(range(10)) + list(range(8, -1, -1))]
+    vol.integrate(rendered[0], vol.T)
+    vol.mesh()
+    vol.mesh(normals=False)
+    vol.surface()
+    with_n, without_n, surf, integ = [], [], [], []
+    for _ in range(calls):
+        t = time.perf_counter(); xyz, nrm, tri, res = vol.mesh(); with_n.append(1e3 * (time.perf_counter() - t))
+        lib_n = res["ms_total"]
+        t = time.perf_counter(); _, _, _, res0 = vol.mesh(normals=False); without_n.append(1e3 * (time.perf_counter() - t))
+        t = time.perf_counter(); _, _, sres = vol.surface(); surf.append(1e3 * (time.perf_counter() - t))
+        integ.append(vol.integrate(rendered[0], vol.T)["ms_total"])
+    referenced = int(len(np.unique(tri)))
+    out = {"config": "mesh (oslam_volume_mesh): the fusion configuration's 256^3 volume after its 19-frame stream",
+           "volume": spec, "calls": calls, "step_ok": [None if r is None else r["ok"] for _, r in steps],
+           "vertices": res["vertices"], "triangles": res["triangles"], "cubes": res["cubes"], "launches": res["launches"],
+           "vertices_referenced": referenced, "vertices_with_normal": int((nrm != 0).any(axis=1).sum()),
+           "mesh_ms_median": float(np.median(with_n)), "mesh_second_call_ms_library": lib_n,
+           "mesh_without_normals_ms_median": float(np.median(without_n)), "mesh_without_normals_second_call_ms_library": res0["ms_total"],
+           "surface_ms_median": float(np.median(surf)), "surface_points": sres["points"],
+           "integrate_ms_median": float(np.median(integ)), "volume_bytes": 4 * 256 ** 3,
+           "mesh_over_surface": float(np.median(with_n) / np.median(surf))}
+    for v in rendered:
+        v.close()
+    vol.close()
+    return out
+
+
 def pyramid(calls=20):
     """Image pyramids (oslam_pyramid_create, oslam_pyramid_egomotion) on frames 0 and 1 of the camera configuration's
     640x480 stream: the median of `calls` calls of Pyramid(view), of egomotion_pyramid and, in the same run, of egomotion
@@ -829,4 +873,4 @@ if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "cfg3"
     print(json.dumps({"cfg2": cfg2, "cfg3": cfg3, "cfg3db": cfg3db, "cfg4": cfg4, "cfg5": cfg5, "planes": planes, "db50": db50,
                       "refine": refine, "verify": verify, "instances": instances, "arbitrate": arbitrate, "track": track, "camera": camera,
-                      "fusion": fusion, "surface": surface, "pyramid": pyramid}[which]()), flush=True)
+                      "fusion": fusion, "surface": surface, "mesh": mesh, "pyramid": pyramid}[which]()), flush=True)
