@@ -87,6 +87,12 @@ struct oslam_view {
     float *d_maps;                    /* vertex and normal map of the tracking stage (oslam_track.c), NULL until the first */
 };
 
+struct oslam_volume {
+    int dev;                          /* stays the first field, as in oslam_view (the argument tests write it) */
+    oslamk_volume k;
+    oslam_volume_params p;
+};
+
 struct oslam_pyramid {
     int dev;                          /* stays the first field, as in oslam_view */
     unsigned n_levels;
@@ -132,6 +138,24 @@ static inline double now_ms(void)
 
 /* offsets of the parts of one device block */
 static inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+/* a counter block from the kept scratch blocks: 256 zeroed bytes of totals, then n_words uint32 that the kernels write
+ * before they read; a hipError_t */
+static inline int oslam_counters_open(uint32_t **d_cnt, size_t n_words, void *stream)
+{
+    const int k = oslam_dev_alloc((void **)d_cnt, 256 + sizeof(uint32_t) * n_words);
+    return k != 0 ? k : (int)hipMemsetAsync(*d_cnt, 0, 256, (hipStream_t)stream);
+}
+
+/* interleaved [n][6] points (x y z nx ny nz) into xyz [n][3] and normals [n][3] */
+static inline void split_points(const float *pts6, size_t n, float *xyz_out, float *nrm_out)
+{
+    size_t i;
+    for (i = 0; i < n; i++) {
+        memcpy(xyz_out + 3 * i, pts6 + 6 * i, 3 * sizeof(float));
+        memcpy(nrm_out + 3 * i, pts6 + 6 * i + 3, 3 * sizeof(float));
+    }
+}
 
 /* the launch stream of this thread's calls (oslam_set_stream) */
 void *oslam_stream(void);
@@ -254,7 +278,10 @@ int oslam_ego_run(const oslam_ego_pair *pair, const float T0[16], const oslam_eg
 /* ---- image pyramid (oslam_pyramid.c) ---- */
 /* pp NULL = defaults; checks them as oslam_pyramid_create does, *out = the parameters in force */
 int oslam_pyramid_check_params(const oslam_pyramid_params *pp, oslam_pyramid_params *out);
-/* ---- surface extraction (oslam_volume.c) ---- */
+/* ---- the volume lock (oslam_volume.c, with its place in the lock order) ---- */
+void oslam_volume_lock(void);
+void oslam_volume_unlock(void);
+/* ---- surface and mesh extraction (oslam_surface.c) ---- */
 /* sp NULL = defaults; checks them as oslam_volume_surface does, *out = the parameters in force */
 int oslam_surface_check_params(const oslam_surface_params *sp, oslam_surface_params *out);
 /* the volume's surface in HBM as [*np][6] (NULL without points) on device *dev; the caller frees the block

@@ -557,8 +557,8 @@ int oslamk_surface_count(const oslamk_volume *vol, uint32_t min_weight, uint32_t
 /* second pass: out6 = device [n_points][6] (x y z nx ny nz), offsets and n_points as oslamk_surface_count left them */
 int oslamk_surface_emit(const oslamk_volume *vol, uint32_t min_weight, uint32_t n_groups, const uint32_t *offsets,
                         uint32_t n_points, float *out6, void *stream);
-/* the scan alone: counts [n] (n <= 2^17) becomes its exclusive prefix sums in place, totals[1] = the sum */
-int oslamk_surface_scan(uint32_t *counts, uint32_t n, uint32_t *totals, void *stream);
+/* the scan alone: counts [n] (n <= 2^17) becomes its exclusive prefix sums in place, *total_out = the sum */
+int oslamk_surface_scan(uint32_t *counts, uint32_t n, uint32_t *total_out, void *stream);
 
 /* ---- mesh extraction (oslam_mesh.hip; semantics in include/oslam.h at oslam_volume_mesh); workgroups and runs are the
  * surface extraction's, n_groups = oslamk_surface_groups(vol) ---- */

@@ -1,21 +1,21 @@
 /*
  * oslam_mesh.hip -- the fused surface of a TSDF volume as a triangle mesh by marching cubes (semantics: include/oslam.h at
- * oslam_volume_mesh; host side: oslam_volume.c; table: oslam_mc_table.h, written by tools/gen_mc_table.py).  As in
+ * oslam_volume_mesh; host side: oslam_surface.c; table: oslam_mc_table.h, written by tools/gen_mc_table.py).  As in
  * oslam_surface.hip nothing proportional to the number of voxels is stored: the volume is read three times.  Workgroups
  * and runs are the surface extraction's (256 threads own OSLAMK_SURF_RUN consecutive voxels as chunks of 256; a wave
  * none of whose words is seen does nothing more: an unseen voxel owns no crossing and is the corner of no full cube).
  *
  *   k_mesh_count      a seen voxel counts the crossings on its three owned edges and, where it is the corner of a full
- *                     cube, the triangles of the cube's row.  Both sums go to the workgroup's two counters (waves summed
- *                     in LDS, no atomic); the full cubes with a case other than 0 and 255 are added to the totals as one
- *                     integer atomic per wave.
+ *                     cube, the triangles of the cube's row.  Both sums go to the workgroup's two counters (waves summed in
+ *                     LDS, no atomic); the full cubes with a case other than 0 and 255 are added to the totals as one integer
+ *                     atomic per wave.
  *   k_surface_scan    (oslam_surface.hip, run once per counter array) turns them into exclusive offsets and totals.
- *   k_mesh_vertices   recomputes the crossings.  The rank of a vertex is k_surface_emit's: three ballots and popcounts
- *                     per chunk, the lower waves and earlier chunks from LDS, the workgroup's offset.  It is known before
- *                     the point is, so each axis computes its point (and, with nrm, its normal) and stores it at once:
- *                     one axis at a time, no record array.  edge_id[rank] = 3 * voxel + axis, ascending by construction.
- *   k_mesh_triangles  recomputes the case.  The rank of a cube's first triangle is a shuffle scan over the lanes' row
- *                     lengths plus the lower waves, earlier chunks and the workgroup's offset.  For each triangle corner
+ *   k_mesh_vertices   recomputes the crossings.  The rank of a vertex is k_surface_emit's (surf_chunk_rank).  It is known
+ *                     before the point is, so each axis computes its point (and, with nrm, its normal) and stores it at
+ *                     once: one axis at a time, no record array.  edge_id[rank] = 3 * voxel + axis, ascending by
+ *                     construction.
+ *   k_mesh_triangles  recomputes the case.  The rank of a cube's first triangle is a scan of the row lengths over the
+ *                     chunk (block_excl_scan) plus the earlier chunks and the workgroup's offset.  For each triangle corner
  *                     the cube edge becomes the global id 3 * (start voxel) + axis and its vertex index is found by
  *                     binary search in edge_id (17 steps for 100 000 vertices, in an array that stays in L2).  The hit
  *                     must match exactly: a miss skips the store and is counted, and the host fails the call.
@@ -69,14 +69,14 @@ __device__ __forceinline__ uint32_t mesh_edge_id(uint32_t idx, uint32_t e, uint3
 __global__ __launch_bounds__(SURF_T) void k_mesh_count(const oslamk_volume vol, uint32_t min_w, uint32_t n_vox, uint32_t *vcounts,
                                                        uint32_t *tcounts, uint32_t *totals)
 {
-    __shared__ uint32_t s_v[SURF_WAVES], s_t[SURF_WAVES];
+    __shared__ uint32_t s_v[SURF_WAVES], s_t[SURF_WAVES];   /* two sums behind one barrier: wave_sum, not two block_sum */
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     uint32_t w0[SURF_ITEMS], verts = 0, tris = 0, cubes = 0;
     const bool any = surf_load(vol, n_vox, min_w, w0);
     if (__ballot(any)) {
         for (int it = 0; it < SURF_ITEMS; it++) {
             if (!surf_seen(w0[it], min_w)) continue;
-            const uint32_t idx = blockIdx.x * (uint32_t)OSLAMK_SURF_RUN + (uint32_t)it * SURF_T + threadIdx.x;
+            const uint32_t idx = surf_idx(it);
             int ijk[3];
             uint32_t nb[3], c;
             verts += (uint32_t)__popc(surf_crossings(vol, idx, w0[it], min_w, ijk, nb));
@@ -85,12 +85,9 @@ __global__ __launch_bounds__(SURF_T) void k_mesh_count(const oslamk_volume vol, 
                 tris += d_mc_ntri[c];
             }
         }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            verts += __shfl_down(verts, off, 64);
-            tris += __shfl_down(tris, off, 64);
-            cubes += __shfl_down(cubes, off, 64);
-        }
+        verts = wave_sum(verts);
+        tris = wave_sum(tris);
+        cubes = wave_sum(cubes);
     }
     if (lane == 0) {
         s_v[wave] = verts;
@@ -115,29 +112,17 @@ __global__ __launch_bounds__(SURF_T) void k_mesh_vertices(const oslamk_volume vo
                                                           uint32_t *edge_id)
 {
     __shared__ uint32_t s_cnt[SURF_ITEMS][SURF_WAVES];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint64_t below = (1ull << lane) - 1ull;
     uint32_t w0[SURF_ITEMS];
     const bool any = surf_load(vol, n_vox, min_w, w0);
     if (!__syncthreads_or(any)) return;
     const bool wave_any = __ballot(any) != 0ull;
     uint32_t run = offsets[blockIdx.x];
     for (int it = 0; it < SURF_ITEMS; it++) {
-        const uint32_t idx = blockIdx.x * (uint32_t)OSLAMK_SURF_RUN + (uint32_t)it * SURF_T + threadIdx.x;
+        const uint32_t idx = surf_idx(it);
         int ijk[3] = {0, 0, 0};
-        uint32_t nb[3] = {0u, 0u, 0u}, mask = 0;
+        uint32_t nb[3] = {0u, 0u, 0u}, mask = 0, all;
         if (wave_any && surf_seen(w0[it], min_w)) mask = surf_crossings(vol, idx, w0[it], min_w, ijk, nb);
-        const uint64_t bx = __ballot(mask & 1u), by = __ballot(mask & 2u), bz = __ballot(mask & 4u);
-        if (lane == 0) s_cnt[it][wave] = (uint32_t)(__popcll(bx) + __popcll(by) + __popcll(bz));
-        __syncthreads();
-        uint32_t before = 0, all = 0;
-#pragma unroll
-        for (uint32_t w = 0; w < SURF_WAVES; w++) {
-            const uint32_t c = s_cnt[it][w];
-            if (w < wave) before += c;
-            all += c;
-        }
-        uint32_t rank = run + before + (uint32_t)(__popcll(bx & below) + __popcll(by & below) + __popcll(bz & below));
+        uint32_t rank = run + surf_chunk_rank(mask, s_cnt[it], &all);
         /* one axis at a time, as in k_surface_emit: the six reads of three normals at once cost 200 registers */
 #pragma unroll 1
         for (int a = 0; a < 3; a++) {
@@ -178,7 +163,6 @@ __global__ __launch_bounds__(SURF_T) void k_mesh_triangles(const oslamk_volume v
                                                            uint32_t n_verts, uint32_t *tri, uint32_t *totals)
 {
     __shared__ uint32_t s_cnt[SURF_ITEMS][SURF_WAVES];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint32_t nx = (uint32_t)vol.nx, nxy = (uint32_t)vol.nx * (uint32_t)vol.ny;
     uint32_t w0[SURF_ITEMS], missed = 0;
     const bool any = surf_load(vol, n_vox, min_w, w0);
@@ -186,30 +170,15 @@ __global__ __launch_bounds__(SURF_T) void k_mesh_triangles(const oslamk_volume v
     const bool wave_any = __ballot(any) != 0ull;
     uint32_t run = offsets[blockIdx.x];
     for (int it = 0; it < SURF_ITEMS; it++) {
-        const uint32_t idx = blockIdx.x * (uint32_t)OSLAMK_SURF_RUN + (uint32_t)it * SURF_T + threadIdx.x;
-        uint32_t c = 0, nt = 0;
+        const uint32_t idx = surf_idx(it);
+        uint32_t c = 0, nt = 0, all;
         if (wave_any && surf_seen(w0[it], min_w)) {
             int ijk[3];
             uint32_t nb[3];
             (void)surf_crossings(vol, idx, w0[it], min_w, ijk, nb);
             if (mesh_case(vol, idx, w0[it], min_w, ijk, nb, &c)) nt = d_mc_ntri[c];
         }
-        uint32_t incl = nt;                                     /* inclusive scan of the row lengths over the wave */
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t y = __shfl_up(incl, off, 64);
-            if (lane >= (uint32_t)off) incl += y;
-        }
-        if (lane == 63) s_cnt[it][wave] = incl;
-        __syncthreads();
-        uint32_t before = 0, all = 0;
-#pragma unroll
-        for (uint32_t w = 0; w < SURF_WAVES; w++) {
-            const uint32_t s = s_cnt[it][w];
-            if (w < wave) before += s;
-            all += s;
-        }
-        uint32_t rank = run + before + (incl - nt);
+        uint32_t rank = run + block_excl_scan<SURF_WAVES>(nt, s_cnt[it], &all);    /* over the cubes' row lengths */
         const uint8_t *row = d_mc_edges + c * OSLAM_MC_ROW;     /* c <= 255 */
         for (uint32_t t = 0; t < nt; t++, rank++) {             /* nt <= OSLAM_MC_MAX_TRI */
             uint32_t v[3];
@@ -230,37 +199,27 @@ __global__ __launch_bounds__(SURF_T) void k_mesh_triangles(const oslamk_volume v
     if (missed) atomicAdd(totals + OSLAMK_MESH_T_MISS, missed);
 }
 
-static bool mesh_ok(const oslamk_volume *vol, uint32_t min_w, uint32_t n_groups, uint32_t *n_vox)
-{
-    if (!(vol && vol->words && vol->nx >= 16 && vol->ny >= 16 && vol->nz >= 16 && vol->nx <= 512 && vol->ny <= 512 &&
-          vol->nz <= 512 && vol->voxel > 0.0f && min_w >= 1u && min_w <= 65535u))
-        return false;
-    *n_vox = (uint32_t)vol->nx * (uint32_t)vol->ny * (uint32_t)vol->nz;          /* at most 2^27: 3 * n_vox fits uint32 */
-    return n_groups == oslamk_surface_groups(vol);
-}
-
 extern "C" int oslamk_mesh_count(const oslamk_volume *vol, uint32_t min_weight, uint32_t n_groups, uint32_t *vcounts,
                                  uint32_t *tcounts, uint32_t *totals, void *stream)
 {
     uint32_t n_vox;
     hipError_t e;
     int rc;
-    if (!mesh_ok(vol, min_weight, n_groups, &n_vox) || !vcounts || !tcounts || !totals) return (int)hipErrorInvalidValue;
+    if (!surf_launch_ok(vol, min_weight, n_groups, &n_vox) || !vcounts || !tcounts || !totals) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(k_mesh_count, dim3(n_groups), dim3(SURF_T), 0, (hipStream_t)stream, *vol, min_weight, n_vox, vcounts, tcounts,
                        totals);
     e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
-    /* k_surface_scan leaves its sum in totals[1] of the pointer it is given */
-    rc = oslamk_surface_scan(vcounts, n_groups, totals + OSLAMK_MESH_T_VERTS - 1, stream);
+    rc = oslamk_surface_scan(vcounts, n_groups, totals + OSLAMK_MESH_T_VERTS, stream);
     if (rc != 0) return rc;
-    return oslamk_surface_scan(tcounts, n_groups, totals + OSLAMK_MESH_T_TRIS - 1, stream);
+    return oslamk_surface_scan(tcounts, n_groups, totals + OSLAMK_MESH_T_TRIS, stream);
 }
 
 extern "C" int oslamk_mesh_vertices(const oslamk_volume *vol, uint32_t min_weight, uint32_t n_groups, const uint32_t *voffsets,
                                     uint32_t n_verts, float *xyz, float *nrm, uint32_t *edge_id, void *stream)
 {
     uint32_t n_vox;
-    if (!mesh_ok(vol, min_weight, n_groups, &n_vox) || !voffsets || !xyz || !edge_id || n_verts == 0) return (int)hipErrorInvalidValue;
+    if (!surf_launch_ok(vol, min_weight, n_groups, &n_vox) || !voffsets || !xyz || !edge_id || n_verts == 0) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(k_mesh_vertices, dim3(n_groups), dim3(SURF_T), 0, (hipStream_t)stream, *vol, min_weight, n_vox, voffsets,
                        n_verts, xyz, nrm, edge_id);
     return (int)hipGetLastError();
@@ -271,7 +230,7 @@ extern "C" int oslamk_mesh_triangles(const oslamk_volume *vol, uint32_t min_weig
                                      void *stream)
 {
     uint32_t n_vox;
-    if (!mesh_ok(vol, min_weight, n_groups, &n_vox) || !toffsets || !edge_id || !tri || !totals || n_tris == 0 || n_verts == 0)
+    if (!surf_launch_ok(vol, min_weight, n_groups, &n_vox) || !toffsets || !edge_id || !tri || !totals || n_tris == 0 || n_verts == 0)
         return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(k_mesh_triangles, dim3(n_groups), dim3(SURF_T), 0, (hipStream_t)stream, *vol, min_weight, n_vox, toffsets,
                        n_tris, edge_id, n_verts, tri, totals);

@@ -4,7 +4,8 @@
  *
  *   scene grid     k_grid_count (cell and rank of every scene point, integer atomics), k_scan_local +
  *                  k_scan_top (exclusive scan of the cell counts: 4096 cells per workgroup, then the block
- *                  totals in one workgroup), k_grid_scatter (cell starts, points in cell order)
+ *                  totals in one workgroup; the scan over a workgroup is oslam_block_scan.h's), k_grid_scatter
+ *                  (cell starts, points in cell order)
  *   correspond     k_refine_corr: one thread per model point, every member of the call in one grid (y = member,
  *                  x = block of 256 model points); the transform (oslam_icp_core.h), the 27-cell walk, then the 29
  *                  (step) or 2 (score) partial sums through the fixed wave64 shuffle tree and the fixed LDS order of
@@ -18,6 +19,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "oslam_block_scan.h"
 #include "oslam_icp_core.h"
 #include "oslam_kernels.h"
 #include "oslam_refine_step.h"
@@ -45,28 +47,6 @@ __global__ __launch_bounds__(256) void k_grid_count(const oslamk_grid g, oslamk_
     g.rank[i] = atomicAdd(&g.local[cell], 1u);
 }
 
-/* exclusive scan of one value per thread across the workgroup (blockDim.x a multiple of 64, at most 1024) */
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *sh, uint32_t *total)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    uint32_t x = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t y = __shfl_up(x, off);
-        if (lane >= off) x += y;
-    }
-    if (lane == 63) sh[w] = x;
-    __syncthreads();
-    uint32_t before = 0, tot = 0;
-    for (int k = 0; k < nw; k++) {
-        const uint32_t s = sh[k];
-        if (k < w) before += s;
-        tot += s;
-    }
-    *total = tot;
-    return before + x - v;
-}
-
 /* local[0 .. n_items): exclusive scan inside each block of 4096 items, in place; bsum[block] = the block's total */
 __global__ __launch_bounds__(256) void k_scan_local(uint32_t *local, uint32_t n_items, uint32_t *bsum)
 {
@@ -78,7 +58,7 @@ __global__ __launch_bounds__(256) void k_scan_local(uint32_t *local, uint32_t n_
         v[k] = base + k < n_items ? local[base + k] : 0u;
         s += v[k];
     }
-    uint32_t run = block_excl_scan(s, sh, &tot);
+    uint32_t run = block_excl_scan<4>(s, sh, &tot);
 #pragma unroll
     for (int k = 0; k < 16; k++) {
         if (base + k < n_items) local[base + k] = run;
@@ -96,7 +76,7 @@ __global__ __launch_bounds__(1024) void k_scan_top(uint32_t *bsum, uint32_t nb)
     uint32_t s = 0, tot;
     for (uint32_t k = 0; k < per; k++)
         if (base + k < nb) s += bsum[base + k];
-    uint32_t run = block_excl_scan(s, sh, &tot);
+    uint32_t run = block_excl_scan<16>(s, sh, &tot);
     for (uint32_t k = 0; k < per; k++)
         if (base + k < nb) {
             const uint32_t x = bsum[base + k];

@@ -1,7 +1,8 @@
 /*
  * oslam_surf_edge.h -- what the surface extraction (oslam_surface.hip) and the mesh extraction (oslam_mesh.hip) share:
  * the shape of a workgroup's run, the "seen" rule and the integer sign test, the crossings of a voxel's three owned
- * edges, the point of a crossing and its normal (include/oslam.h at oslam_volume_surface).  Device code only.
+ * edges, the point of a crossing and its normal (include/oslam.h at oslam_volume_surface), the rank of a crossing in
+ * its chunk.  Device code, and the check of their launchers.
  */
 #ifndef OSLAM_SURF_EDGE_H
 #define OSLAM_SURF_EDGE_H
@@ -9,6 +10,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "oslam_block_scan.h"
 #include "oslam_kernels.h"
 #include "oslam_tsdf_read.h"
 #include "ppf_math.h"
@@ -93,18 +95,42 @@ __device__ __forceinline__ bool surf_point(const oslamk_volume &vol, const int i
     return true;
 }
 
+/* the linear voxel index of a thread's chunk it of its workgroup's run */
+__device__ __forceinline__ uint32_t surf_idx(int it) { return blockIdx.x * (uint32_t)OSLAMK_SURF_RUN + (uint32_t)it * SURF_T + threadIdx.x; }
+
 /* a thread's own words of its workgroup's run (0 = unseen past the end of the volume); true when one of them is seen */
 __device__ __forceinline__ bool surf_load(const oslamk_volume &vol, uint32_t n_vox, uint32_t min_w, uint32_t w0[SURF_ITEMS])
 {
-    const uint32_t base = blockIdx.x * (uint32_t)OSLAMK_SURF_RUN + threadIdx.x;
     bool any = false;
 #pragma unroll
     for (int it = 0; it < SURF_ITEMS; it++) {
-        const uint32_t idx = base + (uint32_t)it * SURF_T;
+        const uint32_t idx = surf_idx(it);
         w0[it] = idx < n_vox ? vol.words[idx] : 0u;
         any |= surf_seen(w0[it], min_w);
     }
     return any;
+}
+
+/* The rank inside its chunk of the thread's first crossing, and *all = the chunk's crossings.  has: the thread's
+ * crossings as a mask of axes; the order is voxel, then axis (the mesh's vertex order is the surface's point order by
+ * this one rule).  Three ballots, the lower lanes by popcounts, the lower waves through row (block_before: one barrier) */
+__device__ __forceinline__ uint32_t surf_chunk_rank(uint32_t has, uint32_t *row, uint32_t *all)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t below = (1ull << lane) - 1ull;
+    const uint64_t bx = __ballot(has & 1u), by = __ballot(has & 2u), bz = __ballot(has & 4u);
+    const uint32_t before = block_before<SURF_WAVES>((uint32_t)(__popcll(bx) + __popcll(by) + __popcll(bz)), lane == 0, row, all);
+    return before + (uint32_t)(__popcll(bx & below) + __popcll(by & below) + __popcll(bz & below));
+}
+
+/* the launchers' check of a volume, the "seen" weight and the number of workgroups; *n_vox = the volume's voxels */
+static inline bool surf_launch_ok(const oslamk_volume *vol, uint32_t min_w, uint32_t n_groups, uint32_t *n_vox)
+{
+    if (!(vol && vol->words && vol->nx >= 16 && vol->ny >= 16 && vol->nz >= 16 && vol->nx <= 512 && vol->ny <= 512 &&
+          vol->nz <= 512 && vol->voxel > 0.0f && min_w >= 1u && min_w <= 65535u))
+        return false;
+    *n_vox = (uint32_t)vol->nx * (uint32_t)vol->ny * (uint32_t)vol->nz;          /* at most 2^27: 3 * n_vox fits uint32 */
+    return n_groups == oslamk_surface_groups(vol);
 }
 
 #endif /* OSLAM_SURF_EDGE_H */

@@ -7,7 +7,7 @@
  *                      k-independent part of p' = ((T0*gx + T1*gy) + T2*gz) + T3 is hoisted out of the z loop (the
  *                      pinned grouping allows it without changing a bit).  A voxel the rule skips is neither loaded nor
  *                      stored; a voxel belongs to one thread, so there is no atomic on the volume.  The updated voxels
- *                      are counted per lane, summed over the wave by a __shfl_down reduction and added as integers
+ *                      are counted per lane, summed over the wave (wave_sum, oslam_block_scan.h) and added as integers
  *                      (one integer atomic per wave: a count does not depend on the order).  No LDS, no scratch.
  *   k_tsdf_raycast     one thread per pixel in 32 x 8 tiles (k_view_normals' tiling), so neighbouring rays read
  *                      neighbouring voxels.  The march, the crossing, the two trilinear reads, the six of the gradient
@@ -25,6 +25,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "oslam_block_scan.h"
 #include "oslam_kernels.h"
 #include "oslam_tsdf_read.h"
 #include "ppf_math.h"
@@ -66,9 +67,7 @@ __global__ __launch_bounds__(256) void k_tsdf_integrate(const oslamk_volume vol,
         }
     }
     /* every lane of the wave arrives here: the wave's count, one integer add */
-    uint32_t s = mine;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) s += __shfl_down(s, off, 64);
+    const uint32_t s = wave_sum(mine);
     if ((threadIdx.x & 63) == 0 && s) atomicAdd(count, s);
 }
 
