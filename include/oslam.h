@@ -68,7 +68,13 @@ typedef struct oslam_params {
     int pose_two_sorts;            /* device pose tail: order the kept cells with two stable sorts of (code, count) pairs even
                                     * when their fields fit one packed 64-bit key (the path clouds of 2^28 points with
                                     * 2^32 votes per cell take; identical results, tests force it) */
-    int reserved[2];
+    int vote_order;                /* how the vote kernel's work is handed out (A/B measurements and tests; the results do not
+                                    * depend on it): 0 (default) largest first -- a model's keys are numbered by descending
+                                    * bucket weight and the reference points of a batch go out by descending demand; 1 neither
+                                    * (keys numbered in union-slot order, reference points in index order); 2 the key numbers
+                                    * alone; 3 the reference points alone.  A model takes its numbering when it is built or
+                                    * loaded, a database group from its first member */
+    int reserved[1];
 } oslam_params;
 
 /* Counters the reference logs at debug level (model.cu:122,152,161-168;
@@ -1219,6 +1225,14 @@ int oslam_model_bucket(oslam_model *m, uint32_t key, uint32_t *pairs_out, size_t
  * consecutive words per lane). */
 int oslam_model_bucket_words(oslam_model *m, uint32_t key, int slice, uint32_t *words_out, size_t cap,
                              size_t *count_out);
+/* The numbering of the model's key table (its group's, while it is in a database): key, number and weight of every
+ * key, in ascending key order; at most cap of each are copied, *n_out = the number of keys.  The weight is the number
+ * of entries in the key's buckets, over every slice and every model that shares the numbering. */
+int oslam_model_key_numbers(oslam_model *m, uint32_t *keys_out, uint32_t *numbers_out, uint64_t *weights_out, size_t cap,
+                            size_t *n_out);
+/* The order in which the vote grid takes a batch of n reference points with the demands keep[n] (host only):
+ * order_out[p] = the reference point of dispatch position p. */
+int oslam_vote_ref_order(const uint32_t *keep, size_t n, uint32_t *order_out);
 /* Dense accumulator acc[M][32] of scene reference point ref_index after voting. */
 int oslam_vote_accumulator(oslam_model *m, oslam_scene *s, size_t ref_index, uint32_t *acc_out);
 /* Cells kept by the last oslam_align / oslam_align_finish on this model, in

@@ -71,6 +71,7 @@ int oslam_db_create(oslam_model *const *models, size_t n, oslam_db **out)
     int rc = OSLAM_OK, g, k;
     size_t j;
     oslam_db *db;
+    oslamk_table *parts = NULL;
     uint32_t *d_small = NULL, h_small[2];
     if (!out) return fail(OSLAM_E_INVALID, "out is NULL");
     *out = NULL;
@@ -103,6 +104,8 @@ int oslam_db_create(oslam_model *const *models, size_t n, oslam_db **out)
         db->groups[g].members[db->groups[g].n++] = j;
     }
     HIPCHK(hipMalloc((void **)&d_small, 2 * sizeof(uint32_t)));
+    parts = (oslamk_table *)malloc(sizeof *parts * n);
+    if (!parts) { rc = fail(OSLAM_E_NOMEM, "host allocation failed"); goto done; }
     for (g = 0; g < db->n_groups; g++) {
         db_group *gr = &db->groups[g];
         oslamk_table t;
@@ -127,7 +130,9 @@ int oslam_db_create(oslam_model *const *models, size_t n, oslam_db **out)
         }
         t.reach = gr->reach;
         KCHK(oslamk_reach_build(t, models[gr->members[0]]->d_dist, oslam_stream()));
-        rc = oslam_build_kmap(&t, models[gr->members[0]]->d_dist);
+        /* the key numbers of the group: by the entries of all its members under each key */
+        for (k = 0; k < gr->n; k++) parts[k] = models[gr->members[k]]->table;
+        rc = oslam_build_kmap(&t, models[gr->members[0]]->d_dist, parts, gr->n, models[gr->members[0]]->params.vote_order);
         gr->kmap = t.kmap;
         gr->uids = t.uids;
         if (rc != OSLAM_OK) goto done;
@@ -159,6 +164,7 @@ int oslam_db_create(oslam_model *const *models, size_t n, oslam_db **out)
         HIPCHK(hipStreamSynchronize((hipStream_t)oslam_stream()));
     }
 done:
+    free(parts);
     if (d_small) (void)hipFree(d_small);
     if (rc != OSLAM_OK) { oslam_db_destroy(db); return rc; }
     *out = db;

@@ -57,6 +57,7 @@ int oslam_params_default(oslam_params *p)
     p->pose_gpu_min = 0;              /* 0 = default (4096 records) */
     p->no_bucket_spread = 0;
     p->scratch_gib = 0;               /* 0 = default (4 GiB) */
+    p->vote_order = 0;                /* largest first */
     return OSLAM_OK;
 }
 

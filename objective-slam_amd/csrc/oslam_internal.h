@@ -171,7 +171,7 @@ int oslam_depth_points(const void *depth, int depth_is_u16, int width, int heigh
                        void **d_img, float **d_pts6, uint32_t *np);
 
 /* ---- model key tables (oslam_model.c), rebuilt by the database ---- */
-int oslam_build_kmap(oslamk_table *t, float d_dist);
+int oslam_build_kmap(oslamk_table *t, float d_dist, const oslamk_table *parts, int n_parts, int vote_order);
 int oslam_build_union(oslam_model *m, uint32_t distinct, uint32_t *d_n_keys, uint32_t *d_overflow);
 int oslam_build_uinfo(oslam_model *m);
 
@@ -185,6 +185,7 @@ int oslam_check_pair(const oslam_model *m, const oslam_scene *s);
 int oslam_pool_enter(int dev, scratch_pool **pool);
 void oslam_pool_unlock(scratch_pool *p);
 int oslam_pool_reserve_counts(scratch_pool *p, size_t n_ref);
+void oslam_ref_order(const uint32_t *keep, size_t n, uint32_t *order);
 int oslam_run_votes_group(scratch_pool *pool, oslam_model *const *ms, int nm, oslam_scene *s, const uint32_t *d_ref_idx,
                           const float *d_tsg, int n_ref, uint32_t fixed_gmax, uint32_t *acc_dump,
                           oslamk_counters *cnt, float *ms_out, float *ms_vote_kernel, float *ms_key_kernel,

@@ -100,11 +100,15 @@ typedef struct oslamk_table {
     /* uids[slot]: the dense number (0 .. n_ids-1) of the key in union-table slot `slot`.  From the scene-key
      * kernel on a key is known by this number: the hit lists sort on id_bits = ceil(log2 n_ids) bits (16 for the
      * 38 000 keys of a 5 k-point model: two 8-bit passes instead of three) and the bucket records below take
-     * 8 B x n_ids per slice instead of 8 B x ucap */
+     * 8 B x n_ids per slice instead of 8 B x ucap.  Number 0 is the key with the most entries in its buckets (all
+     * slices, all members of a group), ties by ascending key: a reference point's runs are sorted by this number, so
+     * a vote workgroup hands its heavy buckets out first (oslam_build_kmap).  The allocation holds the weights
+     * behind the numbers: OSLAMK_UWEIGHTS(t)[slot] = entries under the key of union slot `slot` */
     uint32_t *uids;
     uint32_t n_ids, id_bits, uinfo_stride;
     oslamk_uinfo *uinfo;       /* [n_slices][uinfo_stride], indexed by the key's number */
 } oslamk_table;
+#define OSLAMK_UWEIGHTS(t) ((unsigned long long *)((t).uids + (t).ucap))
 #define OSLAMK_KMAP_NONE 0xffffffffu
 #define OSLAMK_KMAP_MAX_BINS 2048
 
@@ -147,8 +151,9 @@ int oslamk_table_scan(oslamk_table t, uint32_t *total_out, void *stream);
 int oslamk_union_build(oslamk_table t, uint32_t *n_keys, uint32_t *overflow, void *stream);
 /* fill t.reach by enumerating every key each distance bin can produce */
 int oslamk_reach_build(oslamk_table t, float d_dist, void *stream);
-/* t.uids[slot] = 0, 1, 2, ... for the slots of t.ukeys that hold a key; *counter (zero on entry) ends as their number */
-int oslamk_union_ids(oslamk_table t, uint32_t *counter, void *stream);
+/* weights[slot of the key in t.ukeys] += slot.len for every key of t's slice tables (weights zeroed by the caller; a
+ * group calls it once per member, each with its own slice tables under the group's t.ukeys) */
+int oslamk_union_weights(oslamk_table t, unsigned long long *weights, void *stream);
 /* fill t.kmap (t.kmap_bins rows) from t.ukeys / t.uids */
 int oslamk_kmap_build(oslamk_table t, float d_dist, void *stream);
 /* model build, pass 2: write entries. tmg = [M][8] rows y,z of T_m_g (host-computed). */
@@ -211,6 +216,10 @@ typedef struct oslamk_vote_args {
     uint32_t *hit_count;       /* [n_launch] */
     uint32_t *run_count;       /* [n_launch] */
     uint32_t *redo;            /* [vote workgroups of the batch] list of those whose 16-bit counters overflowed */
+    /* optional [n_launch]: the reference point (ref_local) that dispatch position p of the vote grid works on, a
+     * permutation of 0 .. n_launch-1; NULL = identity.  The host orders it by descending demand, so that the last
+     * rounds of workgroups are light ones.  A value outside the batch means no work */
+    const uint32_t *ref_order;
 } oslamk_vote_args;
 
 /* fill t.uinfo from the slice tables (after oslamk_table_scan / oslamk_union_build and the fill pass) */

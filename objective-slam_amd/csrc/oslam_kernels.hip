@@ -176,11 +176,26 @@ __global__ __launch_bounds__(256) void k_reach_build(oslamk_table t, float d_dis
     if (threadIdx.x == 0 && s_found) atomicOr(&t.reach[k1 >> 5], 1u << (k1 & 31u));
 }
 
-/* table.uids: the keys of the union table numbered 0 .. n-1 (any order).  One thread per slot. */
-__global__ void k_union_ids(oslamk_table t, uint32_t *counter)
+/* weights[union slot of the key] += the length of the key's bucket, over the slice tables of one model: the entries a
+ * hit on that key streams.  One thread per slot of the slice tables, probing as k_uinfo_build does. */
+__global__ void k_union_weights(oslamk_table t, unsigned long long *weights)
 {
-    const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
-    if (slot < t.ucap && t.ukeys[slot] != 0u) t.uids[slot] = atomicAdd(counter, 1u);
+    const size_t total = (size_t)t.n_slices * t.cap;
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total) return;
+    const oslamk_slot sl = t.slots[idx];
+    if (sl.key == 0) return;
+    const uint32_t mask = t.ucap - 1;
+    uint32_t slot = slot_of(sl.key, t.ushift);
+    for (uint32_t probe = 0; probe <= mask; probe++) {
+        const uint32_t k = t.ukeys[slot];
+        if (k == sl.key) {
+            atomicAdd(&weights[slot], (unsigned long long)sl.len);
+            return;
+        }
+        if (k == 0) return;
+        slot = (slot + 1) & mask;
+    }
 }
 
 /* table.kmap[k1][combo] = the number (table.uids) of the key that distance bin k1 and the angle bins
@@ -937,9 +952,10 @@ int oslamk_reach_build(oslamk_table t, float d_dist, void *stream)
     return (int)hipGetLastError();
 }
 
-int oslamk_union_ids(oslamk_table t, uint32_t *counter, void *stream)
+int oslamk_union_weights(oslamk_table t, unsigned long long *weights, void *stream)
 {
-    hipLaunchKernelGGL(k_union_ids, dim3((t.ucap + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, t, counter);
+    const size_t total = (size_t)t.n_slices * t.cap;
+    hipLaunchKernelGGL(k_union_weights, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, t, weights);
     return (int)hipGetLastError();
 }
 

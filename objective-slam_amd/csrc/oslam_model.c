@@ -40,13 +40,72 @@ void oslam_model_destroy(oslam_model *m)
     free(m);
 }
 
+/* one key of a union table, for the ranking below */
+typedef struct key_rank {
+    uint64_t weight;
+    uint32_t key, slot;
+} key_rank;
+
+/* one stable pass of a radix sort over 16 bits of `weight` (descending) or of `key` (ascending); count: 65536 words */
+static void rank_pass(const key_rank *src, key_rank *dst, size_t n, int by_weight, unsigned shift, uint32_t *count)
+{
+    size_t i;
+    uint32_t run = 0, d;
+    memset(count, 0, sizeof(uint32_t) * 65536);
+    for (i = 0; i < n; i++) {
+        d = by_weight ? 0xffffu - (uint32_t)((src[i].weight >> shift) & 0xffffu) : (src[i].key >> shift) & 0xffffu;
+        count[d]++;
+    }
+    for (d = 0; d < 65536; d++) {
+        const uint32_t c = count[d];
+        count[d] = run;
+        run += c;
+    }
+    for (i = 0; i < n; i++) {
+        d = by_weight ? 0xffffu - (uint32_t)((src[i].weight >> shift) & 0xffffu) : (src[i].key >> shift) & 0xffffu;
+        dst[count[d]++] = src[i];
+    }
+}
+
+/* The numbers 0 .. n-1 of n keys, by descending weight, ties by ascending key: r[i].slot's number is i afterwards.
+ * tmp [n], count [65536]; returns the array that holds the result (r or tmp). */
+static key_rank *rank_keys(key_rank *r, key_rank *tmp, size_t n, uint32_t *count)
+{
+    uint64_t top = 0;
+    unsigned shift;
+    size_t i;
+    key_rank *t;
+    for (i = 0; i < n; i++) if (r[i].weight > top) top = r[i].weight;
+    for (shift = 0; shift < 32; shift += 16) {            /* least significant first: the key, then the weight */
+        rank_pass(r, tmp, n, 0, shift, count);
+        t = r; r = tmp; tmp = t;
+    }
+    for (shift = 0; shift < 64 && (top >> shift); shift += 16) {
+        rank_pass(r, tmp, n, 1, shift, count);
+        t = r; r = tmp; tmp = t;
+    }
+    return r;
+}
+
 /* table.uids, table.kmap and table.reach_words from table.ukeys / table.reach (both complete on oslam_stream()): the keys
  * numbered, and the number of every key a reachable distance bin can produce, so that the scene-key kernel looks a
- * pair up with one load.  17^3 words per reachable distance bin (0.8 MB for a model that spans 41 bins). */
-int oslam_build_kmap(oslamk_table *t, float d_dist)
+ * pair up with one load.  17^3 words per reachable distance bin (0.8 MB for a model that spans 41 bins).
+ *
+ * parts[n_parts]: the slice tables of every model that looks its buckets up under this union table (one model, or the
+ * members of a group).  A key's weight is the number of entries in its buckets over all of them, and the keys are
+ * numbered by descending weight, ties by ascending key: the hit sort orders a reference point's runs by key number, so
+ * every vote workgroup meets its long buckets first and its waves end on short ones.  The numbers depend on the
+ * tables alone: two builds, or a build and a load, give the same.  vote_order 1 and 3 (oslam_params) number the keys
+ * in union-slot order instead. */
+int oslam_build_kmap(oslamk_table *t, float d_dist, const oslamk_table *parts, int n_parts, int vote_order)
 {
-    int rc = OSLAM_OK;
-    uint32_t h_reach[OSLAMK_REACH_BINS / 32], w, top = 0, n_ids = 0, *d_count = NULL;
+    int rc = OSLAM_OK, j;
+    uint32_t h_reach[OSLAMK_REACH_BINS / 32], w, top = 0, n_ids = 0, slot;
+    uint32_t *h_keys = NULL, *h_ids = NULL, *count = NULL;
+    uint64_t *h_w = NULL;
+    key_rank *r = NULL, *r2 = NULL, *res;
+    const size_t ucap = t->ucap;
+    const int ranked = vote_order == 0 || vote_order == 2;
     t->kmap = NULL;
     t->kmap_bins = 0;
     t->reach_words = 0;
@@ -54,12 +113,44 @@ int oslam_build_kmap(oslamk_table *t, float d_dist)
     t->n_ids = t->id_bits = t->uinfo_stride = 0;
     /* the keys of the union table numbered 0 .. n_ids-1: what the hit lists carry and sort on, and what the bucket
      * records are indexed by */
-    HIPCHK(hipMalloc((void **)&t->uids, sizeof(uint32_t) * (size_t)t->ucap));
-    HIPCHK(hipMalloc((void **)&d_count, sizeof(uint32_t)));
-    HIPCHK(hipMemsetAsync(d_count, 0, sizeof(uint32_t), (hipStream_t)oslam_stream()));
-    KCHK(oslamk_union_ids(*t, d_count, oslam_stream()));
-    HIPCHK(hipMemcpyAsync(&n_ids, d_count, sizeof(uint32_t), hipMemcpyDeviceToHost, (hipStream_t)oslam_stream()));
+    HIPCHK(hipMalloc((void **)&t->uids, (sizeof(uint32_t) + sizeof(uint64_t)) * ucap));
+    HIPCHK(hipMemsetAsync(t->uids, 0, (sizeof(uint32_t) + sizeof(uint64_t)) * ucap, (hipStream_t)oslam_stream()));
+    for (j = 0; j < n_parts; j++) {
+        oslamk_table p = parts[j];
+        p.ukeys = t->ukeys;
+        p.ucap = t->ucap;
+        p.ushift = t->ushift;
+        KCHK(oslamk_union_weights(p, OSLAMK_UWEIGHTS(*t), oslam_stream()));
+    }
+    h_keys = (uint32_t *)malloc(sizeof(uint32_t) * ucap);
+    h_ids = (uint32_t *)calloc(ucap, sizeof(uint32_t));
+    h_w = (uint64_t *)malloc(sizeof(uint64_t) * ucap);
+    count = (uint32_t *)malloc(sizeof(uint32_t) * 65536);
+    if (!h_keys || !h_ids || !h_w || !count) { rc = fail(OSLAM_E_NOMEM, "host allocation failed"); goto done; }
     HIPCHK(hipStreamSynchronize((hipStream_t)oslam_stream()));
+    HIPCHK(hipMemcpy(h_keys, t->ukeys, sizeof(uint32_t) * ucap, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(h_w, OSLAMK_UWEIGHTS(*t), sizeof(uint64_t) * ucap, hipMemcpyDeviceToHost));
+    for (slot = 0; slot < ucap; slot++) n_ids += h_keys[slot] != 0u;
+    if (ranked) {
+        size_t i = 0;
+        r = (key_rank *)malloc(sizeof *r * (n_ids ? n_ids : 1));
+        r2 = (key_rank *)malloc(sizeof *r2 * (n_ids ? n_ids : 1));
+        if (!r || !r2) { rc = fail(OSLAM_E_NOMEM, "host allocation failed"); goto done; }
+        for (slot = 0; slot < ucap; slot++)
+            if (h_keys[slot] != 0u) {
+                r[i].weight = h_w[slot];
+                r[i].key = h_keys[slot];
+                r[i].slot = slot;
+                i++;
+            }
+        res = rank_keys(r, r2, n_ids, count);
+        for (i = 0; i < n_ids; i++) h_ids[res[i].slot] = (uint32_t)i;
+    } else {
+        uint32_t next = 0;
+        for (slot = 0; slot < ucap; slot++)
+            if (h_keys[slot] != 0u) h_ids[slot] = next++;
+    }
+    HIPCHK(hipMemcpy(t->uids, h_ids, sizeof(uint32_t) * ucap, hipMemcpyHostToDevice));
     t->n_ids = n_ids;
     t->id_bits = 1;
     while (t->id_bits < 32u && ((uint64_t)1 << t->id_bits) < (uint64_t)n_ids) t->id_bits++;
@@ -77,7 +168,12 @@ int oslam_build_kmap(oslamk_table *t, float d_dist)
         KCHK(oslamk_kmap_build(*t, d_dist, oslam_stream()));
     }
 done:
-    if (d_count) (void)hipFree(d_count);
+    free(h_keys);
+    free(h_ids);
+    free(h_w);
+    free(count);
+    free(r);
+    free(r2);
     return rc;
 }
 
@@ -109,7 +205,7 @@ int oslam_build_union(oslam_model *m, uint32_t distinct, uint32_t *d_n_keys, uin
     HIPCHK(hipMalloc((void **)&m->table.reach, sizeof(uint32_t) * (OSLAMK_REACH_BINS / 32)));
     HIPCHK(hipMemsetAsync(m->table.reach, 0, sizeof(uint32_t) * (OSLAMK_REACH_BINS / 32), (hipStream_t)oslam_stream()));
     KCHK(oslamk_reach_build(m->table, m->d_dist, oslam_stream()));
-    rc = oslam_build_kmap(&m->table, m->d_dist);
+    rc = oslam_build_kmap(&m->table, m->d_dist, &m->table, 1, m->params.vote_order);
 done:
     return rc;
 }
@@ -469,7 +565,7 @@ int oslam_model_load(const char *path, const oslam_params *params, oslam_model *
     if (sum != hd.checksum) { rc = fail(OSLAM_E_INVALID, "model file checksum mismatch"); goto done; }
     m->h_slots = h_slots;                         /* the bucket tap reads it */
     h_slots = NULL;
-    rc = oslam_build_kmap(&m->table, m->d_dist);
+    rc = oslam_build_kmap(&m->table, m->d_dist, &m->table, 1, m->params.vote_order);
     if (rc != OSLAM_OK) goto done;
     rc = oslam_build_uinfo(m);
     if (rc != OSLAM_OK) goto done;

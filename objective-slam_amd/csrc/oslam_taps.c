@@ -114,6 +114,67 @@ done:
     return rc;
 }
 
+typedef struct key_row {
+    uint64_t weight;
+    uint32_t key, number;
+} key_row;
+
+static int key_row_order(const void *a, const void *b)
+{
+    const uint32_t x = ((const key_row *)a)->key, y = ((const key_row *)b)->key;
+    return x < y ? -1 : (x > y);
+}
+
+int oslam_model_key_numbers(oslam_model *m, uint32_t *keys_out, uint32_t *numbers_out, uint64_t *weights_out, size_t cap,
+                            size_t *n_out)
+{
+    int rc = OSLAM_OK;
+    uint32_t *h_keys = NULL, *h_ids = NULL, slot;
+    uint64_t *h_w = NULL;
+    key_row *rows = NULL;
+    size_t n = 0, i, ucap;
+    if (!m || !n_out) return fail(OSLAM_E_INVALID, "NULL argument");
+    *n_out = 0;
+    if (m->unusable || !m->table.ukeys || !m->table.uids) return fail(OSLAM_E_INVALID, "this model has no key tables");
+    if (hipSetDevice(m->dev) != hipSuccess) return fail(OSLAM_E_DEVICE, "hipSetDevice failed");
+    ucap = m->table.ucap;
+    h_keys = (uint32_t *)malloc(sizeof(uint32_t) * ucap);
+    h_ids = (uint32_t *)malloc(sizeof(uint32_t) * ucap);
+    h_w = (uint64_t *)malloc(sizeof(uint64_t) * ucap);
+    rows = (key_row *)malloc(sizeof *rows * ucap);
+    if (!h_keys || !h_ids || !h_w || !rows) { rc = fail(OSLAM_E_NOMEM, "host allocation failed"); goto done; }
+    HIPCHK(hipMemcpy(h_keys, m->table.ukeys, sizeof(uint32_t) * ucap, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(h_ids, m->table.uids, sizeof(uint32_t) * ucap, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(h_w, OSLAMK_UWEIGHTS(m->table), sizeof(uint64_t) * ucap, hipMemcpyDeviceToHost));
+    for (slot = 0; slot < ucap; slot++)
+        if (h_keys[slot] != 0u) {
+            rows[n].key = h_keys[slot];
+            rows[n].number = h_ids[slot];
+            rows[n].weight = h_w[slot];
+            n++;
+        }
+    qsort(rows, n, sizeof *rows, key_row_order);
+    for (i = 0; i < n && i < cap; i++) {
+        if (keys_out) keys_out[i] = rows[i].key;
+        if (numbers_out) numbers_out[i] = rows[i].number;
+        if (weights_out) weights_out[i] = rows[i].weight;
+    }
+    *n_out = n;
+done:
+    free(h_keys);
+    free(h_ids);
+    free(h_w);
+    free(rows);
+    return rc;
+}
+
+int oslam_vote_ref_order(const uint32_t *keep, size_t n, uint32_t *order_out)
+{
+    if ((!keep || !order_out) && n) return fail(OSLAM_E_INVALID, "NULL argument");
+    oslam_ref_order(keep, n, order_out);
+    return OSLAM_OK;
+}
+
 int oslam_vote_accumulator(oslam_model *m, oslam_scene *s, size_t ref_index, uint32_t *acc_out)
 {
     int rc = OSLAM_OK;

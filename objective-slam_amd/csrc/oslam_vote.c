@@ -43,6 +43,8 @@ struct scratch_pool {
     oslamk_vote_args *d_vargs, *h_vargs;   /* a group's vote arguments, one per member (h: pinned), for the one-grid launch */
     size_t vargs_cap;
     size_t redo_cap;
+    uint32_t *d_order, *h_order;       /* the order in which a batch's reference points are voted (h: pinned), see oslam_ref_order */
+    size_t order_cap;
 };
 static scratch_pool g_pool[MAX_DEVICES];
 static pthread_once_t g_pool_once = PTHREAD_ONCE_INIT;
@@ -86,7 +88,7 @@ int oslam_release_scratch(int dev)
     scratch_pool *p = pool_lock(dev);
     int i;
     if (!p) return fail(OSLAM_E_INVALID, "device ordinal out of range");
-    if (p->buf || p->d_counts || p->have_events || p->d_cluster || p->d_redo || p->d_vargs || p->h_vargs) {
+    if (p->buf || p->d_counts || p->have_events || p->d_cluster || p->d_redo || p->d_vargs || p->h_vargs || p->d_order || p->h_order) {
         if (hipSetDevice(dev) != hipSuccess) { oslam_pool_unlock(p); return fail(OSLAM_E_DEVICE, "hipSetDevice failed"); }
         if (p->buf) (void)hipFree(p->buf);
         if (p->d_counts) (void)hipFree(p->d_counts);
@@ -94,6 +96,8 @@ int oslam_release_scratch(int dev)
         if (p->d_redo) (void)hipFree(p->d_redo);
         if (p->d_vargs) (void)hipFree(p->d_vargs);
         if (p->h_vargs) (void)hipHostFree(p->h_vargs);
+        if (p->d_order) (void)hipFree(p->d_order);
+        if (p->h_order) (void)hipHostFree(p->h_order);
         oslamk_pose_release();
         if (p->have_events)
             for (i = 0; i < 4 + 3 * MAX_BATCH_EVENTS; i++) (void)hipEventDestroy(p->ev[i]);
@@ -116,6 +120,9 @@ int oslam_release_scratch(int dev)
     p->d_vargs = NULL;
     p->h_vargs = NULL;
     p->vargs_cap = 0;
+    p->d_order = NULL;
+    p->h_order = NULL;
+    p->order_cap = 0;
     oslam_pool_unlock(p);
     return OSLAM_OK;
 }
@@ -206,6 +213,27 @@ static int batch_extent(const uint32_t *keep, int first, int n_ref, size_t limit
     return n;
 }
 
+/* The order in which the vote grid takes the n reference points of a batch: order[p] = the reference point of dispatch
+ * position p, by descending demand keep[] (the pairs within reach: what the hit lists are sized by, and a measure of
+ * the votes that needs no pass of its own).  The vote workgroups fill a CU each and go out in position order, so the
+ * last rounds of a grid are then its lightest workgroups and the CUs run dry together.  A counting sort over
+ * REF_ORDER_CLASSES classes of demand, stable (equal classes stay in index order), O(n): the tail has to be light, not
+ * sorted.  order is a permutation of 0 .. n-1 whatever keep holds. */
+#define REF_ORDER_CLASSES 1024
+void oslam_ref_order(const uint32_t *keep, size_t n, uint32_t *order)
+{
+    uint32_t start[REF_ORDER_CLASSES + 1], top = 0;
+    size_t i;
+    int c;
+    for (i = 0; i < n; i++) if (keep[i] > top) top = keep[i];
+    if (top == 0) top = 1;
+    memset(start, 0, sizeof start);
+    /* class 0 = the heaviest */
+    for (i = 0; i < n; i++) start[1 + (REF_ORDER_CLASSES - 1) - (int)((uint64_t)keep[i] * (REF_ORDER_CLASSES - 1) / top)]++;
+    for (c = 0; c < REF_ORDER_CLASSES; c++) start[c + 1] += start[c];
+    for (i = 0; i < n; i++) order[start[(REF_ORDER_CLASSES - 1) - (int)((uint64_t)keep[i] * (REF_ORDER_CLASSES - 1) / top)]++] = (uint32_t)i;
+}
+
 /* The kernels of one registration (or of one reference point for the accumulator tap): count, then per
  * batch scene keys -> hit sort -> votes.  d_ref_idx / d_tsg: the reference points and their frame rows.
  * The caller holds the pool of the device. */
@@ -225,6 +253,8 @@ int oslam_run_votes_group(scratch_pool *pool, oslam_model *const *ms, int nm, os
     const size_t limit_slots = scratch_limit(ms[0]) / SLOT_BYTES;
     size_t cap, max_batch_slots = 0, redo_stride = 0;
     int one_grid = 0;
+    /* heaviest reference points first (oslam_params.vote_order); the accumulator tap votes one reference point */
+    const int ordered = (m->params.vote_order == 0 || m->params.vote_order == 3) && !acc_dump && n_ref > 1;
     uint32_t *h_keep, *h_off, *d_keep, *d_hitc, *d_runc, *d_off;
     float k0 = 0.0f;
     rc = oslam_pool_reserve_counts(pool, (size_t)(n_ref > 0 ? n_ref : 1));
@@ -241,6 +271,15 @@ int oslam_run_votes_group(scratch_pool *pool, oslam_model *const *ms, int nm, os
             HIPCHK(hipMalloc((void **)&pool->d_redo, sizeof(uint32_t) * (need + need / 4)));
             pool->redo_cap = need + need / 4;
         }
+    }
+    if (ordered && pool->order_cap < (size_t)n_ref) {
+        const size_t want = (size_t)n_ref + (size_t)n_ref / 4 + 64;
+        if (pool->d_order) { (void)hipFree(pool->d_order); pool->d_order = NULL; }
+        if (pool->h_order) { (void)hipHostFree(pool->h_order); pool->h_order = NULL; }
+        pool->order_cap = 0;
+        HIPCHK(hipMalloc((void **)&pool->d_order, sizeof(uint32_t) * want));
+        HIPCHK(hipHostMalloc((void **)&pool->h_order, sizeof(uint32_t) * want, hipHostMallocDefault));
+        pool->order_cap = want;
     }
     ev = pool->ev;
     cap = pool->counts_cap;
@@ -345,6 +384,14 @@ int oslam_run_votes_group(scratch_pool *pool, oslam_model *const *ms, int nm, os
             KCHK(oslamk_scene_hits(&a, oslam_stream()));
             KCHK(oslamk_sort_hits(&a, oslam_stream()));
             if (timed) HIPCHK(hipEventRecord(ev[4 + 3 * nb + 1], st));
+            a.ref_order = NULL;
+            if (ordered) {
+                /* made while the two kernels above run; every batch has its own piece of the pinned buffer, which
+                 * nothing writes again before the call's last wait */
+                oslam_ref_order(h_keep + first, (size_t)n, pool->h_order + first);
+                HIPCHK(hipMemcpyAsync(pool->d_order + first, pool->h_order + first, sizeof(uint32_t) * (size_t)n, hipMemcpyHostToDevice, st));
+                a.ref_order = pool->d_order + first;
+            }
             for (j = 0; j < nm; j++) {
                 const oslam_model *mj = ms[j];
                 a.table.uinfo = mj->table.uinfo;          /* its buckets, under the shared union slots */

@@ -397,9 +397,12 @@ __device__ __forceinline__ void vote_body(const oslamk_vote_args &a, const uint3
     const int tid = threadIdx.x, lane = tid & (WAVE - 1), wid = tid / WAVE;
     const uint32_t nsl = (uint32_t)a.table.n_slices;
     const uint32_t xg = wg & 7u, xi = wg >> 3;
-    const int ref_local = (int)((xi / nsl) * 8u + xg);
+    const uint32_t ref_pos = (xi / nsl) * 8u + xg;   /* dispatch position: the slices of a reference point share an XCD */
     const int slice = (int)(xi % nsl);
-    if (ref_local >= a.n_launch) return;             /* the grid is padded to a multiple of 8 reference points */
+    if (ref_pos >= (uint32_t)a.n_launch) return;     /* the grid is padded to a multiple of 8 reference points */
+    /* the reference point of that position: the host hands the heavy ones out first (oslamk_vote_args.ref_order) */
+    const int ref_local = (int)(a.ref_order ? uni_u32(a.ref_order[ref_pos]) : ref_pos);
+    if ((uint32_t)ref_local >= (uint32_t)a.n_launch) return;
     const int ref_ord = a.first_ref + ref_local;
     const uint32_t r = a.ref_idx[ref_ord];
     const uint32_t n_runs = a.run_count[ref_local];

@@ -36,7 +36,7 @@ class Params(C.Structure):
                 ("cpu_clustering", C.c_int), ("use_l1_norm", C.c_int), ("use_averaged_clusters", C.c_int),
                 ("dev", C.c_int), ("vote_mode", C.c_int), ("shard_rank", C.c_int), ("shard_world", C.c_int),
                 ("max_cells", C.c_uint), ("pose_gpu_min", C.c_uint), ("no_bucket_spread", C.c_int),
-                ("scratch_gib", C.c_uint), ("pose_two_sorts", C.c_int), ("reserved", C.c_int * 2)]
+                ("scratch_gib", C.c_uint), ("pose_two_sorts", C.c_int), ("vote_order", C.c_int), ("reserved", C.c_int * 1)]
 
 
 class Stats(C.Structure):
@@ -354,6 +354,8 @@ _SIGNATURES = {
     "oslam_model_bucket": (_i, [_vp, C.c_uint32, _vp, _sz, C.POINTER(_sz)]),
     "oslam_model_bucket_words": (_i, [_vp, C.c_uint32, _i, _vp, _sz, C.POINTER(_sz)]),
     "oslam_vote_accumulator": (_i, [_vp, _vp, _sz, _vp]),
+    "oslam_model_key_numbers": (_i, [_vp, _vp, _vp, _vp, _sz, C.POINTER(_sz)]),
+    "oslam_vote_ref_order": (_i, [_vp, _sz, _vp]),
     "oslam_last_cells": (_i, [_vp, _vp, _vp, _sz, C.POINTER(_sz)]),
     "oslam_set_stream": (_i, [_vp]),
     "oslam_last_error": (C.c_char_p, []),
@@ -400,6 +402,14 @@ def default_params(**kw):
             raise TypeError("unknown parameter %r" % k)
         setattr(p, k, v)
     return p
+
+
+def vote_ref_order(keep):
+    """The order in which the vote grid takes a batch of reference points with the demands `keep` (host only)."""
+    keep = np.ascontiguousarray(keep, np.uint32)
+    out = np.zeros(len(keep), np.uint32)
+    _check(lib().oslam_vote_ref_order(_p(keep), len(keep), _p(out)))
+    return out
 
 
 def default_refine_params(**kw):
@@ -1009,6 +1019,16 @@ class Model:
         n = C.c_size_t(0)
         _check(lib().oslam_model_bucket_words(self._h, int(key), int(slice_index), _p(out), cap, C.byref(n)))
         return out[: min(n.value, cap)].copy()
+
+    def key_numbers(self):
+        """(keys, numbers, weights) of every key of the model's table (its group's inside a database), by ascending key:
+        the number the hit lists carry for the key, and the entries in its buckets that the number is ranked by."""
+        n = C.c_size_t(0)
+        _check(lib().oslam_model_key_numbers(self._h, None, None, None, 0, C.byref(n)))
+        keys, nums, w = np.zeros(n.value, np.uint32), np.zeros(n.value, np.uint32), np.zeros(n.value, np.uint64)
+        if n.value:
+            _check(lib().oslam_model_key_numbers(self._h, _p(keys), _p(nums), _p(w), n.value, C.byref(n)))
+        return keys, nums, w
 
     def vote_accumulator(self, scene, ref_index):
         acc = np.zeros((self.n, 32), np.uint32)
