@@ -967,8 +967,10 @@ int oslam_tracker_camera(const oslam_tracker *t, float T_world_cam[16]);
  *   computed in size_t (512^3 voxels are 512 MiB).
  * Cost: integrate = one memset of the counter, k_tsdf_integrate, one copy back, one host wait; raycast = the same with
  *   k_tsdf_raycast.  Calls on volumes take turns (one lock, held to the end of the host wait).
- * Out of scope: a moving or shifting volume, colour, the along-ray distance, masking tracked objects out of the
- *   integration, several GPUs; oslam_tracker keeps taking T_cam from the caller. */
+ * The volume frame is fixed, the window of voxels the volume holds is not: oslam_volume_shift below moves it by whole
+ *   voxels, and every call above reads the origin that goes with the window.
+ * Out of scope: colour, the along-ray distance, masking tracked objects out of the integration, several GPUs;
+ *   oslam_tracker keeps taking T_cam from the caller. */
 typedef struct oslam_volume oslam_volume;
 typedef struct oslam_volume_params {
     unsigned nx, ny, nz;      /* voxels per side, each 16..512 and a multiple of 8; default 256^3 */
@@ -1189,7 +1191,8 @@ int oslam_volume_set_voxels(oslam_volume *vol, const int16_t *tsdf_q, const uint
  * oslam_mc_table_row is a host-only tap on the compiled-in table for the tests: edges_out [15] gets 3 * *n_tri_out
  *   cube-edge numbers.
  * Out of scope: colour, merging or decimating triangles, dropping unreferenced vertices on the device, smoothing, a
- *   min_weight for the normal's corners, meshing across a shifting volume, several GPUs. */
+ *   min_weight for the normal's corners, one mesh of the live surface and of what oslam_volume_leaving handed over,
+ *   several GPUs. */
 typedef struct oslam_mesh_params {
     unsigned min_weight;      /* 1..65535, default 1: a voxel is seen from this weight on */
     int reserved[7];
@@ -1209,6 +1212,71 @@ int oslam_volume_mesh(oslam_volume *vol, const oslam_mesh_params *mp, float *xyz
 int oslam_ply_write_mesh(const char *path, const float *xyz, const float *nrm, size_t nv, const uint32_t *tri, size_t nt,
                          int binary);
 int oslam_mc_table_row(unsigned mc_case, uint8_t *edges_out, unsigned *n_tri_out);
+
+/* ---- the shifting window: the volume follows the camera by whole voxels and hands over the surface that leaves it
+ * (large-scale KinFu's shifting volume).  The volume frame stays the first camera's, so no pose changes meaning; only
+ * the window of voxels the volume holds moves.  Integration, ray cast, surface and mesh read the window's origin and
+ * are otherwise unchanged.  The restatement in numpy is tests/shift_ref.py; device and restatement agree bit for bit.
+ *
+ * State.  A volume keeps origin0, the origin it was created with, and an integer window offset off[3] in voxels,
+ *   initially 0.  Its origin is derived from the offset, never accumulated: origin_a = origin0_a when off_a == 0 (the
+ *   stored float itself, so a -0.0f keeps its sign), otherwise origin_a = origin0_a + (float)off_a * voxel in float32,
+ *   one multiply, then one add, not fused.  Shifting out and back gives the created origin bit for bit;
+ *   oslam_volume_reset restores off = 0.  A volume that was never shifted behaves bit for bit as one without this section.
+ * oslam_volume_shift moves the window by s = shift: the new word at (i, j, k) is the old word at (i + s_x, j + s_y,
+ *   k + s_z) when that voxel exists and 0 ("never seen") otherwise; then off += s.  |s_a| >= n_a on any axis clears
+ *   everything and is legal.  |s_a| and |off_a + s_a| must stay within 2^20, so that (float)off_a is exact: beyond it
+ *   the call returns OSLAM_E_INVALID and nothing changes.  A zero shift returns at once with launches = 0 and kept = 0.
+ *   res (may be NULL): offset[3] after the call, kept = the voxels with w > 0 after the shift.
+ *   Cost: the words are copied into a second buffer of the volume's size and the two are swapped (in place a workgroup
+ *   would read what another has overwritten).  The second buffer is allocated by the first shift that is not zero and
+ *   freed by oslam_volume_destroy; when that allocation fails the call returns OSLAM_E_NOMEM and nothing changes.  One
+ *   memset of the counter, k_tsdf_shift, one copy back, one host wait.
+ * oslam_volume_window is a tap: the current offset and origin.
+ * oslam_volume_leaving does not change the volume.  It returns the part of oslam_volume_surface's output that a shift
+ *   by `shift` would lose.  Voxel (i, j, k) stays iff 0 <= i - s_x < nx, and likewise for y and z; otherwise it leaves.
+ *   A crossing (start voxel, axis a) is leaving iff its start voxel or its neighbour along a leaves: an edge from a
+ *   staying voxel into a leaving one has no +a edge after the shift, it would be lost to both sides, so it leaves.
+ *   Points, normals and their order are exactly oslam_volume_surface's, restricted to the leaving crossings;
+ *   res->crossings counts the leaving crossings and res->points those with a normal; cap, n_out, OSLAM_E_LIMIT and the
+ *   count-only call work as there.  So oslam_volume_surface's crossings before a shift are the leaving ones plus the
+ *   crossings after it, none lost and none twice.  The caller extracts before it shifts: the normals still read the
+ *   voxels that are about to go.  Normals next to the new border are lost or rounded differently after the shift (a
+ *   trilinear read needs its eight corners, and the origin is another float): positions carry over, normals do not.
+ *   |s_a| is within 2^20 as for oslam_volume_shift.  Cost: oslam_volume_surface's, with k_leave_count and k_leave_emit.
+ * oslam_volume_follow is host arithmetic only: it decides a shift and launches nothing.  In double, from the float
+ *   inputs: c = t + lookahead * (R02, R12, R22) (the camera's position plus its optical axis), centre_a = origin_a + 0.5 *
+ *   n_a * voxel with the window's current origin, d_a = (c_a - centre_a) / voxel.  If |d_a| <= threshold on every axis
+ *   the shift is 0; otherwise s_a = granule * (int)rint(d_a / granule) on every axis, clamped to +-n_a.  fp NULL =
+ *   oslam_follow_params_default: lookahead = 0.5 * nz * voxel (the default volume at the identity pose has d = 0),
+ *   threshold = min(nx, ny, nz) / 4 voxels, granule = 8.  These are policy parameters, not measurements: how far ahead
+ *   of the camera the window is centred, how far it may lag and in what steps it moves is the caller's to choose.
+ * Arguments are checked before any handle is read or any device call is made: NULL vol, shift, offset_out, origin_out,
+ *   T_vol_cam, shift_out or fp (of oslam_follow_params_default), fields that are not finite, lookahead < 0,
+ *   threshold < 0, a granule outside 1..64, a T that is not rigid and the surface arguments oslam_volume_surface
+ *   refuses are OSLAM_E_INVALID.  Every call takes the lock the other calls on volumes take.
+ * Out of scope: reloading what left when the window returns, merging what left with the live surface into one mesh,
+ *   colour, several GPUs, any change to oslam_tracker. */
+typedef struct oslam_shift_result {
+    int32_t offset[3];         /* the window's offset after the call, voxels */
+    uint32_t kept;             /* voxels with w > 0 after the shift */
+    uint32_t launches;
+    float ms_total;            /* whole call, host clock */
+} oslam_shift_result;
+
+typedef struct oslam_follow_params {
+    float lookahead;           /* metres along the optical axis from the camera to the point the window is centred on, >= 0 */
+    float threshold;           /* voxels that point may lie off the window's centre on any axis before the window moves, >= 0 */
+    int granule;               /* the window moves by multiples of this many voxels, 1..64 */
+    int reserved[5];
+} oslam_follow_params;
+
+int oslam_volume_shift(oslam_volume *vol, const int shift[3], oslam_shift_result *res);
+int oslam_volume_window(oslam_volume *vol, int offset_out[3], float origin_out[3]);
+int oslam_volume_leaving(oslam_volume *vol, const int shift[3], const oslam_surface_params *sp, float *xyz_out, float *nrm_out,
+                         size_t cap, size_t *n_out, oslam_surface_result *res);
+int oslam_follow_params_default(const oslam_volume *vol, oslam_follow_params *fp);
+int oslam_volume_follow(oslam_volume *vol, const float T_vol_cam[16], const oslam_follow_params *fp, int shift_out[3]);
 
 /* ---- parity taps (tests): values the reference materialises as arrays.
  * Scene::getHashKeys row r (scene.cu:49-54): keys_out[n] of reference point r,

@@ -89,8 +89,10 @@ struct oslam_view {
 
 struct oslam_volume {
     int dev;                          /* stays the first field, as in oslam_view (the argument tests write it) */
-    oslamk_volume k;
+    oslamk_volume k;                  /* k.origin follows off (oslam_volume_shift); p.origin stays the created one */
     oslam_volume_params p;
+    int off[3];                       /* the window's offset in voxels */
+    uint32_t *spare;                  /* the second buffer of oslam_volume_shift, NULL until the first shift */
 };
 
 struct oslam_pyramid {

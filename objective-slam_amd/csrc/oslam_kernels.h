@@ -588,6 +588,18 @@ int oslamk_mesh_triangles(const oslamk_volume *vol, uint32_t min_weight, uint32_
                           uint32_t n_tris, const uint32_t *edge_id, uint32_t n_verts, uint32_t *tri, uint32_t *totals,
                           void *stream);
 
+/* ---- the shifting window (oslam_shift.hip; semantics in include/oslam.h at oslam_volume_shift) ---- */
+#define OSLAMK_SHIFT_MAX (1 << 20)    /* the largest shift, and the largest window offset, per axis in voxels: exact as a float */
+/* dst [nx*ny*nz] (not vol->words) gets vol's words moved by shift, zeros where no source voxel exists; *kept (zeroed by
+ * the caller) += the words of dst with w > 0.  vol->words is only read: the caller swaps the two buffers */
+int oslamk_tsdf_shift(const oslamk_volume *vol, uint32_t *dst, const int shift[3], uint32_t *kept, void *stream);
+/* oslamk_surface_count and oslamk_surface_emit restricted to the crossings that a shift by shift[3] loses; workgroups,
+ * counts, totals, offsets and out6 as there */
+int oslamk_leave_count(const oslamk_volume *vol, const int shift[3], uint32_t min_weight, uint32_t n_groups, uint32_t *counts,
+                       uint32_t *totals, void *stream);
+int oslamk_leave_emit(const oslamk_volume *vol, const int shift[3], uint32_t min_weight, uint32_t n_groups,
+                      const uint32_t *offsets, uint32_t n_points, float *out6, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,7 @@
 /*
  * oslam_surface.c -- the fused surface of a TSDF volume as a cloud (include/oslam.h at oslam_volume_surface) and as a
- * triangle mesh (oslam_volume_mesh): the host side of the kernels in oslam_surface.hip and oslam_mesh.hip.  A call
+ * triangle mesh (oslam_volume_mesh): the host side of the kernels in oslam_surface.hip and oslam_mesh.hip, and of the
+ * extraction of what a shift loses (oslam_volume_leaving; k_leave_count and k_leave_emit of oslam_shift.hip).  A call
  * counts, waits for the totals, allocates exactly that and emits, under the volume lock of oslam_volume.c.
  */
 #include "oslam_internal.h"
@@ -22,9 +23,11 @@ int oslam_surface_check_params(const oslam_surface_params *sp, oslam_surface_par
     return OSLAM_OK;
 }
 
-/* the two passes, with the volume lock held and the volume's device bound.  cap: the most points the caller takes (the second
- * pass is skipped above it, and with d_out6 == NULL); *d_out6 = device [points][6] from oslam_dev_alloc, NULL without points */
-static int surface_passes(oslam_volume *vol, unsigned min_weight, size_t cap, float **d_out6, uint32_t tot[2], uint32_t *launches)
+/* the two passes, with the volume lock held and the volume's device bound.  shift NULL: the whole surface, otherwise the part a
+ * shift by it loses.  cap: the most points the caller takes (the second pass is skipped above it, and with d_out6 == NULL);
+ * *d_out6 = device [points][6] from oslam_dev_alloc, NULL without points */
+static int surface_passes(oslam_volume *vol, const int *shift, unsigned min_weight, size_t cap, float **d_out6, uint32_t tot[2],
+                          uint32_t *launches)
 {
     int rc = OSLAM_OK;
     const uint32_t n_groups = oslamk_surface_groups(&vol->k);
@@ -33,13 +36,15 @@ static int surface_passes(oslam_volume *vol, unsigned min_weight, size_t cap, fl
     tot[0] = tot[1] = 0;
     *launches = 0;
     KCHK(oslam_counters_open(&d_cnt, n_groups, stream));
-    KCHK(oslamk_surface_count(&vol->k, min_weight, n_groups, d_cnt + 64, d_cnt, stream));
+    if (shift) KCHK(oslamk_leave_count(&vol->k, shift, min_weight, n_groups, d_cnt + 64, d_cnt, stream));
+    else KCHK(oslamk_surface_count(&vol->k, min_weight, n_groups, d_cnt + 64, d_cnt, stream));
     HIPCHK(hipMemcpyAsync(tot, d_cnt, sizeof(uint32_t) * 2, hipMemcpyDeviceToHost, (hipStream_t)stream));
     HIPCHK(hipStreamSynchronize((hipStream_t)stream));
     *launches = 2;
     if (d_out6 && tot[1] > 0 && (size_t)tot[1] <= cap) {
         KCHK(oslam_dev_alloc((void **)d_out6, sizeof(float) * 6 * (size_t)tot[1]));
-        KCHK(oslamk_surface_emit(&vol->k, min_weight, n_groups, d_cnt + 64, tot[1], *d_out6, stream));
+        if (shift) KCHK(oslamk_leave_emit(&vol->k, shift, min_weight, n_groups, d_cnt + 64, tot[1], *d_out6, stream));
+        else KCHK(oslamk_surface_emit(&vol->k, min_weight, n_groups, d_cnt + 64, tot[1], *d_out6, stream));
         HIPCHK(hipStreamSynchronize((hipStream_t)stream));
         *launches = 3;
     }
@@ -52,15 +57,16 @@ done:
     return rc;
 }
 
-int oslam_volume_surface(oslam_volume *vol, const oslam_surface_params *sp, float *xyz_out, float *nrm_out, size_t cap,
-                         size_t *n_out, oslam_surface_result *res)
+/* oslam_volume_surface (shift NULL) and oslam_volume_leaving after their checks of vol and shift */
+static int surface_call(oslam_volume *vol, const int *shift, const oslam_surface_params *sp, float *xyz_out, float *nrm_out,
+                        size_t cap, size_t *n_out, oslam_surface_result *res)
 {
     int rc;
     const double t0 = now_ms();
     oslam_surface_params p;
     float *d_out = NULL, *h_out = NULL;
     uint32_t tot[2] = {0, 0}, launches = 0;
-    if (!vol || !n_out) return fail(OSLAM_E_INVALID, "NULL argument");
+    if (!n_out) return fail(OSLAM_E_INVALID, "NULL argument");
     if (!xyz_out != !nrm_out) return fail(OSLAM_E_INVALID, "xyz_out and nrm_out must both be given or both be NULL");
     if (!xyz_out && cap != 0) return fail(OSLAM_E_INVALID, "cap must be 0 without outputs");
     rc = oslam_surface_check_params(sp, &p);
@@ -69,7 +75,7 @@ int oslam_volume_surface(oslam_volume *vol, const oslam_surface_params *sp, floa
     if (res) memset(res, 0, sizeof *res);
     if (hipSetDevice(vol->dev) != hipSuccess) return fail(OSLAM_E_DEVICE, "hipSetDevice failed");
     oslam_volume_lock();
-    rc = surface_passes(vol, p.min_weight, cap, xyz_out ? &d_out : NULL, tot, &launches);
+    rc = surface_passes(vol, shift, p.min_weight, cap, xyz_out ? &d_out : NULL, tot, &launches);
     if (rc != OSLAM_OK) goto done;
     *n_out = tot[1];
     if (xyz_out && (size_t)tot[1] > cap) { rc = fail(OSLAM_E_LIMIT, "output capacity too small"); goto done; }
@@ -92,6 +98,23 @@ done:
     return rc;
 }
 
+int oslam_volume_surface(oslam_volume *vol, const oslam_surface_params *sp, float *xyz_out, float *nrm_out, size_t cap,
+                         size_t *n_out, oslam_surface_result *res)
+{
+    if (!vol) return fail(OSLAM_E_INVALID, "NULL argument");
+    return surface_call(vol, NULL, sp, xyz_out, nrm_out, cap, n_out, res);
+}
+
+int oslam_volume_leaving(oslam_volume *vol, const int shift[3], const oslam_surface_params *sp, float *xyz_out, float *nrm_out,
+                         size_t cap, size_t *n_out, oslam_surface_result *res)
+{
+    int a;
+    if (!vol || !shift) return fail(OSLAM_E_INVALID, "NULL argument");
+    for (a = 0; a < 3; a++)
+        if (shift[a] < -OSLAMK_SHIFT_MAX || shift[a] > OSLAMK_SHIFT_MAX) return fail(OSLAM_E_INVALID, "a shift is at most 2^20 voxels");
+    return surface_call(vol, shift, sp, xyz_out, nrm_out, cap, n_out, res);
+}
+
 int oslam_volume_surface_cloud(oslam_volume *vol, unsigned min_weight, int *dev, float **d_pts6, uint32_t *np)
 {
     int rc;
@@ -101,7 +124,7 @@ int oslam_volume_surface_cloud(oslam_volume *vol, unsigned min_weight, int *dev,
     *dev = vol->dev;
     if (hipSetDevice(vol->dev) != hipSuccess) return fail(OSLAM_E_DEVICE, "hipSetDevice failed");
     oslam_volume_lock();
-    rc = surface_passes(vol, min_weight, (size_t)-1, d_pts6, tot, &launches);
+    rc = surface_passes(vol, NULL, min_weight, (size_t)-1, d_pts6, tot, &launches);
     oslam_volume_unlock();
     if (rc == OSLAM_OK) *np = tot[1];
     return rc;

@@ -4,7 +4,9 @@
  * counter block, runs one kernel and reads the counters back with one host wait.  oslam_volume_track is glue over the
  * ray cast and oslam_view_egomotion, oslam_volume_track_pyramid over the ray cast, a pyramid of it and
  * oslam_pyramid_egomotion (one body, track_from_raycast); oslam_view_to_cloud runs the depth front end's compaction
- * over a view's maps.  The extraction of the fused volume as a cloud or a triangle list is oslam_surface.c.
+ * over a view's maps.  oslam_volume_shift moves the window of voxels the volume holds (k_tsdf_shift of oslam_shift.hip
+ * into a second buffer, then a swap of the two), oslam_volume_follow decides such a move on the host.  The extraction of
+ * the fused volume, or of what a shift loses, as a cloud or a triangle list is oslam_surface.c.
  */
 #include <math.h>
 #include <pthread.h>
@@ -91,10 +93,27 @@ int oslam_volume_destroy(oslam_volume *vol)
     if (!vol) return fail(OSLAM_E_INVALID, "volume is NULL");
     /* every call that touched the volume ended with a synchronisation of its stream */
     pthread_mutex_lock(&g_vol_mu);
-    if (hipSetDevice(vol->dev) == hipSuccess) (void)hipFree(vol->k.words);
+    if (hipSetDevice(vol->dev) == hipSuccess) {
+        (void)hipFree(vol->k.words);
+        if (vol->spare) (void)hipFree(vol->spare);
+    }
     pthread_mutex_unlock(&g_vol_mu);
     free(vol);
     return OSLAM_OK;
+}
+
+/* the origin of the window at vol->off, derived from the created origin and never accumulated (include/oslam.h at
+ * oslam_volume_shift): one float multiply, then one float add */
+static void window_origin(const oslam_volume *vol, const int off[3], float origin[3])
+{
+    int a;
+    for (a = 0; a < 3; a++) {
+        origin[a] = vol->p.origin[a];
+        if (off[a] != 0) {
+            const float step = (float)off[a] * vol->p.voxel;
+            origin[a] = vol->p.origin[a] + step;
+        }
+    }
 }
 
 int oslam_volume_reset(oslam_volume *vol)
@@ -105,6 +124,8 @@ int oslam_volume_reset(oslam_volume *vol)
     pthread_mutex_lock(&g_vol_mu);
     HIPCHK(hipMemsetAsync(vol->k.words, 0, volume_bytes(&vol->p), (hipStream_t)oslam_stream()));
     HIPCHK(hipStreamSynchronize((hipStream_t)oslam_stream()));
+    memset(vol->off, 0, sizeof vol->off);
+    window_origin(vol, vol->off, vol->k.origin);
 done:
     pthread_mutex_unlock(&g_vol_mu);
     return rc;
@@ -409,4 +430,113 @@ done:
     pthread_mutex_unlock(&g_vol_mu);
     free(h);
     return rc;
+}
+
+/* ---- the shifting window (include/oslam.h at oslam_volume_shift; kernel: oslam_shift.hip) ---- */
+int oslam_volume_shift(oslam_volume *vol, const int shift[3], oslam_shift_result *res)
+{
+    int rc = OSLAM_OK, a, off[3];
+    const double t0 = now_ms();
+    uint32_t *d_cnt = NULL, *spare = NULL, kept = 0;
+    void *stream = oslam_stream();
+    if (!vol || !shift) return fail(OSLAM_E_INVALID, "NULL argument");
+    for (a = 0; a < 3; a++)
+        if (shift[a] < -OSLAMK_SHIFT_MAX || shift[a] > OSLAMK_SHIFT_MAX) return fail(OSLAM_E_INVALID, "a shift is at most 2^20 voxels");
+    pthread_mutex_lock(&g_vol_mu);
+    for (a = 0; a < 3; a++) {
+        off[a] = vol->off[a] + shift[a];
+        if (off[a] < -OSLAMK_SHIFT_MAX || off[a] > OSLAMK_SHIFT_MAX) { rc = fail(OSLAM_E_INVALID, "the window's offset is at most 2^20 voxels"); goto done; }
+    }
+    if (res) memset(res, 0, sizeof *res);
+    if (!(shift[0] | shift[1] | shift[2])) {
+        if (res) memcpy(res->offset, off, sizeof off);
+        goto done;
+    }
+    if (hipSetDevice(vol->dev) != hipSuccess) { rc = fail(OSLAM_E_DEVICE, "hipSetDevice failed"); goto done; }
+    spare = vol->spare;
+    if (!spare && hipMalloc((void **)&spare, volume_bytes(&vol->p)) != hipSuccess) {
+        (void)hipGetLastError();
+        spare = NULL;
+        rc = fail(OSLAM_E_NOMEM, "no device memory for the second buffer of the shift");
+        goto done;
+    }
+    vol->spare = spare;
+    KCHK(oslam_counters_open(&d_cnt, 0, stream));
+    KCHK(oslamk_tsdf_shift(&vol->k, spare, shift, d_cnt, stream));
+    HIPCHK(hipMemcpyAsync(&kept, d_cnt, sizeof kept, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    vol->spare = vol->k.words;
+    vol->k.words = spare;
+    memcpy(vol->off, off, sizeof off);
+    window_origin(vol, vol->off, vol->k.origin);
+    if (res) {
+        memcpy(res->offset, off, sizeof off);
+        res->kept = kept;
+        res->launches = 1;
+    }
+done:
+    if (rc != OSLAM_OK && d_cnt) (void)hipStreamSynchronize((hipStream_t)stream);
+    pthread_mutex_unlock(&g_vol_mu);
+    if (d_cnt) oslam_dev_free(d_cnt);
+    if (rc == OSLAM_OK && res) res->ms_total = (float)(now_ms() - t0);
+    return rc;
+}
+
+int oslam_volume_window(oslam_volume *vol, int offset_out[3], float origin_out[3])
+{
+    if (!vol || !offset_out || !origin_out) return fail(OSLAM_E_INVALID, "NULL argument");
+    pthread_mutex_lock(&g_vol_mu);
+    memcpy(offset_out, vol->off, sizeof vol->off);
+    memcpy(origin_out, vol->k.origin, sizeof vol->k.origin);
+    pthread_mutex_unlock(&g_vol_mu);
+    return OSLAM_OK;
+}
+
+int oslam_follow_params_default(const oslam_volume *vol, oslam_follow_params *fp)
+{
+    unsigned n_min;
+    if (!vol || !fp) return fail(OSLAM_E_INVALID, "NULL argument");
+    memset(fp, 0, sizeof *fp);
+    n_min = vol->p.nx < vol->p.ny ? vol->p.nx : vol->p.ny;
+    if (vol->p.nz < n_min) n_min = vol->p.nz;
+    fp->lookahead = (float)(0.5 * (double)vol->p.nz * (double)vol->p.voxel);
+    fp->threshold = (float)n_min / 4.0f;
+    fp->granule = 8;
+    return OSLAM_OK;
+}
+
+int oslam_volume_follow(oslam_volume *vol, const float T_vol_cam[16], const oslam_follow_params *fp, int shift_out[3])
+{
+    int rc, a, moved = 0;
+    oslam_follow_params p;
+    float origin[3];
+    double d[3];
+    if (!vol || !T_vol_cam || !shift_out) return fail(OSLAM_E_INVALID, "NULL argument");
+    if (fp && (!isfinite(fp->lookahead) || !isfinite(fp->threshold) || !(fp->lookahead >= 0.0f) || !(fp->threshold >= 0.0f)))
+        return fail(OSLAM_E_INVALID, "lookahead and threshold must be finite and not negative");
+    if (fp && (fp->granule < 1 || fp->granule > 64)) return fail(OSLAM_E_INVALID, "granule must lie in 1..64");
+    rc = oslam_refine_check_rigid(T_vol_cam);
+    if (rc != OSLAM_OK) return rc;
+    if (fp) p = *fp;
+    else oslam_follow_params_default(vol, &p);
+    pthread_mutex_lock(&g_vol_mu);
+    memcpy(origin, vol->k.origin, sizeof origin);
+    pthread_mutex_unlock(&g_vol_mu);
+    {
+        const unsigned n[3] = {vol->p.nx, vol->p.ny, vol->p.nz};
+        const double h = (double)vol->p.voxel;
+        for (a = 0; a < 3; a++) {
+            const double c = (double)T_vol_cam[4 * a + 3] + (double)p.lookahead * (double)T_vol_cam[4 * a + 2];
+            const double centre = (double)origin[a] + 0.5 * (double)n[a] * h;
+            d[a] = (c - centre) / h;
+            if (!(fabs(d[a]) <= (double)p.threshold)) moved = 1;
+        }
+        for (a = 0; a < 3; a++) {
+            double s = moved ? (double)p.granule * rint(d[a] / (double)p.granule) : 0.0;
+            if (s > (double)n[a]) s = (double)n[a];
+            if (s < -(double)n[a]) s = -(double)n[a];
+            shift_out[a] = (int)s;
+        }
+    }
+    return OSLAM_OK;
 }

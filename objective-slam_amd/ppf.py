@@ -230,6 +230,18 @@ class MeshResult(C.Structure):
                 "launches": int(self.launches), "ms_total": float(self.ms_total)}
 
 
+class ShiftResult(C.Structure):
+    _fields_ = [("offset", C.c_int32 * 3), ("kept", C.c_uint32), ("launches", C.c_uint32), ("ms_total", C.c_float)]
+
+    def asdict(self):
+        return {"offset": tuple(int(x) for x in self.offset), "kept": int(self.kept), "launches": int(self.launches),
+                "ms_total": float(self.ms_total)}
+
+
+class FollowParams(C.Structure):
+    _fields_ = [("lookahead", C.c_float), ("threshold", C.c_float), ("granule", C.c_int), ("reserved", C.c_int * 5)]
+
+
 ARBITRATE_MAX_HYPOTHESES = 1024
 CELL_DTYPE = np.dtype([("code", "<u8"), ("count", "<u4"), ("pad", "<u4")])
 
@@ -344,6 +356,11 @@ _SIGNATURES = {
     "oslam_scene_from_volume": (_i, [_vp, C.POINTER(SurfaceParams), _f, _f, _u, C.POINTER(Params), C.POINTER(_vp),
                                      C.POINTER(_sz)]),
     "oslam_volume_set_voxels": (_i, [_vp, _vp, _vp]),
+    "oslam_volume_shift": (_i, [_vp, _vp, C.POINTER(ShiftResult)]),
+    "oslam_volume_window": (_i, [_vp, _vp, _vp]),
+    "oslam_volume_leaving": (_i, [_vp, _vp, C.POINTER(SurfaceParams), _vp, _vp, _sz, C.POINTER(_sz), C.POINTER(SurfaceResult)]),
+    "oslam_follow_params_default": (_i, [_vp, C.POINTER(FollowParams)]),
+    "oslam_volume_follow": (_i, [_vp, _vp, C.POINTER(FollowParams), _vp]),
     "oslam_mesh_params_default": (_i, [C.POINTER(MeshParams)]),
     "oslam_volume_mesh": (_i, [_vp, C.POINTER(MeshParams), _vp, _vp, _sz, _vp, _sz, C.POINTER(_sz), C.POINTER(_sz),
                                C.POINTER(MeshResult)]),
@@ -1515,6 +1532,24 @@ def default_mesh_params(**kw):
     return p
 
 
+def default_follow_params(vol, **kw):
+    """oslam_follow_params_default for the volume, then the fields given as keywords."""
+    p = FollowParams()
+    _check(lib().oslam_follow_params_default(vol._h, C.byref(p)))
+    for k, v in kw.items():
+        if not hasattr(p, k) or k == "reserved":
+            raise TypeError("unknown follow parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def _shift3(s):
+    s = np.ascontiguousarray(s, np.int32)
+    if s.shape != (3,):
+        raise ValueError("a shift is three integers")
+    return s
+
+
 class Volume:
     """A TSDF volume on the device (oslam_volume): integrate(view, T_vol_cam) fuses a depth view, raycast(...) returns
     the fused surface as a View, track(view, T_prev) follows the camera against it.  T_vol_cam: the camera's pose in the
@@ -1526,6 +1561,7 @@ class Volume:
                                   mu=float(np.float32(4.0) * np.float32(voxel)) if mu is None else mu, max_weight=max_weight)
         self.params = p
         self.T, self._started = np.eye(4, dtype=np.float32), False      # the pose step() keeps
+        self.world = []                 # what step(..., follow=...) shifted out: (points, normals) in the volume frame
         _check(lib().oslam_volume_create(C.byref(p), int(dev), C.byref(self._h)))
 
     def integrate(self, view, T_vol_cam):
@@ -1563,11 +1599,13 @@ class Volume:
                                                 C.byref(res)))
         return To.reshape(4, 4), res.asdict()
 
-    def step(self, view, params=None):
+    def step(self, view, params=None, follow=None):
         """One frame with the pose kept here: the first call integrates at the initial pose (the identity: the
         volume frame is the first camera's);
         a later call tracks from the kept pose and integrates when the result is ok.  -> (T_vol_cam, egomotion result
-        dict, None on the first call)."""
+        dict, None on the first call).
+        follow: follow parameters (default_follow_params).  After a frame was followed and integrated the window then
+        moves as follow(T) says; what leaves it is appended to self.world first."""
         if not self._started:
             self.integrate(view, self.T)
             self._started = True
@@ -1576,7 +1614,44 @@ class Volume:
         if res["ok"]:
             self.T = T
             self.integrate(view, T)
+            if follow is not None:
+                s = self.follow(T, follow)
+                if any(s):
+                    po, no, _ = self.leaving(s)
+                    self.world.append((po, no))
+                    self.shift(s)
         return self.T.copy(), res
+
+    def shift(self, s):
+        """Moves the window of voxels by s = (sx, sy, sz) whole voxels (oslam_volume_shift): -> result dict."""
+        res = ShiftResult()
+        _check(lib().oslam_volume_shift(self._h, _p(_shift3(s)), C.byref(res)))
+        return res.asdict()
+
+    def window(self):
+        """-> (offset, three ints in voxels; origin float32 [3]) of the window (oslam_volume_window)."""
+        off, org = np.zeros(3, np.int32), np.zeros(3, np.float32)
+        _check(lib().oslam_volume_window(self._h, _p(off), _p(org)))
+        return tuple(int(x) for x in off), org
+
+    def leaving(self, s, min_weight=1):
+        """The part of surface(min_weight) that shift(s) would lose, in its order (oslam_volume_leaving): -> (points
+        [n,3], normals [n,3], result dict).  The volume does not change."""
+        s = _shift3(s)
+        sp = default_surface_params(min_weight=min_weight)
+        n, res = C.c_size_t(0), SurfaceResult()
+        _check(lib().oslam_volume_leaving(self._h, _p(s), C.byref(sp), None, None, 0, C.byref(n), C.byref(res)))
+        po, no = np.zeros((n.value, 3), np.float32), np.zeros((n.value, 3), np.float32)
+        if n.value:
+            _check(lib().oslam_volume_leaving(self._h, _p(s), C.byref(sp), _p(po), _p(no), n.value, C.byref(n), C.byref(res)))
+        return po, no, res.asdict()
+
+    def follow(self, T_vol_cam, params=None):
+        """The shift that keeps the window before the camera at T_vol_cam (oslam_volume_follow; host arithmetic): ->
+        (sx, sy, sz), zeros while the camera's look-ahead point is within the threshold of the window's centre."""
+        s = np.zeros(3, np.int32)
+        _check(lib().oslam_volume_follow(self._h, _p(_pose16(T_vol_cam)), C.byref(params) if params is not None else None, _p(s)))
+        return tuple(int(x) for x in s)
 
     def voxels(self):
         """The whole volume as a test tap: -> (q int16 [nz,ny,nx], w uint16 [nz,ny,nx])."""
@@ -1621,6 +1696,7 @@ class Volume:
     def reset(self):
         _check(lib().oslam_volume_reset(self._h))
         self.T, self._started = np.eye(4, dtype=np.float32), False
+        self.world = []
 
     def close(self):
         if self._h:

@@ -30,6 +30,9 @@ configuration; these are not bench lines).  Needs a HIP device.
                                          Volume.surface and one integrate; median of 20 calls each
   python tools/bench_configs.py pyramid  the camera configuration's 640x480 stream: Pyramid(view), egomotion_pyramid and,
                                          in the same run, egomotion on the same pair; median of 20 calls each
+  python tools/bench_configs.py shift    the same volume: Volume.shift by (8, 0, 0) and (-8, 0, 0) alternately,
+                                         Volume.leaving((8, 0, 0)) and, in the same run, one integrate and Volume.surface;
+                                         median of 20 calls each, and the bytes per second the shift loads and stores
 One JSON line each."""
 import importlib, json, os, sys, time
 
@@ -830,6 +833,63 @@ def mesh(calls=20):
     return out
 
 
+def shift(calls=20):
+    """The shifting window (oslam_volume_shift, oslam_volume_leaving) on the fusion configuration's 256^3 volume after its
+    out-and-back stream: the median of `calls` calls of Volume.shift, by (8, 0, 0) and (-8, 0, 0) alternately, of
+    Volume.leaving((8, 0, 0)) and, in the same run, of one integrate and of Volume.surface (the yardsticks); the four
+    alternate, so that drift hits them alike.  The shift's rule figure counts 4 bytes loaded and 4 stored per kept voxel
+    (w > 0 after the shift) and 4 stored per other one; its traffic figure counts what the kernel moves, 4 loaded and 4
+    stored per word that comes from inside the volume, seen or not, and 4 stored per word that does not.  The two
+    64 MiB buffers fit the Infinity Cache, so both are cache figures.  The first shifts clear the slabs that went out; the volume is restored
+    before leaving and surface are timed."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import camera_ref as E
+    world = E.make_world(synth, 0)
+    sweep = E.trajectory(synth, 0, frames=10)
+    cam = E.CAM
+    rendered = [ppf.View(E.render(synth, world, T), cam["fx"], cam["fy"], cam["cx"], cam["cy"], z_min=cam["z_min"],
+                         z_max=cam["z_max"], max_jump=E.MAX_JUMP) for T in sweep]
+    spec = dict(nx=256, ny=256, nz=256, voxel=0.036, origin=[-2.9, -4.3, 0.3], mu=0.288)
+    vol = ppf.Volume(**spec)
+    steps = [vol.step(rendered[k]) for k in list(range(10)) + list(range(8, -1, -1))]
+    q, w = vol.voxels()
+    vol.integrate(rendered[0], vol.T)
+    vol.surface()
+    vol.leaving((8, 0, 0))
+    vol.shift((8, 0, 0))                                            # allocates the second buffer
+    vol.shift((-8, 0, 0))
+    vol.set_voxels(q, w)
+    leave, surf, integ = [], [], []
+    for _ in range(calls):
+        t = time.perf_counter(); _, _, lres = vol.leaving((8, 0, 0)); leave.append(1e3 * (time.perf_counter() - t))
+        t = time.perf_counter(); _, _, sres = vol.surface(); surf.append(1e3 * (time.perf_counter() - t))
+        integ.append(vol.integrate(rendered[0], vol.T)["ms_total"])
+    fwd, back, kept = [], [], 0
+    for k in range(calls):
+        r = vol.shift((8, 0, 0) if k % 2 == 0 else (-8, 0, 0))
+        (fwd if k % 2 == 0 else back).append(r["ms_total"])
+        kept = r["kept"]
+    n_vox = 256 ** 3
+    moved = (256 - 8) * 256 * 256                                   # words that come from inside the volume
+    ms_s = float(np.median(fwd + back))
+    out = {"config": "shift (oslam_volume_shift, oslam_volume_leaving): the fusion configuration's 256^3 volume after its 19-frame stream",
+           "volume": spec, "calls": calls, "step_ok": [None if r is None else r["ok"] for _, r in steps],
+           "shift_ms_median": ms_s, "shift_plus8_ms_median": float(np.median(fwd)), "shift_minus8_ms_median": float(np.median(back)),
+           "shift_kept_last": kept, "shift_rule_bytes_per_s": (8.0 * kept + 4.0 * (n_vox - kept)) / (ms_s * 1e-3),
+           "shift_traffic_bytes": 8 * moved + 4 * (n_vox - moved),
+           "shift_traffic_bytes_per_s": (8.0 * moved + 4.0 * (n_vox - moved)) / (ms_s * 1e-3), "hbm_peak_bytes_per_s": 8e12,
+           "leaving_ms_median": float(np.median(leave)), "leaving_second_call_ms_library": lres["ms_total"],
+           "leaving_crossings": lres["crossings"], "leaving_points": lres["points"], "leaving_launches": lres["launches"],
+           "surface_ms_median": float(np.median(surf)), "surface_crossings": sres["crossings"], "surface_points": sres["points"],
+           "integrate_ms_median": float(np.median(integ)), "volume_bytes": 4 * n_vox,
+           "shift_over_integrate": ms_s / float(np.median(integ)),
+           "leaving_over_surface": float(np.median(leave) / np.median(surf))}
+    for v in rendered:
+        v.close()
+    vol.close()
+    return out
+
+
 def pyramid(calls=20):
     """Image pyramids (oslam_pyramid_create, oslam_pyramid_egomotion) on frames 0 and 1 of the camera configuration's
     640x480 stream: the median of `calls` calls of Pyramid(view), of egomotion_pyramid and, in the same run, of egomotion
@@ -873,4 +933,4 @@ if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "cfg3"
     print(json.dumps({"cfg2": cfg2, "cfg3": cfg3, "cfg3db": cfg3db, "cfg4": cfg4, "cfg5": cfg5, "planes": planes, "db50": db50,
                       "refine": refine, "verify": verify, "instances": instances, "arbitrate": arbitrate, "track": track, "camera": camera,
-                      "fusion": fusion, "surface": surface, "mesh": mesh, "pyramid": pyramid}[which]()), flush=True)
+                      "fusion": fusion, "surface": surface, "mesh": mesh, "shift": shift, "pyramid": pyramid}[which]()), flush=True)
