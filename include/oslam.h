@@ -1243,7 +1243,8 @@ int oslam_mc_table_row(unsigned mc_case, uint8_t *edges_out, unsigned *n_tri_out
  *   crossings after it, none lost and none twice.  The caller extracts before it shifts: the normals still read the
  *   voxels that are about to go.  Normals next to the new border are lost or rounded differently after the shift (a
  *   trilinear read needs its eight corners, and the origin is another float): positions carry over, normals do not.
- *   |s_a| is within 2^20 as for oslam_volume_shift.  Cost: oslam_volume_surface's, with k_leave_count and k_leave_emit.
+ *   |s_a| is within 2^20 as for oslam_volume_shift.  Cost: oslam_volume_surface's, with k_leave_count and k_leave_emit
+ *   (oslam_surface.hip: the bodies of k_surface_count and k_surface_emit, compiled with the leaving mask).
  * oslam_volume_follow is host arithmetic only: it decides a shift and launches nothing.  In double, from the float
  *   inputs: c = t + lookahead * (R02, R12, R22) (the camera's position plus its optical axis), centre_a = origin_a + 0.5 *
  *   n_a * voxel with the window's current origin, d_a = (c_a - centre_a) / voxel.  If |d_a| <= threshold on every axis

@@ -537,6 +537,17 @@ typedef struct oslamk_volume {
     uint32_t max_weight;
 } oslamk_volume;
 
+/* The limits of a volume's side lengths, for every check of them: 16..512 voxels each, and the first mult8_axes of
+ * nx, ny, nz multiples of 8 (0: the extraction; 1: the shift's quads of a row; 3: a volume as it is created) */
+static inline int oslamk_sides_ok(unsigned nx, unsigned ny, unsigned nz, int mult8_axes)
+{
+    const unsigned n[3] = {nx, ny, nz};
+    int a;
+    for (a = 0; a < 3; a++)
+        if (n[a] < 16u || n[a] > 512u || (a < mult8_axes && n[a] % 8u != 0u)) return 0;
+    return 1;
+}
+
 /* rows of [R | t], float32 */
 typedef struct oslamk_pose {
     float T[12];
@@ -552,20 +563,23 @@ int oslamk_tsdf_raycast(const oslamk_volume *vol, const oslamk_view *v, const fl
  * scan and compact path of oslamk_depth_to_cloud); d_out6 = device [n_pix][6]; returns a hipError_t */
 int oslamk_maps_to_cloud(const float *maps, size_t n_pix, float *d_out6, uint32_t *n_out, void *stream);
 
-/* ---- surface extraction (oslam_surface.hip; semantics in include/oslam.h at oslam_volume_surface) ---- */
+/* ---- surface extraction, of the whole surface and of what a shift loses (oslam_surface.hip; semantics in include/oslam.h
+ * at oslam_volume_surface and oslam_volume_leaving) ---- */
 #define OSLAMK_SURF_THREADS 256
 #define OSLAMK_SURF_ITEMS 4           /* chunks of 256 consecutive voxels per workgroup */
 #define OSLAMK_SURF_RUN (OSLAMK_SURF_THREADS * OSLAMK_SURF_ITEMS)   /* consecutive linear voxel indices a workgroup owns */
 
 /* workgroups of the two passes: ceil(nx * ny * nz / OSLAMK_SURF_RUN), at most 2^17 */
 uint32_t oslamk_surface_groups(const oslamk_volume *vol);
-/* first pass and scan: counts [n_groups] leaves as the exclusive offsets of the workgroups' points; totals[0] +=
+/* In both passes shift NULL means the whole surface; otherwise (three ints that pass oslamk_shift_ok) only the crossings
+ * that a shift by it loses, over the same workgroups and in the same order.
+ * first pass and scan: counts [n_groups] leaves as the exclusive offsets of the workgroups' points; totals[0] +=
  * crossings (zeroed by the caller), totals[1] = points */
-int oslamk_surface_count(const oslamk_volume *vol, uint32_t min_weight, uint32_t n_groups, uint32_t *counts, uint32_t *totals,
-                         void *stream);
+int oslamk_surface_count(const oslamk_volume *vol, const int *shift, uint32_t min_weight, uint32_t n_groups, uint32_t *counts,
+                         uint32_t *totals, void *stream);
 /* second pass: out6 = device [n_points][6] (x y z nx ny nz), offsets and n_points as oslamk_surface_count left them */
-int oslamk_surface_emit(const oslamk_volume *vol, uint32_t min_weight, uint32_t n_groups, const uint32_t *offsets,
-                        uint32_t n_points, float *out6, void *stream);
+int oslamk_surface_emit(const oslamk_volume *vol, const int *shift, uint32_t min_weight, uint32_t n_groups,
+                        const uint32_t *offsets, uint32_t n_points, float *out6, void *stream);
 /* the scan alone: counts [n] (n <= 2^17) becomes its exclusive prefix sums in place, *total_out = the sum */
 int oslamk_surface_scan(uint32_t *counts, uint32_t n, uint32_t *total_out, void *stream);
 
@@ -588,17 +602,24 @@ int oslamk_mesh_triangles(const oslamk_volume *vol, uint32_t min_weight, uint32_
                           uint32_t n_tris, const uint32_t *edge_id, uint32_t n_verts, uint32_t *tri, uint32_t *totals,
                           void *stream);
 
-/* ---- the shifting window (oslam_shift.hip; semantics in include/oslam.h at oslam_volume_shift) ---- */
+/* ---- the shifting window: the limit of a shift, and the copy (oslam_shift.hip; semantics in include/oslam.h at
+ * oslam_volume_shift).  What a shift loses of the surface is the surface extraction's, above ---- */
 #define OSLAMK_SHIFT_MAX (1 << 20)    /* the largest shift, and the largest window offset, per axis in voxels: exact as a float */
+/* a shift as the kernels take it, by value */
+typedef struct oslamk_shift3 {
+    int s[3];
+} oslamk_shift3;
+/* the limit of a shift triple, and of a window offset, for every check of it */
+static inline int oslamk_shift_ok(const int s[3])
+{
+    int a;
+    for (a = 0; a < 3; a++)
+        if (s[a] < -OSLAMK_SHIFT_MAX || s[a] > OSLAMK_SHIFT_MAX) return 0;
+    return 1;
+}
 /* dst [nx*ny*nz] (not vol->words) gets vol's words moved by shift, zeros where no source voxel exists; *kept (zeroed by
  * the caller) += the words of dst with w > 0.  vol->words is only read: the caller swaps the two buffers */
 int oslamk_tsdf_shift(const oslamk_volume *vol, uint32_t *dst, const int shift[3], uint32_t *kept, void *stream);
-/* oslamk_surface_count and oslamk_surface_emit restricted to the crossings that a shift by shift[3] loses; workgroups,
- * counts, totals, offsets and out6 as there */
-int oslamk_leave_count(const oslamk_volume *vol, const int shift[3], uint32_t min_weight, uint32_t n_groups, uint32_t *counts,
-                       uint32_t *totals, void *stream);
-int oslamk_leave_emit(const oslamk_volume *vol, const int shift[3], uint32_t min_weight, uint32_t n_groups,
-                      const uint32_t *offsets, uint32_t n_points, float *out6, void *stream);
 
 #ifdef __cplusplus
 }

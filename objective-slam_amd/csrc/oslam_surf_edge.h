@@ -1,6 +1,6 @@
 /*
- * oslam_surf_edge.h -- what the surface extraction (oslam_surface.hip) and the mesh extraction (oslam_mesh.hip) share:
- * the shape of a workgroup's run, the "seen" rule and the integer sign test, the crossings of a voxel's three owned
+ * oslam_surf_edge.h -- what the surface extraction (oslam_surface.hip: the whole surface and what a shift loses of it)
+ * and the mesh extraction (oslam_mesh.hip) share: the shape of a workgroup's run, the "seen" rule and the integer sign test, the crossings of a voxel's three owned
  * edges, the point of a crossing and its normal (include/oslam.h at oslam_volume_surface), the rank of a crossing in
  * its chunk.  Device code, and the check of their launchers.
  */
@@ -126,8 +126,7 @@ __device__ __forceinline__ uint32_t surf_chunk_rank(uint32_t has, uint32_t *row,
 /* the launchers' check of a volume, the "seen" weight and the number of workgroups; *n_vox = the volume's voxels */
 static inline bool surf_launch_ok(const oslamk_volume *vol, uint32_t min_w, uint32_t n_groups, uint32_t *n_vox)
 {
-    if (!(vol && vol->words && vol->nx >= 16 && vol->ny >= 16 && vol->nz >= 16 && vol->nx <= 512 && vol->ny <= 512 &&
-          vol->nz <= 512 && vol->voxel > 0.0f && min_w >= 1u && min_w <= 65535u))
+    if (!(vol && vol->words && oslamk_sides_ok(vol->nx, vol->ny, vol->nz, 0) && vol->voxel > 0.0f && min_w >= 1u && min_w <= 65535u))
         return false;
     *n_vox = (uint32_t)vol->nx * (uint32_t)vol->ny * (uint32_t)vol->nz;          /* at most 2^27: 3 * n_vox fits uint32 */
     return n_groups == oslamk_surface_groups(vol);

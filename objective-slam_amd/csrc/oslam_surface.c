@@ -1,7 +1,7 @@
 /*
  * oslam_surface.c -- the fused surface of a TSDF volume as a cloud (include/oslam.h at oslam_volume_surface) and as a
  * triangle mesh (oslam_volume_mesh): the host side of the kernels in oslam_surface.hip and oslam_mesh.hip, and of the
- * extraction of what a shift loses (oslam_volume_leaving; k_leave_count and k_leave_emit of oslam_shift.hip).  A call
+ * extraction of what a shift loses (oslam_volume_leaving; the same launchers of oslam_surface.hip with a shift).  A call
  * counts, waits for the totals, allocates exactly that and emits, under the volume lock of oslam_volume.c.
  */
 #include "oslam_internal.h"
@@ -36,15 +36,13 @@ static int surface_passes(oslam_volume *vol, const int *shift, unsigned min_weig
     tot[0] = tot[1] = 0;
     *launches = 0;
     KCHK(oslam_counters_open(&d_cnt, n_groups, stream));
-    if (shift) KCHK(oslamk_leave_count(&vol->k, shift, min_weight, n_groups, d_cnt + 64, d_cnt, stream));
-    else KCHK(oslamk_surface_count(&vol->k, min_weight, n_groups, d_cnt + 64, d_cnt, stream));
+    KCHK(oslamk_surface_count(&vol->k, shift, min_weight, n_groups, d_cnt + 64, d_cnt, stream));
     HIPCHK(hipMemcpyAsync(tot, d_cnt, sizeof(uint32_t) * 2, hipMemcpyDeviceToHost, (hipStream_t)stream));
     HIPCHK(hipStreamSynchronize((hipStream_t)stream));
     *launches = 2;
     if (d_out6 && tot[1] > 0 && (size_t)tot[1] <= cap) {
         KCHK(oslam_dev_alloc((void **)d_out6, sizeof(float) * 6 * (size_t)tot[1]));
-        if (shift) KCHK(oslamk_leave_emit(&vol->k, shift, min_weight, n_groups, d_cnt + 64, tot[1], *d_out6, stream));
-        else KCHK(oslamk_surface_emit(&vol->k, min_weight, n_groups, d_cnt + 64, tot[1], *d_out6, stream));
+        KCHK(oslamk_surface_emit(&vol->k, shift, min_weight, n_groups, d_cnt + 64, tot[1], *d_out6, stream));
         HIPCHK(hipStreamSynchronize((hipStream_t)stream));
         *launches = 3;
     }
@@ -108,10 +106,8 @@ int oslam_volume_surface(oslam_volume *vol, const oslam_surface_params *sp, floa
 int oslam_volume_leaving(oslam_volume *vol, const int shift[3], const oslam_surface_params *sp, float *xyz_out, float *nrm_out,
                          size_t cap, size_t *n_out, oslam_surface_result *res)
 {
-    int a;
     if (!vol || !shift) return fail(OSLAM_E_INVALID, "NULL argument");
-    for (a = 0; a < 3; a++)
-        if (shift[a] < -OSLAMK_SHIFT_MAX || shift[a] > OSLAMK_SHIFT_MAX) return fail(OSLAM_E_INVALID, "a shift is at most 2^20 voxels");
+    if (!oslamk_shift_ok(shift)) return fail(OSLAM_E_INVALID, "a shift is at most 2^20 voxels");
     return surface_call(vol, shift, sp, xyz_out, nrm_out, cap, n_out, res);
 }
 

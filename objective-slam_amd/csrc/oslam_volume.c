@@ -6,7 +6,8 @@
  * oslam_pyramid_egomotion (one body, track_from_raycast); oslam_view_to_cloud runs the depth front end's compaction
  * over a view's maps.  oslam_volume_shift moves the window of voxels the volume holds (k_tsdf_shift of oslam_shift.hip
  * into a second buffer, then a swap of the two), oslam_volume_follow decides such a move on the host.  The extraction of
- * the fused volume, or of what a shift loses, as a cloud or a triangle list is oslam_surface.c.
+ * the fused volume, or of what a shift loses, as a cloud or a triangle list is oslam_surface.c (kernels: oslam_surface.hip
+ * and oslam_mesh.hip).  The limits of a volume's sides and of a shift are oslam_kernels.h's.
  */
 #include <math.h>
 #include <pthread.h>
@@ -33,13 +34,10 @@ int oslam_volume_params_default(oslam_volume_params *p)
 
 static int check_params(const oslam_volume_params *p)
 {
-    const unsigned n[3] = {p->nx, p->ny, p->nz};
-    int a;
     if (!isfinite(p->voxel) || !isfinite(p->mu) || !isfinite(p->origin[0]) || !isfinite(p->origin[1]) || !isfinite(p->origin[2]))
         return fail(OSLAM_E_INVALID, "volume parameters must be finite");
-    for (a = 0; a < 3; a++)
-        if (n[a] < 16 || n[a] > 512 || n[a] % 8 != 0)
-            return fail(OSLAM_E_INVALID, "voxels per side must lie in 16..512 and be a multiple of 8");
+    if (!oslamk_sides_ok(p->nx, p->ny, p->nz, 3))
+        return fail(OSLAM_E_INVALID, "voxels per side must lie in 16..512 and be a multiple of 8");
     if (!(p->voxel > 0.0f)) return fail(OSLAM_E_INVALID, "voxel must be > 0");
     if (!(p->mu >= 2.0f * p->voxel)) return fail(OSLAM_E_INVALID, "mu must be at least 2 voxels");
     if (p->max_weight < 1 || p->max_weight > 65535) return fail(OSLAM_E_INVALID, "max_weight must lie in 1..65535");
@@ -440,13 +438,10 @@ int oslam_volume_shift(oslam_volume *vol, const int shift[3], oslam_shift_result
     uint32_t *d_cnt = NULL, *spare = NULL, kept = 0;
     void *stream = oslam_stream();
     if (!vol || !shift) return fail(OSLAM_E_INVALID, "NULL argument");
-    for (a = 0; a < 3; a++)
-        if (shift[a] < -OSLAMK_SHIFT_MAX || shift[a] > OSLAMK_SHIFT_MAX) return fail(OSLAM_E_INVALID, "a shift is at most 2^20 voxels");
+    if (!oslamk_shift_ok(shift)) return fail(OSLAM_E_INVALID, "a shift is at most 2^20 voxels");
     pthread_mutex_lock(&g_vol_mu);
-    for (a = 0; a < 3; a++) {
-        off[a] = vol->off[a] + shift[a];
-        if (off[a] < -OSLAMK_SHIFT_MAX || off[a] > OSLAMK_SHIFT_MAX) { rc = fail(OSLAM_E_INVALID, "the window's offset is at most 2^20 voxels"); goto done; }
-    }
+    for (a = 0; a < 3; a++) off[a] = vol->off[a] + shift[a];
+    if (!oslamk_shift_ok(off)) { rc = fail(OSLAM_E_INVALID, "the window's offset is at most 2^20 voxels"); goto done; }
     if (res) memset(res, 0, sizeof *res);
     if (!(shift[0] | shift[1] | shift[2])) {
         if (res) memcpy(res->offset, off, sizeof off);

@@ -187,8 +187,8 @@ __global__ __launch_bounds__(256) void k_tsdf_raycast(const oslamk_volume vol, c
 
 static bool volume_ok(const oslamk_volume *vol)
 {
-    return vol->words && vol->nx >= 16 && vol->ny >= 16 && vol->nz >= 16 && vol->nx <= 512 && vol->ny <= 512 && vol->nz <= 512 &&
-           vol->nx % 8 == 0 && vol->ny % 8 == 0 && vol->nz % OSLAMK_VOL_ZRUN == 0 && vol->voxel > 0.0f && vol->mu > 0.0f;
+    return vol->words && oslamk_sides_ok(vol->nx, vol->ny, vol->nz, 2) && vol->nz % OSLAMK_VOL_ZRUN == 0 && vol->voxel > 0.0f &&
+           vol->mu > 0.0f;
 }
 
 extern "C" int oslamk_tsdf_integrate(const oslamk_volume *vol, const oslamk_view *v, const float *T12, uint32_t *count,

@@ -1638,13 +1638,7 @@ class Volume:
         """The part of surface(min_weight) that shift(s) would lose, in its order (oslam_volume_leaving): -> (points
         [n,3], normals [n,3], result dict).  The volume does not change."""
         s = _shift3(s)
-        sp = default_surface_params(min_weight=min_weight)
-        n, res = C.c_size_t(0), SurfaceResult()
-        _check(lib().oslam_volume_leaving(self._h, _p(s), C.byref(sp), None, None, 0, C.byref(n), C.byref(res)))
-        po, no = np.zeros((n.value, 3), np.float32), np.zeros((n.value, 3), np.float32)
-        if n.value:
-            _check(lib().oslam_volume_leaving(self._h, _p(s), C.byref(sp), _p(po), _p(no), n.value, C.byref(n), C.byref(res)))
-        return po, no, res.asdict()
+        return self._points(lib().oslam_volume_leaving, (self._h, _p(s)), min_weight)
 
     def follow(self, T_vol_cam, params=None):
         """The shift that keeps the window before the camera at T_vol_cam (oslam_volume_follow; host arithmetic): ->
@@ -1671,12 +1665,18 @@ class Volume:
     def surface(self, min_weight=1):
         """Every zero crossing of the fused TSDF along a voxel edge as a point with its outward normal, in the volume
         frame and in voxel order (oslam_volume_surface): -> (points [n,3], normals [n,3], result dict)."""
+        return self._points(lib().oslam_volume_surface, (self._h,), min_weight)
+
+    @staticmethod
+    def _points(call, head, min_weight):
+        """The protocol of oslam_volume_surface and oslam_volume_leaving: call(*head, params, outputs...) once without
+        outputs for the number of points, then with arrays of that size: -> (points [n,3], normals [n,3], result dict)."""
         sp = default_surface_params(min_weight=min_weight)
         n, res = C.c_size_t(0), SurfaceResult()
-        _check(lib().oslam_volume_surface(self._h, C.byref(sp), None, None, 0, C.byref(n), C.byref(res)))
+        _check(call(*head, C.byref(sp), None, None, 0, C.byref(n), C.byref(res)))
         po, no = np.zeros((n.value, 3), np.float32), np.zeros((n.value, 3), np.float32)
         if n.value:
-            _check(lib().oslam_volume_surface(self._h, C.byref(sp), _p(po), _p(no), n.value, C.byref(n), C.byref(res)))
+            _check(call(*head, C.byref(sp), _p(po), _p(no), n.value, C.byref(n), C.byref(res)))
         return po, no, res.asdict()
 
     def mesh(self, min_weight=1, normals=True):
