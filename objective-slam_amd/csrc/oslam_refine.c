@@ -102,8 +102,9 @@ void oslam_refine_release_grids(oslam_scene *s)
     s->grids = NULL;
 }
 
-/* A grid of the scene whose cells serve `radius`: a cached one with an edge in [radius, 2 radius], or a new one
- * (enqueued on the stream; *built = 1). */
+/* A grid of the scene whose cells serve `radius`: a cached one with an edge in [radius, 2 radius] (the smallest such
+ * edge), else the one that was built for exactly this radius (a grid enlarged to stay within OSLAMK_GRID_MAX_CELLS has an
+ * edge above 2 radius: no other grid of this radius would be finer), else a new one (enqueued on the stream; *built = 1). */
 static int scene_grid(oslam_scene *s, float radius, oslamk_grid *out, int *built)
 {
     int rc = OSLAM_OK, k, slot = -1, a;
@@ -122,6 +123,8 @@ static int scene_grid(oslam_scene *s, float radius, oslamk_grid *out, int *built
             (slot < 0 || e->edge < s->grids[slot].edge))
             slot = k;
     }
+    for (k = 0; k < GRID_SLOTS && slot < 0; k++)
+        if (s->grids[k].radius == radius) slot = k;
     if (slot >= 0) {
         s->grids[slot].used = g_calls;
         *out = s->grids[slot].g;

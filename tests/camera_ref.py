@@ -66,13 +66,7 @@ def pinned_sums(terms):
     """terms float32 [n, k] (zeros where an index has no correspondence) -> float64 [k] in the header's order."""
     n, k = terms.shape
     nb = (n + THREADS - 1) // THREADS
-    t = np.zeros((nb * THREADS, k), np.float32)
-    t[:n] = terms
-    t = t.reshape(nb, THREADS // 64, 64, k)
-    for off in (32, 16, 8, 4, 2, 1):
-        t[:, :, :off] = t[:, :, :off] + t[:, :, off:2 * off]
-    wv = t[:, :, 0]                                       # [nb, 4, k]
-    blocks = (((wv[:, 0] + wv[:, 1]) + wv[:, 2]) + wv[:, 3]).astype(np.float64)
+    blocks = refine_ref.block_sums_f32(terms).astype(np.float64)          # the tree over 64, the four 64s of a block
     chunk = (nb + MAX_SLOTS - 1) // MAX_SLOTS
     G = (nb + chunk - 1) // chunk
     slots = np.zeros((G, k))
