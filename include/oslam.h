@@ -1256,8 +1256,8 @@ int oslam_mc_table_row(unsigned mc_case, uint8_t *edges_out, unsigned *n_tri_out
  *   T_vol_cam, shift_out or fp (of oslam_follow_params_default), fields that are not finite, lookahead < 0,
  *   threshold < 0, a granule outside 1..64, a T that is not rigid and the surface arguments oslam_volume_surface
  *   refuses are OSLAM_E_INVALID.  Every call takes the lock the other calls on volumes take.
- * Out of scope: reloading what left when the window returns, merging what left with the live surface into one mesh,
- *   colour, several GPUs, any change to oslam_tracker. */
+ * Out of scope: merging what left with the live surface into one mesh, colour, several GPUs, any change to
+ *   oslam_tracker.  Reloading what left when the window returns is the voxel store's, below (oslam_volume_shift_world). */
 typedef struct oslam_shift_result {
     int32_t offset[3];         /* the window's offset after the call, voxels */
     uint32_t kept;             /* voxels with w > 0 after the shift */
@@ -1278,6 +1278,95 @@ int oslam_volume_leaving(oslam_volume *vol, const int shift[3], const oslam_surf
                          size_t cap, size_t *n_out, oslam_surface_result *res);
 int oslam_follow_params_default(const oslam_volume *vol, oslam_follow_params *fp);
 int oslam_volume_follow(oslam_volume *vol, const float T_vol_cam[16], const oslam_follow_params *fp, int shift_out[3]);
+
+/* ---- the voxel store: the voxels that leave the shifting window are kept on the host and come back when the window
+ * returns (the other half of large-scale KinFu's shifting volume).  The window and the store together hold every seen
+ * voxel exactly once.  Words are 32-bit integers and every statement here is exact; the restatement in numpy is
+ * tests/reload_ref.py.  A volume that never meets a store behaves bit for bit as one without this section.
+ *
+ * Global coordinate.  The window voxel (i, j, k) of a volume with offset off has g = (i + off_x, j + off_y, k + off_z).
+ *   By the limits of oslam_volume_shift |g_a| <= 2^20 + 512.
+ * A store (oslam_world) is a host-side map from g to words, made for one (voxel, origin0[3]): oslam_world_create checks
+ *   that they are finite and voxel > 0, oslam_world_params_of fills them from a volume (max_bytes 0).  A volume whose
+ *   voxel and created origin do not have the same float bits is refused by oslam_volume_shift_world with
+ *   OSLAM_E_INVALID.  The store needs no device.
+ * Seen.  A word is seen iff word >> 16 != 0 (w > 0, k_tsdf_shift's kept).  Only seen words are stored: a word with w == 0
+ *   and q != 0 that leaves is dropped and comes back as 0.
+ * Who leaves, who enters.  Voxel (i, j, k) leaves under the shift s iff not (0 <= i - s_x < nx and likewise for y and
+ *   z): oslam_volume_leaving's rule.  New voxel (i, j, k) enters iff its source (i + s_x, j + s_y, k + s_z) does not exist
+ *   in the old window.
+ * oslam_volume_shift_world(vol, world, s, res):
+ *   1. every seen leaving voxel goes into the store under its g; a key already present (the caller seeded the store, or
+ *      shares it between volumes) is overwritten by the leaving word;
+ *   2. the window moves exactly as oslam_volume_shift moves it: the same words, off and derived origin;
+ *   3. every store entry whose g lies in the entering region is removed from the store and written to its voxel, which
+ *      the plain shift left at 0;
+ *   4. res (may be NULL): offset[3] after the call, kept = the voxels with w > 0 after all of that, stored = the seen
+ *      leaving voxels, reloaded = the entries taken from the store.
+ *   |s_a| >= n_a is legal: everything leaves and the whole new window enters.  A zero shift returns at once with
+ *   launches = 0 and kept = stored = reloaded = 0.  The limits on s and off are oslam_volume_shift's.
+ *   So, with no integration in between, the set {seen voxels of the window by g} u {store} does not change over any
+ *   sequence of such shifts and its two parts are disjoint; any path of shifts that returns to an earlier offset restores
+ *   the window's seen words bit for bit and leaves the store as it was then.
+ *   Failure.  Every error is found before k_tsdf_shift is launched, and then neither the volume, the window nor the store
+ *   has changed: NULL arguments and a shift or an offset beyond 2^20 (OSLAM_E_INVALID), an incompatible store
+ *   (OSLAM_E_INVALID), the store's max_bytes exceeded by the bricks the leaving voxels need (OSLAM_E_LIMIT), a failed
+ *   host or device allocation (OSLAM_E_NOMEM).  The order: pack and copy down; create the bricks the leaving records
+ *   need, empty; collect the entering records without changing the store; copy them up, launch k_tsdf_shift and
+ *   k_tsdf_unpack; after the host wait write the leaving words into the store, clear the reloaded ones, free the bricks
+ *   that became empty and swap the buffers.  A failure after the bricks were created removes them again.
+ *   Cost.  launches = 2 (k_tsdf_pack_count and the scan of its counts) + 1 when something seen leaves (k_tsdf_pack_emit)
+ *   + 1 (k_tsdf_shift) + 1 when something is reloaded (k_tsdf_unpack): 5 with records on both sides, 3 with none.  Host
+ *   waits: one for the pack's total, which sizes the records' buffer and their copy; one for that copy when something
+ *   seen leaves (the bricks are created from the records, before the shift is launched); one for k_tsdf_shift and
+ *   k_tsdf_unpack.  The records' staging buffers are pinned, kept with the store and grown on demand: after the first
+ *   shifts a call allocates no host memory beyond new bricks.
+ * The store: bricks of 8 x 8 x 8 words keyed by floor(g_a / 8) (an arithmetic shift: g may be negative) in an
+ *   open-addressing table that grows; a brick carries its number of seen words and is freed when that reaches 0.
+ *   max_bytes bounds bricks plus table (0 = 1 GiB): a call that would exceed it returns OSLAM_E_LIMIT and changes
+ *   nothing.  The store has its own lock, taken inside the lock of the calls on volumes and never the other way round.
+ * oslam_world_put stores n words under g [n][3]; unseen words are skipped, a later record of the same g wins, |g_a| beyond
+ *   2^20 + 512 is OSLAM_E_INVALID.  oslam_world_box reads the box lo <= g < hi densely into words_out
+ *   [hz - lz][hy - ly][hx - lx], 0 where nothing is stored; take != 0 also removes what it read.  lo_a <= hi_a and both
+ *   within 2^21 in size, otherwise OSLAM_E_INVALID; a box of more than 2^27 voxels is OSLAM_E_LIMIT.
+ *   oslam_world_stats_get: stored voxels, bricks, bytes of bricks plus table, and the bounding box of the stored g (hi
+ *   exclusive, all 0 when empty).  oslam_world_clear empties the store.  oslam_volume_reset does not touch a store.
+ * oslam_volume_pack is a test tap and changes nothing: the records {lin, word} that k_tsdf_pack_count and
+ *   k_tsdf_pack_emit make for this shift, lin = (k * ny + j) * nx + i of the old window, ascending.  cap == 0 counts only
+ *   (the outputs may be NULL); more records than cap is OSLAM_E_LIMIT with the count in *n_out and nothing written.
+ * Out of scope: one surface or mesh of store plus window, store files on disk, colour, several GPUs, any change to
+ *   oslam_tracker. */
+typedef struct oslam_world oslam_world;
+typedef struct oslam_world_params {
+    float voxel;               /* the voxel size of the volumes the store serves, metres */
+    float origin0[3];          /* their created origin */
+    uint64_t max_bytes;        /* bound on bricks plus table, 0 = 1 GiB */
+    int reserved[4];
+} oslam_world_params;
+
+typedef struct oslam_world_stats {
+    uint64_t voxels, bricks, bytes;
+    int32_t lo[3], hi[3];      /* bounding box of the stored g, hi exclusive; all 0 when empty */
+} oslam_world_stats;
+
+typedef struct oslam_reload_result {
+    int32_t offset[3];         /* the window's offset after the call, voxels */
+    uint32_t kept;             /* voxels with w > 0 after the shift and the reload */
+    uint32_t stored;           /* seen voxels that left, now in the store */
+    uint32_t reloaded;         /* entries taken from the store into the window */
+    uint32_t launches;
+    float ms_total;            /* whole call, host clock */
+} oslam_reload_result;
+
+int oslam_world_params_of(const oslam_volume *vol, oslam_world_params *p);
+int oslam_world_create(const oslam_world_params *p, oslam_world **out);
+int oslam_world_destroy(oslam_world *w);
+int oslam_world_clear(oslam_world *w);
+int oslam_world_stats_get(oslam_world *w, oslam_world_stats *out);
+int oslam_world_put(oslam_world *w, const int32_t *g, const uint32_t *words, size_t n);
+int oslam_world_box(oslam_world *w, const int32_t lo[3], const int32_t hi[3], uint32_t *words_out, int take);
+int oslam_volume_shift_world(oslam_volume *vol, oslam_world *w, const int shift[3], oslam_reload_result *res);
+int oslam_volume_pack(oslam_volume *vol, const int shift[3], uint32_t *lin_out, uint32_t *word_out, size_t cap, size_t *n_out);
 
 /* ---- parity taps (tests): values the reference materialises as arrays.
  * Scene::getHashKeys row r (scene.cu:49-54): keys_out[n] of reference point r,

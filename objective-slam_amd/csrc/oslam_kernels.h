@@ -621,6 +621,25 @@ static inline int oslamk_shift_ok(const int s[3])
  * the caller) += the words of dst with w > 0.  vol->words is only read: the caller swaps the two buffers */
 int oslamk_tsdf_shift(const oslamk_volume *vol, uint32_t *dst, const int shift[3], uint32_t *kept, void *stream);
 
+/* ---- the voxels a shift moves out, as records for the voxel store, and the store's records back into the window
+ * (oslam_reload.hip; semantics in include/oslam.h at oslam_volume_shift_world).  A record is two words: the linear index
+ * lin = (k * ny + j) * nx + i, then the voxel's word ---- */
+#define OSLAMK_PACK_THREADS 256
+#define OSLAMK_PACK_ITEMS 4           /* chunks of 256 consecutive voxels per workgroup */
+#define OSLAMK_PACK_RUN (OSLAMK_PACK_THREADS * OSLAMK_PACK_ITEMS)   /* consecutive linear voxel indices a workgroup owns */
+/* workgroups of the two passes: ceil(nx * ny * nz / OSLAMK_PACK_RUN), at most 2^17 */
+uint32_t oslamk_pack_groups(const oslamk_volume *vol);
+/* first pass and scan: counts [n_groups] leaves as the exclusive offsets of the workgroups' records, *total_out = the
+ * voxels with w > 0 that lie outside the window after the shift */
+int oslamk_tsdf_pack_count(const oslamk_volume *vol, const int shift[3], uint32_t n_groups, uint32_t *counts, uint32_t *total_out,
+                           void *stream);
+/* second pass: rec_out = device [n_rec][2] (8-byte aligned), ascending lin; offsets and n_rec as the first pass left them */
+int oslamk_tsdf_pack_emit(const oslamk_volume *vol, const int shift[3], uint32_t n_groups, const uint32_t *offsets, uint32_t n_rec,
+                          uint32_t *rec_out, void *stream);
+/* dst[lin] = word for each of the n_rec records of recs = device [n_rec][2] (8-byte aligned, distinct lin, n_rec at most
+ * nx * ny * nz); a record whose lin is not below nx * ny * nz is skipped */
+int oslamk_tsdf_unpack(uint32_t *dst, int nx, int ny, int nz, const uint32_t *recs, uint32_t n_rec, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,7 +5,9 @@
  * ray cast and oslam_view_egomotion, oslam_volume_track_pyramid over the ray cast, a pyramid of it and
  * oslam_pyramid_egomotion (one body, track_from_raycast); oslam_view_to_cloud runs the depth front end's compaction
  * over a view's maps.  oslam_volume_shift moves the window of voxels the volume holds (k_tsdf_shift of oslam_shift.hip
- * into a second buffer, then a swap of the two), oslam_volume_follow decides such a move on the host.  The extraction of
+ * into a second buffer, then a swap of the two), oslam_volume_follow decides such a move on the host,
+ * oslam_volume_shift_world makes it through a voxel store that keeps what leaves and gives back what returns (the store:
+ * oslam_world.c; kernels: oslam_reload.hip).  The extraction of
  * the fused volume, or of what a shift loses, as a cloud or a triangle list is oslam_surface.c (kernels: oslam_surface.hip
  * and oslam_mesh.hip).  The limits of a volume's sides and of a shift are oslam_kernels.h's.
  */
@@ -13,6 +15,7 @@
 #include <pthread.h>
 
 #include "oslam_internal.h"
+#include "oslam_world.h"
 
 /* calls on volumes, oslam_view_to_cloud and oslam_view_maps take turns.  Lock order: g_vol_mu, then the lock of oslam_view_egomotion, then the views' maps */
 static pthread_mutex_t g_vol_mu = PTHREAD_MUTEX_INITIALIZER;
@@ -474,6 +477,268 @@ done:
     pthread_mutex_unlock(&g_vol_mu);
     if (d_cnt) oslam_dev_free(d_cnt);
     if (rc == OSLAM_OK && res) res->ms_total = (float)(now_ms() - t0);
+    return rc;
+}
+
+/* ---- the shift through the voxel store (include/oslam.h at oslam_volume_shift_world; kernels: oslam_reload.hip; the
+ * store: oslam_world.c) ---- */
+int oslam_world_params_of(const oslam_volume *vol, oslam_world_params *p)
+{
+    if (!vol || !p) return fail(OSLAM_E_INVALID, "NULL argument");
+    memset(p, 0, sizeof *p);
+    p->voxel = vol->p.voxel;
+    memcpy(p->origin0, vol->p.origin, sizeof p->origin0);
+    return OSLAM_OK;
+}
+
+/* The two passes of the pack, with g_vol_mu held and the volume's device bound: *n_rec = the seen voxels that leave
+ * under shift; at most cap of them are packed, into *d_rec = device [n_rec][2] (NULL otherwise).  One host wait, for the
+ * total; the second pass is only launched.  The caller frees *d_cnt and *d_rec after its own wait */
+static int pack_leaving(oslam_volume *vol, const int shift[3], size_t cap, uint32_t **d_cnt, uint32_t **d_rec, uint32_t *n_rec,
+                        uint32_t *launches)
+{
+    int rc = OSLAM_OK;
+    const uint32_t n_groups = oslamk_pack_groups(&vol->k);
+    void *stream = oslam_stream();
+    *n_rec = 0;
+    KCHK(oslam_counters_open(d_cnt, n_groups, stream));            /* the total in the first 256 bytes, then one counter per workgroup */
+    KCHK(oslamk_tsdf_pack_count(&vol->k, shift, n_groups, *d_cnt + 64, *d_cnt, stream));
+    *launches += 2;
+    HIPCHK(hipMemcpyAsync(n_rec, *d_cnt, sizeof *n_rec, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    if (*n_rec > 0 && (size_t)*n_rec <= cap) {
+        KCHK(oslam_dev_alloc((void **)d_rec, sizeof(uint32_t) * 2 * (size_t)*n_rec));
+        KCHK(oslamk_tsdf_pack_emit(&vol->k, shift, n_groups, *d_cnt + 64, *n_rec, *d_rec, stream));
+        *launches += 1;
+    }
+done:
+    return rc;
+}
+
+static void stage_release(void *p) { (void)hipHostFree(p); }
+
+/* a pinned staging buffer of the store with room for bytes: grown by half as much again, so a stream of similar shifts
+ * allocates once */
+static int stage_fit(oslam_world_stage *st, size_t bytes)
+{
+    void *p = NULL;
+    const size_t want = bytes + bytes / 2;
+    if (st->bytes >= bytes) return OSLAM_OK;
+    if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(OSLAM_E_NOMEM, "no pinned host memory for the records of the shift");
+    }
+    if (st->p) st->release(st->p);
+    st->p = p;
+    st->bytes = want;
+    st->release = stage_release;
+    return OSLAM_OK;
+}
+
+/* The entering region, the window at off_new minus the window at off_old in global coordinates, as at most 7 disjoint
+ * boxes lo <= g < hi: axis by axis, the slabs of what remains that lie outside the old window, then the rest restricted
+ * to the overlap; all of what remains as soon as an axis has no overlap.  -> the number of boxes */
+static int entering_boxes(const int off_old[3], const int off_new[3], const unsigned n[3], int32_t lo[7][3], int32_t hi[7][3])
+{
+    int a, nb = 0;
+    int32_t cl[3], ch[3];
+    for (a = 0; a < 3; a++) {
+        cl[a] = off_new[a];
+        ch[a] = off_new[a] + (int)n[a];
+    }
+    for (a = 0; a < 3; a++) {
+        const int32_t ol = cl[a] > off_old[a] ? cl[a] : off_old[a];
+        const int32_t oh = ch[a] < off_old[a] + (int)n[a] ? ch[a] : off_old[a] + (int)n[a];
+        if (ol >= oh) {
+            memcpy(lo[nb], cl, sizeof cl);
+            memcpy(hi[nb], ch, sizeof ch);
+            return nb + 1;
+        }
+        if (cl[a] < ol) {
+            memcpy(lo[nb], cl, sizeof cl);
+            memcpy(hi[nb], ch, sizeof ch);
+            hi[nb++][a] = ol;
+        }
+        if (oh < ch[a]) {
+            memcpy(lo[nb], cl, sizeof cl);
+            memcpy(hi[nb], ch, sizeof ch);
+            lo[nb++][a] = oh;
+        }
+        cl[a] = ol;
+        ch[a] = oh;
+    }
+    return nb;                                                      /* what remains is the overlap: it does not enter */
+}
+
+/* the global coordinate of the old window's voxel lin */
+static void global_of(const oslam_volume *vol, uint32_t lin, int32_t g[3])
+{
+    const uint32_t row = lin / vol->p.nx;
+    g[0] = (int32_t)(lin - row * vol->p.nx) + vol->off[0];
+    g[1] = (int32_t)(row % vol->p.ny) + vol->off[1];
+    g[2] = (int32_t)(row / vol->p.ny) + vol->off[2];
+}
+
+typedef struct enter_ctx {
+    uint32_t *rec;                                                  /* [n][2]: lin in the new window, word */
+    size_t n;
+    int off[3];
+    size_t nx, ny;
+} enter_ctx;
+
+static void enter_record(void *ctx, const int32_t g[3], uint32_t word)
+{
+    enter_ctx *e = (enter_ctx *)ctx;
+    e->rec[2 * e->n] = (uint32_t)(((size_t)(g[2] - e->off[2]) * e->ny + (size_t)(g[1] - e->off[1])) * e->nx + (size_t)(g[0] - e->off[0]));
+    e->rec[2 * e->n + 1] = word;
+    e->n++;
+}
+
+int oslam_volume_shift_world(oslam_volume *vol, oslam_world *w, const int shift[3], oslam_reload_result *res)
+{
+    int rc = OSLAM_OK, a, b, nb = 0, off[3], locked = 0, reserved = 0;
+    const double t0 = now_ms();
+    uint32_t *d_cnt = NULL, *d_out = NULL, *d_in = NULL, *d_kept = NULL, *spare = NULL;
+    uint32_t n_out = 0, kept = 0, launches = 0, r;
+    size_t n_in = 0, mark = 0;
+    int32_t lo[7][3], hi[7][3], g[3];
+    const uint32_t *rec_out = NULL;
+    oslam_world_stage *st = NULL;
+    void *stream = oslam_stream();
+    if (!vol || !w || !shift) return fail(OSLAM_E_INVALID, "NULL argument");
+    if (!oslamk_shift_ok(shift)) return fail(OSLAM_E_INVALID, "a shift is at most 2^20 voxels");
+    pthread_mutex_lock(&g_vol_mu);
+    for (a = 0; a < 3; a++) off[a] = vol->off[a] + shift[a];
+    if (!oslamk_shift_ok(off)) { rc = fail(OSLAM_E_INVALID, "the window's offset is at most 2^20 voxels"); goto done; }
+    if (!oslam_world_compatible(w, vol->p.voxel, vol->p.origin)) {
+        rc = fail(OSLAM_E_INVALID, "the voxel store was made for another voxel size or origin");
+        goto done;
+    }
+    if (res) memset(res, 0, sizeof *res);
+    if (!(shift[0] | shift[1] | shift[2])) {
+        if (res) memcpy(res->offset, off, sizeof off);
+        goto done;
+    }
+    if (hipSetDevice(vol->dev) != hipSuccess) { rc = fail(OSLAM_E_DEVICE, "hipSetDevice failed"); goto done; }
+    spare = vol->spare;
+    if (!spare && hipMalloc((void **)&spare, volume_bytes(&vol->p)) != hipSuccess) {
+        (void)hipGetLastError();
+        spare = NULL;
+        rc = fail(OSLAM_E_NOMEM, "no device memory for the second buffer of the shift");
+        goto done;
+    }
+    vol->spare = spare;
+    /* 1. pack what leaves and copy it down */
+    rc = pack_leaving(vol, shift, (size_t)-1, &d_cnt, &d_out, &n_out, &launches);
+    if (rc != OSLAM_OK) goto done;
+    oslam_world_lock(w);
+    locked = 1;
+    st = oslam_world_stages(w);
+    if (n_out) {
+        rc = stage_fit(&st[0], sizeof(uint32_t) * 2 * (size_t)n_out);
+        if (rc != OSLAM_OK) goto done;
+        HIPCHK(hipMemcpyAsync(st[0].p, d_out, sizeof(uint32_t) * 2 * (size_t)n_out, hipMemcpyDeviceToHost, (hipStream_t)stream));
+        HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+        rec_out = (const uint32_t *)st[0].p;
+    }
+    /* 2. the bricks the leaving records need, still empty */
+    mark = oslam_world_mark(w);
+    reserved = 1;
+    for (r = 0; r < n_out; r++) {
+        global_of(vol, rec_out[2 * r], g);
+        rc = oslam_world_reserve(w, g);
+        if (rc != OSLAM_OK) goto done;
+    }
+    /* 3. the entering records: counted, then read; the store does not change */
+    {
+        const unsigned n[3] = {vol->p.nx, vol->p.ny, vol->p.nz};
+        nb = entering_boxes(vol->off, off, n, lo, hi);
+    }
+    for (b = 0; b < nb; b++) n_in += oslam_world_visit(w, lo[b], hi[b], 0, NULL, NULL);
+    if (n_in) {
+        enter_ctx e;
+        rc = stage_fit(&st[1], sizeof(uint32_t) * 2 * n_in);
+        if (rc != OSLAM_OK) goto done;
+        e.rec = (uint32_t *)st[1].p;
+        e.n = 0;
+        memcpy(e.off, off, sizeof off);
+        e.nx = vol->p.nx;
+        e.ny = vol->p.ny;
+        for (b = 0; b < nb; b++) (void)oslam_world_visit(w, lo[b], hi[b], 0, enter_record, &e);
+        /* 4. copy up; shift and unpack in stream order */
+        KCHK(oslam_dev_alloc((void **)&d_in, sizeof(uint32_t) * 2 * n_in));
+        HIPCHK(hipMemcpyAsync(d_in, st[1].p, sizeof(uint32_t) * 2 * n_in, hipMemcpyHostToDevice, (hipStream_t)stream));
+    }
+    KCHK(oslam_counters_open(&d_kept, 0, stream));
+    KCHK(oslamk_tsdf_shift(&vol->k, spare, shift, d_kept, stream));
+    launches++;
+    if (n_in) {
+        KCHK(oslamk_tsdf_unpack(spare, vol->k.nx, vol->k.ny, vol->k.nz, d_in, (uint32_t)n_in, stream));
+        launches++;
+    }
+    HIPCHK(hipMemcpyAsync(&kept, d_kept, sizeof kept, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    /* 5. commit: nothing below can fail */
+    for (r = 0; r < n_out; r++) {
+        global_of(vol, rec_out[2 * r], g);
+        oslam_world_store(w, g, rec_out[2 * r + 1]);
+    }
+    for (b = 0; b < nb; b++) (void)oslam_world_visit(w, lo[b], hi[b], 1, NULL, NULL);
+    reserved = 0;
+    vol->spare = vol->k.words;
+    vol->k.words = spare;
+    memcpy(vol->off, off, sizeof off);
+    window_origin(vol, vol->off, vol->k.origin);
+    if (res) {
+        memcpy(res->offset, off, sizeof off);
+        res->kept = kept + (uint32_t)n_in;                          /* the reloaded words are seen and their voxels were 0 */
+        res->stored = n_out;
+        res->reloaded = (uint32_t)n_in;
+        res->launches = launches;
+    }
+done:
+    if (rc != OSLAM_OK && d_cnt) (void)hipStreamSynchronize((hipStream_t)stream);
+    if (reserved) oslam_world_rollback(w, mark);
+    if (locked) oslam_world_unlock(w);
+    pthread_mutex_unlock(&g_vol_mu);
+    if (d_kept) oslam_dev_free(d_kept);
+    if (d_in) oslam_dev_free(d_in);
+    if (d_out) oslam_dev_free(d_out);
+    if (d_cnt) oslam_dev_free(d_cnt);
+    if (rc == OSLAM_OK && res) res->ms_total = (float)(now_ms() - t0);
+    return rc;
+}
+
+int oslam_volume_pack(oslam_volume *vol, const int shift[3], uint32_t *lin_out, uint32_t *word_out, size_t cap, size_t *n_out)
+{
+    int rc = OSLAM_OK;
+    uint32_t *d_cnt = NULL, *d_rec = NULL, *h = NULL, n = 0, launches = 0, r;
+    if (!vol || !shift || !n_out) return fail(OSLAM_E_INVALID, "NULL argument");
+    if (cap != 0 && (!lin_out || !word_out)) return fail(OSLAM_E_INVALID, "lin_out and word_out must be given with cap != 0");
+    if (!oslamk_shift_ok(shift)) return fail(OSLAM_E_INVALID, "a shift is at most 2^20 voxels");
+    *n_out = 0;
+    if (!(shift[0] | shift[1] | shift[2])) return OSLAM_OK;
+    if (hipSetDevice(vol->dev) != hipSuccess) return fail(OSLAM_E_DEVICE, "hipSetDevice failed");
+    pthread_mutex_lock(&g_vol_mu);
+    rc = pack_leaving(vol, shift, cap, &d_cnt, &d_rec, &n, &launches);
+    if (rc != OSLAM_OK) goto done;
+    *n_out = n;
+    if (cap != 0 && (size_t)n > cap) { rc = fail(OSLAM_E_LIMIT, "output capacity too small"); goto done; }
+    if (d_rec) {
+        h = (uint32_t *)malloc(sizeof(uint32_t) * 2 * (size_t)n);
+        if (!h) { rc = fail(OSLAM_E_NOMEM, "host allocation failed"); goto done; }
+        HIPCHK(hipMemcpy(h, d_rec, sizeof(uint32_t) * 2 * (size_t)n, hipMemcpyDeviceToHost));
+        for (r = 0; r < n; r++) {
+            lin_out[r] = h[2 * r];
+            word_out[r] = h[2 * r + 1];
+        }
+    }
+done:
+    if (d_cnt) (void)hipStreamSynchronize((hipStream_t)oslam_stream());
+    pthread_mutex_unlock(&g_vol_mu);
+    free(h);
+    if (d_rec) oslam_dev_free(d_rec);
+    if (d_cnt) oslam_dev_free(d_cnt);
     return rc;
 }
 

@@ -1,0 +1,46 @@
+/*
+ * oslam_world.h -- the voxel store as oslam_volume.c uses it (semantics: include/oslam.h at oslam_volume_shift_world;
+ * the store itself: oslam_world.c).  Nothing here needs a device: the staging buffers are kept as plain pointers with
+ * the function that frees them, both given by the caller that allocated them.
+ */
+#ifndef OSLAM_WORLD_H
+#define OSLAM_WORLD_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "oslam.h"
+
+/* records the text for oslam_last_error and returns code (oslam_host.c) */
+int oslam_fail(int code, const char *what);
+
+#define OSLAM_WORLD_G_MAX ((1 << 20) + 512)   /* the largest |g_a| a window within the shift's limits can hold */
+
+/* a pinned buffer the shift keeps with the store: bytes grows on demand, release frees p (set with it) */
+typedef struct oslam_world_stage {
+    void *p;
+    size_t bytes;
+    void (*release)(void *p);
+} oslam_world_stage;
+
+/* The calls below are made between oslam_world_lock and oslam_world_unlock, with the volume lock held. */
+void oslam_world_lock(oslam_world *w);
+void oslam_world_unlock(oslam_world *w);
+/* the store was made for these float bits */
+int oslam_world_compatible(const oslam_world *w, float voxel, const float origin0[3]);
+/* the two staging buffers: [0] the records that leave, [1] the records that enter */
+oslam_world_stage *oslam_world_stages(oslam_world *w);
+/* the table's capacity, to be given to oslam_world_rollback */
+size_t oslam_world_mark(const oslam_world *w);
+/* makes the brick of g exist (empty when new): OSLAM_OK, OSLAM_E_LIMIT (max_bytes) or OSLAM_E_NOMEM */
+int oslam_world_reserve(oslam_world *w, const int32_t g[3]);
+/* frees every empty brick and takes the table back to the capacity it had at the mark */
+void oslam_world_rollback(oslam_world *w, size_t mark);
+/* stores a seen word under g, whose brick exists (oslam_world_reserve): cannot fail */
+void oslam_world_store(oslam_world *w, const int32_t g[3], uint32_t word);
+/* calls fn(ctx, g, word) for every stored word with lo <= g < hi; take != 0 removes them and frees the bricks that
+ * become empty.  -> the number of words visited */
+typedef void (*oslam_world_visit_fn)(void *ctx, const int32_t g[3], uint32_t word);
+size_t oslam_world_visit(oslam_world *w, const int32_t lo[3], const int32_t hi[3], int take, oslam_world_visit_fn fn, void *ctx);
+
+#endif /* OSLAM_WORLD_H */

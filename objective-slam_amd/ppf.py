@@ -242,6 +242,28 @@ class FollowParams(C.Structure):
     _fields_ = [("lookahead", C.c_float), ("threshold", C.c_float), ("granule", C.c_int), ("reserved", C.c_int * 5)]
 
 
+class WorldParams(C.Structure):
+    _fields_ = [("voxel", C.c_float), ("origin0", C.c_float * 3), ("max_bytes", C.c_uint64), ("reserved", C.c_int * 4)]
+
+
+class WorldStats(C.Structure):
+    _fields_ = [("voxels", C.c_uint64), ("bricks", C.c_uint64), ("bytes", C.c_uint64), ("lo", C.c_int32 * 3),
+                ("hi", C.c_int32 * 3)]
+
+    def asdict(self):
+        return {"voxels": int(self.voxels), "bricks": int(self.bricks), "bytes": int(self.bytes),
+                "lo": tuple(int(x) for x in self.lo), "hi": tuple(int(x) for x in self.hi)}
+
+
+class ReloadResult(C.Structure):
+    _fields_ = [("offset", C.c_int32 * 3), ("kept", C.c_uint32), ("stored", C.c_uint32), ("reloaded", C.c_uint32),
+                ("launches", C.c_uint32), ("ms_total", C.c_float)]
+
+    def asdict(self):
+        return {"offset": tuple(int(x) for x in self.offset), "kept": int(self.kept), "stored": int(self.stored),
+                "reloaded": int(self.reloaded), "launches": int(self.launches), "ms_total": float(self.ms_total)}
+
+
 ARBITRATE_MAX_HYPOTHESES = 1024
 CELL_DTYPE = np.dtype([("code", "<u8"), ("count", "<u4"), ("pad", "<u4")])
 
@@ -361,6 +383,15 @@ _SIGNATURES = {
     "oslam_volume_leaving": (_i, [_vp, _vp, C.POINTER(SurfaceParams), _vp, _vp, _sz, C.POINTER(_sz), C.POINTER(SurfaceResult)]),
     "oslam_follow_params_default": (_i, [_vp, C.POINTER(FollowParams)]),
     "oslam_volume_follow": (_i, [_vp, _vp, C.POINTER(FollowParams), _vp]),
+    "oslam_world_params_of": (_i, [_vp, C.POINTER(WorldParams)]),
+    "oslam_world_create": (_i, [C.POINTER(WorldParams), C.POINTER(_vp)]),
+    "oslam_world_destroy": (_i, [_vp]),
+    "oslam_world_clear": (_i, [_vp]),
+    "oslam_world_stats_get": (_i, [_vp, C.POINTER(WorldStats)]),
+    "oslam_world_put": (_i, [_vp, _vp, _vp, _sz]),
+    "oslam_world_box": (_i, [_vp, _vp, _vp, _vp, _i]),
+    "oslam_volume_shift_world": (_i, [_vp, _vp, _vp, C.POINTER(ReloadResult)]),
+    "oslam_volume_pack": (_i, [_vp, _vp, _vp, _vp, _sz, C.POINTER(_sz)]),
     "oslam_mesh_params_default": (_i, [C.POINTER(MeshParams)]),
     "oslam_volume_mesh": (_i, [_vp, C.POINTER(MeshParams), _vp, _vp, _sz, _vp, _sz, C.POINTER(_sz), C.POINTER(_sz),
                                C.POINTER(MeshResult)]),
@@ -1550,6 +1581,60 @@ def _shift3(s):
     return s
 
 
+class World:
+    """The voxel store (oslam_world): a host-side map from global voxel coordinates g = window index + window offset to
+    TSDF words, which keeps what leaves a volume's shifting window (Volume.shift(s, world=...)) and gives it back when
+    the window returns.  vol_or_params: a Volume, whose voxel size and created origin the store takes, or a
+    WorldParams.  max_bytes bounds the store's memory, 0 = 1 GiB.  Needs no device."""
+
+    def __init__(self, vol_or_params, max_bytes=0):
+        self._h = C.c_void_p(0)
+        if isinstance(vol_or_params, WorldParams):
+            p = WorldParams.from_buffer_copy(vol_or_params)
+        else:
+            p = WorldParams()
+            _check(lib().oslam_world_params_of(vol_or_params._h, C.byref(p)))
+        if max_bytes:
+            p.max_bytes = int(max_bytes)
+        self.params = p
+        _check(lib().oslam_world_create(C.byref(p), C.byref(self._h)))
+
+    def put(self, g, words):
+        """Stores words uint32 [n] under g int32 [n,3]; unseen words (w == 0) are skipped, a later record wins."""
+        g = np.ascontiguousarray(g, np.int32).reshape(-1, 3)
+        words = np.ascontiguousarray(words, np.uint32).ravel()
+        if len(g) != len(words):
+            raise ValueError("g must be [n,3] and words [n]")
+        _check(lib().oslam_world_put(self._h, _p(g), _p(words), len(words)))
+
+    def box(self, lo, hi, take=False):
+        """The words with lo <= g < hi as uint32 [hz-lz, hy-ly, hx-lx], 0 where nothing is stored; take=True also
+        removes them from the store."""
+        lo, hi = _shift3(lo), _shift3(hi)
+        out = np.zeros(tuple(max(int(hi[a]) - int(lo[a]), 0) for a in (2, 1, 0)), np.uint32)
+        _check(lib().oslam_world_box(self._h, _p(lo), _p(hi), _p(out), int(bool(take))))
+        return out
+
+    def stats(self):
+        s = WorldStats()
+        _check(lib().oslam_world_stats_get(self._h, C.byref(s)))
+        return s.asdict()
+
+    def clear(self):
+        _check(lib().oslam_world_clear(self._h))
+
+    def close(self):
+        if self._h:
+            lib().oslam_world_destroy(self._h)
+            self._h = C.c_void_p(0)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Volume:
     """A TSDF volume on the device (oslam_volume): integrate(view, T_vol_cam) fuses a depth view, raycast(...) returns
     the fused surface as a View, track(view, T_prev) follows the camera against it.  T_vol_cam: the camera's pose in the
@@ -1599,13 +1684,15 @@ class Volume:
                                                 C.byref(res)))
         return To.reshape(4, 4), res.asdict()
 
-    def step(self, view, params=None, follow=None):
+    def step(self, view, params=None, follow=None, world=None):
         """One frame with the pose kept here: the first call integrates at the initial pose (the identity: the
         volume frame is the first camera's);
         a later call tracks from the kept pose and integrates when the result is ok.  -> (T_vol_cam, egomotion result
         dict, None on the first call).
         follow: follow parameters (default_follow_params).  After a frame was followed and integrated the window then
-        moves as follow(T) says; what leaves it is appended to self.world first."""
+        moves as follow(T) says; what leaves it is appended to self.world first.
+        world: a World.  With follow, the shift then goes through the store (shift(s, world)) and nothing is appended to
+        self.world: the store is the map, and a surface handed over now would be handed over again on the next visit."""
         if not self._started:
             self.integrate(view, self.T)
             self._started = True
@@ -1616,17 +1703,36 @@ class Volume:
             self.integrate(view, T)
             if follow is not None:
                 s = self.follow(T, follow)
-                if any(s):
+                if any(s) and world is not None:
+                    self.shift(s, world)
+                elif any(s):
                     po, no, _ = self.leaving(s)
                     self.world.append((po, no))
                     self.shift(s)
         return self.T.copy(), res
 
-    def shift(self, s):
-        """Moves the window of voxels by s = (sx, sy, sz) whole voxels (oslam_volume_shift): -> result dict."""
+    def shift(self, s, world=None):
+        """Moves the window of voxels by s = (sx, sy, sz) whole voxels (oslam_volume_shift): -> result dict.
+        world: a World.  The seen voxels that leave go into it and those it holds for the entering region come back
+        (oslam_volume_shift_world); the result also has "stored" and "reloaded"."""
+        if world is not None:
+            res = ReloadResult()
+            _check(lib().oslam_volume_shift_world(self._h, world._h, _p(_shift3(s)), C.byref(res)))
+            return res.asdict()
         res = ShiftResult()
         _check(lib().oslam_volume_shift(self._h, _p(_shift3(s)), C.byref(res)))
         return res.asdict()
+
+    def packed(self, s):
+        """The records the device makes of the seen voxels that shift(s) would move out, as a test tap
+        (oslam_volume_pack): -> (lin uint32 [n], ascending linear indices (k * ny + j) * nx + i; words uint32 [n])."""
+        s = _shift3(s)
+        n = C.c_size_t(0)
+        _check(lib().oslam_volume_pack(self._h, _p(s), None, None, 0, C.byref(n)))
+        lin, words = np.zeros(n.value, np.uint32), np.zeros(n.value, np.uint32)
+        if n.value:
+            _check(lib().oslam_volume_pack(self._h, _p(s), _p(lin), _p(words), n.value, C.byref(n)))
+        return lin, words
 
     def window(self):
         """-> (offset, three ints in voxels; origin float32 [3]) of the window (oslam_volume_window)."""

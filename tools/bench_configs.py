@@ -890,6 +890,74 @@ def shift(calls=20):
     return out
 
 
+def reload(calls=20):
+    """The shift through the voxel store (oslam_volume_shift_world) on the shift configuration's 256^3 volume after its
+    out-and-back stream: the median of `calls` calls of Volume.shift(+-8 on one axis, world=w), out and back alternately,
+    and, in the same run and interleaved with them, of the plain Volume.shift by the same steps (the yardstick); what
+    the store adds is the ratio of the two medians.  The pair runs on x and, where another axis has more seen voxels in
+    its outer 8 planes, on that axis too, so that records really go out and come back; which axis that is, and the
+    counts, are in the output.  stored and reloaded are per call; the store's bytes are read after an outward call.
+    The volume is restored between the two kinds of shift: the plain one forgets."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import camera_ref as E
+    world = E.make_world(synth, 0)
+    sweep = E.trajectory(synth, 0, frames=10)
+    cam = E.CAM
+    rendered = [ppf.View(E.render(synth, world, T), cam["fx"], cam["fy"], cam["cx"], cam["cy"], z_min=cam["z_min"],
+                         z_max=cam["z_max"], max_jump=E.MAX_JUMP) for T in sweep]
+    spec = dict(nx=256, ny=256, nz=256, voxel=0.036, origin=[-2.9, -4.3, 0.3], mu=0.288)
+    vol = ppf.Volume(**spec)
+    steps = [vol.step(rendered[k]) for k in list(range(10)) + list(range(8, -1, -1))]
+    q, w = vol.voxels()
+    seen = w > 0                                                    # [nz, ny, nx]
+    slab = {"x-": int(seen[:, :, :8].sum()), "x+": int(seen[:, :, -8:].sum()), "y-": int(seen[:, :8, :].sum()),
+            "y+": int(seen[:, -8:, :].sum()), "z-": int(seen[:8, :, :].sum()), "z+": int(seen[-8:, :, :].sum())}
+    best = max(slab, key=lambda k: slab[k])
+    axis, sign = "xyz".index(best[0]), 1 if best[1] == "-" else -1  # a positive shift moves the low planes out
+    pairs = [("x", (8, 0, 0))]
+    if best != "x-":
+        s = [0, 0, 0]
+        s[axis] = 8 * sign
+        pairs.append((best, tuple(s)))
+    store = ppf.World(vol)
+    out = {"config": "reload (oslam_volume_shift_world): the shift configuration's 256^3 volume after its 19-frame stream",
+           "volume": spec, "calls": calls, "step_ok": [None if r is None else r["ok"] for _, r in steps],
+           "seen_in_the_outer_8_planes": slab, "axis_with_surface": best, "pairs": []}
+    for name, s in pairs:
+        back = tuple(-x for x in s)
+        vol.shift(s, store); vol.shift(back, store)                 # the second buffer, the staging buffers, the bricks
+        vol.shift(s); vol.shift(back)
+        vol.set_voxels(q, w)
+        ms_w, ms_p, lib_w, stored, reloaded, launches, store_bytes, store_voxels = [], [], [], [], [], [], 0, 0
+        for k in range(calls):
+            t = time.perf_counter(); r = vol.shift(s if k % 2 == 0 else back, store); ms_w.append(1e3 * (time.perf_counter() - t))
+            lib_w.append(r["ms_total"]); stored.append(r["stored"]); reloaded.append(r["reloaded"]); launches.append(r["launches"])
+            if k % 2 == 0:
+                st = store.stats()
+                store_bytes, store_voxels = st["bytes"], st["voxels"]
+        for k in range(calls):                                      # the plain shift forgets: timed after, on the same window
+            t = time.perf_counter(); vol.shift(s if k % 2 == 0 else back); ms_p.append(1e3 * (time.perf_counter() - t))
+        vol.set_voxels(q, w)
+        inter_w, inter_p = [], []
+        for k in range(calls):                                      # interleaved: one pair through the store, one plain pair
+            t = time.perf_counter(); vol.shift(s, store); vol.shift(back, store); inter_w.append(0.5e3 * (time.perf_counter() - t))
+            t = time.perf_counter(); vol.shift(s); vol.shift(back); inter_p.append(0.5e3 * (time.perf_counter() - t))
+            vol.set_voxels(q, w)
+        out["pairs"].append({"axis": name, "shift": list(s), "world_shift_ms_median": float(np.median(ms_w)),
+                             "world_shift_ms_library_median": float(np.median(lib_w)), "plain_shift_ms_median": float(np.median(ms_p)),
+                             "world_over_plain": float(np.median(ms_w) / np.median(ms_p)),
+                             "interleaved_world_ms_median": float(np.median(inter_w)), "interleaved_plain_ms_median": float(np.median(inter_p)),
+                             "interleaved_world_over_plain": float(np.median(inter_w) / np.median(inter_p)),
+                             "stored_out_back": [stored[0], stored[1]], "reloaded_out_back": [reloaded[0], reloaded[1]],
+                             "launches_out_back": [launches[0], launches[1]], "store_bytes": store_bytes, "store_voxels": store_voxels})
+        store.clear()
+    for v in rendered:
+        v.close()
+    store.close()
+    vol.close()
+    return out
+
+
 def pyramid(calls=20):
     """Image pyramids (oslam_pyramid_create, oslam_pyramid_egomotion) on frames 0 and 1 of the camera configuration's
     640x480 stream: the median of `calls` calls of Pyramid(view), of egomotion_pyramid and, in the same run, of egomotion
@@ -933,4 +1001,4 @@ if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "cfg3"
     print(json.dumps({"cfg2": cfg2, "cfg3": cfg3, "cfg3db": cfg3db, "cfg4": cfg4, "cfg5": cfg5, "planes": planes, "db50": db50,
                       "refine": refine, "verify": verify, "instances": instances, "arbitrate": arbitrate, "track": track, "camera": camera,
-                      "fusion": fusion, "surface": surface, "mesh": mesh, "shift": shift, "pyramid": pyramid}[which]()), flush=True)
+                      "fusion": fusion, "surface": surface, "mesh": mesh, "shift": shift, "reload": reload, "pyramid": pyramid}[which]()), flush=True)

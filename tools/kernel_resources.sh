@@ -5,7 +5,7 @@
 # Each translation unit with the flags the Makefile builds it with.
 cd "$(dirname "$0")/../objective-slam_amd/csrc"
 units="$*"
-[ -z "$units" ] && units="oslam_kernels oslam_vote_wide oslam_sort oslam_posegpu oslam_voxel oslam_depth oslam_refine oslam_verify oslam_arbitrate oslam_track oslam_ego oslam_pyramid oslam_volume oslam_surface oslam_mesh oslam_shift"
+[ -z "$units" ] && units="oslam_kernels oslam_vote_wide oslam_sort oslam_posegpu oslam_voxel oslam_depth oslam_refine oslam_verify oslam_arbitrate oslam_track oslam_ego oslam_pyramid oslam_volume oslam_surface oslam_mesh oslam_shift oslam_reload"
 for f in $units; do
   fl=""; [ $f = oslam_vote_wide ] && fl="-mllvm -disable-machine-licm"
   echo "== $f.hip $fl"
