@@ -53,27 +53,6 @@ int oslam_arbitrate_check_params(const oslam_arbitrate_params *ap, oslam_arbitra
     return OSLAM_OK;
 }
 
-/* everything that can be said without reading a handle, then the handles' devices */
-static int check_list(oslam_model *const *ms, const float *T, size_t H, const oslam_view *v)
-{
-    size_t h;
-    int rc;
-    if (H == 0 || H > OSLAM_ARBITRATE_MAX_HYPOTHESES)
-        return fail(OSLAM_E_INVALID, "the number of hypotheses must lie in 1..OSLAM_ARBITRATE_MAX_HYPOTHESES");
-    for (h = 0; h < H; h++) {
-        if (!ms[h]) return fail(OSLAM_E_INVALID, "NULL model");
-        if (oslam_is_zero_pose(T + 16 * h)) continue;
-        rc = oslam_refine_check_rigid(T + 16 * h);
-        if (rc != OSLAM_OK) return rc;
-    }
-    for (h = 0; h < H; h++) {
-        if (oslam_is_zero_pose(T + 16 * h)) continue;
-        rc = oslam_view_check_pair(ms[h], v);
-        if (rc != OSLAM_OK) return rc;
-    }
-    return OSLAM_OK;
-}
-
 /* the tile of a call (include/oslam.h, "Tile") */
 static int choose_tile(oslam_model *const *ms, const float *T, size_t H, const oslam_view *v, const oslam_arbitrate_params *p)
 {
@@ -85,7 +64,6 @@ static int choose_tile(oslam_model *const *ms, const float *T, size_t H, const o
         const float *A = T + 16 * h;
         float zc;
         if (oslam_is_zero_pose(A)) continue;
-        oslam_model_shape(ms[h]);
         if (ms[h]->d_dist > d_max) d_max = ms[h]->d_dist;
         zc = ((A[8] * ms[h]->inst_c[0] + A[9] * ms[h]->inst_c[1]) + A[10] * ms[h]->inst_c[2]) + A[11];
         if (zc > 0.0f && (z_near == 0.0f || zc < z_near)) z_near = zc;
@@ -228,7 +206,8 @@ int oslam_arbitrate(oslam_model *const *models, const float *T, size_t H, const 
     int rc;
     if (!models || !T || !v || !res) return fail(OSLAM_E_INVALID, "NULL argument");
     rc = oslam_arbitrate_check_params(ap, &p);
-    if (rc == OSLAM_OK) rc = check_list(models, T, H, v);
+    if (rc == OSLAM_OK) rc = oslam_check_poses(models, T, H, 1);
+    if (rc == OSLAM_OK) rc = oslam_check_handles(models, T, H, v);
     if (rc != OSLAM_OK) return rc;
     return arbitrate_members(models, H, v, T, &p, res, NULL, NULL, 0, NULL, NULL);
 }
@@ -242,7 +221,8 @@ int oslam_db_arbitrate(oslam_db *db, const oslam_view *v, const float *T, const 
     rc = oslam_arbitrate_check_params(ap, &p);
     if (rc != OSLAM_OK) return rc;
     if (db->n && !db->models) return fail(OSLAM_E_INVALID, "the database holds no models");
-    rc = check_list(db->models, T, db->n, v);
+    rc = oslam_check_poses(db->models, T, db->n, 1);
+    if (rc == OSLAM_OK) rc = oslam_check_handles(db->models, T, db->n, v);
     if (rc != OSLAM_OK) return rc;
     return arbitrate_members(db->models, db->n, v, T, &p, res, NULL, NULL, 0, NULL, NULL);
 }
@@ -255,7 +235,8 @@ int oslam_arbitrate_claims(oslam_model *const *models, const float *T, size_t H,
     int rc;
     if (!models || !T || !v || !cnt_out || !sum_out) return fail(OSLAM_E_INVALID, "NULL argument");
     rc = oslam_arbitrate_check_params(ap, &p);
-    if (rc == OSLAM_OK) rc = check_list(models, T, H, v);
+    if (rc == OSLAM_OK) rc = oslam_check_poses(models, T, H, 1);
+    if (rc == OSLAM_OK) rc = oslam_check_handles(models, T, H, v);
     if (rc != OSLAM_OK) return rc;
     return arbitrate_members(models, H, v, T, &p, NULL, cnt_out, sum_out, cap, tile_out, n_tiles_out);
 }

@@ -17,34 +17,10 @@ static int check_args(const oslam_instance_params *ip, const oslam_refine_params
     return rp ? oslam_refine_check_params(rp, rpc) : OSLAM_OK;
 }
 
-/* centroid (mean in double, rounded to float) and extent (largest bounding-box side, oslam_d_dist_from_cloud) */
-void oslam_model_shape(oslam_model *m)
-{
-    double cm[3] = {0.0, 0.0, 0.0};
-    float lo[3], hi[3], ext;
-    size_t i, n = (size_t)m->c.n;
-    int a;
-    if (m->inst_shape) return;
-    for (a = 0; a < 3; a++) lo[a] = hi[a] = m->c.h_xyz[a];
-    for (i = 0; i < n; i++)
-        for (a = 0; a < 3; a++) {
-            const float x = m->c.h_xyz[3 * i + a];
-            cm[a] += (double)x;
-            if (x < lo[a]) lo[a] = x;
-            if (x > hi[a]) hi[a] = x;
-        }
-    for (a = 0; a < 3; a++) m->inst_c[a] = (float)(cm[a] / (double)n);
-    ext = hi[0] - lo[0];
-    if (hi[1] - lo[1] > ext) ext = hi[1] - lo[1];
-    if (hi[2] - lo[2] > ext) ext = hi[2] - lo[2];
-    m->inst_extent = 1.0f * ext;
-    m->inst_shape = 1;
-}
-
-static void make_req(oslam_model *m, const oslam_instance_params *ip, oslam_inst_req *req)
+/* the rule resolved for m: its centroid and extent are the model's shape (oslam_model.c) */
+static void make_req(const oslam_model *m, const oslam_instance_params *ip, oslam_inst_req *req)
 {
     int rot_on = 0;
-    oslam_model_shape(m);
     memset(req, 0, sizeof *req);
     req->ip = ip;
     req->extent = m->inst_extent;
@@ -55,19 +31,11 @@ static void make_req(oslam_model *m, const oslam_instance_params *ip, oslam_inst
     memcpy(req->a.c, m->inst_c, sizeof req->a.c);
 }
 
-static int is_zero(const float T[16])
-{
-    int k;
-    for (k = 0; k < 16; k++)
-        if (T[k] != 0.0f) return 0;
-    return 1;
-}
-
 /* the winners of the tail -> out[]; an all-zero instance 0 (oslam_align's all-zero T) gives none */
 static size_t fill_out(const oslamk_inst_out *sel, oslam_instance *out)
 {
     size_t k;
-    if (sel->n == 0 || is_zero(sel->T[0])) return 0;
+    if (sel->n == 0 || oslam_is_zero_pose(sel->T[0])) return 0;
     for (k = 0; k < sel->n; k++) {
         oslam_instance *o = &out[k];
         memset(o, 0, sizeof *o);

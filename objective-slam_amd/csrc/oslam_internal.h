@@ -15,6 +15,7 @@
 
 #include "oslam.h"
 #include "oslam_kernels.h"
+#include "oslam_rigid.h"
 
 typedef struct cloud_buf {
     int n;
@@ -60,8 +61,9 @@ struct oslam_model {
     /* its key tables are gone (a database was destroyed without giving them back, or rebuilding them failed):
      * the model can only be destroyed */
     int unusable;
-    /* centroid and extent of the instance rule (oslam_instances.c), made on first use */
-    int inst_shape;
+    /* the cloud's shape (oslam_cloud_shape), made with the cloud and never written again: the double mean of the
+     * points (the pivot of the refinement and tracking stages), its float rounding and the extent (the instance rule) */
+    double cm[3];
     float inst_c[3], inst_extent;
 };
 
@@ -228,23 +230,35 @@ int oslam_db_align_frame(oslam_db *db, oslam_scene *s, float *T_out, oslam_stats
 /* ---- refinement (oslam_refine.c) ---- */
 /* rp NULL = defaults; checks them as oslam_refine does, *out = the parameters in force */
 int oslam_refine_check_params(const oslam_refine_params *rp, oslam_refine_params *out);
+/* finite, rotation orthonormal to 1e-3 with determinant > 0, last row 0 0 0 1: the pose check of every stage */
 int oslam_refine_check_rigid(const float T[16]);
 /* members ms[0 .. n) with T_in [n][16] (all-zero = skipped) against s, one set of launches; member j's result is
  * oslam_refine's for it alone */
 int oslam_refine_members(oslam_model *const *ms, size_t n, oslam_scene *s, const float *T_in, const oslam_refine_params *p,
                          float *T_out, oslam_refine_result *res);
 
-/* centroid and extent of the instance rule into m->inst_c / m->inst_extent, made once (oslam_instances.c) */
-void oslam_model_shape(oslam_model *m);
+/* ---- views and the checks every stage shares (oslam_verify.c; the arithmetic: oslam_rigid.h) ---- */
+/* the model is usable and lives on the view's device */
+int oslam_view_check_pair(const oslam_model *m, const oslam_view *v);
+/* A list of n poses T [n][16] with their models, in two halves.  The first reads no handle: the count (hypotheses: in
+ * 1..OSLAM_ARBITRATE_MAX_HYPOTHESES; otherwise any, a database's members), no NULL in ms (ms NULL: there are no
+ * pointers yet) and every pose that is not all zero rigid.  The second reads them: the model of every such pose is
+ * usable and on the view's device. */
+int oslam_check_poses(oslam_model *const *ms, const float *T, size_t n, int hypotheses);
+int oslam_check_handles(oslam_model *const *ms, const float *T, size_t n, const oslam_view *v);
+/* 1 when a view of this size can be made for cam (0 otherwise, no error text): sides in 1..16384, finite intrinsics
+ * with fx, fy > 0, 0 < z_min <= z_max finite; depth_scale > 0 and finite, max_jump >= 0 and finite where asked */
+int oslam_view_camera_ok(const oslam_camera *cam, int width, int height, int with_depth_scale, int with_max_jump);
+/* a view of this size for cam on device dev (bound by the caller) with its own z image, not yet written */
+int oslam_view_new(int dev, int width, int height, const oslam_camera *cam, oslam_view **out);
+/* the camera that renders a view like v */
+void oslam_view_camera(const oslam_view *v, oslam_camera *cam);
 
 /* ---- verification (oslam_verify.c) ---- */
 /* vp NULL = defaults; checks them as oslam_verify does, *out = the parameters in force */
 int oslam_verify_check_params(const oslam_verify_params *vp, oslam_verify_params *out);
-int oslam_is_zero_pose(const float T[16]);
 /* *r's counts from the six class counts c[0 .. 6), and from them view_fitness, coverage and found under p */
 void oslam_verify_fill_result(oslam_verify_result *r, const uint32_t *c, const oslam_verify_params *p);
-/* the model is usable and lives on the view's device */
-int oslam_view_check_pair(const oslam_model *m, const oslam_view *v);
 /* the descriptor of one member: its cloud, the rows of T, tol = (float)((double)depth_tol * d_dist), its blocks */
 void oslam_verify_set_member(oslamk_verify_member *d, const oslam_model *m, const float T[16], float depth_tol);
 /* members ms[0 .. n) with T [n][16] (all-zero = skipped) against v, one set of launches; member j's result is

@@ -1,6 +1,6 @@
 /*
  * oslam_model.c -- a model: its key tables built once and kept in HBM (model.cu), saved to and loaded from
- * a file, its point weights.
+ * a file, its point weights, and its cloud's shape (centroid and extent, made where the cloud is).
  */
 #include <stdio.h>
 
@@ -248,6 +248,7 @@ int oslam_model_create(const float *xyz, const float *nrm, size_t n, size_t stri
     if (rc != OSLAM_OK) goto done;
     rc = oslam_cloud_make(&m->c, xyz, nrm, stride_bytes, NULL, n);
     if (rc != OSLAM_OK) goto done;
+    oslam_cloud_shape(m->c.h_xyz, n, m->cm, m->inst_c, &m->inst_extent);
     m->d_dist = d_dist;
     m->inv_d_dist = 1.0f / d_dist;
     m->weights = (float *)malloc(sizeof(float) * n);
@@ -530,6 +531,7 @@ int oslam_model_load(const char *path, const oslam_params *params, oslam_model *
     }
     rc = oslam_cloud_make(&m->c, xyz, nrm, 12, NULL, n);
     if (rc != OSLAM_OK) goto done;
+    oslam_cloud_shape(m->c.h_xyz, n, m->cm, m->inst_c, &m->inst_extent);
     m->d_dist = hd.d_dist;
     m->inv_d_dist = hd.inv_d_dist;
     m->table.cap = hd.cap;

@@ -1,8 +1,8 @@
 /*
  * oslam_pyramid.c -- depth image pyramids (include/oslam.h at oslam_pyramid_create): the host side of the kernel in
  * oslam_pyramid.hip.  A pyramid borrows its base view as level 0 and owns the coarser levels, each a genuine oslam_view
- * (a z image and a camera; its maps are built on first use by the tracking stage's path).  Creating one enqueues one
- * k_pyr_down per coarser level back to back and waits once.  Coarse-to-fine camera motion over two pyramids is
+ * (oslam_view_new: a z image and a camera; its maps are built on first use by the tracking stage's path).  Creating one
+ * enqueues one k_pyr_down per coarser level back to back and waits once.  Coarse-to-fine camera motion over two pyramids is
  * oslam_pyramid_egomotion in oslam_ego.c; frame-to-model tracking over them is oslam_volume_track_pyramid in
  * oslam_volume.c.
  */
@@ -56,23 +56,16 @@ int oslam_pyramid_create(oslam_view *base, const oslam_pyramid_params *pp, oslam
     pyr->level[0] = base;
     for (k = 1; k < p.n_levels; k++) {
         const oslam_view *f = pyr->level[k - 1];
-        oslam_view *v = (oslam_view *)calloc(1, sizeof *v);
-        if (!v) { rc = fail(OSLAM_E_NOMEM, "host allocation failed"); goto done; }
-        pyr->level[k] = v;
-        v->dev = base->dev;
-        v->k.w = (f->k.w + 1) / 2;
-        v->k.h = (f->k.h + 1) / 2;
-        v->k.fx = f->k.fx * 0.5f;
-        v->k.fy = f->k.fy * 0.5f;
-        v->k.cx = f->k.cx * 0.5f;
-        v->k.cy = f->k.cy * 0.5f;
-        v->k.z_min = f->k.z_min;
-        v->k.z_max = f->k.z_max;
-        v->max_jump = f->max_jump * 2.0f;
-        /* the z image lives as long as the level: its own block, as in oslam_view_create */
-        HIPCHK(hipMalloc((void **)&v->d_z, sizeof(float) * (size_t)v->k.w * (size_t)v->k.h));
-        v->k.z = v->d_z;
-        KCHK(oslamk_pyr_down(&f->k, p.depth_band, v->d_z, stream));
+        oslam_camera cam;
+        oslam_view_camera(f, &cam);
+        cam.fx *= 0.5f;
+        cam.fy *= 0.5f;
+        cam.cx *= 0.5f;
+        cam.cy *= 0.5f;
+        cam.max_jump *= 2.0f;
+        rc = oslam_view_new(base->dev, (f->k.w + 1) / 2, (f->k.h + 1) / 2, &cam, &pyr->level[k]);
+        if (rc != OSLAM_OK) goto done;
+        KCHK(oslamk_pyr_down(&f->k, p.depth_band, pyr->level[k]->d_z, stream));
     }
     HIPCHK(hipStreamSynchronize((hipStream_t)stream));
 done:

@@ -55,14 +55,6 @@ int oslam_refine_check_params(const oslam_refine_params *rp, oslam_refine_params
     return OSLAM_OK;
 }
 
-static int is_zero_pose(const float T[16])
-{
-    int k;
-    for (k = 0; k < 16; k++)
-        if (T[k] != 0.0f) return 0;
-    return 1;
-}
-
 /* finite, rotation orthonormal to 1e-3 with determinant > 0, last row 0 0 0 1 */
 int oslam_refine_check_rigid(const float T[16])
 {
@@ -189,28 +181,18 @@ done:
     return rc;
 }
 
-static void set_pose(oslamk_refine_member *d, const float T[16])
+/* the pose bookkeeping of a descriptor: the model's centroid, the pose in double and in float, the centroid under it */
+static void set_pose(oslamk_refine_member *d, const oslam_model *m, const float T[16])
 {
     double c[3];
     int a;
+    memcpy(d->cm, m->cm, sizeof d->cm);
     for (a = 0; a < 12; a++) {
         d->T[a] = (double)T[a];
         d->Tf[a] = T[a];
     }
-    for (a = 0; a < 3; a++) {
-        c[a] = ((d->T[4 * a] * d->cm[0] + d->T[4 * a + 1] * d->cm[1]) + d->T[4 * a + 2] * d->cm[2]) + d->T[4 * a + 3];
-        d->c[a] = (float)c[a];
-    }
-}
-
-static void centroid(const oslam_model *m, double cm[3])
-{
-    size_t i;
-    int a;
-    cm[0] = cm[1] = cm[2] = 0.0;
-    for (i = 0; i < (size_t)m->c.n; i++)
-        for (a = 0; a < 3; a++) cm[a] += (double)m->c.h_xyz[3 * i + a];
-    for (a = 0; a < 3; a++) cm[a] /= (double)m->c.n;
+    oslam_rigid_apply(d->T, d->cm, c);
+    for (a = 0; a < 3; a++) d->c[a] = (float)c[a];
 }
 
 /* The members ms[0 .. n) (T_in[j*16], all-zero = skipped) against scene s: the whole stage. */
@@ -234,7 +216,7 @@ int oslam_refine_members(oslam_model *const *ms, size_t n, oslam_scene *s, const
     act = (size_t *)malloc(sizeof *act * (n ? n : 1));
     if (!act) return oslam_fail(OSLAM_E_NOMEM, "host allocation failed");
     for (j = 0; j < n; j++)
-        if (!is_zero_pose(T_in + 16 * j)) {
+        if (!oslam_is_zero_pose(T_in + 16 * j)) {
             const float r = p->max_corr_dist * ms[j]->d_dist;
             const size_t nb = ((size_t)ms[j]->c.n + OSLAMK_REFINE_THREADS - 1) / OSLAMK_REFINE_THREADS;
             act[n_act++] = j;
@@ -259,8 +241,7 @@ int oslam_refine_members(oslam_model *const *ms, size_t n, oslam_scene *s, const
         const oslam_model *m = ms[act[b]];
         oslamk_refine_member *d = &h[b];
         const float rc_ = p->max_corr_dist * m->d_dist, rs = p->inlier_dist * m->d_dist;
-        centroid(m, d->cm);
-        set_pose(d, T_in + 16 * act[b]);
+        set_pose(d, m, T_in + 16 * act[b]);
         d->m = m->c.k;
         d->r2_corr = rc_ * rc_;
         d->r2_score = rs * rs;
@@ -371,13 +352,10 @@ int oslam_db_refine(oslam_db *db, oslam_scene *s, const float *T_in, const oslam
     int rc;
     if (!db || !s || !T_in || !T_out) return oslam_fail(OSLAM_E_INVALID, "NULL argument");
     rc = oslam_refine_check_params(rp, &p);
+    if (rc == OSLAM_OK) rc = oslam_check_poses(NULL, T_in, db->n, 0);
+    for (j = 0; rc == OSLAM_OK && j < db->n; j++)     /* the handles: against a scene, not a view */
+        if (!oslam_is_zero_pose(T_in + 16 * j)) rc = check_model(db->models[j], s);
     if (rc != OSLAM_OK) return rc;
-    for (j = 0; j < db->n; j++) {
-        if (is_zero_pose(T_in + 16 * j)) continue;
-        rc = oslam_refine_check_rigid(T_in + 16 * j);
-        if (rc == OSLAM_OK) rc = check_model(db->models[j], s);
-        if (rc != OSLAM_OK) return rc;
-    }
     return oslam_refine_members(db->models, db->n, s, T_in, &p, T_out, res);
 }
 
@@ -398,8 +376,7 @@ int oslam_refine_correspondences(oslam_model *m, oslam_scene *s, const float T[1
     if (hipSetDevice(s->dev) != hipSuccess) return oslam_fail(OSLAM_E_DEVICE, "hipSetDevice failed");
     M = (size_t)m->c.n;
     memset(&h, 0, sizeof h);
-    centroid(m, h.cm);
-    set_pose(&h, T);
+    set_pose(&h, m, T);
     h.m = m->c.k;
     h.r2_corr = radius * radius;
     h.min_dot = min_normal_dot;

@@ -56,27 +56,6 @@ int oslam_track_check_params(const oslam_track_params *tp, oslam_track_params *o
     return oslam_verify_check_params(&out->verify, &vp);
 }
 
-/* everything that can be said without reading a handle, then the handles' devices */
-static int check_list(oslam_model *const *ms, const float *T, size_t H, const oslam_view *v)
-{
-    size_t h;
-    int rc;
-    if (H == 0 || H > OSLAM_ARBITRATE_MAX_HYPOTHESES)
-        return fail(OSLAM_E_INVALID, "the number of hypotheses must lie in 1..OSLAM_ARBITRATE_MAX_HYPOTHESES");
-    for (h = 0; h < H; h++) {
-        if (!ms[h]) return fail(OSLAM_E_INVALID, "NULL model");
-        if (oslam_is_zero_pose(T + 16 * h)) continue;
-        rc = oslam_refine_check_rigid(T + 16 * h);
-        if (rc != OSLAM_OK) return rc;
-    }
-    for (h = 0; h < H; h++) {
-        if (oslam_is_zero_pose(T + 16 * h)) continue;
-        rc = oslam_view_check_pair(ms[h], v);
-        if (rc != OSLAM_OK) return rc;
-    }
-    return OSLAM_OK;
-}
-
 /* The view's maps, built on first use (enqueued on the stream; *built = 1).  Called with g_track_mu held and the view's
  * device bound.  The block lives as long as the view and goes back to the kept blocks of the scene path with it: the
  * next frame's view takes it again without a hipMalloc / hipFree pair. */
@@ -107,19 +86,16 @@ int oslam_track_view_maps(oslam_view *v, int *built)
     return rc;
 }
 
-/* the descriptor of one hypothesis: the pose bookkeeping of oslam_refine (oslam_refine.c, set_pose and centroid) */
+/* the descriptor of one hypothesis: the pose bookkeeping of oslam_refine (oslam_refine.c, set_pose) */
 static void set_member(oslamk_track_member *d, const oslam_model *m, const float T[16], const oslam_track_params *p)
 {
     const float rc_ = p->max_corr_dist * m->d_dist;
-    size_t i;
+    double c[3];
     int a;
-    d->cm[0] = d->cm[1] = d->cm[2] = 0.0;
-    for (i = 0; i < (size_t)m->c.n; i++)
-        for (a = 0; a < 3; a++) d->cm[a] += (double)m->c.h_xyz[3 * i + a];
-    for (a = 0; a < 3; a++) d->cm[a] /= (double)m->c.n;
+    memcpy(d->cm, m->cm, sizeof d->cm);
     for (a = 0; a < 12; a++) d->T[a] = (double)T[a];
-    for (a = 0; a < 3; a++)
-        d->c[a] = (float)(((d->T[4 * a] * d->cm[0] + d->T[4 * a + 1] * d->cm[1]) + d->T[4 * a + 2] * d->cm[2]) + d->T[4 * a + 3]);
+    oslam_rigid_apply(d->T, d->cm, c);
+    for (a = 0; a < 3; a++) d->c[a] = (float)c[a];
     d->m = m->c.k;
     d->r2_corr = rc_ * rc_;
     d->min_dot = p->min_normal_dot;
@@ -209,7 +185,8 @@ int oslam_track(oslam_model *const *models, const float *T_prev, size_t H, const
     int rc;
     if (!models || !T_prev || !v || !T_out) return fail(OSLAM_E_INVALID, "NULL argument");
     rc = oslam_track_check_params(tp, &p);
-    if (rc == OSLAM_OK) rc = check_list(models, T_prev, H, v);
+    if (rc == OSLAM_OK) rc = oslam_check_poses(models, T_prev, H, 1);
+    if (rc == OSLAM_OK) rc = oslam_check_handles(models, T_prev, H, v);
     if (rc != OSLAM_OK) return rc;
     return track_members(models, H, v, T_prev, &p, T_out, res);
 }
@@ -223,20 +200,14 @@ int oslam_db_track(oslam_db *db, const uint32_t *member, const float *T_prev, si
     int rc;
     if (!db || !member || !T_prev || !v || !T_out) return fail(OSLAM_E_INVALID, "NULL argument");
     rc = oslam_track_check_params(tp, &p);
+    if (rc == OSLAM_OK) rc = oslam_check_poses(NULL, T_prev, H, 1);    /* the members' models are not looked up yet */
     if (rc != OSLAM_OK) return rc;
-    if (H == 0 || H > OSLAM_ARBITRATE_MAX_HYPOTHESES)
-        return fail(OSLAM_E_INVALID, "the number of hypotheses must lie in 1..OSLAM_ARBITRATE_MAX_HYPOTHESES");
-    for (h = 0; h < H; h++)
-        if (!oslam_is_zero_pose(T_prev + 16 * h)) {
-            rc = oslam_refine_check_rigid(T_prev + 16 * h);
-            if (rc != OSLAM_OK) return rc;
-        }
     for (h = 0; h < H; h++)
         if (member[h] >= db->n) return fail(OSLAM_E_INVALID, "member index outside the database");
     ms = (oslam_model **)malloc(sizeof *ms * H);
     if (!ms) return fail(OSLAM_E_NOMEM, "host allocation failed");
     for (h = 0; h < H; h++) ms[h] = db->models[member[h]];
-    rc = check_list(ms, T_prev, H, v);
+    rc = oslam_check_handles(ms, T_prev, H, v);
     if (rc == OSLAM_OK) rc = track_members(ms, H, v, T_prev, &p, T_out, res);
     free(ms);
     return rc;

@@ -94,7 +94,6 @@ int oslam_tracker_create(oslam_db *db, const oslam_tracker_params *p, oslam_trac
     if (rc != OSLAM_OK) return rc;
     (*out)->db = db;
     for (j = 0; j < db->n; j++) {
-        oslam_model_shape(db->models[j]);
         memcpy((*out)->centroid + 3 * j, db->models[j]->inst_c, 3 * sizeof(float));
         (*out)->extent[j] = db->models[j]->inst_extent;
     }
@@ -205,32 +204,18 @@ int oslam_tracker_tracks(const oslam_tracker *t, oslam_track_state *out, size_t 
 /* step 0 of oslam_tracker_step_cam: T <- float32(T_cam * T) of every live track, T_world_cam <- T_world_cam * T_cam^-1 */
 static void predict(oslam_tracker *t, const float C[16])
 {
-    double W[16], inv[12];
+    double W[12], inv[12];
     size_t k;
-    int a, b;
+    int a;
     for (k = 0; k < t->n; k++) {
         float *T = t->tracks[k].T, N[12];
-        for (a = 0; a < 3; a++)
-            for (b = 0; b < 4; b++) {
-                double x = ((double)C[4 * a] * (double)T[b] + (double)C[4 * a + 1] * (double)T[4 + b]) +
-                           (double)C[4 * a + 2] * (double)T[8 + b];
-                if (b == 3) x += (double)C[4 * a + 3];
-                N[4 * a + b] = (float)x;
-            }
+        oslam_rigid_product_f(C, T, N);
         for (a = 0; a < 12; a++)
             if (N[a] != T[a]) T[a] = N[a];      /* an element whose value does not change keeps its bits */
     }
-    for (a = 0; a < 3; a++) {
-        for (b = 0; b < 3; b++) inv[4 * a + b] = (double)C[4 * b + a];
-        inv[4 * a + 3] = -(((double)C[a] * (double)C[3] + (double)C[4 + a] * (double)C[7]) + (double)C[8 + a] * (double)C[11]);
-    }
+    oslam_rigid_inverse(C, inv);
     memcpy(W, t->T_world_cam, sizeof W);
-    for (a = 0; a < 3; a++)
-        for (b = 0; b < 4; b++) {
-            double x = (W[4 * a] * inv[b] + W[4 * a + 1] * inv[4 + b]) + W[4 * a + 2] * inv[8 + b];
-            if (b == 3) x += W[4 * a + 3];
-            t->T_world_cam[4 * a + b] = x;
-        }
+    oslam_rigid_product(W, inv, t->T_world_cam);
 }
 
 int oslam_tracker_predict(oslam_tracker *t, const float T_cam[16])

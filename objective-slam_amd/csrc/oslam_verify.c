@@ -2,38 +2,32 @@
  * oslam_verify.c -- verification against a depth image (include/oslam.h at oslam_verify): the host side of the kernels
  * in oslam_verify.hip.  A view is the image as float z on the device; a call checks its arguments, uploads one
  * descriptor per member (its pose, its tolerance and the model's device cloud), zeroes the counters, runs k_verify
- * once for every member and reads the counters back with one host wait.
+ * once for every member and reads the counters back with one host wait.  Views are made here for every stage
+ * (oslam_view_new: oslam_view_create, the ray cast, a pyramid's levels), and here is the check of a list of poses and
+ * models that verification, refinement, arbitration and tracking share (oslam_check_poses, oslam_check_handles).
  */
 #include <math.h>
 
 #include "oslam_internal.h"
 
-int oslam_view_create(const void *depth, int depth_is_u16, int width, int height, const oslam_camera *cam, int dev,
-                      oslam_view **out)
+int oslam_view_camera_ok(const oslam_camera *cam, int width, int height, int with_depth_scale, int with_max_jump)
 {
-    int rc = OSLAM_OK, devsel;
-    const size_t n_pix = (size_t)width * (size_t)height, px_bytes = depth_is_u16 ? 2 : 4;
-    void *d_raw = NULL;
-    oslam_view *v = NULL;
-    if (out) *out = NULL;
-    if (!depth || !cam || !out || width < 1 || height < 1 || width > 16384 || height > 16384 || !isfinite(cam->fx) ||
-        !isfinite(cam->fy) || !isfinite(cam->cx) || !isfinite(cam->cy) || !(cam->fx > 0.0f) || !(cam->fy > 0.0f) ||
-        !(cam->depth_scale > 0.0f) || !isfinite(cam->depth_scale) || !(cam->z_max >= cam->z_min) ||
+    if (width < 1 || height < 1 || width > 16384 || height > 16384 || !isfinite(cam->fx) || !isfinite(cam->fy) ||
+        !isfinite(cam->cx) || !isfinite(cam->cy) || !(cam->fx > 0.0f) || !(cam->fy > 0.0f) || !(cam->z_max >= cam->z_min) ||
         !(cam->z_min > 0.0f) || !isfinite(cam->z_max))
-        return fail(OSLAM_E_INVALID, "bad view arguments");
-    rc = oslam_pick_device(dev, &devsel);
-    if (rc != OSLAM_OK) return rc;
-    v = (oslam_view *)calloc(1, sizeof *v);
+        return 0;
+    if (with_depth_scale && (!(cam->depth_scale > 0.0f) || !isfinite(cam->depth_scale))) return 0;
+    if (with_max_jump && (!(cam->max_jump >= 0.0f) || !isfinite(cam->max_jump))) return 0;
+    return 1;
+}
+
+int oslam_view_new(int dev, int width, int height, const oslam_camera *cam, oslam_view **out)
+{
+    int rc = OSLAM_OK;
+    oslam_view *v = (oslam_view *)calloc(1, sizeof *v);
+    *out = NULL;
     if (!v) return fail(OSLAM_E_NOMEM, "host allocation failed");
-    v->dev = devsel;
-    /* the z image lives as long as the view: its own block, not one of the kept scratch blocks */
-    HIPCHK(hipMalloc((void **)&v->d_z, sizeof(float) * n_pix));
-    HIPCHK((hipError_t)oslam_dev_alloc(&d_raw, n_pix * px_bytes));
-    HIPCHK(hipMemcpyAsync(d_raw, depth, n_pix * px_bytes, hipMemcpyHostToDevice, (hipStream_t)oslam_stream()));
-    KCHK(oslamk_view_z(d_raw, depth_is_u16 != 0, width, height, cam->depth_scale, cam->z_min, cam->z_max, v->d_z,
-                       oslam_stream()));
-    HIPCHK(hipStreamSynchronize((hipStream_t)oslam_stream()));
-    v->k.z = v->d_z;
+    v->dev = dev;
     v->k.w = width;
     v->k.h = height;
     v->k.fx = cam->fx;
@@ -43,12 +37,52 @@ int oslam_view_create(const void *depth, int depth_is_u16, int width, int height
     v->k.z_min = cam->z_min;
     v->k.z_max = cam->z_max;
     v->max_jump = cam->max_jump;
+    /* the z image lives as long as the view: its own block, not one of the kept scratch blocks */
+    HIPCHK(hipMalloc((void **)&v->d_z, sizeof(float) * (size_t)width * (size_t)height));
+    v->k.z = v->d_z;
+    *out = v;
+done:
+    if (rc != OSLAM_OK) free(v);
+    return rc;
+}
+
+void oslam_view_camera(const oslam_view *v, oslam_camera *cam)
+{
+    memset(cam, 0, sizeof *cam);
+    cam->fx = v->k.fx;
+    cam->fy = v->k.fy;
+    cam->cx = v->k.cx;
+    cam->cy = v->k.cy;
+    cam->depth_scale = 1.0f;
+    cam->z_min = v->k.z_min;
+    cam->z_max = v->k.z_max;
+    cam->max_jump = v->max_jump;
+}
+
+int oslam_view_create(const void *depth, int depth_is_u16, int width, int height, const oslam_camera *cam, int dev,
+                      oslam_view **out)
+{
+    int rc = OSLAM_OK, devsel;
+    const size_t n_pix = (size_t)width * (size_t)height, px_bytes = depth_is_u16 ? 2 : 4;
+    void *d_raw = NULL;
+    oslam_view *v = NULL;
+    if (out) *out = NULL;
+    if (!depth || !cam || !out || !oslam_view_camera_ok(cam, width, height, 1, 0))
+        return fail(OSLAM_E_INVALID, "bad view arguments");
+    rc = oslam_pick_device(dev, &devsel);
+    if (rc != OSLAM_OK) return rc;
+    rc = oslam_view_new(devsel, width, height, cam, &v);
+    if (rc != OSLAM_OK) return rc;
+    HIPCHK((hipError_t)oslam_dev_alloc(&d_raw, n_pix * px_bytes));
+    HIPCHK(hipMemcpyAsync(d_raw, depth, n_pix * px_bytes, hipMemcpyHostToDevice, (hipStream_t)oslam_stream()));
+    KCHK(oslamk_view_z(d_raw, depth_is_u16 != 0, width, height, cam->depth_scale, cam->z_min, cam->z_max, v->d_z,
+                       oslam_stream()));
+    HIPCHK(hipStreamSynchronize((hipStream_t)oslam_stream()));
 done:
     if (rc != OSLAM_OK) (void)hipStreamSynchronize((hipStream_t)oslam_stream());
     oslam_dev_free(d_raw);
     if (rc != OSLAM_OK) {
-        if (v->d_z) (void)hipFree(v->d_z);
-        free(v);
+        oslam_view_destroy(v);
         return rc;
     }
     *out = v;
@@ -92,18 +126,37 @@ int oslam_verify_check_params(const oslam_verify_params *vp, oslam_verify_params
     return OSLAM_OK;
 }
 
-int oslam_is_zero_pose(const float T[16])
-{
-    int k;
-    for (k = 0; k < 16; k++)
-        if (T[k] != 0.0f) return 0;
-    return 1;
-}
-
 int oslam_view_check_pair(const oslam_model *m, const oslam_view *v)
 {
     if (m->unusable) return fail(OSLAM_E_INVALID, "this model lost its key tables with its database: it can only be destroyed");
     if (m->dev != v->dev) return fail(OSLAM_E_INVALID, "model and view live on different devices");
+    return OSLAM_OK;
+}
+
+int oslam_check_poses(oslam_model *const *ms, const float *T, size_t n, int hypotheses)
+{
+    size_t j;
+    int rc;
+    if (hypotheses && (n == 0 || n > OSLAM_ARBITRATE_MAX_HYPOTHESES))
+        return fail(OSLAM_E_INVALID, "the number of hypotheses must lie in 1..OSLAM_ARBITRATE_MAX_HYPOTHESES");
+    for (j = 0; j < n; j++) {
+        if (ms && !ms[j]) return fail(OSLAM_E_INVALID, "NULL model");
+        if (oslam_is_zero_pose(T + 16 * j)) continue;
+        rc = oslam_refine_check_rigid(T + 16 * j);
+        if (rc != OSLAM_OK) return rc;
+    }
+    return OSLAM_OK;
+}
+
+int oslam_check_handles(oslam_model *const *ms, const float *T, size_t n, const oslam_view *v)
+{
+    size_t j;
+    int rc;
+    for (j = 0; j < n; j++) {
+        if (oslam_is_zero_pose(T + 16 * j)) continue;
+        rc = oslam_view_check_pair(ms[j], v);
+        if (rc != OSLAM_OK) return rc;
+    }
     return OSLAM_OK;
 }
 
@@ -199,17 +252,12 @@ int oslam_db_verify(oslam_db *db, const oslam_view *v, const float *T, const osl
                     oslam_verify_result *res)
 {
     oslam_verify_params p;
-    size_t j;
     int rc;
     if (!db || !v || !T || !res) return fail(OSLAM_E_INVALID, "NULL argument");
     rc = oslam_verify_check_params(vp, &p);
+    if (rc == OSLAM_OK) rc = oslam_check_poses(NULL, T, db->n, 0);
+    if (rc == OSLAM_OK) rc = oslam_check_handles(db->models, T, db->n, v);
     if (rc != OSLAM_OK) return rc;
-    for (j = 0; j < db->n; j++) {
-        if (oslam_is_zero_pose(T + 16 * j)) continue;
-        rc = oslam_refine_check_rigid(T + 16 * j);
-        if (rc == OSLAM_OK) rc = oslam_view_check_pair(db->models[j], v);
-        if (rc != OSLAM_OK) return rc;
-    }
     return oslam_verify_members(db->models, db->n, v, T, &p, res);
 }
 

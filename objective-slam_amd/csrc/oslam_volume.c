@@ -132,20 +132,11 @@ done:
     return rc;
 }
 
-/* rows of the inverse of the rigid T: [R^T | -(R^T t)] in double, rounded to float */
-static void invert_rigid(const float T[16], float inv[12])
-{
-    int a, b;
-    for (a = 0; a < 3; a++) {
-        for (b = 0; b < 3; b++) inv[4 * a + b] = T[4 * b + a];
-        inv[4 * a + 3] = (float)-(((double)T[a] * (double)T[3] + (double)T[4 + a] * (double)T[7]) + (double)T[8 + a] * (double)T[11]);
-    }
-}
-
 int oslam_volume_integrate(oslam_volume *vol, const oslam_view *v, const float T_vol_cam[16], oslam_integrate_result *res)
 {
-    int rc;
+    int rc, a;
     const double t0 = now_ms();
+    double inv_d[12];
     float inv[12];
     uint32_t *d_cnt = NULL, cnt = 0;
     void *stream = oslam_stream();
@@ -154,7 +145,8 @@ int oslam_volume_integrate(oslam_volume *vol, const oslam_view *v, const float T
     if (rc != OSLAM_OK) return rc;
     if (vol->dev != v->dev) return fail(OSLAM_E_INVALID, "volume and view live on different devices");
     if (res) memset(res, 0, sizeof *res);
-    invert_rigid(T_vol_cam, inv);
+    oslam_rigid_inverse(T_vol_cam, inv_d);
+    for (a = 0; a < 12; a++) inv[a] = (float)inv_d[a];
     if (hipSetDevice(vol->dev) != hipSuccess) return fail(OSLAM_E_DEVICE, "hipSetDevice failed");
     pthread_mutex_lock(&g_vol_mu);
     KCHK(oslam_counters_open(&d_cnt, 0, stream));
@@ -176,10 +168,7 @@ done:
 static int check_raycast(const oslam_volume *vol, const float *T, const oslam_camera *cam, int width, int height)
 {
     if (!vol || !T || !cam) return fail(OSLAM_E_INVALID, "NULL argument");
-    if (width < 1 || height < 1 || width > 16384 || height > 16384 || !isfinite(cam->fx) || !isfinite(cam->fy) ||
-        !isfinite(cam->cx) || !isfinite(cam->cy) || !(cam->fx > 0.0f) || !(cam->fy > 0.0f) || !(cam->z_max >= cam->z_min) ||
-        !(cam->z_min > 0.0f) || !isfinite(cam->z_max) || !(cam->max_jump >= 0.0f) || !isfinite(cam->max_jump))
-        return fail(OSLAM_E_INVALID, "bad ray cast camera or size");
+    if (!oslam_view_camera_ok(cam, width, height, 0, 1)) return fail(OSLAM_E_INVALID, "bad ray cast camera or size");
     return oslam_refine_check_rigid(T);
 }
 
@@ -187,24 +176,13 @@ static int check_raycast(const oslam_volume *vol, const float *T, const oslam_ca
 static int raycast(oslam_volume *vol, const float T[16], const oslam_camera *cam, int width, int height, oslam_view **out,
                    uint32_t cnt[2])
 {
-    int rc = OSLAM_OK;
+    int rc;
     const size_t n_pix = (size_t)width * (size_t)height;
     uint32_t *d_cnt = NULL;
     void *stream = oslam_stream();
-    oslam_view *v = (oslam_view *)calloc(1, sizeof *v);
-    if (!v) return fail(OSLAM_E_NOMEM, "host allocation failed");
-    v->dev = vol->dev;
-    v->k.w = width;
-    v->k.h = height;
-    v->k.fx = cam->fx;
-    v->k.fy = cam->fy;
-    v->k.cx = cam->cx;
-    v->k.cy = cam->cy;
-    v->k.z_min = cam->z_min;
-    v->k.z_max = cam->z_max;
-    v->max_jump = cam->max_jump;
-    HIPCHK(hipMalloc((void **)&v->d_z, sizeof(float) * n_pix));
-    v->k.z = v->d_z;
+    oslam_view *v;
+    rc = oslam_view_new(vol->dev, width, height, cam, &v);
+    if (rc != OSLAM_OK) return rc;
     KCHK(oslam_dev_alloc((void **)&v->d_maps, sizeof(float) * 8 * n_pix));
     KCHK(oslam_counters_open(&d_cnt, 0, stream));
     KCHK(oslamk_tsdf_raycast(&vol->k, &v->k, T, v->d_z, v->d_maps, d_cnt, stream));
@@ -214,9 +192,7 @@ done:
     if (rc != OSLAM_OK) (void)hipStreamSynchronize((hipStream_t)stream);
     if (d_cnt) oslam_dev_free(d_cnt);
     if (rc != OSLAM_OK) {
-        if (v->d_maps) oslam_dev_free(v->d_maps);
-        if (v->d_z) (void)hipFree(v->d_z);
-        free(v);
+        oslam_view_destroy(v);
         return rc;
     }
     *out = v;
@@ -247,35 +223,6 @@ int oslam_volume_raycast(oslam_volume *vol, const float T_vol_cam[16], const osl
     return rc;
 }
 
-/* T_out = float32(double(T_prev) * double(T)), the element order of oslam_tracker_step_cam */
-static void pose_product(const float T_prev[16], const float T[16], float T_out[16])
-{
-    int a, b;
-    for (a = 0; a < 3; a++)
-        for (b = 0; b < 4; b++) {
-            double x = ((double)T_prev[4 * a] * (double)T[b] + (double)T_prev[4 * a + 1] * (double)T[4 + b]) +
-                       (double)T_prev[4 * a + 2] * (double)T[8 + b];
-            if (b == 3) x += (double)T_prev[4 * a + 3];
-            T_out[4 * a + b] = (float)x;
-        }
-    T_out[12] = T_out[13] = T_out[14] = 0.0f;
-    T_out[15] = 1.0f;
-}
-
-/* the camera that renders a view like v */
-static void camera_of_view(const oslam_view *v, oslam_camera *cam)
-{
-    memset(cam, 0, sizeof *cam);
-    cam->fx = v->k.fx;
-    cam->fy = v->k.fy;
-    cam->cx = v->k.cx;
-    cam->cy = v->k.cy;
-    cam->depth_scale = 1.0f;
-    cam->z_min = v->k.z_min;
-    cam->z_max = v->k.z_max;
-    cam->max_jump = v->max_jump;
-}
-
 /* The body of oslam_volume_track (frame and q both NULL: v against the ray cast from T_prev) and of
  * oslam_volume_track_pyramid (frame and q both given, v = the base of frame: frame against a pyramid of the ray cast
  * made with q), after their argument checks; p and q are the parameters in force, t0 the start of the call.  frame is
@@ -291,7 +238,7 @@ static int track_from_raycast(oslam_volume *vol, oslam_view *v, oslam_pyramid *f
     oslam_pyramid *model_pyr = NULL;
     uint32_t cnt[2];
     float T[16];
-    camera_of_view(v, &cam);
+    oslam_view_camera(v, &cam);
     if (hipSetDevice(vol->dev) != hipSuccess) return fail(OSLAM_E_DEVICE, "hipSetDevice failed");
     pthread_mutex_lock(&g_vol_mu);
     rc = raycast(vol, T_prev, &cam, v->k.w, v->k.h, &model, cnt);
@@ -303,7 +250,9 @@ static int track_from_raycast(oslam_volume *vol, oslam_view *v, oslam_pyramid *f
     if (model_pyr) oslam_pyramid_destroy(model_pyr);
     if (model) oslam_view_destroy(model);
     if (rc != OSLAM_OK) return rc;
-    pose_product(T_prev, T, T_out);
+    oslam_rigid_product_f(T_prev, T, T_out);      /* the element order of oslam_tracker_step_cam */
+    T_out[12] = T_out[13] = T_out[14] = 0.0f;
+    T_out[15] = 1.0f;
     if (ego_res) {
         *ego_res = er;
         ego_res->launches += 1 + (frame ? q->n_levels - 1 : 0);     /* the ray cast and the down-sampling launches */

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import arbitrate_ref as A  # noqa: E402
 import refine_ref as R  # noqa: E402
 from test_refine_host import CASES, make_trial  # noqa: E402
 
@@ -271,3 +272,34 @@ def test_launches_do_not_depend_on_members(built_lib, ppf, synth):
             db.close()
     for m in models:
         m.close()
+
+
+def test_loaded_model_has_the_created_models_shape(built_lib, ppf, tmp_path):
+    """A model's centroid and extent are made with its cloud, by oslam_model_create and by oslam_model_load alike: the
+    stages that read them (refine: the pivot; find_instances: the instance rule; arbitrate: the tile) give the same
+    from a model and from its saved and loaded copy.  The tile is also the restatement's (tests/arbitrate_ref.py) and
+    not a clamped one: it was computed from the centroid."""
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "case_m64_s128.npz"))
+    d, T0 = float(g["d_dist"]), np.ascontiguousarray(g["T_gpu"], np.float32)
+    made = ppf.Model(g["mp"], g["mn"], d_dist=d)
+    path = str(tmp_path / "m64.oslam")
+    made.save(path)
+    loaded = ppf.Model.load(path)
+    scene = ppf.Scene(g["sp"], g["sn"], d_dist=d)
+    view = ppf.View(np.full((48, 64), 2.0, np.float32), 100.0, 100.0, 32.0, 24.0, depth_scale=1.0)
+    Ta, ra = made.refine(scene, T0)
+    Tb, rb = loaded.refine(scene, T0)
+    assert Ta.any() and Ta.tobytes() == Tb.tobytes()
+    assert {k: v for k, v in ra.items() if k not in DYN} == {k: v for k, v in rb.items() if k not in DYN}
+    ip = ppf.default_instance_params(keep_not_found=1)
+    ia, ib = made.find_instances(scene, params=ip), loaded.find_instances(scene, params=ip)
+    assert len(ia) >= 1 and len(ia) == len(ib)
+    for (Pa, fa), (Pb, fb) in zip(ia, ib):
+        assert Pa.tobytes() == Pb.tobytes() and fa["T_vote"].tobytes() == fb["T_vote"].tobytes()
+        assert (fa["score"], fa["candidate"]) == (fb["score"], fb["candidate"])
+        assert {k: v for k, v in fa["refine"].items() if k not in DYN} == {k: v for k, v in fb["refine"].items() if k not in DYN}
+    want = A.choose_tile([(np.asarray(g["mp"], np.float32), None, d)], T0[None], 100.0)
+    tiles = [ppf.arbitrate([m], view, T0[None])[0][0]["tile"] for m in (made, loaded)]
+    assert 4 < want < 128 and tiles == [want, want], (tiles, want)
+    for h in (view, scene, loaded, made):
+        h.close()
