@@ -217,7 +217,7 @@ __device__ __forceinline__ uint32_t forced_item(lds_ctx *sc, lds_u32 *acc, lds_u
  * atomics are issued with EXEC narrowed to the lanes that hold entries, so idle lanes cost no LDS cycles
  * and cause no bank conflicts; the padding behind a bucket votes into the sink row.  Written in asm because
  * the compiler has no way to say this; the workgroup waits for these atomics (lgkmcnt) before it reads the
- * accumulator.  Per hit (256 votes): v_readlane + 4 x (v_sub, v_mul_hi, v_lshl_add) + 4 LDS atomics + three scalar
+ * accumulator.  Per hit (256 votes): v_readlane + 4 x (v_sub, v_mul_hi, v_fma_f32) + 4 LDS atomics + three scalar
  * instructions of loop control = 20 instructions, in both modes.  Items that carry a marker never come here
  * (forced_item). */
 /* word 3 of a raw buffer descriptor on gfx9: 32-bit data format, no swizzle, no stride */
@@ -281,7 +281,7 @@ struct VoteRegs {
         /* Every vote goes into its quantised bin, in both modes.  The kernel is bound by the number of instructions its
          * waves issue, of whatever kind (3.6 cycles per instruction and SIMD over the whole kernel, scalar ones
          * included: profiles/r03_pmc_sq_k_vote.txt), so the loop over the hits is written out: per hit and chunk
-         * v_readlane + 4 x (v_sub, v_mul_hi, v_lshl_add) + 4 ds_add_u32 + s_add, s_cmp, s_cbranch = 20 instructions,
+         * v_readlane + 4 x (v_sub, v_mul_hi, v_fma_f32) + 4 ds_add_u32 + s_add, s_cmp, s_cbranch = 20 instructions,
          * EXEC narrowed to the live lanes once per step, not per hit (the compiler's loop had 24: EXEC saved, set and
          * restored around the atomics of every hit, and a hazard s_nop).  The two scalar instructions between
          * v_readlane and the first v_sub are the wait states gfx950 asks for between a vector write of a scalar
@@ -299,6 +299,25 @@ struct VoteRegs {
 #else
 #define VOTE_ATOMICS "ds_add_u32 %[t0], %[n0]\n\tds_add_u32 %[t1], %[n1]\n\tds_add_u32 %[t2], %[n2]\n\tds_add_u32 %[t3], %[n3]\n\t"
 #endif
+            /* The vote's address, row address + 4 * bin, is computed on the float pipe.  A 32-bit pattern below 2^23 read
+             * as a float is zero or a denormal worth n * 2^-149, so v_fma_f32 on such patterns is exact integer
+             * arithmetic, and on gfx950 it issues in 2.5 cycles where v_lshl_add_u32 takes 4.2
+             * (tools/micro/valu_rate_bench.hip, profiles/r19_float_pipe_microbench.txt).  What the form depends on:
+             *   - patterns below 2^23 on both sides, so that nothing is rounded: the largest value is the last bin of
+             *     the sink row, acc_base + 1023 * 124 + 4 * 30 (checked here for any acc_base in the 160 KiB of LDS);
+             *   - f32 denormals kept, in and out: float_denorm_mode_32 = 3 in the kernel descriptor, which
+             *     tools/kernel_resources.sh prints for the vote kernels.  Flushed, every vote would land in word 0.
+             * In asm like the rest of the loop, so the compiler sees no float arithmetic that it could fold.  The
+             * integer form stays behind -DVOTE_INT_ADDR for A/B builds from one source (make EXTRA=-DVOTE_INT_ADDR).
+             * The row address and the first-pass increment of the step were built the same way (v_fmamk_f32, v_fma_f32)
+             * and gained too little to keep: profiles/r19_bench_parent_vs_float_pipe.txt. */
+            static_assert(160u * 1024u + (OSLAMK_ROWS - 1u) * (4u * ACC_STRIDE) + 4u * 30u < (1u << 23),
+                          "the float form of the vote address needs every pattern below 2^23");
+#ifdef VOTE_INT_ADDR
+#define VOTE_ADDR(t, r) "v_lshl_add_u32 " t ", " t ", 2, " r "\n\t"
+#else
+#define VOTE_ADDR(t, r) "v_fma_f32 " t ", " t ", 4.0, " r "\n\t"
+#endif
             uint32_t i = d.i0;
             asm volatile("s_mov_b64 %[sv], exec\n\t"
                          "s_mov_b64 exec, %[live]\n"
@@ -314,10 +333,7 @@ struct VoteRegs {
                          "v_mul_hi_u32 %[t1], %[t1], 30\n\t"
                          "v_mul_hi_u32 %[t2], %[t2], 30\n\t"
                          "v_mul_hi_u32 %[t3], %[t3], 30\n\t"
-                         "v_lshl_add_u32 %[t0], %[t0], 2, %[r0]\n\t"
-                         "v_lshl_add_u32 %[t1], %[t1], 2, %[r1]\n\t"
-                         "v_lshl_add_u32 %[t2], %[t2], 2, %[r2]\n\t"
-                         "v_lshl_add_u32 %[t3], %[t3], 2, %[r3]\n\t" VOTE_ATOMICS
+                         VOTE_ADDR("%[t0]", "%[r0]") VOTE_ADDR("%[t1]", "%[r1]") VOTE_ADDR("%[t2]", "%[r2]") VOTE_ADDR("%[t3]", "%[r3]") VOTE_ATOMICS
                          "s_cbranch_scc1 .Lvote_hit_%=\n\t"
                          "s_mov_b64 exec, %[sv]"
                          : [sv] "=&s"(saved), [c] "=&s"(c), [i] "+s"(i), [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2), [t3] "=&v"(t3)
@@ -326,6 +342,7 @@ struct VoteRegs {
                            [n1] "v"(inc[1]), [n2] "v"(inc[2]), [n3] "v"(inc[3])
                          : "scc", "memory");
 #undef VOTE_ATOMICS
+#undef VOTE_ADDR
         }
     }
 };

@@ -1,5 +1,8 @@
 // Microbenchmark: issue cost of the integer vector instructions the vote loop uses, gfx950.
 // 16 waves per CU (4 per SIMD), each runs a dependent-free stream of N copies of one instruction.
+// The "small patterns" rows are float instructions whose operands and results are all 32-bit patterns below 2^23 (zero
+// or a denormal, worth n * 2^-149): exact integer arithmetic as long as f32 denormals are kept.  The program compares
+// each of them bit for bit with the integer form it could replace and prints the number of differences.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #define REP 64
@@ -37,13 +40,40 @@
 #define I_MOV(n) "v_mov_b32 %" #n ", %8\n"
 #define I_ADDLSHL(n) "v_add_lshl_u32 %" #n ", %8, %9, 2\n"
 #define I_MAD64A(n) "v_mad_u64_u32 %" #n ", vcc, %8, 30, %" #n "\n"
+// a = bin (0..30), b = row address, %10 = a scalar register with the literal (124.0 or 65535/1024)
+#define I_FMA_ADDR(n) "v_fma_f32 %" #n ", %8, 4.0, %9\n"
+#define I_MUL_ROW(n) "v_mul_f32 %" #n ", 0x42f80000, %8\n"
+#define I_FMA_ROW(n) "v_fma_f32 %" #n ", %8, %10, %9\n"
+#define I_FMA_INC(n) "v_fma_f32 %" #n ", %8, %10, 1\n"
+#define I_FMAMK_ROW(n) "v_fmamk_f32 %" #n ", %8, 0x42f80000, %9\n"
+#define I_SUB_S(n) "v_sub_u32 %" #n ", %10, %8\n"
+#define I_MAX_F32(n) "v_max_f32 %" #n ", 1, %8\n"
+#define BODY_S(INSTR, K)                                                                             \
+    for (int i = 0; i < ITER; i++) {                                                                 \
+        _Pragma("unroll") for (int k = 0; k < REP / 8; k++) {                                        \
+            asm volatile(INSTR(0) INSTR(1) INSTR(2) INSTR(3) INSTR(4) INSTR(5) INSTR(6) INSTR(7)     \
+                         : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(r[4]), "+v"(r[5]),   \
+                           "+v"(r[6]), "+v"(r[7])                                                    \
+                         : "v"(a), "v"(b), "s"(K));                                                  \
+        }                                                                                            \
+    }
 template <int W>
 __global__ __launch_bounds__(1024) void k(unsigned long long *cyc, uint32_t *sink)
 {
     uint32_t r[8] = {1, 2, 3, 4, 5, 6, 7, 8};
     uint32_t a = threadIdx.x * 2654435761u, b = threadIdx.x + 17;
+    if (W == 24) { a = threadIdx.x % 31u; b = 64u + (threadIdx.x & 1023u) * 124u; }      /* bin, row address */
+    if (W == 25 || W == 26 || W == 28) { a = threadIdx.x & 1023u; b = 64u; }                         /* row, accumulator base */
+    if (W == 27) { a = (threadIdx.x & 1u) << 10; }                                        /* the half bit in place */
     __syncthreads();
     const long long t0 = clock64();
+    if (W == 24) { BODY(I_FMA_ADDR) }
+    if (W == 25) { BODY(I_MUL_ROW) }
+    if (W == 26) { BODY_S(I_FMA_ROW, 0x42f80000u) }
+    if (W == 27) { BODY_S(I_FMA_INC, 0x427fff00u) }
+    if (W == 28) { BODY(I_FMAMK_ROW) }
+    if (W == 29) { BODY_S(I_SUB_S, 0x12345678u) }
+    if (W == 30) { BODY(I_MAX_F32) }
     if (W == 0) { BODY(I_MULHI24) }
     if (W == 1) { BODY(I_MUL24) }
     if (W == 2) { BODY(I_MULHI32) }
@@ -105,6 +135,25 @@ void run(const char *name, unsigned long long *d_cyc, uint32_t *d_sink)
     // per SIMD: 4 waves x ITER x REP instructions
     printf("%-30s %6.2f cycles per wave-instruction per SIMD (4 waves per SIMD)\n", name, s / (4.0 * ITER * REP));
 }
+/* Every row, bin and half bit, at three accumulator bases: the float forms against the integer forms, bit for bit. */
+__global__ void k_exact(uint32_t *diff)
+{
+    const uint32_t row = blockIdx.x, bin = threadIdx.x & 31u, base = (threadIdx.x >> 5) * 2048u;   /* 0, 2048, 4096, 6144 */
+    if (bin > 30u) return;
+    const uint32_t w = row | ((row & 1u) << 10) | (bin << 11);         /* an entry word: row, a half bit, bits above */
+    uint32_t rowi, rowf, rowk, rowm, adi, adf, inci, incf, t;
+    rowi = base + (w & 0x3ffu) * 124u;
+    asm volatile("v_and_b32 %0, 0x3ff, %1\n\tv_fma_f32 %0, %0, %2, %3" : "=&v"(rowf) : "v"(w), "s"(0x42f80000u), "v"(base));
+    asm volatile("v_and_b32 %0, 0x3ff, %1\n\tv_fmamk_f32 %0, %0, 0x42f80000, %2" : "=&v"(rowk) : "v"(w), "v"(base));
+    asm volatile("v_and_b32 %0, 0x3ff, %1\n\tv_mul_f32 %0, 0x42f80000, %0" : "=&v"(rowm) : "v"(w));
+    asm volatile("v_lshl_add_u32 %0, %1, 2, %2" : "=v"(adi) : "v"(bin), "v"(rowi));
+    asm volatile("v_fma_f32 %0, %1, 4.0, %2" : "=v"(adf) : "v"(bin), "v"(rowi));
+    asm volatile("v_bfe_u32 %0, %1, 10, 1\n\tv_mad_u32_u24 %0, %0, %2, 1" : "=&v"(inci) : "v"(w), "s"(0xffffu));
+    asm volatile("v_and_b32 %0, 0x400, %1\n\tv_fma_f32 %0, %0, %2, 1" : "=&v"(incf) : "v"(w), "s"(0x427fff00u));
+    t = (rowi != rowf) + (rowi != rowk) + (rowm != (w & 0x3ffu) * 124u) + (adi != adf) + (inci != incf);
+    if (inci != 1u && inci != 0x10000u) t++;
+    if (t) atomicAdd(diff, t);
+}
 int main()
 {
     unsigned long long *d_cyc; uint32_t *d_sink;
@@ -133,5 +182,17 @@ int main()
     run<20>("v_readlane_b32", d_cyc, d_sink);
     run<21>("v_mov_b32", d_cyc, d_sink);
     run<22>("v_add_lshl_u32", d_cyc, d_sink);
-    return 0;
+    run<24>("v_fma_f32 bin * 4.0 + row address, small patterns", d_cyc, d_sink);
+    run<25>("v_mul_f32 row * 124.0, small patterns", d_cyc, d_sink);
+    run<26>("v_fma_f32 row * 124.0 (scalar register) + base, small patterns", d_cyc, d_sink);
+    run<27>("v_fma_f32 x * 65535/1024 (scalar register) + 1, small patterns", d_cyc, d_sink);
+    run<28>("v_fmamk_f32 row * 124.0 + base, small patterns", d_cyc, d_sink);
+    run<29>("v_sub_u32, scalar register first", d_cyc, d_sink);
+    run<30>("v_max_f32 with 1, small patterns", d_cyc, d_sink);
+    (void)hipMemset(d_sink, 0, 4);
+    hipLaunchKernelGGL(k_exact, dim3(1024), dim3(128), 0, 0, d_sink);
+    uint32_t diff = 0;
+    const hipError_t e = hipMemcpy(&diff, d_sink, 4, hipMemcpyDeviceToHost);
+    printf("float forms against integer forms, 1024 rows x 31 bins x 4 bases: %u differences%s\n", diff, e == hipSuccess ? "" : " (copy failed)");
+    return diff != 0 || e != hipSuccess;
 }

@@ -4,6 +4,8 @@
 //   W = 2  both, as the kernel issues them          W = 3  both, addresses from the arithmetic (random banks)
 //   W = 4  fast-mode mix (13 vector instructions) + atomics
 //   W = 5  as 2 with two workgroups of 8 waves per CU (grid 512 x 512 threads)
+//   W = 6  fast-mode mix without atomics             W = 7  as 6, address by v_fma_f32 (bin * 4.0 + row address, patterns < 2^23)
+//   W = 8  as 4, address by v_fma_f32
 // Prints SIMD cycles per iteration per wave (wall cycles x 4 waves per SIMD would be the naive bound).
 // hipcc --offload-arch=gfx950 -O3 tools/micro/vote_mix_bench.hip -o /tmp/vote_mix && /tmp/vote_mix
 #include <hip/hip_runtime.h>
@@ -38,15 +40,16 @@ __global__ __launch_bounds__(1024) void k(unsigned long long *cyc, uint32_t *sin
                 uint32_t bin = (uint32_t)(p >> 32);
                 pos[j] = (uint32_t)p;
                 asm("" : "+v"(bin));
-                addr[j] = rowb[j] + (bin << 2);
+                if (W == 7 || W == 8) asm("v_fma_f32 %0, %1, 4.0, %2" : "=v"(addr[j]) : "v"(bin), "v"(rowb[j]));
+                else addr[j] = rowb[j] + (bin << 2);
             }
-            if (W != 4) {
+            if (W < 4 || W == 5) {
                 const uint32_t lo3 = min(min(pos[0], pos[1]), pos[2]);
                 const unsigned long long near = __ballot(min(lo3, pos[3]) < 16u);
                 if (__builtin_expect(near != 0ull, 0)) trig += near;
             }
         }
-        if (W == 0) {
+        if (W == 0 || W == 6 || W == 7) {
             asm volatile("" ::"v"(addr[0]), "v"(addr[1]), "v"(addr[2]), "v"(addr[3]));
         } else if (W == 1 || W == 2 || W == 5) {
             asm volatile("ds_add_u32 %0, %4\n\tds_add_u32 %1, %5\n\tds_add_u32 %2, %6\n\tds_add_u32 %3, %7"
@@ -89,5 +92,8 @@ int main()
     run<3>("both, atomics at the computed (random-bank) addresses", 256, 1024, d_cyc, d_sink);
     run<4>("fast-mode mix (13 vector instructions) + atomics at computed addresses", 256, 1024, d_cyc, d_sink);
     run<5>("both, conflict-free, two workgroups of 8 waves per CU", 512, 512, d_cyc, d_sink);
+    run<6>("fast-mode mix (13 vector instructions), no atomics", 256, 1024, d_cyc, d_sink);
+    run<7>("fast-mode mix, address by v_fma_f32, no atomics", 256, 1024, d_cyc, d_sink);
+    run<8>("fast-mode mix, address by v_fma_f32, + atomics at computed addresses", 256, 1024, d_cyc, d_sink);
     return 0;
 }
