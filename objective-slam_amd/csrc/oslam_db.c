@@ -201,15 +201,17 @@ int oslam_db_align_frame(oslam_db *db, oslam_scene *s, float *T_out, oslam_stats
     else rc = oslam_pool_enter(db->dev, &pool);
     for (g = 0; g < db->n_groups && rc == OSLAM_OK; g++) {
         db_group *gr = &db->groups[g];
-        float ms_all = 0.0f, msv = 0.0f, msk = 0.0f;
-        uint32_t launches = 0;
-        uint64_t probed = 0;
+        oslam_vote_times share;      /* of one member in the group's pass */
+        memset(&share, 0, sizeof share);
         for (k = 0; k < gr->n; k++) ms[k] = db->models[gr->members[k]];
         if (gr->n > 1) {
             /* one scene pass, every member's votes behind it */
-            rc = oslam_run_votes_group(pool, ms, gr->n, s, s->d_ref_idx, s->d_tsg, s->n_ref, 0, NULL, cnt, &ms_all, &msv, &msk,
-                                       &launches, &probed);
+            rc = oslam_run_votes_group(pool, ms, gr->n, s, s->d_ref_idx, s->d_tsg, s->n_ref, 0, NULL, cnt, &share);
             if (rc != OSLAM_OK) break;
+            /* num_hits is the group pass's (pairs whose key is in some member); its times are shared out evenly */
+            share.ms /= (float)gr->n;
+            share.ms_vote_kernel /= (float)gr->n;
+            share.ms_key_kernel /= (float)gr->n;
         }
         /* The pose tails of the group's members, in flight together: every member's selection of its peak records is
          * enqueued, one wait, then every member's chain (order, poses, clustering scores, winner), one wait -- two
@@ -265,10 +267,7 @@ int oslam_db_align_frame(oslam_db *db, oslam_scene *s, float *T_out, oslam_stats
             int arc;
             memset(st, 0, sizeof *st);
             if (gr->n > 1 && cnt[k].out_count <= m->out_cap) {
-                /* num_hits is the group pass's (pairs whose key is in some member); its kernel times are shared out
-                 * evenly */
-                oslam_vote_stats(st, pool, m, s, &cnt[k], ms_all / (float)gr->n, msv / (float)gr->n, msk / (float)gr->n,
-                                 launches, probed);
+                oslam_vote_stats(st, pool, m, s, &cnt[k], &share);
                 if (on_dev[k]) {                            /* its chain has run: the winner is in its slot */
                     uint32_t best = 0;
                     oslamk_pose_result((uint32_t)k, &best, T);

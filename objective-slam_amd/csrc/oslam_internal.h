@@ -190,13 +190,18 @@ int oslam_pool_enter(int dev, scratch_pool **pool);
 void oslam_pool_unlock(scratch_pool *p);
 int oslam_pool_reserve_counts(scratch_pool *p, size_t n_ref);
 void oslam_ref_order(const uint32_t *keep, size_t n, uint32_t *order);
+/* what a vote pass reports; a pass sets ms and probed and adds to the rest.  NULL where it is not wanted */
+typedef struct oslam_vote_times {
+    float ms;                         /* the whole pass on the stream */
+    float ms_vote_kernel, ms_key_kernel;
+    uint32_t launches;                /* batches */
+    uint64_t probed;                  /* pairs within reach */
+} oslam_vote_times;
 int oslam_run_votes_group(scratch_pool *pool, oslam_model *const *ms, int nm, oslam_scene *s, const uint32_t *d_ref_idx,
-                          const float *d_tsg, int n_ref, uint32_t fixed_gmax, uint32_t *acc_dump,
-                          oslamk_counters *cnt, float *ms_out, float *ms_vote_kernel, float *ms_key_kernel,
-                          uint32_t *launches, uint64_t *probed);
+                          const float *d_tsg, int n_ref, uint32_t fixed_gmax, uint32_t *acc_dump, oslamk_counters *cnt,
+                          oslam_vote_times *t);
 void oslam_vote_stats(oslam_stats *st, const scratch_pool *pool, const oslam_model *m, const oslam_scene *s,
-                      const oslamk_counters *cnt, float ms_vote, float ms_vote_kernel, float ms_key_kernel,
-                      uint32_t launches, uint64_t probed);
+                      const oslamk_counters *cnt, const oslam_vote_times *t);
 int oslam_vote_records(scratch_pool *pool, oslam_model *m, oslam_scene *s, oslamk_counters *cnt, size_t *n_cells,
                        oslam_stats *st, int to_host);
 int oslam_grow_records(oslam_model *m, uint64_t need);

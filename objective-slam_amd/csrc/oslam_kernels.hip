@@ -468,6 +468,39 @@ __device__ __forceinline__ bool bin_in_reach(const uint32_t *reach, uint32_t rea
     return w < reach_words && ((reach[w] >> ((uint32_t)k & 31u)) & 1u);
 }
 
+/* Phase 1 of the two scene-key kernels, written once: k_scene_count sizes the hit lists by it and k_scene_hits fills
+ * them by it, and list_overflow & 1 (hits_chunk) checks at run time that the two agreed.
+ * The COUNT_REFS reference points of workgroup column g0 / COUNT_REFS: index and position, in scalar registers (a
+ * group beyond the launch: no point's index, at the origin). */
+struct KeyRefs {
+    uint32_t rr[COUNT_REFS];
+    float prx[COUNT_REFS], pry[COUNT_REFS], prz[COUNT_REFS];
+};
+__device__ __forceinline__ void key_refs_load(KeyRefs &r, const oslamk_vote_args &a, int g0)
+{
+#pragma unroll
+    for (int g = 0; g < COUNT_REFS; g++) {
+        const bool v = g0 + g < a.n_launch;
+        r.rr[g] = v ? a.ref_idx[a.first_ref + g0 + g] : 0xffffffffu;
+        r.prx[g] = v ? a.scene.px[r.rr[g]] : 0.0f;
+        r.pry[g] = v ? a.scene.py[r.rr[g]] : 0.0f;
+        r.prz[g] = v ? a.scene.pz[r.rr[g]] : 0.0f;
+    }
+}
+/* the workgroup's LDS copy of the reach bitset (256 threads; the caller's barrier follows) */
+__device__ __forceinline__ void reach_fill(uint32_t *s_reach, const uint32_t *reach, uint32_t reach_words)
+{
+    for (uint32_t w = threadIdx.x; w < reach_words; w += 256) s_reach[w] = reach[w];
+}
+/* Is the pair (reference point g of the workgroup, scene point i at x y z) kept?  `in`: i is a point of the scene;
+ * `valid`: what the kernel asks of g itself (k_scene_hits: it is inside the launch; k_scene_count guards its last add). */
+__device__ __forceinline__ bool pair_keep(const KeyRefs &r, int g, bool valid, int i, bool in, float x, float y, float z,
+                                          const oslamk_vote_args &a, const uint32_t *s_reach, uint32_t reach_words)
+{
+    const int k = pair_dist_bin_quick(x - r.prx[g], y - r.pry[g], z - r.prz[g], a.d_dist, a.inv_d_dist);
+    return in && (uint32_t)i != r.rr[g] && valid && bin_in_reach(s_reach, reach_words, k);
+}
+
 /* Sizes the hit lists by demand: keep_count[ref] = pairs of the reference point whose distance bin is within
  * reach (what k_scene_hits keys and looks up), an upper bound of its hits -- 16 % above them on the bench
  * scene.  A workgroup tests its tile of scene points against COUNT_REFS reference points (their coordinates
@@ -480,19 +513,11 @@ __global__ __launch_bounds__(256) void k_scene_count(oslamk_vote_args a)
     const int S = a.scene.n, lane = threadIdx.x & (WAVE - 1);
     const int g0 = blockIdx.x * COUNT_REFS;
     const uint32_t reach_words = a.table.reach_words;
-    uint32_t rr[COUNT_REFS], cnt[COUNT_REFS];
-    float prx[COUNT_REFS], pry[COUNT_REFS], prz[COUNT_REFS];
-#pragma unroll
-    for (int g = 0; g < COUNT_REFS; g++) {
-        const bool v = g0 + g < a.n_launch;
-        rr[g] = v ? a.ref_idx[a.first_ref + g0 + g] : 0xffffffffu;
-        prx[g] = v ? a.scene.px[rr[g]] : 0.0f;
-        pry[g] = v ? a.scene.py[rr[g]] : 0.0f;
-        prz[g] = v ? a.scene.pz[rr[g]] : 0.0f;
-        cnt[g] = 0;
-    }
+    KeyRefs r;
+    uint32_t cnt[COUNT_REFS] = {0};
+    key_refs_load(r, a, g0);
     if (threadIdx.x < COUNT_REFS) s_cnt[threadIdx.x] = 0;
-    for (uint32_t w = threadIdx.x; w < reach_words; w += 256) s_reach[w] = a.table.reach[w];
+    reach_fill(s_reach, a.table.reach, reach_words);
     __syncthreads();
     for (int c = 0; c < KEY_TILE / 256; c++) {
         const int i = blockIdx.y * KEY_TILE + c * 256 + threadIdx.x;
@@ -500,9 +525,7 @@ __global__ __launch_bounds__(256) void k_scene_count(oslamk_vote_args a)
         const float x = in ? a.scene.px[i] : 0.0f, y = in ? a.scene.py[i] : 0.0f, z = in ? a.scene.pz[i] : 0.0f;
 #pragma unroll
         for (int g = 0; g < COUNT_REFS; g++) {
-            const int k = pair_dist_bin_quick(x - prx[g], y - pry[g], z - prz[g], a.d_dist, a.inv_d_dist);
-            const bool keep = in && (uint32_t)i != rr[g] && bin_in_reach(s_reach, reach_words, k);
-            cnt[g] += (uint32_t)__popcll(__ballot(keep));
+            cnt[g] += (uint32_t)__popcll(__ballot(pair_keep(r, g, true, i, in, x, y, z, a, s_reach, reach_words)));
         }
     }
     if (lane == 0) {
@@ -606,18 +629,10 @@ __global__ __launch_bounds__(256) void k_scene_hits(oslamk_vote_args a)
     const uint32_t wave = threadIdx.x >> 6;
     const int g0 = blockIdx.x * COUNT_REFS, tile0 = blockIdx.y * HIT_TILE;
     const uint32_t reach_words = a.table.reach_words;
-    uint32_t rr[COUNT_REFS];
-    float prx[COUNT_REFS], pry[COUNT_REFS], prz[COUNT_REFS];
-#pragma unroll
-    for (int g = 0; g < COUNT_REFS; g++) {
-        const bool v = g0 + g < a.n_launch;
-        rr[g] = v ? a.ref_idx[a.first_ref + g0 + g] : 0xffffffffu;
-        prx[g] = v ? a.scene.px[rr[g]] : 0.0f;
-        pry[g] = v ? a.scene.py[rr[g]] : 0.0f;
-        prz[g] = v ? a.scene.pz[rr[g]] : 0.0f;
-    }
+    KeyRefs r;
+    key_refs_load(r, a, g0);
     if (threadIdx.x < COUNT_REFS) s_n[threadIdx.x] = 0;
-    for (uint32_t w = threadIdx.x; w < reach_words; w += 256) s_reach[w] = a.table.reach[w];
+    reach_fill(s_reach, a.table.reach, reach_words);
     s_lut[threadIdx.x] = d_acos_lut[threadIdx.x];
     __syncthreads();
 
@@ -627,8 +642,7 @@ __global__ __launch_bounds__(256) void k_scene_hits(oslamk_vote_args a)
         const float x = in ? a.scene.px[i] : 0.0f, y = in ? a.scene.py[i] : 0.0f, z = in ? a.scene.pz[i] : 0.0f;
 #pragma unroll
         for (int g = 0; g < COUNT_REFS; g++) {
-            const int k = pair_dist_bin_quick(x - prx[g], y - pry[g], z - prz[g], a.d_dist, a.inv_d_dist);
-            const bool keep = in && (uint32_t)i != rr[g] && g0 + g < a.n_launch && bin_in_reach(s_reach, reach_words, k);
+            const bool keep = pair_keep(r, g, g0 + g < a.n_launch, i, in, x, y, z, a, s_reach, reach_words);
             const unsigned long long km = __ballot(keep);
             if (km) {
                 uint32_t base = 0;

@@ -198,7 +198,7 @@ int oslam_vote_accumulator(oslam_model *m, oslam_scene *s, size_t ref_index, uin
     HIPCHK(hipMemcpy(d_ref, &ref, sizeof ref, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d_tsg, rows, sizeof rows, hipMemcpyHostToDevice));
     /* one reference point through the same kernels; fixed_gmax = all ones: nothing is emitted */
-    rc = oslam_run_votes_group(pool, &m, 1, s, d_ref, d_tsg, 1, 0xffffffffu, d_dump, &cnt, NULL, NULL, NULL, NULL, NULL);
+    rc = oslam_run_votes_group(pool, &m, 1, s, d_ref, d_tsg, 1, 0xffffffffu, d_dump, &cnt, NULL);
     if (rc != OSLAM_OK) goto done;
     h_dump = (uint32_t *)malloc(sizeof(uint32_t) * cells);
     if (!h_dump) { rc = fail(OSLAM_E_NOMEM, "host allocation failed"); goto done; }

@@ -276,6 +276,54 @@ def test_record_buffer_overflow_takes_the_second_pass(ppf, oracle, built_lib, ca
     assert cells_equal(mo.last_cells()[0], ocells) and mo.stats["vote_launches"] >= 1
 
 
+def test_pool_buffers_grow_release_and_grow_again(ppf, oracle, built_lib, synth, case_small):
+    """Every block of the scratch pool grows, is given back and grows again, and each registration on the way has the
+    oracle's cells: the small case from an empty pool; a 3000-point scene (counts, order and hit lists grow); a group of
+    three 200-point models on that scene with 1500 reference points, which votes in one grid (its argument block, and
+    a redo list per member), each member equal to its own registration; the pool released; the small case again, with
+    the hit lists it had the first time."""
+    def register(c, sc=None):
+        own = sc is None
+        if own:
+            sc = ppf.Scene(c["sp"], c["sn"], d_dist=c["d"])
+        mo = ppf.Model(c["mp"], c["mn"], d_dist=c["d"])
+        T = mo.ppf_lookup(sc).copy()
+        df = 1 if own else 2
+        assert cells_equal(mo.last_cells()[0], oracle.votes_fused(c["mp"], c["mn"], c["sp"], c["sn"], df, c["d"], 0.4)[0])
+        assert mo.stats["scratch_bytes"] > 0
+        scratch = mo.stats["scratch_bytes"]
+        mo.close()
+        if own:
+            sc.close()
+        return T, scratch
+
+    ppf.release_scratch(0)
+    _, first = register(case_small)
+    clouds = [synth.make_model(k, 200) for k in range(3)]
+    d = synth.d_dist_for(clouds[0][0], 0.05)
+    sp, sn, _ = synth.make_scene([0, 1, 2], 3000, 2061, instance_points=200)
+    cases = [dict(mp=p, mn=n, sp=sp, sn=sn, d=d) for p, n in clouds]
+    _, large = register(cases[0])
+    assert large > first
+    sc = ppf.Scene(sp, sn, d_dist=d, ref_point_downsample_factor=2)
+    models = [ppf.Model(p, n, d_dist=d) for p, n in clouds]
+    db = ppf.Database(models)
+    assert db.n_groups == 1
+    T, stats = db.align(sc)
+    for j, (m, c) in enumerate(zip(models, cases)):
+        assert stats[j]["scratch_bytes"] > 0 and stats[j]["vote_launches"] == 1, j
+        assert cells_equal(m.last_cells()[0], oracle.votes_fused(c["mp"], c["mn"], sp, sn, 2, d, 0.4)[0]), j
+    db.close()
+    for m in models:
+        m.close()
+    for j, c in enumerate(cases):
+        assert np.array_equal(register(c, sc)[0], T[j]), j
+    sc.close()
+    ppf.release_scratch(0)
+    _, again = register(case_small)
+    assert again == first
+
+
 @pytest.fixture(scope="module")
 def full_size(synth):
     """BASELINE.json metric configuration: 5k-point model, 100k-point scene."""
