@@ -1082,6 +1082,104 @@ int oslam_volume_track_pyramid(oslam_volume *vol, oslam_pyramid *frame, const fl
                                const oslam_pyramid_params *pp, const oslam_egomotion_params *ep,
                                float T_vol_cam_out[16], oslam_egomotion_result *ego_res);
 
+/* ---- hypotheses rendered into a labelled depth view, and views masked by it.  The image a set of hypotheses
+ * (model, T) would produce in a given camera: a z image and, per pixel, the index of the hypothesis in front.  With it a
+ * view can be split into the static background and the tracked objects before oslam_volume_integrate and
+ * oslam_view_egomotion see it, which both treat every pixel as static world.  The models are clouds, so the render is a
+ * point splat, not a mesh raster.  The restatement in numpy is tests/render_ref.py; device and restatement agree bit
+ * for bit in both images, every counter and the masked view.
+ *
+ * Hypothesis h is (models[h], T + 16 h): T float32, row-major, model to camera; 1 <= H <= OSLAM_ARBITRATE_MAX_HYPOTHESES;
+ *   an all-zero T is a skipped hypothesis (drawn 0, pixels 0; the labels keep the caller's indices).
+ * Splat, for model point i of hypothesis h, in float32 without fused multiply-add:
+ *   p' = (R p + t), n' = R n by oslam_verify's sequence (the one of refine, verify and track).
+ *   Unless keep_back, the point is dropped when (n'x p'x + n'y p'y) + n'z p'z >= 0: oslam_verify's BACK.
+ *   The point is dropped when p'z lies outside [z_min, z_max] or its centre pixel (fu, fv), oslam_verify's rounding
+ *   floorf(((p'x fx) / p'z + cx) + 0.5f), lies outside the image: oslam_verify's OUT.  A point whose centre falls just
+ *   outside the image draws nothing even where its splat would reach in; the mask's dilate covers that seam.
+ *   Half-width: rho = (float)((double)footprint * d_dist) with the model's d_dist, kf = floorf((rho * fx) / p'z + 0.5f),
+ *   k = kf < (float)max_splat ? (int)kf : max_splat.
+ *   The point draws every pixel of [fu - k, fu + k] x [fv - k, fv + k], clipped to the image, at its own depth p'z: a
+ *   splat is a fronto-parallel square, whatever the normal says.  drawn counts the points that got this far.
+ *   A pixel keeps the smallest key (uint64)bits(p'z) << 32 | h of the points that drew it (p'z > 0: its bits order as the
+ *   value does): the nearest point wins, at bit-equal z the lower hypothesis index.  The result does not depend on the
+ *   order of points or hypotheses beyond that rule.
+ * Resolve: a pixel nobody drew has z = 0 (invalid) and label -1; otherwise z is the float of the key's high word and the
+ *   label its low word.  pixels[h] counts the pixels labelled h.  Every counter is an integer sum.
+ * The z image lands in a genuine oslam_view with the caller's camera (depth_scale is not used; max_jump limits its normal
+ *   map): every stage that takes a view takes the render.  oslam_render_view lends that view (borrowed, as
+ *   oslam_pyramid_level's; oslam_render_destroy gives it back); its vertex and normal maps are built on first use.  The
+ *   render also keeps tol[h] = (float)((double)depth_tol * d_dist), oslam_verify's tolerance, for the mask.
+ * oslam_db_render is oslam_render_create with models[h] = the database's member[h].
+ * Cost, the same for 1 hypothesis and for 1024: one upload, one memset, k_render_splat and k_render_resolve, one small
+ *   copy back, one host wait; launches == 2, the kernels.  When every hypothesis is skipped the render is empty (z all
+ *   0, labels all -1), k_render_splat is not launched and launches == 1.
+ *
+ * oslam_view_mask: pixel (u, v) of the observed view v with depth z_o is an object pixel iff z_o > 0 and some pixel
+ *   (x, y) of the (2 dilate + 1)^2 window around it, clipped to the image, has a label l >= 0 (with only >= 0: l == only)
+ *   and fabsf(z_o - z_r(x, y)) <= tol[l].  That mirrors oslam_verify's SUPPORTED: an occluder in front of the object
+ *   stays background, and so does a surface seen through a wrong pose.  OSLAM_MASK_REMOVE writes object ? 0 : z_o,
+ *   OSLAM_MASK_KEEP object ? z_o : 0, into a new view with v's camera and max_jump that the caller owns
+ *   (oslam_view_destroy).  valid_in counts z_o > 0, object_pixels the object pixels, valid_out the valid pixels of the
+ *   output: the two modes partition valid_in.  One memset, k_view_mask, one copy back, one host wait; launches == 1.
+ * oslam_view_info returns the camera (depth_scale 1) and size of any view: the camera to render for it.
+ * Arguments are checked before any handle is read or any device call is made: NULL pointers (rp, mp and res may be
+ *   NULL), H outside 1..OSLAM_ARBITRATE_MAX_HYPOTHESES, parameters that are not finite, footprint <= 0, max_splat above
+ *   OSLAM_RENDER_MAX_SPLAT, depth_tol <= 0, a camera or size oslam_view_create would refuse (or a max_jump it would), a T
+ *   that is neither all zero nor rigid, a mode other than the two, dilate above 8 and only below -1 are OSLAM_E_INVALID.
+ *   Then the handles: models on different devices, a member index outside the database, an only beyond the render's
+ *   hypotheses, and a view and a render that differ in device, size, or bit for bit in fx, fy, cx, cy, z_min or z_max
+ *   are OSLAM_E_INVALID too.
+ * Out of scope: points whose centre is off-image, splats tilted by their normals, mesh rasterisation, colour, any change
+ *   to oslam_verify, oslam_arbitrate, oslam_track or oslam_tracker (verification against the model's own z-buffer is
+ *   what this makes possible), several GPUs. */
+#define OSLAM_RENDER_MAX_SPLAT 8
+typedef struct oslam_render_params {
+    float footprint;           /* splat radius in units of the model's d_dist, > 0, default 0.75 (calibration: DESIGN.md 7p) */
+    unsigned max_splat;        /* cap of the pixel half-width, 0..OSLAM_RENDER_MAX_SPLAT, default 8 */
+    float depth_tol;           /* as oslam_verify_params: in units of d_dist, > 0, default 1.0; kept per hypothesis for the mask */
+    int keep_back;             /* 0 (default): points that face away are not drawn */
+    int reserved[4];
+} oslam_render_params;
+typedef struct oslam_render_result {   /* per hypothesis */
+    uint32_t drawn;            /* model points that were splatted */
+    uint32_t pixels;           /* pixels whose label is this hypothesis */
+    uint32_t launches;         /* of the whole call */
+    float ms_total;            /* of the whole call */
+} oslam_render_result;
+typedef struct oslam_render oslam_render;
+
+int oslam_render_params_default(oslam_render_params *p);
+/* rp may be NULL (defaults), res [H] may be NULL */
+int oslam_render_create(oslam_model *const *models, const float *T, size_t H, const oslam_camera *cam, int width,
+                        int height, const oslam_render_params *rp, oslam_render **out, oslam_render_result *res);
+int oslam_db_render(oslam_db *db, const uint32_t *member, const float *T, size_t H, const oslam_camera *cam, int width,
+                    int height, const oslam_render_params *rp, oslam_render **out, oslam_render_result *res);
+int oslam_render_view(oslam_render *r, oslam_view **view_out);
+/* labels_out [height * width], -1 = nothing drawn */
+int oslam_render_labels(oslam_render *r, int32_t *labels_out);
+int oslam_render_destroy(oslam_render *r);
+int oslam_view_info(const oslam_view *v, oslam_camera *cam_out, int *width_out, int *height_out);
+
+#define OSLAM_MASK_REMOVE 0    /* the static background: object pixels become invalid */
+#define OSLAM_MASK_KEEP 1      /* the objects alone */
+#define OSLAM_MASK_MAX_DILATE 8
+typedef struct oslam_mask_params {
+    int mode;                  /* OSLAM_MASK_REMOVE (default) or OSLAM_MASK_KEEP */
+    unsigned dilate;           /* half-width of the window in pixels, 0..OSLAM_MASK_MAX_DILATE, default 2 */
+    int32_t only;              /* -1 (default): every label; otherwise that hypothesis alone */
+    int reserved[4];
+} oslam_mask_params;
+typedef struct oslam_mask_result {
+    uint32_t valid_in, object_pixels, valid_out, launches;
+    float ms_total;
+} oslam_mask_result;
+
+int oslam_mask_params_default(oslam_mask_params *p);
+/* mp may be NULL (defaults), res may be NULL */
+int oslam_view_mask(const oslam_view *v, const oslam_render *r, const oslam_mask_params *mp, oslam_view **out,
+                    oslam_mask_result *res);
+
 /* ---- the fused surface of a whole volume as a cloud and as a scene (KinFu's fetchCloud plus fetchNormals): every zero
  * crossing of the TSDF along a voxel edge becomes a point with a normal, in the volume frame.  The restatement in numpy
  * is tests/surface_ref.py; device and restatement agree bit for bit, order included.

@@ -103,6 +103,14 @@ struct oslam_pyramid {
     oslam_view *level[3];             /* [0] is the caller's base (borrowed), the rest are owned */
 };
 
+struct oslam_render {
+    int dev;                          /* stays the first field, as in oslam_view */
+    oslam_view *view;                 /* the z image as a genuine view (owned; oslam_render_view lends it) */
+    size_t n_hyp;                     /* the hypotheses of the call: labels lie in -1 .. n_hyp - 1 */
+    int32_t *d_labels;                /* [h * w], then tol[n_hyp] behind it in the same block */
+    float *d_tol;
+};
+
 typedef struct db_group {
     int n;
     size_t *members;                  /* indices into db->models */

@@ -522,6 +522,25 @@ int oslamk_ego_corr(const oslamk_view *src, const float *src_maps, const oslamk_
 /* the z image of the next coarser level of *src: z_out [(h + 1) / 2][(w + 1) / 2], clamped to src's [z_min, z_max] */
 int oslamk_pyr_down(const oslamk_view *src, float depth_band, float *z_out, void *stream);
 
+/* ---- render stage (oslam_render.hip; semantics in include/oslam.h at oslam_render_create / oslam_view_mask) ---- */
+#define OSLAMK_RENDER_MAX_SPLAT 8     /* the largest half-width of a splat in pixels */
+#define OSLAMK_MASK_MAX_DILATE 8      /* the largest half-width of the mask's window in pixels */
+
+/* keys[w * h] (all ones before the launch) = min over the drawn points of (bits of p'z) << 32 | member; the camera and
+ * size are *v's (v->z is not read); rho[j]: member j's splat radius in metres; drawn[j] (zeroed by the caller) += the
+ * points of member j that were splatted.  The grid and the descriptors are oslamk_verify's */
+int oslamk_render_splat(const oslamk_view *v, const oslamk_verify_member *d_mem, const float *d_rho, uint32_t n_mem,
+                        uint32_t max_blocks, int max_splat, int keep_back, unsigned long long *keys, uint32_t *drawn,
+                        void *stream);
+/* keys -> z_out [w * h] (0 = nothing drawn) and labels [w * h] (-1 = nothing drawn); pixels[j] (zeroed by the caller) +=
+ * the pixels labelled j; tol_out[j] = d_mem[j].tol for j < n_mem */
+int oslamk_render_resolve(const unsigned long long *keys, int w, int h, const oslamk_verify_member *d_mem, uint32_t n_mem,
+                          float *z_out, int32_t *labels, float *tol_out, uint32_t *pixels, void *stream);
+/* *v without (mode 0) or with only (mode 1) the object pixels under the render z_r / labels / tol of the same size ->
+ * z_out [w * h]; counts[0 .. 3) (zeroed by the caller) += valid pixels of *v, object pixels, valid pixels of z_out */
+int oslamk_view_mask(const oslamk_view *v, const float *z_r, const int32_t *labels, const float *tol, int mode, int dilate,
+                     int32_t only, float *z_out, uint32_t *counts, void *stream);
+
 /* ---- fusion stage (oslam_volume.hip; semantics in include/oslam.h at oslam_volume_integrate / oslam_volume_raycast) ---- */
 #define OSLAMK_VOL_ZRUN 8             /* consecutive z a thread of k_tsdf_integrate walks; nz is a multiple of it */
 #define OSLAMK_VOL_MAX_STEPS 1024     /* samples of one ray at most: step >= one voxel and the box's diagonal is below

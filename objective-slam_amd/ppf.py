@@ -185,6 +185,33 @@ class PyramidParams(C.Structure):
     _fields_ = [("n_levels", C.c_uint), ("depth_band", C.c_float), ("reserved", C.c_int * 4)]
 
 
+class RenderParams(C.Structure):
+    _fields_ = [("footprint", C.c_float), ("max_splat", C.c_uint), ("depth_tol", C.c_float), ("keep_back", C.c_int),
+                ("reserved", C.c_int * 4)]
+
+
+class RenderResult(C.Structure):
+    _fields_ = [("drawn", C.c_uint32), ("pixels", C.c_uint32), ("launches", C.c_uint32), ("ms_total", C.c_float)]
+
+    def asdict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+class MaskParams(C.Structure):
+    _fields_ = [("mode", C.c_int), ("dilate", C.c_uint), ("only", C.c_int32), ("reserved", C.c_int * 4)]
+
+
+class MaskResult(C.Structure):
+    _fields_ = [("valid_in", C.c_uint32), ("object_pixels", C.c_uint32), ("valid_out", C.c_uint32),
+                ("launches", C.c_uint32), ("ms_total", C.c_float)]
+
+    def asdict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+MASK_REMOVE, MASK_KEEP = 0, 1
+
+
 class VolumeParams(C.Structure):
     _fields_ = [("nx", C.c_uint), ("ny", C.c_uint), ("nz", C.c_uint), ("voxel", C.c_float), ("origin", C.c_float * 3),
                 ("mu", C.c_float), ("max_weight", C.c_uint), ("reserved", C.c_int * 4)]
@@ -373,6 +400,15 @@ _SIGNATURES = {
     "oslam_pyramid_egomotion": (_i, [_vp, _vp, _vp, C.POINTER(EgomotionParams), _vp, C.POINTER(EgomotionResult)]),
     "oslam_volume_track_pyramid": (_i, [_vp, _vp, _vp, C.POINTER(PyramidParams), C.POINTER(EgomotionParams), _vp,
                                         C.POINTER(EgomotionResult)]),
+    "oslam_render_params_default": (_i, [C.POINTER(RenderParams)]),
+    "oslam_render_create": (_i, [_vp, _vp, _sz, _vp, _i, _i, C.POINTER(RenderParams), C.POINTER(_vp), _vp]),
+    "oslam_db_render": (_i, [_vp, _vp, _vp, _sz, _vp, _i, _i, C.POINTER(RenderParams), C.POINTER(_vp), _vp]),
+    "oslam_render_view": (_i, [_vp, C.POINTER(_vp)]),
+    "oslam_render_labels": (_i, [_vp, _vp]),
+    "oslam_render_destroy": (_i, [_vp]),
+    "oslam_view_info": (_i, [_vp, _vp, C.POINTER(_i), C.POINTER(_i)]),
+    "oslam_mask_params_default": (_i, [C.POINTER(MaskParams)]),
+    "oslam_view_mask": (_i, [_vp, _vp, C.POINTER(MaskParams), C.POINTER(_vp), C.POINTER(MaskResult)]),
     "oslam_surface_params_default": (_i, [C.POINTER(SurfaceParams)]),
     "oslam_volume_surface": (_i, [_vp, C.POINTER(SurfaceParams), _vp, _vp, _sz, C.POINTER(_sz), C.POINTER(SurfaceResult)]),
     "oslam_scene_from_volume": (_i, [_vp, C.POINTER(SurfaceParams), _f, _f, _u, C.POINTER(Params), C.POINTER(_vp),
@@ -686,6 +722,16 @@ class Tracker:
             _check(lib().oslam_tracker_step_cam(self._h, sc, view._h, _p(_pose16(T_cam)), out, cap, C.byref(n),
                                                 C.byref(searched)))
         return [out[k].asdict() for k in range(n.value)], bool(searched.value)
+
+    def render(self, view, found_only=True, params=None):
+        """The live tracks rendered into view's camera (render: hypothesis k is the k-th track taken, in id order).
+        found_only: only the tracks the last step found.  -> a Render, or None when there is no such track."""
+        if self.db is None:
+            raise ValueError("a tracker made from shapes has no models to render")
+        live = [t for t in self.tracks() if t["found"] or not found_only]
+        if not live:
+            return None
+        return self.db.render(view, [t["model"] for t in live], np.stack([t["T"] for t in live]), params)
 
     def predict(self, T_cam):
         """Step 0 of step(T_cam=...) alone, on the host (oslam_tracker_predict).  -> the live tracks."""
@@ -1179,6 +1225,10 @@ class Database:
         _check(lib().oslam_db_track(self._h, _p(mem), _p(Ti), H, view._h, C.byref(p), _p(To), res))
         return _track_out(To[:H], res, H)
 
+    def render(self, view_or_camera, members, T, params=None):
+        """render() with models[h] = the database's member members[h] (oslam_db_render).  -> a Render."""
+        return Render._make(None, view_or_camera, T, params, db=self, members=members)
+
     def find_instances(self, scene, refine=True, params=None, refine_params=None):
         """Every instance of every member in one frame (oslam_db_align_instances): -> one list per member, as
         Model.find_instances returns it."""
@@ -1512,6 +1562,105 @@ class _BorrowedView(View):
         self._h = C.c_void_p(0)
 
 
+def view_camera(view):
+    """The camera and size of any view (oslam_view_info): -> (Camera with depth_scale 1, width, height)."""
+    cam = Camera()
+    w, h = C.c_int(0), C.c_int(0)
+    _check(lib().oslam_view_info(view._h, C.byref(cam), C.byref(w), C.byref(h)))
+    return cam, w.value, h.value
+
+
+def default_render_params(**kw):
+    """oslam_render_params_default, then the fields given as keywords."""
+    p = RenderParams()
+    _check(lib().oslam_render_params_default(C.byref(p)))
+    for k, v in kw.items():
+        if not hasattr(p, k) or k == "reserved":
+            raise TypeError("unknown render parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+class Render:
+    """Hypotheses rendered into a labelled depth view (oslam_render): .view is the z image as a View that does not own
+    its handle, .labels() the int32 [h, w] label image (-1 = nothing drawn), .results one dict per hypothesis (drawn,
+    pixels, launches, ms_total).  Made by render(), Database.render() and Tracker.render()."""
+
+    @classmethod
+    def _make(cls, models, view_or_camera, T, params, db=None, members=None):
+        r = cls.__new__(cls)
+        r._h = C.c_void_p(0)
+        if isinstance(view_or_camera, View):
+            cam, w, h = view_camera(view_or_camera)
+        else:
+            cam, w, h = view_or_camera              # (Camera, width, height)
+        p = params if params is not None else default_render_params()
+        if db is None:
+            r._keep = list(models)                  # the models live as long as the render's caller needs them
+            arr, Ti, H = _hypotheses(r._keep, T)
+            res = (RenderResult * max(H, 1))()
+            _check(lib().oslam_render_create(arr, _p(Ti), H, C.byref(cam), int(w), int(h), C.byref(p), C.byref(r._h), res))
+        else:
+            r._keep = db
+            mem = np.ascontiguousarray(members, np.uint32).reshape(-1)
+            H = len(mem)
+            Ti = np.ascontiguousarray(np.asarray(T, np.float32).reshape(H, 16))
+            res = (RenderResult * max(H, 1))()
+            _check(lib().oslam_db_render(db._h, _p(mem), _p(Ti), H, C.byref(cam), int(w), int(h), C.byref(p),
+                                         C.byref(r._h), res))
+        r.results = [res[k].asdict() for k in range(H)]
+        r.width, r.height = int(w), int(h)
+        return r
+
+    @property
+    def view(self):
+        hv = C.c_void_p(0)
+        _check(lib().oslam_render_view(self._h, C.byref(hv)))
+        v = _BorrowedView.__new__(_BorrowedView)
+        v._h, v._owner = hv, self                   # the render lives as long as a view of it does
+        v.width, v.height = self.width, self.height
+        return v
+
+    def labels(self):
+        out = np.zeros(self.width * self.height, np.int32)
+        _check(lib().oslam_render_labels(self._h, _p(out)))
+        return out.reshape(self.height, self.width)
+
+    def close(self):
+        if self._h:
+            lib().oslam_render_destroy(self._h)
+            self._h = C.c_void_p(0)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def render(models, T, view_or_camera, params=None):
+    """The image the hypotheses (models[h], T[h]) would produce (oslam_render_create); an all-zero T[h] is skipped.
+    view_or_camera: a View, whose camera and size are taken, or (Camera, width, height).  -> a Render."""
+    return Render._make(models, view_or_camera, T, params)
+
+
+def mask_view(view, render, mode="remove", dilate=2, only=-1):
+    """The view without (mode "remove") or with only (mode "keep") the pixels that show the rendered objects
+    (oslam_view_mask).  -> (View owned by the caller, result dict: valid_in, object_pixels, valid_out, launches, ms_total)."""
+    modes = {"remove": MASK_REMOVE, "keep": MASK_KEEP, MASK_REMOVE: MASK_REMOVE, MASK_KEEP: MASK_KEEP}
+    if mode not in modes:
+        raise ValueError("mode must be 'remove' or 'keep'")
+    p = MaskParams()
+    _check(lib().oslam_mask_params_default(C.byref(p)))
+    p.mode, p.dilate, p.only = modes[mode], int(dilate), int(only)
+    res = MaskResult()
+    v = View.__new__(View)
+    v._h = C.c_void_p(0)
+    v.width, v.height = view.width, view.height
+    _check(lib().oslam_view_mask(view._h, render._h, C.byref(p), C.byref(v._h), C.byref(res)))
+    return v, res.asdict()
+
+
 def egomotion_pyramid(src_pyr, dst_pyr, T_init=None, params=None, **fields):
     """Coarse-to-fine camera motion over two pyramids (oslam_pyramid_egomotion): stride 1, 2, 4 of a schedule level names
     pyramid level 0, 1, 2.  params: an EgomotionParams, or none and the fields of default_egomotion_params as keywords.
@@ -1647,6 +1796,7 @@ class Volume:
         self.params = p
         self.T, self._started = np.eye(4, dtype=np.float32), False      # the pose step() keeps
         self.world = []                 # what step(..., follow=...) shifted out: (points, normals) in the volume frame
+        self.last_integrate = None      # the integrate result of the last step() that integrated
         _check(lib().oslam_volume_create(C.byref(p), int(dev), C.byref(self._h)))
 
     def integrate(self, view, T_vol_cam):
@@ -1684,7 +1834,7 @@ class Volume:
                                                 C.byref(res)))
         return To.reshape(4, 4), res.asdict()
 
-    def step(self, view, params=None, follow=None, world=None):
+    def step(self, view, params=None, follow=None, world=None, static=None):
         """One frame with the pose kept here: the first call integrates at the initial pose (the identity: the
         volume frame is the first camera's);
         a later call tracks from the kept pose and integrates when the result is ok.  -> (T_vol_cam, egomotion result
@@ -1692,15 +1842,28 @@ class Volume:
         follow: follow parameters (default_follow_params).  After a frame was followed and integrated the window then
         moves as follow(T) says; what leaves it is appended to self.world first.
         world: a World.  With follow, the shift then goes through the store (shift(s, world)) and nothing is appended to
-        self.world: the store is the map, and a surface handed over now would be handed over again on the next visit."""
+        self.world: the store is the map, and a surface handed over now would be handed over again on the next visit.
+        static: a Render of the objects that move.  The view is masked with it (mask_view, mode "remove") before it is
+        tracked and integrated, the first frame too, and the mask's counters come back as result["mask"] (on the first
+        call the result is {"mask": ...} instead of None).
+        self.last_integrate keeps the result dict of the frame's integration."""
+        if static is not None:
+            masked, mres = mask_view(view, static, "remove")
+            try:
+                T, res = self.step(masked, params, follow, world)
+            finally:
+                masked.close()
+            res = dict(res) if res is not None else {}
+            res["mask"] = mres
+            return T, res
         if not self._started:
-            self.integrate(view, self.T)
+            self.last_integrate = self.integrate(view, self.T)
             self._started = True
             return self.T.copy(), None
         T, res = self.track(view, self.T, params)
         if res["ok"]:
             self.T = T
-            self.integrate(view, T)
+            self.last_integrate = self.integrate(view, T)
             if follow is not None:
                 s = self.follow(T, follow)
                 if any(s) and world is not None:
