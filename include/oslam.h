@@ -1180,6 +1180,106 @@ int oslam_mask_params_default(oslam_mask_params *p);
 int oslam_view_mask(const oslam_view *v, const oslam_render *r, const oslam_mask_params *mp, oslam_view **out,
                     oslam_mask_result *res);
 
+/* ---- hypotheses judged against their own z-buffers and arbitrated by their conflict rates.  oslam_verify asks whether
+ * a model's points find support in the image, oslam_arbitrate compares depth residuals tile by tile and so follows the
+ * poses.  This stage turns the question around: does the image show what the hypothesis says the camera must see, pixel
+ * by pixel over its whole silhouette?  A hypothesis that predicts surface where the camera saw through to the wall pays
+ * for every such pixel.  It complements oslam_verify (a hypothesis hidden behind an occluder scores well here and is
+ * rejected by verify's coverage) and uses oslam_arbitrate's elimination.  The restatement in numpy is
+ * tests/explain_ref.py; device and restatement agree bit for bit in every integer and every float field.
+ *
+ * All arithmetic is float32 without fused multiply-add, grouped as written, unless stated.
+ * Input: a view v and H hypotheses (models[h], T + 16 h), 1 <= H <= OSLAM_ARBITRATE_MAX_HYPOTHESES.  An all-zero T is a
+ *   skipped hypothesis: every counter of it is 0 and it is never live.
+ * Solo z image.  Z_h is exactly the z image oslam_render_create produces for the one-element list {(models[h], T_h)} in
+ *   v's camera and size with the call's footprint, max_splat and keep_back: the same transform, BACK and OUT tests,
+ *   centre pixel and half-width k, a fronto-parallel square at the point's depth, the nearest point wins.  Alone, the key
+ *   needs no label: the unsigned minimum of bits(p'z), empty = all ones, resolved to 0.  drawn[h] is the render's count.
+ *   tol_h = (float)((double)depth_tol * d_dist) of its model, as everywhere.
+ * Class of pixel (x, y) with Z_h > 0 and z_o the view's z there, tested in this order: UNKNOWN if z_o == 0; AGREE if
+ *   fabsf(z_o - Z_h) <= tol_h; OCCLUDED if z_o < Z_h; THROUGH otherwise.  An AGREE pixel has the residual
+ *   x = fabsf(z_o - Z_h) * (65535.0f / tol_h), r = x < 65535.0f ? (uint32_t)x : 65535: oslam_arbitrate's quantisation.
+ * Per hypothesis: pixels, agree, occluded, through, unknown (integers, pixels their sum); resid_sum (uint64, the sum of
+ *   r); explained = (float)agree / (float)(agree + through), 0 when the denominator is 0; visible = (float)agree /
+ *   (float)(agree + occluded + through), 0 likewise; mean_residual = (float)((((double)resid_sum / (double)agree) /
+ *   65535.0) * (double)tol_h), 0 when agree is 0; conflict_q = (uint32_t)((65535 * (uint64_t)through) / (agree +
+ *   through)), 0 when agree == 0: the conflict rate through / (agree + through) in 16 bits.
+ * Claims.  An AGREE pixel claims tile t = (y / tile) * tiles_x + x / tile.  cnt[h][t] is the number of claiming pixels,
+ *   sum[h][t] = cnt[h][t] * conflict_q[h].  tile in pixels is 4..128; 0 (the default) chooses oslam_arbitrate's automatic
+ *   tile from tile_spacing, by the same function.  A tile holds at most 128^2 pixels, so cnt < 2^24 and sum < 2^40 as
+ *   k_arbitrate's words require.
+ * Elimination.  oslam_arbitrate's, unchanged, over this table.  Because sum / cnt is the hypothesis's one conflict rate in
+ *   every tile, a tile belongs to the live claimant that explains its own silhouette best; ties go to the lower index,
+ *   so a bit-identical duplicate of a hypothesis is suppressed by its first copy.  Liveness, min_tiles, the loser,
+ *   suppressed_by, rounds, and share / owned at elimination are as documented for oslam_arbitrate.
+ * Rectangle.  A hypothesis's z-buffer covers a rectangle of the image that contains everything it can draw, from its
+ *   model's bounding sphere (centre: the model's double mean under T; radius: the largest distance of a model point
+ *   from the mean): the four extreme combinations of x, y and z projected, padded by max_splat + 2 pixels and clipped to
+ *   the image; the whole image when the sphere reaches z <= 0; empty when it lies outside [z_min, z_max].  It is a
+ *   container, not part of the rule: no result depends on it.  Every write is checked against it; a point that would
+ *   fall outside is not written, and the call fails with OSLAM_E_DEVICE.  oslam_explain_rect is that arithmetic alone,
+ *   on the host, without a device: rect_out = x0, y0, width, height (a width of 0: empty).
+ * Arguments are checked before any handle is read or any device call is made, as oslam_render_create and oslam_arbitrate
+ *   check the fields they share: NULL pointers (ep may be NULL), H outside 1..OSLAM_ARBITRATE_MAX_HYPOTHESES, parameters
+ *   that are not finite, footprint <= 0, max_splat above OSLAM_RENDER_MAX_SPLAT, depth_tol <= 0, tile not 0 and outside
+ *   4..128, tile_spacing <= 0, min_owned_share outside [0, 1], a T that is neither all zero nor rigid are
+ *   OSLAM_E_INVALID.  Then the handles: a model and the view on different devices.  A claims table above 256 MiB
+ *   (H * tiles * 8 B), or z-buffers above 256 MiB in total, is OSLAM_E_LIMIT before anything is launched.
+ * Cost, the same for 1 hypothesis and for 1024: one upload, two memsets, k_explain_splat, k_explain_score,
+ *   k_explain_claims and k_arbitrate, one copy back of a 32-byte record per hypothesis and stage, one host wait;
+ *   launches == 4.  When every hypothesis is skipped nothing is launched.  Integer sums and minima only: every result is
+ *   the same on every run and for every order of the hypotheses' points.
+ * Defaults: footprint, max_splat and keep_back are the render's, tile, tile_spacing and min_tiles the arbitration's,
+ *   depth_tol 1.0.  min_owned_share is the arbitration's 0.52: it lies inside the gap the calibration table shows between
+ *   the present model (first-round share 1.000) and its suppressed near twin (at most 0.116); the table is in
+ *   tests/test_explain_host.py.  The thin margin of the rule is the gap of the conflict rates themselves, 0.031 to 0.064.
+ * Out of scope: any change to oslam_db_detect or oslam_tracker (folding this stage into them is the follow-up), tilted
+ *   splats, normals, colour, several GPUs. */
+typedef struct oslam_explain_params {
+    float footprint;           /* as oslam_render_params, default 0.75 */
+    unsigned max_splat;        /* as oslam_render_params, default 8 */
+    int keep_back;             /* as oslam_render_params, default 0 */
+    float depth_tol;           /* in units of d_dist, > 0, default 1.0 */
+    unsigned tile;             /* as oslam_arbitrate_params, default 0 (automatic) */
+    float tile_spacing;        /* as oslam_arbitrate_params, default 2.0 */
+    unsigned min_tiles;        /* as oslam_arbitrate_params, default 4 */
+    float min_owned_share;     /* [0, 1]: the loser is suppressed below this share, default 0.52 */
+    int reserved[4];
+} oslam_explain_params;
+
+typedef struct oslam_explain_result {  /* per hypothesis */
+    uint32_t drawn;            /* model points that were splatted */
+    uint32_t pixels;           /* pixels of its z image: agree + occluded + through + unknown */
+    uint32_t agree, occluded, through, unknown;
+    uint64_t resid_sum;        /* the sum of the AGREE pixels' quantised residuals */
+    float explained, visible, mean_residual;
+    uint32_t conflict_q;
+    uint32_t claimed, owned;
+    float share;
+    int32_t kept, suppressed_by;
+    uint32_t tile, rounds;     /* the whole call, shared by all hypotheses */
+    uint32_t launches;         /* kernels this call enqueued */
+    float ms_total;            /* whole call, host clock */
+} oslam_explain_result;
+
+int oslam_explain_params_default(oslam_explain_params *p);
+/* models [H], T [H][16], res [H]; ep may be NULL (defaults) */
+int oslam_explain(oslam_model *const *models, const float *T, size_t H, const oslam_view *v, const oslam_explain_params *ep,
+                  oslam_explain_result *res);
+/* hypothesis j = member j of the database with T[j] (zeros: skipped); equals oslam_explain on the same list */
+int oslam_db_explain(oslam_db *db, const oslam_view *v, const float *T, const oslam_explain_params *ep,
+                     oslam_explain_result *res);
+/* the rectangle alone, no device: centre [3] and radius of the model's bounding sphere in the model frame */
+int oslam_explain_rect(const double centre[3], double radius, const float T[16], const oslam_camera *cam, int width,
+                       int height, unsigned max_splat, int rect_out[4]);
+/* test tap: the solo z image of hypothesis h expanded to the full image, z_out [height * width] */
+int oslam_explain_z(oslam_model *const *models, const float *T, size_t H, const oslam_view *v,
+                    const oslam_explain_params *ep, size_t h, float *z_out);
+/* test tap: the table after k_explain_claims, as oslam_arbitrate_claims returns its own */
+int oslam_explain_claims(oslam_model *const *models, const float *T, size_t H, const oslam_view *v,
+                         const oslam_explain_params *ep, uint32_t *cnt_out, uint64_t *sum_out, size_t cap,
+                         uint32_t *tile_out, size_t *n_tiles_out);
+
 /* ---- the fused surface of a whole volume as a cloud and as a scene (KinFu's fetchCloud plus fetchNormals): every zero
  * crossing of the TSDF along a voxel edge becomes a point with a normal, in the volume frame.  The restatement in numpy
  * is tests/surface_ref.py; device and restatement agree bit for bit, order included.

@@ -54,7 +54,8 @@ int oslam_arbitrate_check_params(const oslam_arbitrate_params *ap, oslam_arbitra
 }
 
 /* the tile of a call (include/oslam.h, "Tile") */
-static int choose_tile(oslam_model *const *ms, const float *T, size_t H, const oslam_view *v, const oslam_arbitrate_params *p)
+int oslam_arbitrate_choose_tile(oslam_model *const *ms, const float *T, size_t H, const oslam_view *v,
+                                const oslam_arbitrate_params *p)
 {
     float d_max = 0.0f, z_near = 0.0f;
     size_t h;
@@ -139,7 +140,7 @@ static int arbitrate_members(oslam_model *const *ms, size_t H, const oslam_view 
     for (h = 0; h < H; h++)
         if (!oslam_is_zero_pose(T + 16 * h) && (size_t)ms[h]->c.n >= ((size_t)1 << 24))
             return fail(OSLAM_E_LIMIT, "a model of 2^24 points or more cannot be arbitrated");
-    g.tile = choose_tile(ms, T, H, v, p);
+    g.tile = oslam_arbitrate_choose_tile(ms, T, H, v, p);
     g.tiles_x = (v->k.w + g.tile - 1) / g.tile;
     g.n_tiles = (uint32_t)g.tiles_x * (uint32_t)((v->k.h + g.tile - 1) / g.tile);
     n_ent = H * (size_t)g.n_tiles;

@@ -65,6 +65,9 @@ struct oslam_model {
      * points (the pivot of the refinement and tracking stages), its float rounding and the extent (the instance rule) */
     double cm[3];
     float inst_c[3], inst_extent;
+    /* the largest distance of a point from cm, made on first use by the explain stage (oslam_explain.c) */
+    double bound_r;
+    int bound_set;
 };
 
 struct oslam_scene {
@@ -319,6 +322,12 @@ int oslam_surface_check_params(const oslam_surface_params *sp, oslam_surface_par
 int oslam_volume_surface_cloud(oslam_volume *vol, unsigned min_weight, int *dev, float **d_pts6, uint32_t *np);
 /* the arbitration's parameter check (oslam_arbitrate.c) */
 int oslam_arbitrate_check_params(const oslam_arbitrate_params *ap, oslam_arbitrate_params *out);
+
+/* the tile of an arbitration over ms / T [H] against v under p (include/oslam.h, "Tile"): the explain stage's too */
+int oslam_arbitrate_choose_tile(oslam_model *const *ms, const float *T, size_t H, const oslam_view *v,
+                                const oslam_arbitrate_params *p);
+/* rp NULL = defaults; checks them as oslam_render_create does, *out = the parameters in force (oslam_render.c) */
+int oslam_render_check_params(const oslam_render_params *rp, oslam_render_params *out);
 
 /* gives back the pinned record of the arbitration stage (oslam_arbitrate.c); called by oslam_release_scratch */
 void oslam_arbitrate_release(void);

@@ -541,6 +541,35 @@ int oslamk_render_resolve(const unsigned long long *keys, int w, int h, const os
 int oslamk_view_mask(const oslamk_view *v, const float *z_r, const int32_t *labels, const float *tol, int mode, int dilate,
                      int32_t only, float *z_out, uint32_t *counts, void *stream);
 
+/* ---- explain stage (oslam_explain.hip; semantics in include/oslam.h at oslam_explain) ---- */
+/* the private z-buffer of one hypothesis: pixels [x0, x0 + w) x [y0, y0 + h) of the image, row-major from word `off` of
+ * the pool; w == 0 or h == 0: it can draw nothing */
+typedef struct oslamk_explain_rect {
+    int x0, y0, w, h;
+    unsigned long long off;
+} oslamk_explain_rect;
+
+/* the counters of one hypothesis (zeroed by the caller) */
+typedef struct oslamk_explain_rec {
+    uint32_t drawn, agree, occluded, through, unknown;
+    uint32_t clipped;          /* points whose splat would have left the rectangle: not written */
+    unsigned long long resid_sum;
+} oslamk_explain_rec;
+
+/* pool[rect[j].off + ...] (all ones before the launch) = min over member j's drawn points of the bits of p'z, the splat
+ * of oslamk_render_splat into the member's own rectangle; rec[j].drawn and rec[j].clipped += */
+int oslamk_explain_splat(const oslamk_view *v, const oslamk_verify_member *d_mem, const float *d_rho,
+                         const oslamk_explain_rect *d_rect, uint32_t n_mem, uint32_t max_blocks, int max_splat,
+                         int keep_back, uint32_t *pool, oslamk_explain_rec *rec, void *stream);
+/* every pixel of every member's rectangle against *v: rec[j]'s class counters and resid_sum +=, and cnt[j * g.n_tiles +
+ * t] (zeroed by the caller) += the AGREE pixels of member j in tile t; max_w, max_h: the largest rectangle's sides */
+int oslamk_explain_score(const oslamk_view *v, const oslamk_verify_member *d_mem, const oslamk_explain_rect *d_rect,
+                         uint32_t n_mem, int max_w, int max_h, const uint32_t *pool, oslamk_arb_grid g,
+                         unsigned long long *cnt, oslamk_explain_rec *rec, void *stream);
+/* cnt[j * n_tiles + t] = c  ->  c << 40 | c * conflict_q(rec[j]): the words oslamk_arbitrate reads */
+int oslamk_explain_claims(const oslamk_explain_rec *rec, uint32_t n_mem, uint32_t n_tiles, unsigned long long *cnt,
+                          void *stream);
+
 /* ---- fusion stage (oslam_volume.hip; semantics in include/oslam.h at oslam_volume_integrate / oslam_volume_raycast) ---- */
 #define OSLAMK_VOL_ZRUN 8             /* consecutive z a thread of k_tsdf_integrate walks; nz is a multiple of it */
 #define OSLAMK_VOL_MAX_STEPS 1024     /* samples of one ray at most: step >= one voxel and the box's diagonal is below

@@ -21,7 +21,7 @@ int oslam_render_params_default(oslam_render_params *p)
     return OSLAM_OK;
 }
 
-static int render_check_params(const oslam_render_params *rp, oslam_render_params *out)
+int oslam_render_check_params(const oslam_render_params *rp, oslam_render_params *out)
 {
     if (rp) *out = *rp;
     else oslam_render_params_default(out);
@@ -54,7 +54,7 @@ static void release(oslam_render *r)
 static int render_check(oslam_model *const *ms, const float *T, size_t H, const oslam_camera *cam, int width, int height,
                         const oslam_render_params *rp, oslam_render_params *p)
 {
-    int rc = render_check_params(rp, p);
+    int rc = oslam_render_check_params(rp, p);
     if (rc == OSLAM_OK) rc = oslam_check_poses(ms, T, H, 1);
     if (rc == OSLAM_OK && !oslam_view_camera_ok(cam, width, height, 1, 1))
         rc = fail(OSLAM_E_INVALID, "bad render camera or size");

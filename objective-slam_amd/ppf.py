@@ -212,6 +212,23 @@ class MaskResult(C.Structure):
 MASK_REMOVE, MASK_KEEP = 0, 1
 
 
+class ExplainParams(C.Structure):
+    _fields_ = [("footprint", C.c_float), ("max_splat", C.c_uint), ("keep_back", C.c_int), ("depth_tol", C.c_float),
+                ("tile", C.c_uint), ("tile_spacing", C.c_float), ("min_tiles", C.c_uint), ("min_owned_share", C.c_float),
+                ("reserved", C.c_int * 4)]
+
+
+class ExplainResult(C.Structure):
+    _fields_ = [("drawn", C.c_uint32), ("pixels", C.c_uint32), ("agree", C.c_uint32), ("occluded", C.c_uint32),
+                ("through", C.c_uint32), ("unknown", C.c_uint32), ("resid_sum", C.c_uint64), ("explained", C.c_float),
+                ("visible", C.c_float), ("mean_residual", C.c_float), ("conflict_q", C.c_uint32), ("claimed", C.c_uint32),
+                ("owned", C.c_uint32), ("share", C.c_float), ("kept", C.c_int32), ("suppressed_by", C.c_int32),
+                ("tile", C.c_uint32), ("rounds", C.c_uint32), ("launches", C.c_uint32), ("ms_total", C.c_float)]
+
+    def asdict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 class VolumeParams(C.Structure):
     _fields_ = [("nx", C.c_uint), ("ny", C.c_uint), ("nz", C.c_uint), ("voxel", C.c_float), ("origin", C.c_float * 3),
                 ("mu", C.c_float), ("max_weight", C.c_uint), ("reserved", C.c_int * 4)]
@@ -404,6 +421,13 @@ _SIGNATURES = {
     "oslam_render_create": (_i, [_vp, _vp, _sz, _vp, _i, _i, C.POINTER(RenderParams), C.POINTER(_vp), _vp]),
     "oslam_db_render": (_i, [_vp, _vp, _vp, _sz, _vp, _i, _i, C.POINTER(RenderParams), C.POINTER(_vp), _vp]),
     "oslam_render_view": (_i, [_vp, C.POINTER(_vp)]),
+    "oslam_explain_params_default": (_i, [C.POINTER(ExplainParams)]),
+    "oslam_explain": (_i, [_vp, _vp, _sz, _vp, C.POINTER(ExplainParams), _vp]),
+    "oslam_db_explain": (_i, [_vp, _vp, _vp, C.POINTER(ExplainParams), _vp]),
+    "oslam_explain_rect": (_i, [_vp, C.c_double, _vp, _vp, _i, _i, C.c_uint, _vp]),
+    "oslam_explain_z": (_i, [_vp, _vp, _sz, _vp, C.POINTER(ExplainParams), _sz, _vp]),
+    "oslam_explain_claims": (_i, [_vp, _vp, _sz, _vp, C.POINTER(ExplainParams), _vp, _vp, _sz, C.POINTER(C.c_uint32),
+                                  C.POINTER(_sz)]),
     "oslam_render_labels": (_i, [_vp, _vp]),
     "oslam_render_destroy": (_i, [_vp]),
     "oslam_view_info": (_i, [_vp, _vp, C.POINTER(_i), C.POINTER(_i)]),
@@ -627,6 +651,62 @@ def arbitrate(models, view, T, params=None):
     _check(lib().oslam_arbitrate(arr, _p(Ti), H, view._h, C.byref(p), res))
     out = [res[h].asdict() for h in range(H)]
     return out, np.array([bool(r["kept"]) for r in out], dtype=bool)
+
+
+def default_explain_params(**kw):
+    """oslam_explain_params_default, then the fields given as keywords."""
+    p = ExplainParams()
+    _check(lib().oslam_explain_params_default(C.byref(p)))
+    for k, v in kw.items():
+        if k not in dict(ExplainParams._fields_) or k == "reserved":
+            raise TypeError("unknown explain parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def explain(models, view, T, params=None):
+    """Every hypothesis (models[h], T[h]) judged against its own z-buffer in the view's camera and arbitrated by its
+    conflict rate (oslam_explain); an all-zero T[h] is skipped.  -> list of result dicts."""
+    arr, Ti, H = _hypotheses(models, T)
+    res = (ExplainResult * max(H, 1))()
+    p = params if params is not None else default_explain_params()
+    _check(lib().oslam_explain(arr, _p(Ti), H, view._h, C.byref(p), res))
+    return [res[h].asdict() for h in range(H)]
+
+
+def explain_z(models, view, T, h, params=None):
+    """The solo z image of hypothesis h as a test tap (oslam_explain_z): -> float32 [height, width], 0 = nothing drawn."""
+    arr, Ti, H = _hypotheses(models, T)
+    p = params if params is not None else default_explain_params()
+    out = np.zeros((view.height, view.width), np.float32)
+    _check(lib().oslam_explain_z(arr, _p(Ti), H, view._h, C.byref(p), int(h), _p(out)))
+    return out
+
+
+def explain_claims(models, view, T, params=None):
+    """The claims table after k_explain_claims as a test tap (oslam_explain_claims): -> (cnt uint32 [H, n_tiles], sum
+    uint64 [H, n_tiles], tile in pixels)."""
+    arr, Ti, H = _hypotheses(models, T)
+    p = params if params is not None else default_explain_params()
+    n_tiles = ((view.width + 3) // 4) * ((view.height + 3) // 4)       # the smallest tile: the largest table
+    cnt = np.zeros(max(H * n_tiles, 1), np.uint32)
+    sm = np.zeros(max(H * n_tiles, 1), np.uint64)
+    tile, nt = C.c_uint32(0), C.c_size_t(0)
+    _check(lib().oslam_explain_claims(arr, _p(Ti), H, view._h, C.byref(p), _p(cnt), _p(sm), len(cnt), C.byref(tile),
+                                      C.byref(nt)))
+    n = H * nt.value
+    return cnt[:n].reshape(H, nt.value).copy(), sm[:n].reshape(H, nt.value).copy(), int(tile.value)
+
+
+def explain_rect(centre, radius, T, camera, width, height, max_splat=8):
+    """The rectangle of the image that holds whatever a hypothesis can draw, on the host (oslam_explain_rect): centre
+    [3] and radius of the model's bounding sphere in the model frame, T 4x4, camera a Camera.  -> (x0, y0, w, h)."""
+    c = np.ascontiguousarray(centre, np.float64).reshape(3)
+    Ti = _pose16(T)
+    out = np.zeros(4, np.int32)
+    _check(lib().oslam_explain_rect(_p(c), float(radius), _p(Ti), C.byref(camera), int(width), int(height), int(max_splat),
+                                    _p(out)))
+    return tuple(int(x) for x in out)
 
 
 def _track_out(To, res, H):
@@ -1201,6 +1281,16 @@ class Database:
         _check(lib().oslam_db_arbitrate(self._h, view._h, _p(Ti), C.byref(p), res))
         out = [res[j].asdict() for j in range(n)]
         return out, np.array([bool(r["kept"]) for r in out], dtype=bool)
+
+    def explain(self, view, T, params=None):
+        """explain() with hypothesis j = member j and T[j] (oslam_db_explain; all-zero = skipped, e.g. the members that
+        verify did not find).  -> list of result dicts."""
+        n = len(self.models)
+        Ti = np.ascontiguousarray(np.asarray(T, np.float32).reshape(n, 16))
+        res = (ExplainResult * max(n, 1))()
+        p = params if params is not None else default_explain_params()
+        _check(lib().oslam_db_explain(self._h, view._h, _p(Ti), C.byref(p), res))
+        return [res[j].asdict() for j in range(n)]
 
     def detect(self, scene, view, params=None):
         """The whole chain for one frame (oslam_db_detect): every instance of every member, refined, verified against

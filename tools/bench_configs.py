@@ -33,6 +33,10 @@ configuration; these are not bench lines).  Needs a HIP device.
   python tools/bench_configs.py shift    the same volume: Volume.shift by (8, 0, 0) and (-8, 0, 0) alternately,
                                          Volume.leaving((8, 0, 0)) and, in the same run, one integrate and Volume.surface;
                                          median of 20 calls each, and the bytes per second the shift loads and stores
+  python tools/bench_configs.py explain  the db50 stream with the twin: db.align + db.refine + db.verify per frame, then
+                                         db.arbitrate and db.explain over what verification found: who is verified, who
+                                         each stage keeps and both stages' ms per frame; and ms_total of explain,
+                                         arbitrate and render for 1 and 50 hypotheses, median of 20 calls each
 One JSON line each."""
 import importlib, json, os, sys, time
 
@@ -520,6 +524,69 @@ def arbitrate(frames=10):
     return out
 
 
+def explain(frames=10, calls=20):
+    """The explain stage (oslam_db_explain) next to arbitration on the db50 stream (member 36 is the near twin of the
+    rendered model 0): per frame the members verification found, the ones db.arbitrate keeps and the ones db.explain
+    keeps over the same list, and both calls' ms; then ms_total of ppf.explain, ppf.arbitrate and ppf.render in the same
+    run for 1 and 50 hypotheses (every member at its refined pose of frame 0), median of `calls` calls after 5."""
+    n_models = 50
+    raw = [synth.make_model(k, 1500) for k in range(n_models)]
+    d = synth.d_dist_for(raw[0][0], 0.05)
+    grids = [ppf.voxel_grid(c[0], c[1], leaf=d) for c in raw]
+    dense, _ = synth.make_model(0, 300000)
+    rng = synth.SplitMix64(93)
+    imgs = []
+    for f in range(frames):
+        T = np.eye(4, dtype=np.float32)
+        T[:3, :3] = synth.random_rotation(rng)
+        T[:3, 3] = [0.5 * np.cos(0.7 * f), 0.3 * np.sin(0.7 * f), 5.5 + 0.1 * f]
+        imgs.append(synth.render_depth(dense @ T[:3, :3].T + T[:3, 3], background_z=9.0, splat=1))
+    models = [ppf.Model(g[0], g[1], d_dist=d) for g in grids]
+    db = ppf.Database(models)
+
+    def frame(img):
+        sc = ppf.Scene.from_depth(img, 525.0, 525.0, 319.5, 239.5, leaf=d, d_dist=0.0, ref_point_downsample_factor=4,
+                                  z_min=0.5, z_max=12.0, max_jump=0.08)
+        Ta, _ = db.align(sc)
+        Tr, _, _ = db.refine(sc, Ta)
+        view = ppf.View(img, 525.0, 525.0, 319.5, 239.5, z_min=0.5, z_max=12.0)
+        _, found = db.verify(view, Tr)
+        Tf = np.where(found[:, None, None], Tr, np.float32(0))
+        t = time.perf_counter(); ares, akept = db.arbitrate(view, Tf); ms_a = 1e3 * (time.perf_counter() - t)
+        t = time.perf_counter(); eres = db.explain(view, Tf); ms_e = 1e3 * (time.perf_counter() - t)
+        view.close()
+        sc.close()
+        return dict(verified=[int(j) for j in np.flatnonzero(found)], kept_arbitrate=[int(j) for j in np.flatnonzero(akept)],
+                    kept_explain=[j for j, r in enumerate(eres) if r["kept"]], ms_arbitrate=round(ms_a, 3), ms_explain=round(ms_e, 3),
+                    conflict_rate={j: round(eres[j]["conflict_q"] / 65535.0, 3) for j in np.flatnonzero(found).tolist()},
+                    share_explain={j: round(eres[j]["share"], 3) for j in np.flatnonzero(found).tolist()}), Tr
+    frame(imgs[0])
+    rows = []
+    for f, im in enumerate(imgs):
+        row, Tr = frame(im)
+        rows.append(dict(frame=f, **row))
+        if f == 0:
+            T0 = Tr
+    view = ppf.View(imgs[0], 525.0, 525.0, 319.5, 239.5, z_min=0.5, z_max=12.0)
+    per_call = {}
+    for n in (1, n_models):
+        ms = {"explain": [], "arbitrate": [], "render": []}
+        for k in range(calls + 5):
+            ms["explain"].append(ppf.explain(models[:n], view, T0[:n])[0]["ms_total"])
+            ms["arbitrate"].append(ppf.arbitrate(models[:n], view, T0[:n])[0][0]["ms_total"])
+            r = ppf.render(models[:n], T0[:n], view)
+            ms["render"].append(r.results[0]["ms_total"])
+            r.close()
+        per_call[n] = {k: round(float(np.median(v[5:])), 4) for k, v in ms.items()}
+        per_call[n]["launches_explain"] = ppf.explain(models[:n], view, T0[:n])[0]["launches"]
+    view.close()
+    db.close()
+    for m in models:
+        m.close()
+    return {"config": "explain (oslam_db_explain) next to arbitrate on the db50 stream", "frames": frames, "models": n_models,
+            "per_frame": rows, "ms_total_median_640x480": per_call}
+
+
 def track(frames=30, calls=20):
     """Tracking (oslam_db_track, oslam_tracker_step) on the db50 stream with smooth motion (synth.smooth_motion_poses: 3
     degrees and 0.5 d_dist per frame): (a) db.detect on every frame, (b) Tracker.step with detect_every 10, building the
@@ -1000,5 +1067,5 @@ def pyramid(calls=20):
 if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "cfg3"
     print(json.dumps({"cfg2": cfg2, "cfg3": cfg3, "cfg3db": cfg3db, "cfg4": cfg4, "cfg5": cfg5, "planes": planes, "db50": db50,
-                      "refine": refine, "verify": verify, "instances": instances, "arbitrate": arbitrate, "track": track, "camera": camera,
+                      "refine": refine, "verify": verify, "instances": instances, "arbitrate": arbitrate, "explain": explain, "track": track, "camera": camera,
                       "fusion": fusion, "surface": surface, "mesh": mesh, "shift": shift, "reload": reload, "pyramid": pyramid}[which]()), flush=True)
