@@ -1566,6 +1566,90 @@ int oslam_world_box(oslam_world *w, const int32_t lo[3], const int32_t hi[3], ui
 int oslam_volume_shift_world(oslam_volume *vol, oslam_world *w, const int shift[3], oslam_reload_result *res);
 int oslam_volume_pack(oslam_volume *vol, const int shift[3], uint32_t *lin_out, uint32_t *word_out, size_t cap, size_t *n_out);
 
+/* ---- normals for clouds and meshes that come without them.  Every entry into the recognition path takes points and
+ * normals; the reference made them outside its program (matlab/compute_normals.m for meshes, PCL for scans).  Two entry
+ * points, because the two kinds of input need different sign rules: a cloud seen from somewhere (oslam_cloud_normals, on
+ * the device) and a closed mesh (oslam_mesh_normals, on the host).  The restatement in numpy is tests/normals_ref.py; the
+ * device agrees with it bit for bit.
+ *
+ * oslam_cloud_normals: the rule.  It does not depend on the order in which neighbours are met (the cells of the grid
+ * hold their points in an order that differs from run to run).  For point i with finite coordinates:
+ *   1. Neighbours.  Every point j, i included, with d = p_j - p_i and d2 = (dx*dx + dy*dy) + dz*dz <= radius*radius, all in
+ *      float32 with this grouping (the refinement's correspondence test has the same form).  A non-finite coordinate
+ *      fails the test by itself: such a point is nobody's neighbour and gets no normal.
+ *   2. Moments as whole numbers.  q_a = (int32) rintf(d_a * scale), scale = 16384.0f / radius (float32, made once by the
+ *      host).  Summed in int64: the count n, Sq_a (x y z) and Sqq_ab in the order xx xy xz yy yz zz.  These ten integers
+ *      are what oslam_cloud_normal_moments returns per point ([n][10]: n, Sx, Sy, Sz, Sxx, Sxy, Sxz, Syy, Syz, Szz).
+ *   3. Covariance in double, about the neighbours' mean, from the ten integers converted with round-to-nearest:
+ *      a_ab = Sqq_ab / n - (Sq_a / n) * (Sq_b / n), in exactly this operation order.
+ *   4. Principal axes.  OSLAM_NORMALS_SWEEPS cyclic Jacobi sweeps in double over the pairs (p, q) = (0,1), (0,2), (1,2),
+ *      from V = I, with + - * / sqrt and comparisons only.  A pair whose a_pq is exactly 0 is skipped; otherwise
+ *      theta = (a_qq - a_pp) / (2 * a_pq), t = sign(theta) / (|theta| + sqrt(theta*theta + 1)) (sign(0) = +1),
+ *      c = 1 / sqrt(t*t + 1), s = t * c; h = t * a_pq, a_pp -= h, a_qq += h, a_pq = 0; with r the third index
+ *      (a_rp, a_rq) = (c*a_rp - s*a_rq, s*a_rp + c*a_rq); every row k of V: (v_kp, v_kq) = (c*v_kp - s*v_kq,
+ *      s*v_kp + c*v_kq).  The count is fixed (no convergence test that could differ between lanes): 4 is the smallest
+ *      count after which one more sweep changes no float32 output on the calibration clouds (the fourth
+ *      sweep still changes 20 to 809 outputs per cloud, the fifth, sixth and seventh change none).
+ *      lmin, lmid, lmax = the diagonal sorted by comparisons; the normal is the column of V under the smallest diagonal
+ *      element (lowest index on a tie), divided in double by sqrt((x*x + y*y) + z*z), then rounded to float32.
+ *      curvature = (float)(lmin / ((a_00 + a_11) + a_22)), or 0 when that sum is 0.
+ *   5. Validity.  n >= min_neighbours and lmid > (double)line_ratio * lmax: coincident or collinear neighbours have no
+ *      normal.  An invalid point gets normal (0, 0, 0), curvature 0 and valid 0.
+ *   6. Sign.  With orient = 1 the normal is negated when (nx*(vx - px) + ny*(vy - py)) + nz*(vz - pz) < 0, evaluated in
+ *      double with the unrounded normal, v = viewpoint and p = p_i converted to double.  An exact 0 keeps the sign.
+ * xyz: host points with stride_bytes between them (12 = packed, 48 = pcl::PointNormal); nrm_out packed float[n][3],
+ * curvature_out float[n] and valid_out uint8[n] may be NULL.  n >= 1.  The neighbourhood grid is the refinement stage's
+ * (edge = radius, enlarged by the same rule when the cell count would pass 2^24; res->edge is the edge in force), then one
+ * kernel with one thread per grid position.  The call holds the device's lock like every call that launches, returns
+ * OSLAM_E_DEVICE without a device and OSLAM_E_INVALID for NULL xyz / nrm_out / params, n == 0 or above 2^31 - 1,
+ * stride_bytes < 12, a radius that is not > 0 and finite, min_neighbours < 3, a non-finite viewpoint and a line_ratio
+ * that is not >= 0 and finite.  A refused call writes nothing.
+ *
+ * oslam_mesh_normals (host): for every triangle (a, b, c) in order, (p_b - p_a) x (p_c - p_a) in double is added to its
+ * three vertices (area weighting); each sum is divided by sqrt((x*x + y*y) + z*z) and rounded to float32.  Counter-
+ * clockwise triangles seen from outside give outward normals.  A vertex whose sum is zero or not finite (unreferenced,
+ * only degenerate triangles) gets (0, 0, 0) and valid 0.  An index >= nv fails the call with OSLAM_E_INVALID and writes
+ * nothing.  valid_out may be NULL.  The reference does not say how MATLAB's vertexNormal weights faces: this rule is the
+ * library's own.
+ *
+ * oslam_ply_read_mesh (host): ascii and binary_little_endian; the vertex element first with x y z, normals only when
+ * nx ny nz (or normal_x normal_y normal_z) are all there (*nrm_out = NULL otherwise); the face element's list property
+ * vertex_indices or vertex_index with any integer count and index type; polygons with more than 3 corners become the
+ * fans (0, k, k+1), fewer than 3 corners are dropped; an index outside the vertices is OSLAM_E_INVALID.  A file without
+ * faces gives *nt_out = 0 and *tri_out = NULL.  Other elements and properties are skipped.  The arrays are malloc'd,
+ * release with oslam_free.  oslam_ply_read is unchanged: it still needs normals and skips faces.
+ * Out of scope: handing the device-resident normals to oslam_scene_create without the host round trip, k-nearest
+ * neighbourhoods, a sign propagation for viewpoint-free clouds, oslam_pcl.hpp. */
+#define OSLAM_NORMALS_SWEEPS 4
+typedef struct oslam_normals_params {
+    float radius;              /* no default: must be > 0 and finite, in the cloud's units */
+    unsigned min_neighbours;   /* 5; at least 3; the point itself counts */
+    float viewpoint[3];        /* 0 0 0 */
+    int orient;                /* 1 = towards the viewpoint, 0 = leave the solver's sign */
+    float line_ratio;          /* 0.01: valid needs lmid > line_ratio * lmax */
+    int reserved[4];
+} oslam_normals_params;
+
+typedef struct oslam_normals_result {
+    uint32_t n_valid;
+    uint32_t n_cells;          /* cells of the neighbourhood grid */
+    float edge;                /* its edge: the radius (times 1 + 1e-4), or larger when the cell cap enlarged it */
+    uint32_t launches;
+    float ms_total;            /* whole call, host clock */
+    float ms_grid, ms_kernel;  /* the grid build and the normals kernel on the stream (device events) */
+} oslam_normals_result;
+
+int oslam_normals_params_default(oslam_normals_params *p);
+int oslam_cloud_normals(const float *xyz, size_t n, size_t stride_bytes, const oslam_normals_params *np, int dev,
+                        float *nrm_out, float *curvature_out, uint8_t *valid_out, oslam_normals_result *res);
+/* test tap: the ten integers of step 2 per point, moments_out int64[n][10] */
+int oslam_cloud_normal_moments(const float *xyz, size_t n, size_t stride_bytes, const oslam_normals_params *np, int dev,
+                               int64_t *moments_out);
+int oslam_mesh_normals(const float *xyz, size_t nv, size_t stride_bytes, const uint32_t *tri, size_t nt, float *nrm_out,
+                       uint8_t *valid_out);
+int oslam_ply_read_mesh(const char *path, float **xyz_out, float **nrm_out, uint32_t **tri_out, size_t *nv_out,
+                        size_t *nt_out);
+
 /* ---- parity taps (tests): values the reference materialises as arrays.
  * Scene::getHashKeys row r (scene.cu:49-54): keys_out[n] of reference point r,
  * computed by the GPU key kernel with this d_dist (key 0 on the diagonal). */

@@ -6,16 +6,22 @@
  *       [--scene_leaf_size 10.0] [--ref_point_df 1] [--vote_count_threshold 0.4]
  *       [--cpu_clustering false] [--use_l1_norm false] [--use_averaged_clusters false]
  *       [--validation_files truth.txt] [--validation_translation_threshold 0.1]
- *       [--validation_rotation_threshold 12] [--dev 1]
+ *       [--validation_rotation_threshold 12] [--dev 1] [--normal_radius R]
  *
  * Same flow as alignment.cpp:191-335: load PLY clouds (:212,241), d_dist = tau_d * max bbox
  * extent of the full model (:246-253), voxel-grid every scene at scene_leaf_size and every
  * model at its d_dist (:265-288), ppf_registration (:290-298), and with --validation_files
  * compare each result with the ground-truth 4x4 (one text file per scene x model) and print
  * 1 or 0 per pair to stdout (:300-335).  Everything else goes to stderr.
+ *
+ * A PLY without normals (the reference ran matlab/compute_normals.m or PCL over such files first): with faces its
+ * vertex normals come from the triangles (oslam_mesh_normals); without faces --normal_radius R (in the file's units) is
+ * needed, and the normals are estimated at full resolution, before the voxel grid, with the origin as viewpoint
+ * (oslam_cloud_normals).  Points without a valid normal are dropped.
  */
 #include <getopt.h>
 #include <math.h>
+#include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -51,6 +57,46 @@ static int downsample(cloud *c, float leaf, int dev)
     return OSLAM_OK;
 }
 
+/* a PLY with normals as before; otherwise its normals from its faces, or from its neighbourhoods of normal_radius */
+static int load_cloud(const char *path, cloud *c, float normal_radius, int dev)
+{
+    uint32_t *tri = NULL;
+    uint8_t *valid = NULL;
+    size_t nt = 0, i, k = 0;
+    int rc;
+    if (oslam_ply_read(path, &c->xyz, &c->nrm, &c->n) == OSLAM_OK) return OSLAM_OK;
+    if (oslam_ply_read_mesh(path, &c->xyz, &c->nrm, &tri, &c->n, &nt) != OSLAM_OK) return OSLAM_E_INVALID;
+    if (c->nrm) { oslam_free(tri); return OSLAM_OK; }
+    c->nrm = (float *)malloc(sizeof(float) * 3 * (c->n ? c->n : 1));
+    valid = (uint8_t *)malloc(c->n ? c->n : 1);
+    if (!c->nrm || !valid) { free(valid); oslam_free(tri); return OSLAM_E_NOMEM; }
+    if (nt) {
+        fprintf(stderr, "%s has no normals: taking them from its %zu triangles\n", path, nt);
+        rc = oslam_mesh_normals(c->xyz, c->n, 12, tri, nt, c->nrm, valid);
+    } else if (normal_radius > 0.0f) {
+        oslam_normals_params np;
+        oslam_normals_params_default(&np);
+        np.radius = normal_radius;
+        fprintf(stderr, "%s has neither normals nor faces: estimating normals within %g\n", path, normal_radius);
+        rc = oslam_cloud_normals(c->xyz, c->n, 12, &np, dev, c->nrm, NULL, valid, NULL);
+    } else {
+        fprintf(stderr, "%s has neither normals nor faces: give --normal_radius R (in the file's units) to estimate them\n", path);
+        rc = OSLAM_E_INVALID;
+    }
+    oslam_free(tri);
+    if (rc != OSLAM_OK) { free(valid); fprintf(stderr, "normals: %s\n", oslam_last_error()); return rc; }
+    for (i = 0; i < c->n; i++)
+        if (valid[i]) {
+            memmove(c->xyz + 3 * k, c->xyz + 3 * i, 3 * sizeof(float));
+            memmove(c->nrm + 3 * k, c->nrm + 3 * i, 3 * sizeof(float));
+            k++;
+        }
+    if (k != c->n) fprintf(stderr, "%zu of %zu points have no normal and are dropped\n", c->n - k, c->n);
+    c->n = k;
+    free(valid);
+    return OSLAM_OK;
+}
+
 int main(int argc, char **argv)
 {
     static struct option opts[] = {
@@ -59,10 +105,10 @@ int main(int argc, char **argv)
         {"cpu_clustering", 1, 0, 'c'}, {"use_l1_norm", 1, 0, '1'}, {"use_averaged_clusters", 1, 0, 'a'},
         {"validation_translation_threshold", 1, 0, 'T'}, {"validation_rotation_threshold", 1, 0, 'R'},
         {"scene_files", 1, 0, 'S'}, {"model_files", 1, 0, 'M'}, {"validation_files", 1, 0, 'V'},
-        {"show_normals", 1, 0, 'n'}, {"visualize", 1, 0, 'z'}, {"help", 0, 0, 'h'}, {0, 0, 0, 0}};
+        {"show_normals", 1, 0, 'n'}, {"visualize", 1, 0, 'z'}, {"normal_radius", 1, 0, 'N'}, {"help", 0, 0, 'h'}, {0, 0, 0, 0}};
     char *scene_files[MAX_FILES], *model_files[MAX_FILES], *val_files[MAX_FILES], *tau_strs[MAX_FILES];
     int n_scenes = 0, n_models = 0, n_val = 0, n_tau = 0, dev = 1, cpu_clustering = 0, l1 = 0, averaged = 0, o, i, j;
-    float scene_leaf = 10.0f, thresh = 0.4f, vt = 0.1f, vr = 12.0f;
+    float scene_leaf = 10.0f, thresh = 0.4f, vt = 0.1f, vr = 12.0f, normal_radius = 0.0f;
     unsigned df = 1;
     cloud scenes[MAX_FILES], models[MAX_FILES];
     float d_dists[MAX_FILES], tau[MAX_FILES], *T;
@@ -85,6 +131,7 @@ int main(int argc, char **argv)
         case 'S': n_scenes = split(optarg, scene_files, MAX_FILES); break;
         case 'M': n_models = split(optarg, model_files, MAX_FILES); break;
         case 'V': n_val = split(optarg, val_files, MAX_FILES); break;
+        case 'N': normal_radius = (float)atof(optarg); break;
         case 'L': case 'l': case 'n': case 'z': break;          /* logging / display flags: accepted, unused */
         default:
             fprintf(stderr, "usage: %s --scene_files a.ply[,..] --model_files m.ply[,..] --tau_d t[,..] [options]\n", argv[0]);
@@ -97,7 +144,7 @@ int main(int argc, char **argv)
 
     for (i = 0; i < n_scenes; i++) {
         fprintf(stderr, "Loading scene point cloud: %s\n", scene_files[i]);
-        if (oslam_ply_read(scene_files[i], &scenes[i].xyz, &scenes[i].nrm, &scenes[i].n) != OSLAM_OK) {
+        if (load_cloud(scene_files[i], &scenes[i], normal_radius, dev) != OSLAM_OK) {
             fprintf(stderr, "Error loading scene file!\n");
             return 1;
         }
@@ -105,7 +152,7 @@ int main(int argc, char **argv)
     for (j = 0; j < n_models; j++) {
         tau[j] = (float)atof(tau_strs[j]);
         fprintf(stderr, "Loading model point cloud: %s\n", model_files[j]);
-        if (oslam_ply_read(model_files[j], &models[j].xyz, &models[j].nrm, &models[j].n) != OSLAM_OK) {
+        if (load_cloud(model_files[j], &models[j], normal_radius, dev) != OSLAM_OK) {
             fprintf(stderr, "Error loading model file!\n");
             return 1;
         }

@@ -387,6 +387,22 @@ int oslamk_refine_corr(int mode, const oslamk_grid *g, const oslamk_refine_membe
 int oslamk_refine_solve(oslamk_refine_member *d_mem, uint32_t n_mem, uint32_t max_blocks, const float *slab,
                         uint32_t *n_done, void *stream);
 
+/* ---- normal estimation (oslam_normals.hip; semantics in include/oslam.h at oslam_cloud_normals) ---- */
+#define OSLAMK_NORMALS_THREADS 256   /* grid positions per workgroup of k_normals */
+typedef struct oslamk_normals_args {
+    float r2, scale;           /* radius * radius and 16384.0f / radius, both rounded by the host */
+    double view[3];
+    double line_ratio;
+    int64_t min_neighbours;
+    int orient;
+    float *nrm;                /* [n][3], by input index */
+    float *curvature;          /* [n] */
+    uint8_t *valid;            /* [n] */
+    int64_t *moments;          /* [n][10], or NULL */
+} oslamk_normals_args;
+/* one thread per position of g->pts (a grid built by oslamk_refine_grid_build): writes every point's outputs */
+int oslamk_normals(const oslamk_grid *g, const oslamk_normals_args *a, void *stream);
+
 /* ---- verification stage (oslam_verify.hip; semantics in include/oslam.h at oslam_verify) ---- */
 #define OSLAMK_VERIFY_THREADS 256    /* model points per workgroup of k_verify */
 #define OSLAMK_VERIFY_CLASSES 6

@@ -185,4 +185,144 @@ int oslam_ply_write_mesh(const char *path, const float *xyz, const float *nrm, s
     return fclose(f) ? OSLAM_E_INVALID : OSLAM_OK;
 }
 
+/* ---- meshes, with or without normals (include/oslam.h at oslam_ply_read_mesh) ---- */
+#define MAX_ELEMS 8
+typedef struct { int is_list, slot; char ctype[16], type[16]; } mesh_prop;      /* slot: 0..5 = x y z nx ny nz, 6 = the
+                                                                                    face's index list, -1 = skipped */
+typedef struct { char name[32]; size_t count; int nprop; mesh_prop p[MAX_PROPS]; } mesh_elem;
+
+/* the next value of type t: a number of the text, or the bytes of a binary file */
+static int next_value(FILE *f, int ascii, const char *t, double *out)
+{
+    unsigned char b[8];
+    if (ascii) return fscanf(f, "%lf", out) == 1;
+    if (fread(b, (size_t)type_size(t), 1, f) != 1) return 0;
+    *out = read_scalar(b, t);
+    return 1;
+}
+
+static int is_float_type(const char *t)
+{
+    return !strcmp(t, "float") || !strcmp(t, "float32") || !strcmp(t, "double") || !strcmp(t, "float64");
+}
+
+int oslam_ply_read_mesh(const char *path, float **xyz_out, float **nrm_out, uint32_t **tri_out, size_t *nv_out, size_t *nt_out)
+{
+    static const char *names[6][2] = {{"x", "x"}, {"y", "y"}, {"z", "z"}, {"nx", "normal_x"}, {"ny", "normal_y"},
+                                      {"nz", "normal_z"}};
+    FILE *f;
+    char line[1024];
+    mesh_elem *el = NULL, *cur = NULL;
+    int n_el = 0, ascii = -1, have[6] = {0, 0, 0, 0, 0, 0}, with_nrm, e, i, rc = OSLAM_E_INVALID;
+    size_t nv = 0, nt = 0, cap = 0, k, j;
+    float *xyz = NULL, *nrm = NULL;
+    uint32_t *tri = NULL;
+    if (!path || !xyz_out || !nrm_out || !tri_out || !nv_out || !nt_out) return OSLAM_E_INVALID;
+    *xyz_out = *nrm_out = NULL;
+    *tri_out = NULL;
+    *nv_out = *nt_out = 0;
+    f = fopen(path, "rb");
+    if (!f) return OSLAM_E_INVALID;
+    el = (mesh_elem *)calloc(MAX_ELEMS, sizeof *el);
+    if (!el) { rc = OSLAM_E_NOMEM; goto done; }
+    if (!fgets(line, sizeof line, f) || strncmp(line, "ply", 3)) goto done;
+    while (fgets(line, sizeof line, f)) {
+        char a[64] = "", b[64] = "", c[64] = "", d[64] = "", g[64] = "";
+        int kk = sscanf(line, "%63s %63s %63s %63s %63s", a, b, c, d, g);
+        if (kk < 1) continue;
+        if (!strcmp(a, "end_header")) break;
+        if (!strcmp(a, "format")) {
+            if (!strcmp(b, "ascii")) ascii = 1;
+            else if (!strcmp(b, "binary_little_endian")) ascii = 0;
+            else goto done;
+        } else if (!strcmp(a, "element")) {
+            if (n_el == MAX_ELEMS) goto done;
+            cur = &el[n_el++];
+            snprintf(cur->name, sizeof cur->name, "%.31s", b);
+            cur->count = (size_t)strtoull(c, NULL, 10);
+            if ((n_el == 1) != !strcmp(b, "vertex")) goto done;      /* the vertices come first, once */
+        } else if (!strcmp(a, "property")) {
+            mesh_prop *p;
+            if (!cur || cur->nprop == MAX_PROPS) goto done;
+            p = &cur->p[cur->nprop++];
+            p->slot = -1;
+            if (!strcmp(b, "list")) {
+                if (!type_size(c) || !type_size(d) || is_float_type(c)) goto done;
+                p->is_list = 1;
+                snprintf(p->ctype, sizeof p->ctype, "%.15s", c);
+                snprintf(p->type, sizeof p->type, "%.15s", d);
+                if (!strcmp(cur->name, "face") && (!strcmp(g, "vertex_indices") || !strcmp(g, "vertex_index"))) {
+                    if (is_float_type(d)) goto done;
+                    p->slot = 6;
+                }
+            } else {
+                if (!type_size(b)) goto done;
+                snprintf(p->type, sizeof p->type, "%.15s", b);
+                if (cur == &el[0])
+                    for (i = 0; i < 6; i++)
+                        if (!strcmp(c, names[i][0]) || !strcmp(c, names[i][1])) { p->slot = i; have[i] = 1; }
+            }
+        }
+    }
+    if (ascii < 0 || n_el == 0 || !(have[0] && have[1] && have[2])) goto done;
+    with_nrm = have[3] && have[4] && have[5];
+    nv = el[0].count;
+    xyz = (float *)malloc(sizeof(float) * 3 * (nv ? nv : 1));
+    if (with_nrm) nrm = (float *)malloc(sizeof(float) * 3 * (nv ? nv : 1));
+    if (!xyz || (with_nrm && !nrm)) { rc = OSLAM_E_NOMEM; goto done; }
+    for (e = 0; e < n_el; e++) {
+        const mesh_elem *E = &el[e];
+        for (k = 0; k < E->count; k++)
+            for (i = 0; i < E->nprop; i++) {
+                const mesh_prop *p = &E->p[i];
+                double v, first = 0.0, prev = 0.0;
+                size_t cnt;
+                if (!p->is_list) {
+                    if (!next_value(f, ascii, p->type, &v)) goto done;
+                    if (p->slot >= 0 && p->slot < 3) xyz[3 * k + p->slot] = (float)v;
+                    else if (p->slot >= 3 && with_nrm) nrm[3 * k + p->slot - 3] = (float)v;
+                    continue;
+                }
+                if (!next_value(f, ascii, p->ctype, &v) || v < 0.0) goto done;
+                cnt = (size_t)v;
+                for (j = 0; j < cnt; j++) {
+                    if (!next_value(f, ascii, p->type, &v)) goto done;
+                    if (p->slot != 6) continue;
+                    if (!(v >= 0.0) || !(v < (double)nv)) goto done;              /* an index outside the vertices */
+                    if (j == 0) first = v;
+                    if (j >= 2) {                                                  /* the fan (0, j - 1, j) */
+                        if (nt == cap) {
+                            uint32_t *t2;
+                            cap = cap ? 2 * cap : (E->count > 1024 ? E->count : 1024);
+                            t2 = (uint32_t *)realloc(tri, sizeof(uint32_t) * 3 * cap);
+                            if (!t2) { rc = OSLAM_E_NOMEM; goto done; }
+                            tri = t2;
+                        }
+                        tri[3 * nt] = (uint32_t)first;
+                        tri[3 * nt + 1] = (uint32_t)prev;
+                        tri[3 * nt + 2] = (uint32_t)v;
+                        nt++;
+                    }
+                    prev = v;
+                }
+            }
+    }
+    *xyz_out = xyz;
+    *nrm_out = nrm;
+    *tri_out = nt ? tri : NULL;
+    if (!nt) free(tri);
+    *nv_out = nv;
+    *nt_out = nt;
+    xyz = nrm = NULL;
+    tri = NULL;
+    rc = OSLAM_OK;
+done:
+    free(xyz);
+    free(nrm);
+    free(tri);
+    free(el);
+    fclose(f);
+    return rc;
+}
+
 void oslam_free(void *p) { free(p); }

@@ -308,6 +308,22 @@ class ReloadResult(C.Structure):
                 "reloaded": int(self.reloaded), "launches": int(self.launches), "ms_total": float(self.ms_total)}
 
 
+class NormalsParams(C.Structure):
+    _fields_ = [("radius", C.c_float), ("min_neighbours", C.c_uint), ("viewpoint", C.c_float * 3), ("orient", C.c_int),
+                ("line_ratio", C.c_float), ("reserved", C.c_int * 4)]
+
+
+class NormalsResult(C.Structure):
+    _fields_ = [("n_valid", C.c_uint32), ("n_cells", C.c_uint32), ("edge", C.c_float), ("launches", C.c_uint32),
+                ("ms_total", C.c_float), ("ms_grid", C.c_float), ("ms_kernel", C.c_float)]
+
+    def asdict(self):
+        return {"n_valid": int(self.n_valid), "n_cells": int(self.n_cells), "edge": float(self.edge),
+                "launches": int(self.launches), "ms_total": float(self.ms_total), "ms_grid": float(self.ms_grid),
+                "ms_kernel": float(self.ms_kernel)}
+
+
+NORMALS_SWEEPS = 4
 ARBITRATE_MAX_HYPOTHESES = 1024
 CELL_DTYPE = np.dtype([("code", "<u8"), ("count", "<u4"), ("pad", "<u4")])
 
@@ -457,6 +473,11 @@ _SIGNATURES = {
                                C.POINTER(MeshResult)]),
     "oslam_ply_write_mesh": (_i, [C.c_char_p, _vp, _vp, _sz, _vp, _sz, _i]),
     "oslam_mc_table_row": (_i, [_u, _vp, C.POINTER(_u)]),
+    "oslam_normals_params_default": (_i, [C.POINTER(NormalsParams)]),
+    "oslam_cloud_normals": (_i, [_vp, _sz, _sz, C.POINTER(NormalsParams), _i, _vp, _vp, _vp, C.POINTER(NormalsResult)]),
+    "oslam_cloud_normal_moments": (_i, [_vp, _sz, _sz, C.POINTER(NormalsParams), _i, _vp]),
+    "oslam_mesh_normals": (_i, [_vp, _sz, _sz, _vp, _sz, _vp, _vp]),
+    "oslam_ply_read_mesh": (_i, [C.c_char_p, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_sz), C.POINTER(_sz)]),
     "oslam_scene_keys": (_i, [_vp, _sz, _vp]),
     "oslam_model_keys": (_i, [_vp, _sz, _vp]),
     "oslam_model_bucket": (_i, [_vp, C.c_uint32, _vp, _sz, C.POINTER(_sz)]),
@@ -924,8 +945,72 @@ def d_dist_from_cloud(points, tau_d):
     return out.value
 
 
+def default_normals_params(**kw):
+    """oslam_normals_params_default, then the fields given as keywords (viewpoint: three numbers)."""
+    p = NormalsParams()
+    _check(lib().oslam_normals_params_default(C.byref(p)))
+    for k, v in kw.items():
+        if not hasattr(p, k) or k == "reserved":
+            raise TypeError("unknown normals parameter %r" % k)
+        setattr(p, k, (C.c_float * 3)(*[float(x) for x in v]) if k == "viewpoint" else v)
+    return p
+
+
+def _normals_cloud(points):
+    """-> (array kept alive, n, stride): a packed [n,3] float32 array, or [n,12] (pcl::PointNormal) with stride 48"""
+    a = np.ascontiguousarray(points, np.float32)
+    if a.ndim != 2 or a.shape[1] not in (3, 12):
+        raise ValueError("points must be [n,3] or [n,12] float32")
+    return a, len(a), a.strides[0]
+
+
+def estimate_normals(points, radius, viewpoint=(0, 0, 0), dev=0, want=("curvature", "valid"), result=None, **fields):
+    """Normals of a cloud seen from `viewpoint`, from the principal axes of the neighbours within `radius`
+    (oslam_cloud_normals) -> (normals [n,3] f32, curvature [n] f32, valid [n] bool).  fields: min_neighbours, orient,
+    line_ratio.  want: which of the optional outputs the library is asked for (the others come back as None); result: a
+    dict that receives oslam_normals_result."""
+    a, n, stride = _normals_cloud(points)
+    p = default_normals_params(radius=float(radius), viewpoint=viewpoint, **fields)
+    nrm = np.zeros((n, 3), np.float32)
+    curv = np.zeros(n, np.float32) if "curvature" in want else None
+    valid = np.zeros(n, np.uint8) if "valid" in want else None
+    res = NormalsResult()
+    _check(lib().oslam_cloud_normals(_p(a), n, stride, C.byref(p), int(dev), _p(nrm), None if curv is None else _p(curv),
+                                     None if valid is None else _p(valid), C.byref(res)))
+    if result is not None:
+        result.update(res.asdict())
+    return nrm, curv, None if valid is None else valid.astype(bool)
+
+
+def normal_moments(points, radius, dev=0, **fields):
+    """The ten int64 moments per point that estimate_normals forms its covariance from (test tap) -> [n,10]."""
+    a, n, stride = _normals_cloud(points)
+    p = default_normals_params(radius=float(radius), **fields)
+    out = np.zeros((n, 10), np.int64)
+    _check(lib().oslam_cloud_normal_moments(_p(a), n, stride, C.byref(p), int(dev), _p(out)))
+    return out
+
+
+def mesh_normals(points, triangles):
+    """Area-weighted vertex normals of a triangle mesh (oslam_mesh_normals, host) -> (normals [nv,3] f32, valid [nv] bool)."""
+    a, n, stride = _normals_cloud(points)
+    t = np.ascontiguousarray(triangles, np.uint32).reshape(-1, 3)
+    nrm, valid = np.zeros((n, 3), np.float32), np.zeros(n, np.uint8)
+    _check(lib().oslam_mesh_normals(_p(a), n, stride, _p(t), len(t), _p(nrm), _p(valid)))
+    return nrm, valid.astype(bool)
+
+
 class Scene:
     """Scene(cloud, d_dist, ref_point_downsample_factor=1)  (scene.h:15-16)."""
+
+    @classmethod
+    def from_points(cls, points, radius, viewpoint=(0, 0, 0), d_dist=None, ref_point_downsample_factor=1, params=None,
+                    dev=0, **fields):
+        """A scene from points alone: estimate_normals, drop the points without a valid normal, then Scene(...)."""
+        pts = np.ascontiguousarray(points, np.float32)
+        nrm, _, valid = estimate_normals(pts, radius, viewpoint, dev=dev, want=("valid",), **fields)
+        return cls(pts[valid], nrm[valid], d_dist=d_dist, ref_point_downsample_factor=ref_point_downsample_factor,
+                   params=params)
 
     def __init__(self, points, normals=None, d_dist=None, ref_point_downsample_factor=1, params=None):
         if d_dist is None:
@@ -1015,6 +1100,13 @@ class Model:
         self.best_T = None
         self.stats = None
         _check(lib().oslam_model_create(xyz, nrm, n, stride, self.d_dist, C.byref(self.params), C.byref(self._h)))
+
+    @classmethod
+    def from_mesh(cls, points, triangles, d_dist=None, **kw):
+        """A model from a triangle mesh: mesh_normals, drop the vertices without a normal, then Model(...)."""
+        pts = np.ascontiguousarray(points, np.float32)
+        nrm, valid = mesh_normals(pts, triangles)
+        return cls(pts[valid], nrm[valid], d_dist=d_dist, **kw)
 
     def numPoints(self):
         return self.n
@@ -1496,6 +1588,29 @@ def ply_read(path):
         L.oslam_free(px)
         L.oslam_free(pn)
     return pts, nrm
+
+
+def ply_read_mesh(path):
+    """(points [nv,3], normals [nv,3] or None, triangles [nt,3] uint32) of a PLY file with or without normals and faces
+    (oslam_ply_read_mesh)."""
+    L = lib()
+    px, pn, pt, nv, nt = C.c_void_p(0), C.c_void_p(0), C.c_void_p(0), C.c_size_t(0), C.c_size_t(0)
+    rc = L.oslam_ply_read_mesh(os.fsencode(path), C.byref(px), C.byref(pn), C.byref(pt), C.byref(nv), C.byref(nt))
+    if rc != OSLAM_OK:
+        raise OslamError(rc, "cannot read PLY file %s" % path)
+    try:
+        def take(ptr, n, ctype, dtype):
+            if not ptr or not n:
+                return np.zeros((n, 3), dtype)
+            return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ctype)), shape=(n, 3)).copy()
+        pts = take(px, nv.value, C.c_float, np.float32)
+        nrm = take(pn, nv.value, C.c_float, np.float32) if pn else None
+        tri = take(pt, nt.value, C.c_uint32, np.uint32)
+    finally:
+        L.oslam_free(px)
+        L.oslam_free(pn)
+        L.oslam_free(pt)
+    return pts, nrm, tri
 
 
 def ply_write(path, points, normals, binary=True):

@@ -37,6 +37,10 @@ configuration; these are not bench lines).  Needs a HIP device.
                                          db.arbitrate and db.explain over what verification found: who is verified, who
                                          each stage keeps and both stages' ms per frame; and ms_total of explain,
                                          arbitrate and render for 1 and 50 hypotheses, median of 20 calls each
+  python tools/bench_configs.py normals  oslam_cloud_normals on the 100k-point bench scene and on the 500k-point slice's
+                                         scene (points only), at radii of 2 and 4 times the median spacing: whole call,
+                                         grid build and kernel, median of 20 calls after 5, and the neighbours visited and
+                                         accepted per second of kernel time
 One JSON line each."""
 import importlib, json, os, sys, time
 
@@ -1064,8 +1068,62 @@ def pyramid(calls=20):
     return out
 
 
+def _spacing(p, sample=500):
+    """median distance to the nearest other point, from a seeded sample"""
+    q = p.astype(np.float64)
+    idx = np.random.default_rng(1).choice(len(q), size=min(sample, len(q)), replace=False)
+    best = np.full(len(idx), np.inf)
+    for b in range(0, len(q), 1 << 14):
+        d2 = ((q[idx, None, :] - q[None, b:b + (1 << 14), :]) ** 2).sum(axis=2)
+        d2[d2 == 0.0] = np.inf
+        best = np.minimum(best, d2.min(axis=1))
+    return float(np.median(np.sqrt(best)))
+
+
+def _visited(p, edge):
+    """the points in the 27 cells around every point's cell, summed: what the kernel's walk loads"""
+    q = p.astype(np.float64)
+    cell = np.floor((q - q.min(axis=0)) / edge).astype(np.int64) + 1
+    dim = cell.max(axis=0) + 2
+    key = np.sort((cell[:, 2] * dim[1] + cell[:, 1]) * dim[0] + cell[:, 0])
+    total = 0
+    for dz in (-1, 0, 1):
+        for dy in (-1, 0, 1):
+            k0 = key + (dz * dim[1] + dy) * dim[0] - 1
+            total += int((np.searchsorted(key, k0 + 2, "right") - np.searchsorted(key, k0, "left")).sum())
+    return total
+
+
+def normals(calls=20, warm=5):
+    mp, _ = synth.make_model(0, 5000)
+    d = synth.d_dist_for(mp, 0.05)
+    clouds = {"bench_scene_100k": synth.make_scene([0], 100000, 2002, instance_points=5000, noise_sigma=0.1 * d)[0],
+              "slice_scene_500k": synth.make_scene([0, 1], 500000, 2004, instance_points=5000, noise_sigma=0.1 * d)[0]}
+    out = {"config": "oslam_cloud_normals, points only, viewpoint at the origin; median of %d calls after %d" % (calls, warm),
+           "sweeps": ppf.NORMALS_SWEEPS, "clouds": {}}
+    for name, p in clouds.items():
+        sp = _spacing(p)
+        rows = []
+        for k in (2.0, 4.0):
+            radius = k * sp
+            res, t = {}, {"ms_total": [], "ms_grid": [], "ms_kernel": []}
+            for c in range(warm + calls):
+                ppf.estimate_normals(p, radius, result=res)
+                if c >= warm:
+                    for key in t:
+                        t[key].append(res[key])
+            med = {key: float(np.median(v)) for key, v in t.items()}
+            accepted = int(ppf.normal_moments(p, radius)[:, 0].sum())
+            visited = _visited(p, res["edge"])
+            rows.append({"radius_spacings": k, "radius": radius, **med, "n_valid": res["n_valid"], "n_cells": res["n_cells"],
+                         "edge": res["edge"], "neighbours_accepted": accepted, "neighbours_visited": visited,
+                         "accepted_per_s": accepted / (med["ms_kernel"] * 1e-3), "visited_per_s": visited / (med["ms_kernel"] * 1e-3)})
+        out["clouds"][name] = {"points": len(p), "median_spacing": sp, "radii": rows}
+    return out
+
+
 if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "cfg3"
     print(json.dumps({"cfg2": cfg2, "cfg3": cfg3, "cfg3db": cfg3db, "cfg4": cfg4, "cfg5": cfg5, "planes": planes, "db50": db50,
                       "refine": refine, "verify": verify, "instances": instances, "arbitrate": arbitrate, "explain": explain, "track": track, "camera": camera,
-                      "fusion": fusion, "surface": surface, "mesh": mesh, "shift": shift, "reload": reload, "pyramid": pyramid}[which]()), flush=True)
+                      "fusion": fusion, "surface": surface, "mesh": mesh, "shift": shift, "reload": reload, "pyramid": pyramid, "normals": normals}[which]()), flush=True)
