@@ -1059,7 +1059,7 @@ int oslam_view_maps(oslam_view *v, float *maps_out, float *z_out);
  *   depth_band that is not finite or <= 0, a k beyond the pyramid, the parameter checks of oslam_view_egomotion, a stride
  *   other than 1, 2, 4 and a T that is not rigid are OSLAM_E_INVALID; so are pyramids (or a volume and a pyramid) on
  *   different devices.
- * Out of scope: a bilateral filter of the raw depth, resizing the ray cast's TSDF normals instead of recomputing them
+ * Out of scope: resizing the ray cast's TSDF normals instead of recomputing them
  *   from z, per-level gates, feeding oslam_tracker or a volume's own stepping from the pyramid (callers opt in through
  *   these calls), several GPUs. */
 typedef struct oslam_pyramid oslam_pyramid;
@@ -1081,6 +1081,62 @@ int oslam_pyramid_egomotion(oslam_pyramid *src, oslam_pyramid *dst, const float 
 int oslam_volume_track_pyramid(oslam_volume *vol, oslam_pyramid *frame, const float T_vol_cam_prev[16],
                                const oslam_pyramid_params *pp, const oslam_egomotion_params *ep,
                                float T_vol_cam_out[16], oslam_egomotion_result *ego_res);
+
+/* ---- a bilateral filter of a view's depth image (KinFu's first step on every frame).  Every stage that looks at a
+ * depth image takes its vertices and normals from raw z differences of the four axis neighbours, so depth noise of a
+ * few millimetres turns the normals by tens of degrees and the camera tracker loses its correspondences.
+ * The filter smooths z within a surface and leaves depth steps alone.  Its result is a genuine oslam_view: oslam_verify,
+ * oslam_track, oslam_view_egomotion, oslam_pyramid_create and oslam_volume_integrate take it unchanged.  The restatement
+ * in numpy is tests/bilateral_ref.py; device and restatement agree bit for bit in the z image and both counters.
+ *
+ * All arithmetic is float32 without fused multiply-add, grouped as written.
+ * Constants, computed once on the host: inv_s = (float)(1.0 / ((double)sigma_space * (double)sigma_space)) and
+ *   inv_r = (float)(1.0 / ((double)sigma_depth * (double)sigma_depth)).  R = radius.
+ * Depth.  c = z[v][u]; c == 0 (invalid) gives 0.  Otherwise the (2R + 1)^2 window dy = -R..R (outer), dx = -R..R
+ *   (inner), clipped to the image, is walked from sd = 0.0f, sw = 0.0f, taps = 0.  For the pixel z = z[v + dy][u + dx]:
+ *   it takes part only if z > 0; then d = z - c and t = (float)(dx * dx + dy * dy) * inv_s + (d * d) * inv_r, and it takes
+ *   part only if t < 9.0f; then w = G[(int)(t * 32.0f)], sd += w * d, sw += w, taps++, in that row-major order.  The centre
+ *   always takes part with d = 0 and t = 0, so sw > 0.  The sum runs over the differences d, not over the depths: at
+ *   6 m a float32 depth has 0.5 um of resolution left, a difference of a few centimetres has all of its bits.
+ *   The output is fminf(fmaxf(c + sd / sw, z_min), z_max) with the correctly rounded division.  The valid pixels of the
+ *   output are exactly those of the input.
+ * Table.  G[i] = (float)exp(-0.5 * (i + 0.5) / 32) for i = 0..287 (csrc/oslam_gauss_table.h, written by
+ *   tools/gen_gauss_table.py as bit patterns): one fixed Gaussian sampled at the midpoints of bins of 1/32, independent of
+ *   both sigmas because t is already in units of sigma squared.  t < 9 is the 3-sigma cut; t * 32 is exact in float and
+ *   below 288, so the index never leaves the table.  The table, not expf, is what lets device and numpy agree bit for bit.
+ *   oslam_gauss_table is a host-only tap on the compiled-in table for the tests.
+ * Output view.  It has v's size, camera and max_jump and is owned by the caller (oslam_view_destroy).  It starts without
+ *   maps and gets its vertex and normal map on first use from its own z image, as a masked view or a pyramid level does.
+ *   That holds for a ray-cast input too: its filtered copy takes its normals from z differences, not the TSDF gradient.
+ * Result.  valid counts the output pixels with z > 0; taps is the integer sum of taps over all pixels (at 640 x 480 and
+ *   R = 8 at most 88 780 800 < 2^27), the order-free check of the gate; launches == 1.
+ * Cost: one memset of the counters, k_bilateral, one small copy back, one host wait.
+ * Arguments are checked before any handle is read or any device call is made: NULL pointers (bp and res may be NULL), a
+ *   radius outside 1..OSLAM_BILATERAL_MAX_RADIUS and a sigma that is not finite or <= 0 (or so small that 1 / sigma^2
+ *   is not a finite float) are OSLAM_E_INVALID.  *out is NULL on every failure.
+ * Out of scope: a noise model that grows with z^2, filtering inside oslam_scene_from_depth, feeding oslam_tracker or a
+ *   pyramid from the filter automatically (callers pass a filtered view), any default of another params struct, several
+ *   GPUs. */
+#define OSLAM_BILATERAL_MAX_RADIUS 8
+typedef struct oslam_bilateral_params {
+    unsigned radius;           /* half-width of the window in pixels, 1..OSLAM_BILATERAL_MAX_RADIUS, default 6 */
+    float sigma_space;         /* pixels, > 0, default 4.5 */
+    float sigma_depth;         /* metres, > 0, default 0.03; at least twice the depth noise (calibration: DESIGN.md 7s) */
+    int reserved[4];
+} oslam_bilateral_params;
+typedef struct oslam_bilateral_result {
+    uint32_t valid;            /* output pixels with z > 0 */
+    uint32_t taps;             /* window pixels that took part, summed over the image */
+    uint32_t launches;
+    float ms_total;
+} oslam_bilateral_result;
+
+int oslam_bilateral_params_default(oslam_bilateral_params *p);
+/* bp may be NULL (defaults), res may be NULL */
+int oslam_view_bilateral(const oslam_view *v, const oslam_bilateral_params *bp, oslam_view **out,
+                         oslam_bilateral_result *res);
+/* *w_out = G[i], i in 0..287 */
+int oslam_gauss_table(unsigned i, float *w_out);
 
 /* ---- hypotheses rendered into a labelled depth view, and views masked by it.  The image a set of hypotheses
  * (model, T) would produce in a given camera: a z image and, per pixel, the index of the hypothesis in front.  With it a

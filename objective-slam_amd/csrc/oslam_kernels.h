@@ -538,6 +538,15 @@ int oslamk_ego_corr(const oslamk_view *src, const float *src_maps, const oslamk_
 /* the z image of the next coarser level of *src: z_out [(h + 1) / 2][(w + 1) / 2], clamped to src's [z_min, z_max] */
 int oslamk_pyr_down(const oslamk_view *src, float depth_band, float *z_out, void *stream);
 
+/* ---- bilateral depth filter (oslam_bilateral.hip; semantics in include/oslam.h at oslam_view_bilateral) ---- */
+#define OSLAMK_BILATERAL_MAX_RADIUS 8 /* the largest half-width of the window in pixels: sizes the kernel's LDS tile */
+
+/* z_out [h][w] = the z image of *src filtered over the (2 radius + 1)^2 window with inv_s = 1 / sigma_space^2 and
+ * inv_r = 1 / sigma_depth^2, clamped to src's [z_min, z_max]; counts[0 .. 2) (zeroed by the caller) += the valid pixels
+ * of z_out, the taps that took part */
+int oslamk_bilateral(const oslamk_view *src, int radius, float inv_s, float inv_r, float *z_out, uint32_t *counts,
+                     void *stream);
+
 /* ---- render stage (oslam_render.hip; semantics in include/oslam.h at oslam_render_create / oslam_view_mask) ---- */
 #define OSLAMK_RENDER_MAX_SPLAT 8     /* the largest half-width of a splat in pixels */
 #define OSLAMK_MASK_MAX_DILATE 8      /* the largest half-width of the mask's window in pixels */

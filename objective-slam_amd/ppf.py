@@ -212,6 +212,21 @@ class MaskResult(C.Structure):
 MASK_REMOVE, MASK_KEEP = 0, 1
 
 
+class BilateralParams(C.Structure):
+    _fields_ = [("radius", C.c_uint), ("sigma_space", C.c_float), ("sigma_depth", C.c_float), ("reserved", C.c_int * 4)]
+
+
+class BilateralResult(C.Structure):
+    _fields_ = [("valid", C.c_uint32), ("taps", C.c_uint32), ("launches", C.c_uint32), ("ms_total", C.c_float)]
+
+    def asdict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+BILATERAL_MAX_RADIUS = 8
+GAUSS_TABLE_N = 288
+
+
 class ExplainParams(C.Structure):
     _fields_ = [("footprint", C.c_float), ("max_splat", C.c_uint), ("keep_back", C.c_int), ("depth_tol", C.c_float),
                 ("tile", C.c_uint), ("tile_spacing", C.c_float), ("min_tiles", C.c_uint), ("min_owned_share", C.c_float),
@@ -449,6 +464,9 @@ _SIGNATURES = {
     "oslam_view_info": (_i, [_vp, _vp, C.POINTER(_i), C.POINTER(_i)]),
     "oslam_mask_params_default": (_i, [C.POINTER(MaskParams)]),
     "oslam_view_mask": (_i, [_vp, _vp, C.POINTER(MaskParams), C.POINTER(_vp), C.POINTER(MaskResult)]),
+    "oslam_bilateral_params_default": (_i, [C.POINTER(BilateralParams)]),
+    "oslam_view_bilateral": (_i, [_vp, C.POINTER(BilateralParams), C.POINTER(_vp), C.POINTER(BilateralResult)]),
+    "oslam_gauss_table": (_i, [_u, C.POINTER(_f)]),
     "oslam_surface_params_default": (_i, [C.POINTER(SurfaceParams)]),
     "oslam_volume_surface": (_i, [_vp, C.POINTER(SurfaceParams), _vp, _vp, _sz, C.POINTER(_sz), C.POINTER(SurfaceResult)]),
     "oslam_scene_from_volume": (_i, [_vp, C.POINTER(SurfaceParams), _f, _f, _u, C.POINTER(Params), C.POINTER(_vp),
@@ -1866,6 +1884,40 @@ def mask_view(view, render, mode="remove", dilate=2, only=-1):
     return v, res.asdict()
 
 
+def default_bilateral_params(**kw):
+    """oslam_bilateral_params_default, then the fields given as keywords."""
+    p = BilateralParams()
+    _check(lib().oslam_bilateral_params_default(C.byref(p)))
+    for k, v in kw.items():
+        if not hasattr(p, k) or k == "reserved":
+            raise TypeError("unknown bilateral parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def bilateral_view(view, radius=6, sigma_space=4.5, sigma_depth=0.03, params=None):
+    """The view with its depth image smoothed by a bilateral filter (oslam_view_bilateral): within a surface the noise
+    goes, depth steps above about 3 sigma_depth stay.  params: a BilateralParams, which then replaces the three keywords.
+    -> (View owned by the caller, result dict: valid, taps, launches, ms_total)."""
+    p = params if params is not None else default_bilateral_params(radius=int(radius), sigma_space=sigma_space,
+                                                                   sigma_depth=sigma_depth)
+    res = BilateralResult()
+    v = View.__new__(View)
+    v._h = C.c_void_p(0)
+    v.width, v.height = view.width, view.height
+    _check(lib().oslam_view_bilateral(view._h, C.byref(p), C.byref(v._h), C.byref(res)))
+    return v, res.asdict()
+
+
+def gauss_table():
+    """The library's compiled-in weight table of the bilateral filter (oslam_gauss_table): float32 [288]."""
+    out, w = np.zeros(GAUSS_TABLE_N, np.float32), C.c_float(0)
+    for i in range(GAUSS_TABLE_N):
+        _check(lib().oslam_gauss_table(i, C.byref(w)))
+        out[i] = w.value
+    return out
+
+
 def egomotion_pyramid(src_pyr, dst_pyr, T_init=None, params=None, **fields):
     """Coarse-to-fine camera motion over two pyramids (oslam_pyramid_egomotion): stride 1, 2, 4 of a schedule level names
     pyramid level 0, 1, 2.  params: an EgomotionParams, or none and the fields of default_egomotion_params as keywords.
@@ -2039,7 +2091,7 @@ class Volume:
                                                 C.byref(res)))
         return To.reshape(4, 4), res.asdict()
 
-    def step(self, view, params=None, follow=None, world=None, static=None):
+    def step(self, view, params=None, follow=None, world=None, static=None, smooth=None):
         """One frame with the pose kept here: the first call integrates at the initial pose (the identity: the
         volume frame is the first camera's);
         a later call tracks from the kept pose and integrates when the result is ok.  -> (T_vol_cam, egomotion result
@@ -2051,11 +2103,16 @@ class Volume:
         static: a Render of the objects that move.  The view is masked with it (mask_view, mode "remove") before it is
         tracked and integrated, the first frame too, and the mask's counters come back as result["mask"] (on the first
         call the result is {"mask": ...} instead of None).
+        smooth: a BilateralParams (default_bilateral_params).  KinFu's order: the frame is tracked on the filtered view
+        (bilateral_view) and integrated from the raw one, so the map keeps the sensor's detail and the tracker sees
+        smooth normals.  The first frame is only integrated, raw, and not filtered.  With static the mask comes first and
+        the filter sees the masked view.  The filter's counters come back as result["smooth"]; the filtered view is
+        closed before returning.
         self.last_integrate keeps the result dict of the frame's integration."""
         if static is not None:
             masked, mres = mask_view(view, static, "remove")
             try:
-                T, res = self.step(masked, params, follow, world)
+                T, res = self.step(masked, params, follow, world, smooth=smooth)
             finally:
                 masked.close()
             res = dict(res) if res is not None else {}
@@ -2065,7 +2122,15 @@ class Volume:
             self.last_integrate = self.integrate(view, self.T)
             self._started = True
             return self.T.copy(), None
-        T, res = self.track(view, self.T, params)
+        if smooth is not None:
+            filtered, sres = bilateral_view(view, params=smooth)
+            try:
+                T, res = self.track(filtered, self.T, params)
+            finally:
+                filtered.close()
+            res["smooth"] = sres
+        else:
+            T, res = self.track(view, self.T, params)
         if res["ok"]:
             self.T = T
             self.last_integrate = self.integrate(view, T)

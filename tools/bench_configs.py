@@ -37,6 +37,9 @@ configuration; these are not bench lines).  Needs a HIP device.
                                          db.arbitrate and db.explain over what verification found: who is verified, who
                                          each stage keeps and both stages' ms per frame; and ms_total of explain,
                                          arbitrate and render for 1 and 50 hypotheses, median of 20 calls each
+  python tools/bench_configs.py bilateral  the camera configuration's 640x480 stream: bilateral_view, Pyramid(view) as the
+                                         yardstick, and egomotion on the raw and on the filtered first pair, in the same
+                                         run; median of 20 calls each
   python tools/bench_configs.py normals  oslam_cloud_normals on the 100k-point bench scene and on the 500k-point slice's
                                          scene (points only), at radii of 2 and 4 times the median spacing: whole call,
                                          grid build and kernel, median of 20 calls after 5, and the neighbours visited and
@@ -1068,6 +1071,49 @@ def pyramid(calls=20):
     return out
 
 
+def bilateral(calls=20):
+    """The bilateral depth filter (oslam_view_bilateral) on frames 0 and 1 of the camera configuration's 640x480 stream:
+    the median of `calls` calls of bilateral_view at the default parameters and at radius 8, of Pyramid(view) (the
+    yardstick: another one-kernel call over the same image) and of egomotion on the raw and on the filtered pair, all in
+    the same run.  Host clock around calls that end in a host wait; every shape is warmed up first."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import camera_ref as E
+    import refine_ref
+    world = E.make_world(synth, 0)
+    traj = E.trajectory(synth, 0, frames=2)
+    cam = E.CAM
+    views = [ppf.View(E.render(synth, world, T), cam["fx"], cam["fy"], cam["cx"], cam["cy"], z_min=cam["z_min"],
+                      z_max=cam["z_max"], max_jump=E.MAX_JUMP) for T in traj]
+    filt = [ppf.bilateral_view(v)[0] for v in views]
+    ppf.bilateral_view(views[0], radius=8)[0].close()
+    ppf.Pyramid(views[0]).close()
+    ppf.egomotion(views[0], views[1])
+    ppf.egomotion(filt[0], filt[1])
+    t6, t6_lib, t8, make, ego_r, ego_f = [], [], [], [], [], []
+    for _ in range(calls):                                          # the five alternate, so that drift hits them alike
+        t = time.perf_counter(); f, r6 = ppf.bilateral_view(views[0]); t6.append(1e3 * (time.perf_counter() - t)); f.close()
+        t6_lib.append(r6["ms_total"])
+        t = time.perf_counter(); f, r8 = ppf.bilateral_view(views[0], radius=8); t8.append(1e3 * (time.perf_counter() - t)); f.close()
+        t = time.perf_counter(); q = ppf.Pyramid(views[0]); make.append(1e3 * (time.perf_counter() - t)); q.close()
+        t = time.perf_counter(); Tr, rr = ppf.egomotion(views[0], views[1]); ego_r.append(1e3 * (time.perf_counter() - t))
+        t = time.perf_counter(); Tf, rf = ppf.egomotion(filt[0], filt[1]); ego_f.append(1e3 * (time.perf_counter() - t))
+    G = E.truth(traj[0], traj[1])
+    out = {"config": "bilateral (oslam_view_bilateral): 640x480, the camera stream's first pair", "calls": calls,
+           "library": os.path.basename(ppf.LIB_PATH),
+           "bilateral_r6_ms_median": float(np.median(t6)), "bilateral_r6_ms_library_median": float(np.median(t6_lib)),
+           "bilateral_r8_ms_median": float(np.median(t8)), "pyramid_create_ms_median": float(np.median(make)),
+           "egomotion_raw_ms_median": float(np.median(ego_r)), "egomotion_filtered_ms_median": float(np.median(ego_f)),
+           "bilateral_r6": {"valid": r6["valid"], "taps": r6["taps"], "launches": r6["launches"]},
+           "bilateral_r8": {"valid": r8["valid"], "taps": r8["taps"], "launches": r8["launches"]},
+           "egomotion_raw": {"iterations": rr["iterations"], "overlap": round(rr["overlap"], 3),
+                             "rot_deg_trans_m": [round(x, 5) for x in refine_ref.pose_error(Tr, G)]},
+           "egomotion_filtered": {"iterations": rf["iterations"], "overlap": round(rf["overlap"], 3),
+                                  "rot_deg_trans_m": [round(x, 5) for x in refine_ref.pose_error(Tf, G)]}}
+    for v in filt + views:
+        v.close()
+    return out
+
+
 def _spacing(p, sample=500):
     """median distance to the nearest other point, from a seeded sample"""
     q = p.astype(np.float64)
@@ -1126,4 +1172,4 @@ if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "cfg3"
     print(json.dumps({"cfg2": cfg2, "cfg3": cfg3, "cfg3db": cfg3db, "cfg4": cfg4, "cfg5": cfg5, "planes": planes, "db50": db50,
                       "refine": refine, "verify": verify, "instances": instances, "arbitrate": arbitrate, "explain": explain, "track": track, "camera": camera,
-                      "fusion": fusion, "surface": surface, "mesh": mesh, "shift": shift, "reload": reload, "pyramid": pyramid, "normals": normals}[which]()), flush=True)
+                      "fusion": fusion, "surface": surface, "mesh": mesh, "shift": shift, "reload": reload, "pyramid": pyramid, "bilateral": bilateral, "normals": normals}[which]()), flush=True)
