@@ -969,7 +969,7 @@ int oslam_tracker_camera(const oslam_tracker *t, float T_world_cam[16]);
  *   k_tsdf_raycast.  Calls on volumes take turns (one lock, held to the end of the host wait).
  * The volume frame is fixed, the window of voxels the volume holds is not: oslam_volume_shift below moves it by whole
  *   voxels, and every call above reads the origin that goes with the window.
- * Out of scope: colour, the along-ray distance, masking tracked objects out of the integration, several GPUs;
+ * Out of scope: the along-ray distance, masking tracked objects out of the integration, several GPUs;
  *   oslam_tracker keeps taking T_cam from the caller. */
 typedef struct oslam_volume oslam_volume;
 typedef struct oslam_volume_params {
@@ -1444,7 +1444,7 @@ int oslam_volume_set_voxels(oslam_volume *vol, const int16_t *tsdf_q, const uint
  *   OSLAM_E_INVALID.  oslam_ply_read reads such a file's vertices back and skips the faces.
  * oslam_mc_table_row is a host-only tap on the compiled-in table for the tests: edges_out [15] gets 3 * *n_tri_out
  *   cube-edge numbers.
- * Out of scope: colour, merging or decimating triangles, dropping unreferenced vertices on the device, smoothing, a
+ * Out of scope: merging or decimating triangles, dropping unreferenced vertices on the device, smoothing, a
  *   min_weight for the normal's corners, one mesh of the live surface and of what oslam_volume_leaving handed over,
  *   several GPUs. */
 typedef struct oslam_mesh_params {
@@ -1510,7 +1510,7 @@ int oslam_mc_table_row(unsigned mc_case, uint8_t *edges_out, unsigned *n_tri_out
  *   T_vol_cam, shift_out or fp (of oslam_follow_params_default), fields that are not finite, lookahead < 0,
  *   threshold < 0, a granule outside 1..64, a T that is not rigid and the surface arguments oslam_volume_surface
  *   refuses are OSLAM_E_INVALID.  Every call takes the lock the other calls on volumes take.
- * Out of scope: merging what left with the live surface into one mesh, colour, several GPUs, any change to
+ * Out of scope: merging what left with the live surface into one mesh, several GPUs, any change to
  *   oslam_tracker.  Reloading what left when the window returns is the voxel store's, below (oslam_volume_shift_world). */
 typedef struct oslam_shift_result {
     int32_t offset[3];         /* the window's offset after the call, voxels */
@@ -1570,7 +1570,8 @@ int oslam_volume_follow(oslam_volume *vol, const float T_vol_cam[16], const osla
  *   k_tsdf_unpack; after the host wait write the leaving words into the store, clear the reloaded ones, free the bricks
  *   that became empty and swap the buffers.  A failure after the bricks were created removes them again.
  *   Cost.  launches = 2 (k_tsdf_pack_count and the scan of its counts) + 1 when something seen leaves (k_tsdf_pack_emit)
- *   + 1 (k_tsdf_shift) + 1 when something is reloaded (k_tsdf_unpack): 5 with records on both sides, 3 with none.  Host
+ *   + 1 (k_tsdf_shift) + 1 when something is reloaded (k_tsdf_unpack): 5 with records on both sides, 3 with none; one
+ *   more on a volume with colour, whose colours are shifted too (oslam_volume_integrate_colour below).  Host
  *   waits: one for the pack's total, which sizes the records' buffer and their copy; one for that copy when something
  *   seen leaves (the bricks are created from the records, before the shift is launched); one for k_tsdf_shift and
  *   k_tsdf_unpack.  The records' staging buffers are pinned, kept with the store and grown on demand: after the first
@@ -1705,6 +1706,80 @@ int oslam_mesh_normals(const float *xyz, size_t nv, size_t stride_bytes, const u
                        uint8_t *valid_out);
 int oslam_ply_read_mesh(const char *path, float **xyz_out, float **nrm_out, uint32_t **tri_out, size_t *nv_out,
                         size_t *nt_out);
+
+/* ---- colour next to the TSDF (KinFu's colour volume): a view can carry the colour image its sensor registered with the
+ * depth image, a volume a colour per voxel, and the fused colour comes back at the points of the surface and the mesh and
+ * as the picture of a view.  No stage that existed before reads colour: a view or a volume without it behaves bit for
+ * bit as before.  The restatement in numpy is tests/colour_ref.py; device and restatement agree bit for bit.
+ * A colour image on a view: rgb is [h] rows of w times 3 bytes R G B, row_stride_bytes apart (0 = 3 * w), registered
+ *   with the depth image (same camera, same size); valid is [h][w], 0 = the pixel has no colour, or NULL when every
+ *   pixel has one.  On the device a pixel is one word r | g << 8 | b << 16 | a << 24, a = 255 with colour, the whole
+ *   word 0 without.  A second call replaces the image, oslam_view_destroy frees it.  Views made by oslam_view_bilateral,
+ *   oslam_view_mask, oslam_pyramid_create and oslam_volume_raycast start without colour.  oslam_view_colour is the tap:
+ *   [h][w] words, OSLAM_E_INVALID on a view without colour.
+ * A colour buffer on a volume: oslam_volume_colour_enable allocates a second buffer of nx * ny * nz words, all zero
+ *   (computed in size_t; OSLAM_E_NOMEM changes nothing; enabling twice is OSLAM_E_INVALID).  A voxel's word is
+ *   r | g << 8 | b << 16 | wc << 24, wc = 0 reads as never coloured.  oslam_volume_reset zeroes the colours,
+ *   oslam_volume_set_voxels does not touch them, oslam_volume_destroy frees them.  oslam_volume_colour_words and
+ *   oslam_volume_set_colour_words are the taps, [nz][ny][nx].
+ * oslam_volume_integrate_colour is oslam_volume_integrate(vol, v, T_vol_cam) followed by the colour pass in the same
+ *   call (one more launch, res->launches = 2; the TSDF words are those of the plain call bit for bit).  c is the view that
+ *   carries the colour: it must have colour, and its size and fx, fy, cx, cy must have the float bits of v's (c == v is
+ *   the ordinary case; a masked or filtered v takes its colour from the raw view).  For voxel (i, j, k): the centre, p',
+ *   the pixel and z_o are oslam_volume_integrate's; the voxel is skipped unless p'z > 0, the pixel lies inside the image,
+ *   z_o > 0, sdf = z_o - p'z satisfies -band <= sdf <= band, and the pixel's a != 0.  Update in uint32 arithmetic per
+ *   channel: ch' = (ch * wc + pix + ((wc + 1) >> 1)) / (wc + 1), wc' = min(wc + 1, max_weight).  A skipped voxel is
+ *   neither read nor written; a voxel belongs to one thread; two calls give the same bits.  *coloured_out (may be NULL) =
+ *   the voxels updated.
+ * The colour at a volume-frame point P: c_a, b_a, f_a of the ray cast's trilinear read above; when all of
+ *   0 <= b_a <= n_a - 2 and all 8 corners have wc > 0, per channel the corner bytes as float, lerp(p, q, f) =
+ *   p * (1.0f - f) + q * f along x, then y, then z, floorf(value + 0.5f), clipped to 0..255.  Otherwise the voxel that
+ *   holds P, floorf((P_a - origin_a) * inv_voxel) per axis, range-checked in float, gives its colour when wc > 0.
+ *   Otherwise there is no colour: valid 0 and rgb 0.  A NaN or infinite coordinate has no colour and reads nothing.
+ * oslam_volume_colours: xyz = n points stride_bytes apart (0 = 12; a multiple of 4, at least 12), rgb_out [n][3],
+ *   valid_out [n], *n_valid_out (may be NULL) = the points with a colour; n == 0 is allowed.  It serves the points of
+ *   oslam_volume_surface, oslam_volume_mesh and oslam_volume_leaving; they go up from the host.
+ * oslam_volume_paint_view: for every pixel of v with z > 0 the vertex (dx * z, dy * z, z) with the ray cast's dx, dy,
+ *   P_x = ((M0*vx + M1*vy) + M2*vz) + M3 (y, z alike) with M = T_vol_cam, and the colour at P into v's colour image
+ *   (created when v has none; a = 255 or the word 0).  On a ray-cast view this is the map's picture from that pose.
+ *   *painted_out (may be NULL) = the pixels that got a colour.
+ * The moving window: oslam_volume_shift moves the colours with the TSDF words (the same kernel on the colour buffer into
+ *   a second spare buffer: oslam_shift_result.launches is 2 on a coloured volume; when a spare cannot be allocated
+ *   neither buffer moves).  oslam_volume_shift_world shifts the colours the same way (one launch more), but the voxel
+ *   store keeps no colour: voxels that leave lose theirs, and voxels that are reloaded come back with wc = 0 until they
+ *   are seen again.
+ * The PLY writers with colour write the vertex element of oslam_ply_write / oslam_ply_write_mesh plus property uchar
+ *   red, green, blue; oslam_ply_read and oslam_ply_read_mesh skip them.
+ * Arguments are checked before any device call: NULL pointers, a pose that is not rigid, parameters outside their
+ *   ranges, views and volumes on different devices, a c without colour or with another size or other intrinsics, and a
+ *   volume without colour where one is needed are OSLAM_E_INVALID, with nothing changed.
+ * Out of scope: colour in the voxel store, colour through bilateral, mask and pyramid views, a colour term in tracking,
+ *   verification or arbitration, keeping surface points in HBM between the extraction and oslam_volume_colours, several
+ *   GPUs. */
+typedef struct oslam_colour_params {
+    unsigned max_weight;      /* 1..255, default 8.  The mean is kept in 8 bits: at weight wc a pixel moves it only when it
+                                 differs by (wc + 1) / 2 levels or more, so a large weight freezes the colour */
+    float band;               /* metres; a voxel is coloured when |sdf| <= band.  0 (the default) = the volume's mu,
+                                 otherwise 0 < band <= mu */
+    int reserved[6];
+} oslam_colour_params;
+
+int oslam_view_set_colour(oslam_view *v, const uint8_t *rgb, size_t row_stride_bytes, const uint8_t *valid);
+int oslam_view_colour(oslam_view *v, uint32_t *rgba_out);
+int oslam_view_has_colour(const oslam_view *v);
+int oslam_colour_params_default(oslam_colour_params *p);
+/* cp may be NULL (defaults) */
+int oslam_volume_colour_enable(oslam_volume *vol, const oslam_colour_params *cp);
+int oslam_volume_colour_words(oslam_volume *vol, uint32_t *words_out);
+int oslam_volume_set_colour_words(oslam_volume *vol, const uint32_t *words);
+int oslam_volume_integrate_colour(oslam_volume *vol, const oslam_view *v, const oslam_view *c, const float T_vol_cam[16],
+                                  oslam_integrate_result *res, uint32_t *coloured_out);
+int oslam_volume_colours(oslam_volume *vol, const float *xyz, size_t n, size_t stride_bytes, uint8_t *rgb_out,
+                         uint8_t *valid_out, size_t *n_valid_out);
+int oslam_volume_paint_view(oslam_volume *vol, const float T_vol_cam[16], oslam_view *v, uint32_t *painted_out);
+int oslam_ply_write_colour(const char *path, const float *xyz, const float *nrm, const uint8_t *rgb, size_t n, int binary);
+int oslam_ply_write_mesh_colour(const char *path, const float *xyz, const float *nrm, const uint8_t *rgb, size_t nv,
+                                const uint32_t *tri, size_t nt, int binary);
 
 /* ---- parity taps (tests): values the reference materialises as arrays.
  * Scene::getHashKeys row r (scene.cu:49-54): keys_out[n] of reference point r,

@@ -90,6 +90,7 @@ struct oslam_view {
     float *d_z;
     float max_jump;                   /* of the camera: the normal map's depth-step limit */
     float *d_maps;                    /* vertex and normal map of the tracking stage (oslam_track.c), NULL until the first */
+    uint32_t *d_colour;               /* the registered colour image, [h][w] words (oslam_colour.c), NULL without one */
 };
 
 struct oslam_volume {
@@ -98,6 +99,8 @@ struct oslam_volume {
     oslam_volume_params p;
     int off[3];                       /* the window's offset in voxels */
     uint32_t *spare;                  /* the second buffer of oslam_volume_shift, NULL until the first shift */
+    oslamk_colour colour;             /* the colour buffer (oslam_colour.c); words NULL until oslam_volume_colour_enable */
+    uint32_t *colour_spare;           /* its second buffer for a shift, NULL until the first shift of a coloured volume */
 };
 
 struct oslam_pyramid {
@@ -314,6 +317,17 @@ int oslam_pyramid_check_params(const oslam_pyramid_params *pp, oslam_pyramid_par
 /* ---- the volume lock (oslam_volume.c, with its place in the lock order) ---- */
 void oslam_volume_lock(void);
 void oslam_volume_unlock(void);
+/* the bytes of one buffer of the volume, computed in size_t */
+static inline size_t oslam_volume_bytes(const oslam_volume_params *p)
+{
+    return (size_t)p->nx * (size_t)p->ny * (size_t)p->nz * sizeof(uint32_t);
+}
+/* oslam_volume_integrate after its argument checks; with c (a view with colour, checked against v by the caller) the
+ * colour pass follows in the same call: one more launch, *coloured = the voxels it updated (oslam_volume.c) */
+int oslam_volume_integrate_views(oslam_volume *vol, const oslam_view *v, const oslam_view *c, const float T_vol_cam[16],
+                                 oslam_integrate_result *res, uint32_t *coloured);
+/* gives back the view's colour image; called by oslam_view_destroy with the view's device bound (oslam_colour.c) */
+void oslam_colour_release_view(oslam_view *v);
 /* ---- surface and mesh extraction (oslam_surface.c) ---- */
 /* sp NULL = defaults; checks them as oslam_volume_surface does, *out = the parameters in force */
 int oslam_surface_check_params(const oslam_surface_params *sp, oslam_surface_params *out);

@@ -713,6 +713,28 @@ int oslamk_tsdf_pack_emit(const oslamk_volume *vol, const int shift[3], uint32_t
  * nx * ny * nz); a record whose lin is not below nx * ny * nz is skipped */
 int oslamk_tsdf_unpack(uint32_t *dst, int nx, int ny, int nz, const uint32_t *recs, uint32_t n_rec, void *stream);
 
+/* ---- the colour volume (oslam_colour.hip; semantics in include/oslam.h at oslam_volume_integrate_colour,
+ * oslam_volume_colours and oslam_volume_paint_view).  A voxel's colour word is r | g << 8 | b << 16 | wc << 24, an image's
+ * r | g << 8 | b << 16 | a << 24 with a = 255 or 0 ---- */
+/* the colour buffer of a volume: one word per voxel in the volume's order, and the rule's two parameters */
+typedef struct oslamk_colour {
+    uint32_t *words;
+    float band;                /* metres, 0 < band <= mu */
+    uint32_t max_weight;       /* 1..255 */
+} oslamk_colour;
+/* the colour pass of one frame: rgba = the colour image that goes with v's z image ([h][w] words); T12 = rows of the
+ * inverse of T_vol_cam; *count (zeroed by the caller) += voxels coloured */
+int oslamk_tsdf_colour(const oslamk_volume *vol, const oslamk_colour *col, const oslamk_view *v, const uint32_t *rgba,
+                       const float *T12, uint32_t *count, void *stream);
+/* out[t] = the image word of the colour at the volume-frame point xyz[t] (device [n][3], n > 0), 0 without a colour; words =
+ * the volume's colour buffer; *count (zeroed by the caller) += points with a colour */
+int oslamk_colour_points(const oslamk_volume *vol, const uint32_t *words, const float *xyz, uint32_t n, uint32_t *out,
+                         uint32_t *count, void *stream);
+/* out [h][w] = the image word of the colour at every pixel of v with z > 0, seen from T12 = rows of T_vol_cam, 0 elsewhere;
+ * *count (zeroed by the caller) += pixels with a colour */
+int oslamk_colour_view(const oslamk_volume *vol, const uint32_t *words, const oslamk_view *v, const float *T12, uint32_t *out,
+                       uint32_t *count, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -123,54 +123,89 @@ done:
     return rc;
 }
 
-/* the header up to the vertex properties, then (n_faces != (size_t)-1) the face element, then end_header */
-static void ply_header(FILE *f, int binary, size_t n, size_t n_faces)
+/* the header up to the vertex properties (with_rgb: red, green, blue behind the normal), then (n_faces != (size_t)-1) the
+ * face element, then end_header */
+static void ply_header(FILE *f, int binary, size_t n, size_t n_faces, int with_rgb)
 {
     fprintf(f, "ply\nformat %s 1.0\ncomment written by liboslam_hip\nelement vertex %zu\n"
                "property float x\nproperty float y\nproperty float z\n"
                "property float normal_x\nproperty float normal_y\nproperty float normal_z\n",
             binary ? "binary_little_endian" : "ascii", n);
+    if (with_rgb) fprintf(f, "property uchar red\nproperty uchar green\nproperty uchar blue\n");
     if (n_faces != (size_t)-1) fprintf(f, "element face %zu\nproperty list uchar int vertex_indices\n", n_faces);
     fprintf(f, "end_header\n");
 }
 
-static void ply_vertices(FILE *f, int binary, const float *xyz, const float *nrm, size_t n)
+/* rgb NULL: without colour */
+static void ply_vertices(FILE *f, int binary, const float *xyz, const float *nrm, const uint8_t *rgb, size_t n)
 {
     size_t v;
     for (v = 0; v < n; v++) {
         if (binary) {
             fwrite(xyz + 3 * v, sizeof(float), 3, f);
             fwrite(nrm + 3 * v, sizeof(float), 3, f);
+            if (rgb) fwrite(rgb + 3 * v, 1, 3, f);
         } else {
-            fprintf(f, "%.9g %.9g %.9g %.9g %.9g %.9g\n", xyz[3 * v], xyz[3 * v + 1], xyz[3 * v + 2], nrm[3 * v],
-                    nrm[3 * v + 1], nrm[3 * v + 2]);
+            fprintf(f, "%.9g %.9g %.9g %.9g %.9g %.9g", xyz[3 * v], xyz[3 * v + 1], xyz[3 * v + 2], nrm[3 * v], nrm[3 * v + 1],
+                    nrm[3 * v + 2]);
+            if (rgb) fprintf(f, " %u %u %u", (unsigned)rgb[3 * v], (unsigned)rgb[3 * v + 1], (unsigned)rgb[3 * v + 2]);
+            fputc('\n', f);
         }
     }
 }
 
-int oslam_ply_write(const char *path, const float *xyz, const float *nrm, size_t n, int binary)
+/* oslam_ply_write and oslam_ply_write_colour (rgb given) after their checks */
+static int write_cloud(const char *path, const float *xyz, const float *nrm, const uint8_t *rgb, size_t n, int binary)
 {
-    FILE *f;
-    if (!path || !xyz || !nrm) return OSLAM_E_INVALID;
-    f = fopen(path, "wb");
+    FILE *f = fopen(path, "wb");
     if (!f) return OSLAM_E_INVALID;
-    ply_header(f, binary, n, (size_t)-1);
-    ply_vertices(f, binary, xyz, nrm, n);
+    ply_header(f, binary, n, (size_t)-1, rgb != NULL);
+    ply_vertices(f, binary, xyz, nrm, rgb, n);
     return fclose(f) ? OSLAM_E_INVALID : OSLAM_OK;
 }
 
+int oslam_ply_write(const char *path, const float *xyz, const float *nrm, size_t n, int binary)
+{
+    if (!path || !xyz || !nrm) return OSLAM_E_INVALID;
+    return write_cloud(path, xyz, nrm, NULL, n, binary);
+}
+
+int oslam_ply_write_colour(const char *path, const float *xyz, const float *nrm, const uint8_t *rgb, size_t n, int binary)
+{
+    if (!path || !xyz || !nrm || !rgb) return OSLAM_E_INVALID;
+    return write_cloud(path, xyz, nrm, rgb, n, binary);
+}
+
+static int write_mesh(const char *path, const float *xyz, const float *nrm, const uint8_t *rgb, size_t nv, const uint32_t *tri,
+                      size_t nt, int binary);
+
 int oslam_ply_write_mesh(const char *path, const float *xyz, const float *nrm, size_t nv, const uint32_t *tri, size_t nt, int binary)
+{
+    if (!path || (nv && (!xyz || !nrm)) || (nt && !tri)) return OSLAM_E_INVALID;
+    return write_mesh(path, xyz, nrm, NULL, nv, tri, nt, binary);
+}
+
+int oslam_ply_write_mesh_colour(const char *path, const float *xyz, const float *nrm, const uint8_t *rgb, size_t nv,
+                                const uint32_t *tri, size_t nt, int binary)
+{
+    static const uint8_t none[3] = {0, 0, 0};
+    if (!path || (nv && (!xyz || !nrm || !rgb)) || (nt && !tri)) return OSLAM_E_INVALID;
+    return write_mesh(path, xyz, nrm, rgb ? rgb : none, nv, tri, nt, binary);
+}
+
+/* the two mesh writers (rgb given: with colour) after their NULL checks */
+static int write_mesh(const char *path, const float *xyz, const float *nrm, const uint8_t *rgb, size_t nv, const uint32_t *tri,
+                      size_t nt, int binary)
 {
     FILE *f;
     size_t t;
     int k;
-    if (!path || (nv && (!xyz || !nrm)) || (nt && !tri)) return OSLAM_E_INVALID;
     for (t = 0; t < 3 * nt; t++)
         if (tri[t] >= nv || tri[t] > 0x7fffffffu) return OSLAM_E_INVALID;      /* the list's entries are int */
     f = fopen(path, "wb");
     if (!f) return OSLAM_E_INVALID;
-    ply_header(f, binary, nv, nt);
-    ply_vertices(f, binary, xyz, nrm, nv);
+    ply_header(f, binary, nv, nt, rgb != NULL);
+    ply_vertices(f, binary, xyz, nrm, rgb, nv);
     for (t = 0; t < nt; t++) {
         if (binary) {
             const unsigned char three = 3;

@@ -95,6 +95,7 @@ int oslam_view_destroy(oslam_view *v)
     /* every call that read the image ended with a synchronisation of its stream */
     if (hipSetDevice(v->dev) == hipSuccess) {
         oslam_track_release_maps(v);
+        oslam_colour_release_view(v);
         (void)hipFree(v->d_z);
     }
     free(v);

@@ -9,7 +9,9 @@
  * oslam_volume_shift_world makes it through a voxel store that keeps what leaves and gives back what returns (the store:
  * oslam_world.c; kernels: oslam_reload.hip).  The extraction of
  * the fused volume, or of what a shift loses, as a cloud or a triangle list is oslam_surface.c (kernels: oslam_surface.hip
- * and oslam_mesh.hip).  The limits of a volume's sides and of a shift are oslam_kernels.h's.
+ * and oslam_mesh.hip).  The limits of a volume's sides and of a shift are oslam_kernels.h's.  A volume with colour
+ * (oslam_colour.c) gets its colour pass from the integration's body here, in the same call, and its colour buffer moves
+ * with every shift.
  */
 #include <math.h>
 #include <pthread.h>
@@ -48,11 +50,6 @@ static int check_params(const oslam_volume_params *p)
     return OSLAM_OK;
 }
 
-static size_t volume_bytes(const oslam_volume_params *p)
-{
-    return (size_t)p->nx * (size_t)p->ny * (size_t)p->nz * sizeof(uint32_t);
-}
-
 int oslam_volume_create(const oslam_volume_params *p, int dev, oslam_volume **out)
 {
     int rc, devsel;
@@ -68,8 +65,8 @@ int oslam_volume_create(const oslam_volume_params *p, int dev, oslam_volume **ou
     vol->dev = devsel;
     vol->p = *p;
     /* the volume lives as long as the handle: its own block, not one of the kept scratch blocks */
-    HIPCHK(hipMalloc((void **)&vol->k.words, volume_bytes(p)));
-    HIPCHK(hipMemsetAsync(vol->k.words, 0, volume_bytes(p), (hipStream_t)oslam_stream()));
+    HIPCHK(hipMalloc((void **)&vol->k.words, oslam_volume_bytes(p)));
+    HIPCHK(hipMemsetAsync(vol->k.words, 0, oslam_volume_bytes(p), (hipStream_t)oslam_stream()));
     HIPCHK(hipStreamSynchronize((hipStream_t)oslam_stream()));
     vol->k.nx = (int)p->nx;
     vol->k.ny = (int)p->ny;
@@ -97,6 +94,8 @@ int oslam_volume_destroy(oslam_volume *vol)
     if (hipSetDevice(vol->dev) == hipSuccess) {
         (void)hipFree(vol->k.words);
         if (vol->spare) (void)hipFree(vol->spare);
+        if (vol->colour.words) (void)hipFree(vol->colour.words);
+        if (vol->colour_spare) (void)hipFree(vol->colour_spare);
     }
     pthread_mutex_unlock(&g_vol_mu);
     free(vol);
@@ -123,7 +122,8 @@ int oslam_volume_reset(oslam_volume *vol)
     if (!vol) return fail(OSLAM_E_INVALID, "volume is NULL");
     if (hipSetDevice(vol->dev) != hipSuccess) return fail(OSLAM_E_DEVICE, "hipSetDevice failed");
     pthread_mutex_lock(&g_vol_mu);
-    HIPCHK(hipMemsetAsync(vol->k.words, 0, volume_bytes(&vol->p), (hipStream_t)oslam_stream()));
+    HIPCHK(hipMemsetAsync(vol->k.words, 0, oslam_volume_bytes(&vol->p), (hipStream_t)oslam_stream()));
+    if (vol->colour.words) HIPCHK(hipMemsetAsync(vol->colour.words, 0, oslam_volume_bytes(&vol->p), (hipStream_t)oslam_stream()));
     HIPCHK(hipStreamSynchronize((hipStream_t)oslam_stream()));
     memset(vol->off, 0, sizeof vol->off);
     window_origin(vol, vol->off, vol->k.origin);
@@ -134,16 +134,23 @@ done:
 
 int oslam_volume_integrate(oslam_volume *vol, const oslam_view *v, const float T_vol_cam[16], oslam_integrate_result *res)
 {
-    int rc, a;
-    const double t0 = now_ms();
-    double inv_d[12];
-    float inv[12];
-    uint32_t *d_cnt = NULL, cnt = 0;
-    void *stream = oslam_stream();
+    int rc;
     if (!vol || !v || !T_vol_cam) return fail(OSLAM_E_INVALID, "NULL argument");
     rc = oslam_refine_check_rigid(T_vol_cam);
     if (rc != OSLAM_OK) return rc;
     if (vol->dev != v->dev) return fail(OSLAM_E_INVALID, "volume and view live on different devices");
+    return oslam_volume_integrate_views(vol, v, NULL, T_vol_cam, res, NULL);
+}
+
+int oslam_volume_integrate_views(oslam_volume *vol, const oslam_view *v, const oslam_view *c, const float T_vol_cam[16],
+                                 oslam_integrate_result *res, uint32_t *coloured)
+{
+    int rc = OSLAM_OK, a;
+    const double t0 = now_ms();
+    double inv_d[12];
+    float inv[12];
+    uint32_t *d_cnt = NULL, cnt[2] = {0, 0};
+    void *stream = oslam_stream();
     if (res) memset(res, 0, sizeof *res);
     oslam_rigid_inverse(T_vol_cam, inv_d);
     for (a = 0; a < 12; a++) inv[a] = (float)inv_d[a];
@@ -151,17 +158,19 @@ int oslam_volume_integrate(oslam_volume *vol, const oslam_view *v, const float T
     pthread_mutex_lock(&g_vol_mu);
     KCHK(oslam_counters_open(&d_cnt, 0, stream));
     KCHK(oslamk_tsdf_integrate(&vol->k, &v->k, inv, d_cnt, stream));
-    HIPCHK(hipMemcpyAsync(&cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    if (c) KCHK(oslamk_tsdf_colour(&vol->k, &vol->colour, &v->k, c->d_colour, inv, d_cnt + 1, stream));
+    HIPCHK(hipMemcpyAsync(cnt, d_cnt, sizeof(uint32_t) * (c ? 2 : 1), hipMemcpyDeviceToHost, (hipStream_t)stream));
     HIPCHK(hipStreamSynchronize((hipStream_t)stream));
 done:
     if (rc != OSLAM_OK) (void)hipStreamSynchronize((hipStream_t)stream);
     pthread_mutex_unlock(&g_vol_mu);
     if (d_cnt) oslam_dev_free(d_cnt);
     if (rc == OSLAM_OK && res) {
-        res->updated = cnt;
-        res->launches = 1;
+        res->updated = cnt[0];
+        res->launches = c ? 2 : 1;
         res->ms_total = (float)(now_ms() - t0);
     }
+    if (rc == OSLAM_OK && coloured) *coloured = cnt[1];
     return rc;
 }
 
@@ -383,6 +392,39 @@ done:
 }
 
 /* ---- the shifting window (include/oslam.h at oslam_volume_shift; kernel: oslam_shift.hip) ---- */
+/* the second buffers a shift needs, with g_vol_mu held and the volume's device bound: the TSDF's and, on a coloured
+ * volume, the colours'.  Both exist afterwards or the call fails before anything moved */
+static int shift_spares(oslam_volume *vol)
+{
+    uint32_t **want[2] = {&vol->spare, vol->colour.words ? &vol->colour_spare : NULL};
+    int b;
+    for (b = 0; b < 2; b++) {
+        if (!want[b] || *want[b]) continue;
+        if (hipMalloc((void **)want[b], oslam_volume_bytes(&vol->p)) != hipSuccess) {
+            (void)hipGetLastError();
+            *want[b] = NULL;
+            return fail(OSLAM_E_NOMEM, "no device memory for the second buffer of the shift");
+        }
+    }
+    return OSLAM_OK;
+}
+
+/* the colours of a coloured volume moved as k_tsdf_shift moves words, into colour_spare: launched behind the TSDF's shift;
+ * scratch = a zeroed counter for the kernel's count, which nobody reads.  The caller swaps after its wait */
+static int shift_colours(const oslam_volume *vol, const int shift[3], uint32_t *scratch, void *stream)
+{
+    oslamk_volume k = vol->k;
+    k.words = vol->colour.words;
+    return oslamk_tsdf_shift(&k, vol->colour_spare, shift, scratch, stream);
+}
+
+static void swap_colours(oslam_volume *vol)
+{
+    uint32_t *t = vol->colour.words;
+    vol->colour.words = vol->colour_spare;
+    vol->colour_spare = t;
+}
+
 int oslam_volume_shift(oslam_volume *vol, const int shift[3], oslam_shift_result *res)
 {
     int rc = OSLAM_OK, a, off[3];
@@ -400,26 +442,23 @@ int oslam_volume_shift(oslam_volume *vol, const int shift[3], oslam_shift_result
         goto done;
     }
     if (hipSetDevice(vol->dev) != hipSuccess) { rc = fail(OSLAM_E_DEVICE, "hipSetDevice failed"); goto done; }
+    rc = shift_spares(vol);
+    if (rc != OSLAM_OK) goto done;
     spare = vol->spare;
-    if (!spare && hipMalloc((void **)&spare, volume_bytes(&vol->p)) != hipSuccess) {
-        (void)hipGetLastError();
-        spare = NULL;
-        rc = fail(OSLAM_E_NOMEM, "no device memory for the second buffer of the shift");
-        goto done;
-    }
-    vol->spare = spare;
     KCHK(oslam_counters_open(&d_cnt, 0, stream));
     KCHK(oslamk_tsdf_shift(&vol->k, spare, shift, d_cnt, stream));
+    if (vol->colour.words) KCHK(shift_colours(vol, shift, d_cnt + 1, stream));
     HIPCHK(hipMemcpyAsync(&kept, d_cnt, sizeof kept, hipMemcpyDeviceToHost, (hipStream_t)stream));
     HIPCHK(hipStreamSynchronize((hipStream_t)stream));
     vol->spare = vol->k.words;
     vol->k.words = spare;
+    if (vol->colour.words) swap_colours(vol);
     memcpy(vol->off, off, sizeof off);
     window_origin(vol, vol->off, vol->k.origin);
     if (res) {
         memcpy(res->offset, off, sizeof off);
         res->kept = kept;
-        res->launches = 1;
+        res->launches = vol->colour.words ? 2 : 1;
     }
 done:
     if (rc != OSLAM_OK && d_cnt) (void)hipStreamSynchronize((hipStream_t)stream);
@@ -569,14 +608,9 @@ int oslam_volume_shift_world(oslam_volume *vol, oslam_world *w, const int shift[
         goto done;
     }
     if (hipSetDevice(vol->dev) != hipSuccess) { rc = fail(OSLAM_E_DEVICE, "hipSetDevice failed"); goto done; }
+    rc = shift_spares(vol);
+    if (rc != OSLAM_OK) goto done;
     spare = vol->spare;
-    if (!spare && hipMalloc((void **)&spare, volume_bytes(&vol->p)) != hipSuccess) {
-        (void)hipGetLastError();
-        spare = NULL;
-        rc = fail(OSLAM_E_NOMEM, "no device memory for the second buffer of the shift");
-        goto done;
-    }
-    vol->spare = spare;
     /* 1. pack what leaves and copy it down */
     rc = pack_leaving(vol, shift, (size_t)-1, &d_cnt, &d_out, &n_out, &launches);
     if (rc != OSLAM_OK) goto done;
@@ -621,6 +655,10 @@ int oslam_volume_shift_world(oslam_volume *vol, oslam_world *w, const int shift[
     KCHK(oslam_counters_open(&d_kept, 0, stream));
     KCHK(oslamk_tsdf_shift(&vol->k, spare, shift, d_kept, stream));
     launches++;
+    if (vol->colour.words) {                                            /* the store keeps no colour: what is reloaded has wc = 0 */
+        KCHK(shift_colours(vol, shift, d_kept + 1, stream));
+        launches++;
+    }
     if (n_in) {
         KCHK(oslamk_tsdf_unpack(spare, vol->k.nx, vol->k.ny, vol->k.nz, d_in, (uint32_t)n_in, stream));
         launches++;
@@ -636,6 +674,7 @@ int oslam_volume_shift_world(oslam_volume *vol, oslam_world *w, const int shift[
     reserved = 0;
     vol->spare = vol->k.words;
     vol->k.words = spare;
+    if (vol->colour.words) swap_colours(vol);
     memcpy(vol->off, off, sizeof off);
     window_origin(vol, vol->off, vol->k.origin);
     if (res) {

@@ -256,6 +256,10 @@ class IntegrateResult(C.Structure):
         return {"updated": int(self.updated), "launches": int(self.launches), "ms_total": float(self.ms_total)}
 
 
+class ColourParams(C.Structure):
+    _fields_ = [("max_weight", C.c_uint), ("band", C.c_float), ("reserved", C.c_int * 6)]
+
+
 class RaycastResult(C.Structure):
     _fields_ = [("hits", C.c_uint32), ("normals", C.c_uint32), ("launches", C.c_uint32), ("ms_total", C.c_float)]
 
@@ -496,6 +500,18 @@ _SIGNATURES = {
     "oslam_cloud_normal_moments": (_i, [_vp, _sz, _sz, C.POINTER(NormalsParams), _i, _vp]),
     "oslam_mesh_normals": (_i, [_vp, _sz, _sz, _vp, _sz, _vp, _vp]),
     "oslam_ply_read_mesh": (_i, [C.c_char_p, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_sz), C.POINTER(_sz)]),
+    "oslam_view_set_colour": (_i, [_vp, _vp, _sz, _vp]),
+    "oslam_view_colour": (_i, [_vp, _vp]),
+    "oslam_view_has_colour": (_i, [_vp]),
+    "oslam_colour_params_default": (_i, [C.POINTER(ColourParams)]),
+    "oslam_volume_colour_enable": (_i, [_vp, C.POINTER(ColourParams)]),
+    "oslam_volume_colour_words": (_i, [_vp, _vp]),
+    "oslam_volume_set_colour_words": (_i, [_vp, _vp]),
+    "oslam_volume_integrate_colour": (_i, [_vp, _vp, _vp, _vp, C.POINTER(IntegrateResult), C.POINTER(C.c_uint32)]),
+    "oslam_volume_colours": (_i, [_vp, _vp, _sz, _sz, _vp, _vp, C.POINTER(_sz)]),
+    "oslam_volume_paint_view": (_i, [_vp, _vp, _vp, C.POINTER(C.c_uint32)]),
+    "oslam_ply_write_colour": (_i, [C.c_char_p, _vp, _vp, _vp, _sz, _i]),
+    "oslam_ply_write_mesh_colour": (_i, [C.c_char_p, _vp, _vp, _vp, _sz, _vp, _sz, _i]),
     "oslam_scene_keys": (_i, [_vp, _sz, _vp]),
     "oslam_model_keys": (_i, [_vp, _sz, _vp]),
     "oslam_model_bucket": (_i, [_vp, C.c_uint32, _vp, _sz, C.POINTER(_sz)]),
@@ -1631,23 +1647,40 @@ def ply_read_mesh(path):
     return pts, nrm, tri
 
 
-def ply_write(path, points, normals, binary=True):
+def _rgb_rows(rgb, n):
+    c = np.ascontiguousarray(rgb, np.uint8).reshape(-1, 3)
+    if len(c) != n:
+        raise ValueError("rgb must be [n,3] like the points")
+    return c
+
+
+def ply_write(path, points, normals, binary=True, rgb=None):
+    """rgb: uint8 [n,3]; the vertices then carry red, green, blue (oslam_ply_write_colour)."""
     p = np.ascontiguousarray(points, np.float32)
     q = np.ascontiguousarray(normals, np.float32)
-    rc = lib().oslam_ply_write(os.fsencode(path), _p(p), _p(q), len(p), int(binary))
+    if rgb is not None:
+        c = _rgb_rows(rgb, len(p))
+        rc = lib().oslam_ply_write_colour(os.fsencode(path), _p(p), _p(q), _p(c), len(p), int(binary))
+    else:
+        rc = lib().oslam_ply_write(os.fsencode(path), _p(p), _p(q), len(p), int(binary))
     if rc != OSLAM_OK:
         raise OslamError(rc, "cannot write PLY file %s" % path)
 
 
-def ply_write_mesh(path, points, normals, triangles, binary=True):
+def ply_write_mesh(path, points, normals, triangles, binary=True, rgb=None):
     """A triangle mesh as a PLY file (oslam_ply_write_mesh): points [nv,3], normals [nv,3] or None (zeros are written),
-    triangles [nt,3] vertex indices."""
+    triangles [nt,3] vertex indices.  rgb: uint8 [nv,3]; the vertices then carry red, green, blue
+    (oslam_ply_write_mesh_colour)."""
     p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
     q = np.zeros_like(p) if normals is None else np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
     t = np.ascontiguousarray(triangles, np.uint32).reshape(-1, 3)
     if q.shape != p.shape:
         raise ValueError("points and normals must have the same shape")
-    rc = lib().oslam_ply_write_mesh(os.fsencode(path), _p(p), _p(q), len(p), _p(t), len(t), int(binary))
+    if rgb is not None:
+        c = _rgb_rows(rgb, len(p))
+        rc = lib().oslam_ply_write_mesh_colour(os.fsencode(path), _p(p), _p(q), _p(c), len(p), _p(t), len(t), int(binary))
+    else:
+        rc = lib().oslam_ply_write_mesh(os.fsencode(path), _p(p), _p(q), len(p), _p(t), len(t), int(binary))
     if rc != OSLAM_OK:
         raise OslamError(rc, "cannot write PLY file %s" % path)
 
@@ -1701,6 +1734,28 @@ class View:
         self.width, self.height = d.shape[1], d.shape[0]
         _check(lib().oslam_view_create(_p(d), int(d.dtype == np.uint16), self.width, self.height, C.byref(cam), int(dev),
                                        C.byref(self._h)))
+
+    def set_colour(self, rgb, valid=None):
+        """The colour image registered with the depth image (oslam_view_set_colour): rgb uint8 [h,w,3]; valid [h,w],
+        0 = the pixel has no colour, None = every pixel has one.  A second call replaces the image."""
+        c = np.ascontiguousarray(rgb, np.uint8)
+        if c.shape != (self.height, self.width, 3):
+            raise ValueError("rgb must be [h,w,3] = %r" % ((self.height, self.width, 3),))
+        m = None
+        if valid is not None:
+            m = np.ascontiguousarray(np.asarray(valid) != 0, np.uint8)
+            if m.shape != (self.height, self.width):
+                raise ValueError("valid must be [h,w]")
+        _check(lib().oslam_view_set_colour(self._h, _p(c), 0, _p(m) if m is not None else None))
+
+    def colour(self):
+        """The view's colour image as a test tap (oslam_view_colour): uint32 [h,w], r | g << 8 | b << 16 | a << 24."""
+        out = np.zeros((self.height, self.width), np.uint32)
+        _check(lib().oslam_view_colour(self._h, _p(out)))
+        return out
+
+    def has_colour(self):
+        return bool(lib().oslam_view_has_colour(self._h))
 
     def close(self):
         if self._h:
@@ -1947,6 +2002,17 @@ def default_volume_params(**kw):
     return p
 
 
+def default_colour_params(**kw):
+    """oslam_colour_params_default, then the fields given as keywords."""
+    p = ColourParams()
+    _check(lib().oslam_colour_params_default(C.byref(p)))
+    for k, v in kw.items():
+        if not hasattr(p, k) or k == "reserved":
+            raise TypeError("unknown colour parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
 def default_surface_params(**kw):
     """oslam_surface_params_default, then the fields given as keywords."""
     p = SurfaceParams()
@@ -2056,10 +2122,50 @@ class Volume:
         self.last_integrate = None      # the integrate result of the last step() that integrated
         _check(lib().oslam_volume_create(C.byref(p), int(dev), C.byref(self._h)))
 
-    def integrate(self, view, T_vol_cam):
+    def integrate(self, view, T_vol_cam, colour=None):
+        """colour: the View that carries the frame's colour image (view itself, or the raw view of a masked or filtered
+        one); the volume needs enable_colour().  The result then has "coloured" too (oslam_volume_integrate_colour)."""
         res = IntegrateResult()
+        if colour is not None:
+            n = C.c_uint32(0)
+            _check(lib().oslam_volume_integrate_colour(self._h, view._h, colour._h, _p(_pose16(T_vol_cam)), C.byref(res),
+                                                       C.byref(n)))
+            return dict(res.asdict(), coloured=int(n.value))
         _check(lib().oslam_volume_integrate(self._h, view._h, _p(_pose16(T_vol_cam)), C.byref(res)))
         return res.asdict()
+
+    def enable_colour(self, **fields):
+        """A colour per voxel next to the TSDF (oslam_volume_colour_enable); fields: default_colour_params'."""
+        p = default_colour_params(**fields)
+        _check(lib().oslam_volume_colour_enable(self._h, C.byref(p)))
+        self.colour_params = p
+
+    def colour_words(self):
+        """The colour buffer as a test tap: uint32 [nz,ny,nx], r | g << 8 | b << 16 | wc << 24."""
+        out = np.zeros((self.params.nz, self.params.ny, self.params.nx), np.uint32)
+        _check(lib().oslam_volume_colour_words(self._h, _p(out)))
+        return out
+
+    def set_colour_words(self, words):
+        w = np.ascontiguousarray(words, np.uint32)
+        if w.shape != (self.params.nz, self.params.ny, self.params.nx):
+            raise ValueError("words must be [nz,ny,nx]")
+        _check(lib().oslam_volume_set_colour_words(self._h, _p(w)))
+
+    def colours(self, points):
+        """The fused colour at volume-frame points [n,3] (oslam_volume_colours): -> (rgb uint8 [n,3], valid bool [n])."""
+        p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        rgb, valid, n = np.zeros((len(p), 3), np.uint8), np.zeros(len(p), np.uint8), C.c_size_t(0)
+        _check(lib().oslam_volume_colours(self._h, _p(p), len(p), 0, _p(rgb), _p(valid), C.byref(n)))
+        assert n.value == int(valid.sum())
+        return rgb, valid.astype(bool)
+
+    def paint(self, view, T_vol_cam):
+        """The fused colour at every pixel of view seen from T_vol_cam, into the view's colour image
+        (oslam_volume_paint_view; View.colour() reads it): -> the number of pixels painted."""
+        n = C.c_uint32(0)
+        _check(lib().oslam_volume_paint_view(self._h, _p(_pose16(T_vol_cam)), view._h, C.byref(n)))
+        return int(n.value)
 
     def raycast(self, T_vol_cam, fx, fy, cx, cy, width, height, z_min=0.1, z_max=10.0, max_jump=0.05):
         """-> (View, result dict)"""
@@ -2091,7 +2197,7 @@ class Volume:
                                                 C.byref(res)))
         return To.reshape(4, 4), res.asdict()
 
-    def step(self, view, params=None, follow=None, world=None, static=None, smooth=None):
+    def step(self, view, params=None, follow=None, world=None, static=None, smooth=None, colour=None):
         """One frame with the pose kept here: the first call integrates at the initial pose (the identity: the
         volume frame is the first camera's);
         a later call tracks from the kept pose and integrates when the result is ok.  -> (T_vol_cam, egomotion result
@@ -2108,18 +2214,21 @@ class Volume:
         smooth normals.  The first frame is only integrated, raw, and not filtered.  With static the mask comes first and
         the filter sees the masked view.  The filter's counters come back as result["smooth"]; the filtered view is
         closed before returning.
+        colour: the View that carries the frame's colour image, usually view itself.  Every integration of the step then
+        fuses it too (integrate(..., colour=)); with static and smooth the z comes from the masked view and the colour
+        from this raw one.  With world the reloaded voxels come back without colour.
         self.last_integrate keeps the result dict of the frame's integration."""
         if static is not None:
             masked, mres = mask_view(view, static, "remove")
             try:
-                T, res = self.step(masked, params, follow, world, smooth=smooth)
+                T, res = self.step(masked, params, follow, world, smooth=smooth, colour=colour)
             finally:
                 masked.close()
             res = dict(res) if res is not None else {}
             res["mask"] = mres
             return T, res
         if not self._started:
-            self.last_integrate = self.integrate(view, self.T)
+            self.last_integrate = self.integrate(view, self.T, colour)
             self._started = True
             return self.T.copy(), None
         if smooth is not None:
@@ -2133,7 +2242,7 @@ class Volume:
             T, res = self.track(view, self.T, params)
         if res["ok"]:
             self.T = T
-            self.last_integrate = self.integrate(view, T)
+            self.last_integrate = self.integrate(view, T, colour)
             if follow is not None:
                 s = self.follow(T, follow)
                 if any(s) and world is not None:
@@ -2201,10 +2310,12 @@ class Volume:
             raise ValueError("q and w must both be [nz,ny,nx] = %r" % (shape,))
         _check(lib().oslam_volume_set_voxels(self._h, _p(q), _p(w)))
 
-    def surface(self, min_weight=1):
+    def surface(self, min_weight=1, colour=False):
         """Every zero crossing of the fused TSDF along a voxel edge as a point with its outward normal, in the volume
-        frame and in voxel order (oslam_volume_surface): -> (points [n,3], normals [n,3], result dict)."""
-        return self._points(lib().oslam_volume_surface, (self._h,), min_weight)
+        frame and in voxel order (oslam_volume_surface): -> (points [n,3], normals [n,3], result dict); with colour=True
+        -> (points, normals, result dict, rgb uint8 [n,3], valid bool [n]) with colours() of the points."""
+        out = self._points(lib().oslam_volume_surface, (self._h,), min_weight)
+        return out + self.colours(out[0]) if colour else out
 
     @staticmethod
     def _points(call, head, min_weight):
@@ -2218,10 +2329,11 @@ class Volume:
             _check(call(*head, C.byref(sp), _p(po), _p(no), n.value, C.byref(n), C.byref(res)))
         return po, no, res.asdict()
 
-    def mesh(self, min_weight=1, normals=True):
+    def mesh(self, min_weight=1, normals=True, colour=False):
         """The fused surface as a triangle mesh by marching cubes, in the volume frame (oslam_volume_mesh): -> (vertices
         [nv,3], normals [nv,3] with (0, 0, 0) where a vertex has none, or None with normals=False, triangles uint32
-        [nt,3], result dict).  The vertices are surface()'s crossings, in its order."""
+        [nt,3], result dict).  The vertices are surface()'s crossings, in its order.  With colour=True rgb uint8 [nv,3] and
+        valid bool [nv], colours() of the vertices, follow the result dict."""
         mp = default_mesh_params(min_weight=min_weight)
         nv, nt, res = C.c_size_t(0), C.c_size_t(0), MeshResult()
         _check(lib().oslam_volume_mesh(self._h, C.byref(mp), None, None, 0, None, 0, C.byref(nv), C.byref(nt), C.byref(res)))
@@ -2230,7 +2342,8 @@ class Volume:
         if nv.value:
             _check(lib().oslam_volume_mesh(self._h, C.byref(mp), _p(xyz), _p(nrm) if normals else None, nv.value, _p(tri),
                                            nt.value, C.byref(nv), C.byref(nt), C.byref(res)))
-        return xyz, nrm, tri, res.asdict()
+        out = (xyz, nrm, tri, res.asdict())
+        return out + self.colours(xyz) if colour else out
 
     def reset(self):
         _check(lib().oslam_volume_reset(self._h))

@@ -44,6 +44,11 @@ configuration; these are not bench lines).  Needs a HIP device.
                                          scene (points only), at radii of 2 and 4 times the median spacing: whole call,
                                          grid build and kernel, median of 20 calls after 5, and the neighbours visited and
                                          accepted per second of kernel time
+  python tools/bench_configs.py colour   the fusion configuration's 256^3 volume and 640x480 stream with a colour image per
+                                         frame: integrate without and with colour, paint on a ray-cast view, colours on
+                                         the surface's points, median of 20 calls each, Volume.step in frames/s without
+                                         and with colour, and the coloured mesh of the calibration room written as PLY
+                                         with its colour error
 One JSON line each."""
 import importlib, json, os, sys, time
 
@@ -825,6 +830,99 @@ def fusion(calls=20):
     return out
 
 
+def colour(calls=20):
+    """Colour next to the TSDF (oslam_volume_integrate_colour, oslam_volume_paint_view, oslam_volume_colours) on the fusion
+    configuration's volume and stream; every frame carries the colour image of tests/colour_world.py.  The yardstick of
+    the colour pass is the plain integrate of the same volume in the same run: the pass walks the same voxels, loads and
+    stores one word per voxel inside its band and does integer arithmetic on it.  Then the calibration room of
+    tests/test_colour_host.py (320x240, 5 cm voxels, ten frames at their true poses) as a coloured mesh, written with
+    ply_write_mesh(..., rgb=), and its colour error against the colour function."""
+    import tempfile
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import camera_ref as E
+    import colour_world as W
+    import volume_ref as V
+    world = E.make_world(synth, 0)
+    rgb = W.world_colours(world, 0)
+    sweep = E.trajectory(synth, 0, frames=10)
+    order = list(range(10)) + list(range(8, -1, -1))
+    cam = E.CAM
+    rendered = []
+    for T in sweep:
+        depth, img, ok = W.render(synth, world, rgb, T)
+        v = ppf.View(depth, cam["fx"], cam["fy"], cam["cx"], cam["cy"], z_min=cam["z_min"], z_max=cam["z_max"], max_jump=E.MAX_JUMP)
+        v.set_colour(img, ok)
+        rendered.append(v)
+    spec = dict(nx=256, ny=256, nz=256, voxel=0.036, origin=[-2.9, -4.3, 0.3], mu=0.288)
+    vol = ppf.Volume(**spec)
+    vol.enable_colour()
+    eye = np.eye(4, dtype=np.float32)
+    vol.integrate(rendered[0], eye)
+    vol.integrate(rendered[0], eye, colour=rendered[0])
+    plain, both, r = [], [], None
+    for _ in range(calls):                                       # alternately, so that both see the same machine
+        plain.append(vol.integrate(rendered[0], eye)["ms_total"])
+        r = vol.integrate(rendered[0], eye, colour=rendered[0])
+        both.append(r["ms_total"])
+    rv, rres = vol.raycast(eye, cam["fx"], cam["fy"], cam["cx"], cam["cy"], 640, 480, z_min=cam["z_min"], z_max=cam["z_max"],
+                           max_jump=E.MAX_JUMP)
+    paint, painted = [], 0
+    for _ in range(calls + 1):
+        t = time.perf_counter()
+        painted = vol.paint(rv, eye)
+        paint.append((time.perf_counter() - t) * 1e3)
+    rv.close()
+    xyz, _, sres = vol.surface()
+    cols, valid = [], None
+    for _ in range(calls + 1):
+        t = time.perf_counter()
+        _, valid = vol.colours(xyz)
+        cols.append((time.perf_counter() - t) * 1e3)
+    fps = {}
+    for name, kw in (("plain", lambda k: {}), ("colour", lambda k: dict(colour=rendered[k]))):
+        for _ in range(2):                                        # the first pass warms up
+            vol.reset()
+            t = time.perf_counter()
+            steps = [vol.step(rendered[k], **kw(k)) for k in order]
+            fps[name] = len(order) / (time.perf_counter() - t)
+        fps[name + "_ok"] = [None if r_ is None else r_["ok"] for _, r_ in steps]
+    ms_p, ms_b = float(np.median(plain)), float(np.median(both))
+    out = {"config": "colour (oslam_volume_integrate_colour): the fusion configuration's 256^3 volume and 640x480 stream with colour",
+           "volume": spec, "colour_params": {"max_weight": vol.colour_params.max_weight, "band": vol.colour_params.band},
+           "integrate_ms_median": ms_p, "integrate_colour_ms_median": ms_b, "colour_pass_ms": ms_b - ms_p,
+           "colour_pass_over_integrate": (ms_b - ms_p) / ms_p, "voxels_updated": r["updated"], "voxels_coloured": r["coloured"],
+           "paint_ms_median": float(np.median(paint[1:])), "paint_pixels": painted, "raycast_hits": rres["hits"],
+           "colours_ms_median": float(np.median(cols[1:])), "colours_points": len(xyz), "colours_valid": int(valid.sum()),
+           "step_frames_per_s": fps["plain"], "step_colour_frames_per_s": fps["colour"], "step_ok": fps["plain_ok"],
+           "step_colour_ok": fps["colour_ok"]}
+    for v in rendered:
+        v.close()
+    vol.close()
+    # the calibration room as a coloured mesh
+    room = V.room_volume(0, cls=ppf.Volume)
+    room.enable_colour()
+    for T in sweep:
+        depth, img, ok = W.render(synth, world, rgb, T, **V.SMALL)
+        c = V.SMALL_CAM
+        v = ppf.View(depth, c["fx"], c["fy"], c["cx"], c["cy"], z_min=c["z_min"], z_max=c["z_max"], max_jump=E.MAX_JUMP)
+        v.set_colour(img, ok)
+        room.integrate(v, T.astype(np.float32), colour=v)
+        v.close()
+    mx, mn, tri, mres, mrgb, mvalid = room.mesh(colour=True)
+    err = np.abs(mrgb[mvalid].astype(np.float64) - W.colour(mx.astype(np.float64), 0)[mvalid])
+    with tempfile.TemporaryDirectory() as d:
+        f = os.path.join(d, "room.ply")
+        ppf.ply_write_mesh(f, mx, mn, tri, rgb=mrgb)
+        size = os.path.getsize(f)
+        back = ppf.ply_read_mesh(f)
+    out["calibration_mesh"] = {"vertices": len(mx), "triangles": len(tri), "with_colour": float(mvalid.mean()),
+                               "error_median_levels": float(np.median(err)), "error_p95_levels": float(np.percentile(err, 95)),
+                               "ply_bytes": size, "ply_geometry_read_back": bool(back[0].tobytes() == mx.tobytes() and
+                                                                                 back[2].tobytes() == tri.tobytes())}
+    room.close()
+    return out
+
+
 def surface(calls=20):
     """Whole-volume surface extraction (oslam_volume_surface / oslam_scene_from_volume) on the fusion configuration's
     256^3 volume after its out-and-back stream.  The yardstick is one integrate on the same volume: both stream the
@@ -1172,4 +1270,4 @@ if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "cfg3"
     print(json.dumps({"cfg2": cfg2, "cfg3": cfg3, "cfg3db": cfg3db, "cfg4": cfg4, "cfg5": cfg5, "planes": planes, "db50": db50,
                       "refine": refine, "verify": verify, "instances": instances, "arbitrate": arbitrate, "explain": explain, "track": track, "camera": camera,
-                      "fusion": fusion, "surface": surface, "mesh": mesh, "shift": shift, "reload": reload, "pyramid": pyramid, "bilateral": bilateral, "normals": normals}[which]()), flush=True)
+                      "fusion": fusion, "colour": colour, "surface": surface, "mesh": mesh, "shift": shift, "reload": reload, "pyramid": pyramid, "bilateral": bilateral, "normals": normals}[which]()), flush=True)
