@@ -1589,8 +1589,8 @@ int oslam_volume_follow(oslam_volume *vol, const float T_vol_cam[16], const osla
  * oslam_volume_pack is a test tap and changes nothing: the records {lin, word} that k_tsdf_pack_count and
  *   k_tsdf_pack_emit make for this shift, lin = (k * ny + j) * nx + i of the old window, ascending.  cap == 0 counts only
  *   (the outputs may be NULL); more records than cap is OSLAM_E_LIMIT with the count in *n_out and nothing written.
- * Out of scope: one surface or mesh of store plus window, store files on disk, colour, several GPUs, any change to
- *   oslam_tracker. */
+ * Out of scope: one mesh of store plus window (their one surface: oslam_world_surface below), store files on disk,
+ *   colour, several GPUs, any change to oslam_tracker. */
 typedef struct oslam_world oslam_world;
 typedef struct oslam_world_params {
     float voxel;               /* the voxel size of the volumes the store serves, metres */
@@ -1622,6 +1622,82 @@ int oslam_world_put(oslam_world *w, const int32_t *g, const uint32_t *words, siz
 int oslam_world_box(oslam_world *w, const int32_t lo[3], const int32_t hi[3], uint32_t *words_out, int take);
 int oslam_volume_shift_world(oslam_volume *vol, oslam_world *w, const int shift[3], oslam_reload_result *res);
 int oslam_volume_pack(oslam_volume *vol, const int shift[3], uint32_t *lin_out, uint32_t *word_out, size_t cap, size_t *n_out);
+
+/* ---- the surface of the whole map: voxel store plus window as one cloud, extracted on the device from sparse
+ * 8 x 8 x 8 bricks with no dense box anywhere.  The restatement in numpy is tests/world_surface_ref.py; device and
+ * restatement agree bit for bit, order and keys included.
+ *
+ * The map.  G(g) is a 32-bit word for every global voxel coordinate g.  Inside the window's box (off <= g < off + n) it is
+ *   the window's word, seen or not; elsewhere it is the store's word, or 0 where the store has nothing.  A store entry
+ *   inside the window's box is ignored (there is none after oslam_volume_shift_world alone; a caller's oslam_world_put can
+ *   make one).  With vol == NULL the map is the store alone.
+ * The frame.  An anchor A[3] in voxels picks it: by default the window's offset when a volume is given and 0 otherwise;
+ *   the caller may set it (anchor_set != 0), |A_a| <= 2^20.  O = origin(A), derived exactly as oslam_volume_shift derives
+ *   an origin from an offset: origin0_a itself where A_a == 0, otherwise origin0_a + (float)A_a * voxel, one multiply,
+ *   then one add, not fused.  A voxel's index is r = g - A, a signed int, |r_a| < 2^22.
+ * Crossings, points, normals are oslam_volume_surface's with idx = r, origin = O and "outside the volume" replaced by
+ *   "G is 0 there":
+ *   Crossings.  Every voxel has its three +axis edges; there is no last-voxel rule, because there is no box.  Both ends
+ *     must be seen (w >= min_weight), with the integer sign test (q0 < 0) != (q1 < 0).
+ *   Point.  P_b = O_b + ((float)r_b + 0.5f) * voxel, plus t * voxel on the edge's axis, t = F0 / (F0 - F1).
+ *   Normal.  oslam_volume_surface's six trilinear reads with the arithmetic unchanged in grouping: g = (p - O_b) *
+ *     inv_voxel - 0.5f with inv_voxel = 1.0f / voxel, b = floorf(g); the range test on bx, by, bz becomes "finite and
+ *     |b| < 2^22"; the eight corners are read from G at A + b + (0|1), each needing w > 0.  A crossing without a normal
+ *     is counted (result.crossings) and dropped.
+ * Equality with a dense volume.  Take a dense oslam_volume with the same voxel and created origin, at offset A, whose
+ *   words are G over a box that contains every seen voxel of the map with a margin of at least 3 voxels on every side.
+ *   Then oslam_volume_surface returns the same crossings, the same number of them, and bit-identical points and normals.
+ *   With the default anchor a crossing whose stencil lies inside the window has the bits oslam_volume_surface gives it.
+ * Order.  Bricks ascend by key (bz, by, bx) with b = floor(g / 8); inside a brick the order is 3 * (i + 8 * (j + 8 * k))
+ *   + a.  Two calls give the same bits; there are no float atomics.  key_out (may be NULL; needs the other outputs)
+ *   int32 [cap][4] holds (g_x, g_y, g_z, a) of every returned point: sorting by (g_z, g_y, g_x, a) gives the dense
+ *   volume's order.
+ * oslam_world_surface: the output conventions are oslam_volume_surface's: xyz_out and nrm_out both or neither, both NULL
+ *   needs cap == 0 and only counts; OSLAM_E_LIMIT comes with *n_out and the result filled in and nothing written.
+ *   Refused before any device call with OSLAM_E_INVALID: NULL w or n_out, a min_weight outside 1..65535, an anchor beyond
+ *   2^20, a volume whose voxel or created origin bits are not the store's (as oslam_volume_shift_world refuses it).  A map
+ *   of more than 2^22 bricks is OSLAM_E_LIMIT.  The lock of the calls on volumes is taken, then the store's, as
+ *   everywhere; neither the store nor the volume changes.  params.dev is read only when vol == NULL.
+ * oslam_world_bricks is device-free: the brick keys floor(g / 8) of the store as keys_out [cap][3], ascending by
+ *   (bz, by, bx).  cap == 0 counts only (keys_out may be NULL); more bricks than cap is OSLAM_E_LIMIT with the count in
+ *   *n_out and nothing written.  A test tap, and what the surface call uses.
+ * oslam_scene_from_world is oslam_scene_from_volume's chain with this extraction at its head, the cloud never leaving
+ *   HBM: it equals oslam_scene_create over oslam_voxel_grid over oslam_world_surface.  The scene lives on the volume's
+ *   device, or on sp->dev without a volume (params->dev is not read).
+ * Cost.  Host: the store's brick keys are collected and sorted and united with the keys of the aligned bricks that the
+ *   window's box overlaps (its offset need not be a multiple of 8).  The device holds a table (packed 64-bit key, slot),
+ *   ascending, and an array of [512]-word bricks: the store's go up through the store's pinned buffer together with the
+ *   table in one copy, window-only bricks are zeroed by one memset, and k_brick_window writes the window's words into the
+ *   bricks it overlaps, so they never cross the host link.  A brick the window fills with nothing seen stays in the table
+ *   and yields nothing.  Then k_brick_count, one k_surface_scan per 2^17 bricks, one copy back and host wait for the
+ *   totals, k_brick_emit into a block of exactly the points' size and one more wait.  Device memory is freed before
+ *   return on every path.
+ * Out of scope: the mesh of the whole map, colour, store files on disk, several GPUs. */
+typedef struct oslam_world_surface_params {
+    unsigned min_weight;       /* 1..65535, default 1: a voxel is seen from this weight on */
+    int anchor_set;            /* 0: the window's offset, or 0 without a volume */
+    int32_t anchor[3];
+    int dev;                   /* read only when vol == NULL */
+    int reserved[6];
+} oslam_world_surface_params;
+
+typedef struct oslam_world_surface_result {
+    uint32_t crossings;        /* sign changes along edges between seen voxels of the map */
+    uint32_t points;           /* crossings that have a normal: what the call returns */
+    uint32_t bricks;           /* table entries: the store's bricks united with the window's */
+    uint32_t window_bricks;    /* aligned bricks the window's box overlaps */
+    uint32_t launches;
+    int32_t anchor[3];         /* the anchor in force */
+    float ms_total;            /* whole call, host clock */
+} oslam_world_surface_result;
+
+int oslam_world_surface_params_default(oslam_world_surface_params *p);
+int oslam_world_surface(oslam_world *w, oslam_volume *vol, const oslam_world_surface_params *sp, float *xyz_out, float *nrm_out,
+                        int32_t *key_out, size_t cap, size_t *n_out, oslam_world_surface_result *res);
+int oslam_world_bricks(oslam_world *w, int32_t *keys_out, size_t cap, size_t *n_out);
+int oslam_scene_from_world(oslam_world *w, oslam_volume *vol, const oslam_world_surface_params *sp, float leaf, float d_dist,
+                           unsigned ref_point_downsample_factor, const oslam_params *params, oslam_scene **out,
+                           size_t *n_points_out);
 
 /* ---- normals for clouds and meshes that come without them.  Every entry into the recognition path takes points and
  * normals; the reference made them outside its program (matlab/compute_normals.m for meshes, PCL for scans).  Two entry

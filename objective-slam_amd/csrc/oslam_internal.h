@@ -334,6 +334,16 @@ int oslam_surface_check_params(const oslam_surface_params *sp, oslam_surface_par
 /* the volume's surface in HBM as [*np][6] (NULL without points) on device *dev; the caller frees the block
  * (oslam_dev_free).  Takes the volume lock for the extraction */
 int oslam_volume_surface_cloud(oslam_volume *vol, unsigned min_weight, int *dev, float **d_pts6, uint32_t *np);
+/* ---- the surface of the whole map (oslam_world_surface.c) ---- */
+struct oslam_world_stage;
+/* a pinned staging buffer of a voxel store with room for bytes, with the store's lock held (oslam_volume.c) */
+int oslam_world_stage_fit(struct oslam_world_stage *st, size_t bytes);
+/* sp NULL = defaults; checks them as oslam_world_surface does, before any handle is read; *out = the parameters in force */
+int oslam_world_surface_check_params(const oslam_world_surface_params *sp, oslam_world_surface_params *out);
+/* the map's surface in HBM as [*np][6] (NULL without points) on device *dev; the caller frees the block (oslam_dev_free).
+ * p: checked parameters.  Takes the volume lock and the store's for the extraction */
+int oslam_world_surface_cloud(oslam_world *w, oslam_volume *vol, const oslam_world_surface_params *p, int *dev, float **d_pts6,
+                              uint32_t *np);
 /* the arbitration's parameter check (oslam_arbitrate.c) */
 int oslam_arbitrate_check_params(const oslam_arbitrate_params *ap, oslam_arbitrate_params *out);
 

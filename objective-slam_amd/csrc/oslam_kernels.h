@@ -735,6 +735,45 @@ int oslamk_colour_points(const oslamk_volume *vol, const uint32_t *words, const 
 int oslamk_colour_view(const oslamk_volume *vol, const uint32_t *words, const oslamk_view *v, const float *T12, uint32_t *out,
                        uint32_t *count, void *stream);
 
+/* ---- the surface of the whole map, voxel store plus window, from sparse bricks (oslam_world_surface.hip; semantics in
+ * include/oslam.h at oslam_world_surface; host side: oslam_world_surface.c) ---- */
+#define OSLAMK_BRICK_SIDE 8
+#define OSLAMK_BRICK_WORDS 512        /* [z][y][x] */
+#define OSLAMK_BRICK_BIAS (1 << 20)   /* a brick coordinate floor(g / 8) lies in [-2^20, 2^20): 21 bits with this added */
+#define OSLAMK_BRICK_MAX (1u << 22)   /* the most bricks of one map */
+#define OSLAMK_BRICK_SCAN (1u << 17)  /* the most counters one run of oslamk_surface_scan takes: the counts are scanned in
+                                         chunks of this many, and a chunk's base is added by the second pass */
+#define OSLAMK_BRICK_CHUNKS (OSLAMK_BRICK_MAX / OSLAMK_BRICK_SCAN)
+/* the packed key of brick (bx, by, bz): ascending keys are ascending (bz, by, bx).  A macro: host and device use it */
+#define OSLAMK_BRICK_KEY(bx, by, bz)                                                                                       \
+    ((uint64_t)(uint32_t)((bz) + OSLAMK_BRICK_BIAS) << 42 | (uint64_t)(uint32_t)((by) + OSLAMK_BRICK_BIAS) << 21 |           \
+     (uint64_t)(uint32_t)((bx) + OSLAMK_BRICK_BIAS))
+/* the map on the device: n table entries (keys ascending and distinct; slots[e] < n is entry e's brick in words
+ * [n][512]) and the frame: voxel index r = g - anchor, origin = the window origin at offset anchor */
+typedef struct oslamk_brick_map {
+    const uint64_t *keys;
+    const uint32_t *slots;
+    uint32_t *words;
+    uint32_t n;
+    int anchor[3];
+    float origin[3];
+    float voxel, inv_voxel;
+} oslamk_brick_map;
+/* the bases the second pass adds to the scanned offsets: base[c] for the entries c * 2^17 .. */
+typedef struct oslamk_brick_bases {
+    uint32_t base[OSLAMK_BRICK_CHUNKS];
+} oslamk_brick_bases;
+/* writes the window's words (vol, at offset off[3]) into the bricks the window's box overlaps, voxel by voxel; the bricks
+ * kb0 .. kb0 + nb - 1 per axis, each of which has a table entry */
+int oslamk_brick_window(const oslamk_brick_map *map, const oslamk_volume *vol, const int off[3], const int kb0[3], const int nb[3],
+                        void *stream);
+/* first pass and scans: counts [map->n] leaves as the exclusive offsets of the entries' points inside each chunk of
+ * 2^17 entries; totals[0] += crossings (zeroed by the caller), totals[2 + c] = the points of chunk c */
+int oslamk_brick_count(const oslamk_brick_map *map, uint32_t min_weight, uint32_t *counts, uint32_t *totals, void *stream);
+/* second pass: out6 = device [n_points][6] (x y z nx ny nz), key_out = device [n_points][4] (g_x g_y g_z axis) or NULL */
+int oslamk_brick_emit(const oslamk_brick_map *map, uint32_t min_weight, const uint32_t *offsets, const oslamk_brick_bases *bases,
+                      uint32_t n_points, float *out6, int32_t *key_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,6 @@
 /*
- * oslam_scene.c -- a scene: from host buffers, from a depth image or from a volume's surface, with its reference
- * points and their frames (scene.cu:24-55).
+ * oslam_scene.c -- a scene: from host buffers, from a depth image, from a volume's surface or from the surface of the
+ * whole map (voxel store plus window), with its reference points and their frames (scene.cu:24-55).
  */
 
 #include "oslam_internal.h"
@@ -132,27 +132,71 @@ int oslam_scene_from_depth(const void *depth, int depth_is_u16, int width, int h
     return rc;
 }
 
-int oslam_scene_from_volume(oslam_volume *vol, const oslam_surface_params *sp, float leaf, float d_dist, unsigned df,
-                            const oslam_params *params, oslam_scene **out, size_t *n_points_out)
+/* the extraction at the head of a chain: checks its own parameters before anything else, then leaves the cloud in HBM as
+ * [*np][6] on device *dev (NULL without points) */
+typedef int (*scene_extract_fn)(void *ctx, int *dev, float **d_pts6, uint32_t *np);
+
+/* oslam_scene_from_volume and oslam_scene_from_world: the checks, the extraction, then grid and scene.  handle_ok: the
+ * handle the extraction reads was given */
+static int scene_from_extraction(scene_extract_fn extract, void *ctx, int handle_ok, const char *no_handle, float leaf, float d_dist,
+                                 unsigned df, const oslam_params *params, const char *few, oslam_scene **out, size_t *n_points_out)
 {
     int rc;
     oslam_params p;
-    oslam_surface_params s;
     float *d_pts6 = NULL;
     uint32_t np = 0;
     if (!out) return fail(OSLAM_E_INVALID, "out is NULL");
     *out = NULL;
     if (n_points_out) *n_points_out = 0;
-    if (!vol) return fail(OSLAM_E_INVALID, "volume is NULL");
+    if (!handle_ok) return fail(OSLAM_E_INVALID, no_handle);
     if (!(leaf >= 0.0f) || !(d_dist >= 0.0f) || df == 0) return fail(OSLAM_E_INVALID, "bad scene arguments");
-    rc = oslam_surface_check_params(sp, &s);
-    if (rc != OSLAM_OK) return rc;
     if (params) p = *params; else oslam_params_default(&p);
-    /* the scene lives where the volume does */
-    rc = oslam_volume_surface_cloud(vol, s.min_weight, &p.dev, &d_pts6, &np);
-    if (rc == OSLAM_OK)
-        rc = scene_from_points6(d_pts6, np, leaf, d_dist, df, &p, "the volume's surface leaves fewer than 2 scene points", out,
-                                n_points_out);
+    /* the scene lives where the extraction ran */
+    rc = extract(ctx, &p.dev, &d_pts6, &np);
+    if (rc == OSLAM_OK) rc = scene_from_points6(d_pts6, np, leaf, d_dist, df, &p, few, out, n_points_out);
     oslam_dev_free(d_pts6);
     return rc;
+}
+
+typedef struct volume_extract {
+    oslam_volume *vol;
+    const oslam_surface_params *sp;
+} volume_extract;
+
+static int extract_volume(void *ctx, int *dev, float **d_pts6, uint32_t *np)
+{
+    const volume_extract *x = (const volume_extract *)ctx;
+    oslam_surface_params s;
+    const int rc = oslam_surface_check_params(x->sp, &s);
+    return rc != OSLAM_OK ? rc : oslam_volume_surface_cloud(x->vol, s.min_weight, dev, d_pts6, np);
+}
+
+int oslam_scene_from_volume(oslam_volume *vol, const oslam_surface_params *sp, float leaf, float d_dist, unsigned df,
+                            const oslam_params *params, oslam_scene **out, size_t *n_points_out)
+{
+    volume_extract x = {vol, sp};
+    return scene_from_extraction(extract_volume, &x, vol != NULL, "volume is NULL", leaf, d_dist, df, params,
+                                 "the volume's surface leaves fewer than 2 scene points", out, n_points_out);
+}
+
+typedef struct world_extract {
+    oslam_world *w;
+    oslam_volume *vol;
+    const oslam_world_surface_params *sp;
+} world_extract;
+
+static int extract_world(void *ctx, int *dev, float **d_pts6, uint32_t *np)
+{
+    const world_extract *x = (const world_extract *)ctx;
+    oslam_world_surface_params s;
+    const int rc = oslam_world_surface_check_params(x->sp, &s);
+    return rc != OSLAM_OK ? rc : oslam_world_surface_cloud(x->w, x->vol, &s, dev, d_pts6, np);
+}
+
+int oslam_scene_from_world(oslam_world *w, oslam_volume *vol, const oslam_world_surface_params *sp, float leaf, float d_dist,
+                           unsigned df, const oslam_params *params, oslam_scene **out, size_t *n_points_out)
+{
+    world_extract x = {w, vol, sp};
+    return scene_from_extraction(extract_world, &x, w != NULL, "world is NULL", leaf, d_dist, df, params,
+                                 "the map's surface leaves fewer than 2 scene points", out, n_points_out);
 }

@@ -506,8 +506,8 @@ done:
 static void stage_release(void *p) { (void)hipHostFree(p); }
 
 /* a pinned staging buffer of the store with room for bytes: grown by half as much again, so a stream of similar shifts
- * allocates once */
-static int stage_fit(oslam_world_stage *st, size_t bytes)
+ * allocates once (oslam_world_surface.c stages the store's bricks through it too) */
+int oslam_world_stage_fit(oslam_world_stage *st, size_t bytes)
 {
     void *p = NULL;
     const size_t want = bytes + bytes / 2;
@@ -618,7 +618,7 @@ int oslam_volume_shift_world(oslam_volume *vol, oslam_world *w, const int shift[
     locked = 1;
     st = oslam_world_stages(w);
     if (n_out) {
-        rc = stage_fit(&st[0], sizeof(uint32_t) * 2 * (size_t)n_out);
+        rc = oslam_world_stage_fit(&st[0], sizeof(uint32_t) * 2 * (size_t)n_out);
         if (rc != OSLAM_OK) goto done;
         HIPCHK(hipMemcpyAsync(st[0].p, d_out, sizeof(uint32_t) * 2 * (size_t)n_out, hipMemcpyDeviceToHost, (hipStream_t)stream));
         HIPCHK(hipStreamSynchronize((hipStream_t)stream));
@@ -640,7 +640,7 @@ int oslam_volume_shift_world(oslam_volume *vol, oslam_world *w, const int shift[
     for (b = 0; b < nb; b++) n_in += oslam_world_visit(w, lo[b], hi[b], 0, NULL, NULL);
     if (n_in) {
         enter_ctx e;
-        rc = stage_fit(&st[1], sizeof(uint32_t) * 2 * n_in);
+        rc = oslam_world_stage_fit(&st[1], sizeof(uint32_t) * 2 * n_in);
         if (rc != OSLAM_OK) goto done;
         e.rec = (uint32_t *)st[1].p;
         e.n = 0;

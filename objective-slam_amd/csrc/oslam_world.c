@@ -4,7 +4,8 @@
  * it: oslam_volume.c; its view of the store: oslam_world.h).  Bricks of 8 x 8 x 8 words, keyed by floor(g / 8) per axis,
  * in a table with linear probing that doubles when half full; removal shifts the following entries back, so there are
  * no tombstones and a lookup that misses stops at the first empty slot.  Every stored word is seen (w > 0), so a zero
- * word in a brick means "nothing stored".  No device call and no HIP header: this file links alone.
+ * word in a brick means "nothing stored".  The bricks' keys in ascending order, for the extraction of the whole map's
+ * surface (oslam_world_surface.c), are made here too.  No device call and no HIP header: this file links alone.
  */
 #include <math.h>
 #include <pthread.h>
@@ -392,4 +393,49 @@ int oslam_world_box(oslam_world *w, const int32_t lo[3], const int32_t hi[3], ui
     (void)oslam_world_visit(w, lo, hi, take, dense_write, &d);
     pthread_mutex_unlock(&w->mu);
     return OSLAM_OK;
+}
+
+/* ---- brick enumeration (include/oslam.h at oslam_world_surface; its device side: oslam_world_surface.c) ---- */
+static int key_cmp(const void *pa, const void *pb)
+{
+    const int32_t *a = (const int32_t *)pa, *b = (const int32_t *)pb;
+    int c;
+    for (c = 2; c >= 0; c--)
+        if (a[c] != b[c]) return a[c] < b[c] ? -1 : 1;
+    return 0;
+}
+
+void oslam_world_frame(const oslam_world *w, float *voxel, float origin0[3])
+{
+    *voxel = w->voxel;
+    memcpy(origin0, w->origin0, sizeof w->origin0);
+}
+
+size_t oslam_world_brick_count(const oslam_world *w) { return w->n_bricks; }
+
+void oslam_world_brick_keys(const oslam_world *w, int32_t *keys_out)
+{
+    size_t s, n = 0;
+    for (s = 0; s < w->cap; s++)
+        if (w->slots[s]) memcpy(keys_out + 3 * n++, w->slots[s]->key, sizeof w->slots[s]->key);
+    qsort(keys_out, n, 3 * sizeof *keys_out, key_cmp);
+}
+
+const uint32_t *oslam_world_brick_words(const oslam_world *w, const int32_t key[3])
+{
+    const size_t s = table_find(w, key);
+    return s == NO_SLOT ? NULL : w->slots[s]->words;
+}
+
+int oslam_world_bricks(oslam_world *w, int32_t *keys_out, size_t cap, size_t *n_out)
+{
+    int rc = OSLAM_OK;
+    if (!w || !n_out) return oslam_fail(OSLAM_E_INVALID, "NULL argument");
+    if (!keys_out && cap != 0) return oslam_fail(OSLAM_E_INVALID, "cap must be 0 without an output");
+    pthread_mutex_lock(&w->mu);
+    *n_out = w->n_bricks;
+    if (keys_out && w->n_bricks > cap) rc = oslam_fail(OSLAM_E_LIMIT, "output capacity too small");
+    else if (keys_out) oslam_world_brick_keys(w, keys_out);
+    pthread_mutex_unlock(&w->mu);
+    return rc;
 }

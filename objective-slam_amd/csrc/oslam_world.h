@@ -42,5 +42,13 @@ void oslam_world_store(oslam_world *w, const int32_t g[3], uint32_t word);
  * become empty.  -> the number of words visited */
 typedef void (*oslam_world_visit_fn)(void *ctx, const int32_t g[3], uint32_t word);
 size_t oslam_world_visit(oslam_world *w, const int32_t lo[3], const int32_t hi[3], int take, oslam_world_visit_fn fn, void *ctx);
+/* the float bits the store was made for */
+void oslam_world_frame(const oslam_world *w, float *voxel, float origin0[3]);
+/* the store's bricks for the extraction of the whole map (oslam_world_surface.c): how many; their keys floor(g / 8) as
+ * keys_out [count][3], ascending by (bz, by, bx); the 512 words [z][y][x] of the brick with this key (NULL without one),
+ * valid until the store changes */
+size_t oslam_world_brick_count(const oslam_world *w);
+void oslam_world_brick_keys(const oslam_world *w, int32_t *keys_out);
+const uint32_t *oslam_world_brick_words(const oslam_world *w, const int32_t key[3]);
 
 #endif /* OSLAM_WORLD_H */

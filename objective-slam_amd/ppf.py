@@ -327,6 +327,21 @@ class ReloadResult(C.Structure):
                 "reloaded": int(self.reloaded), "launches": int(self.launches), "ms_total": float(self.ms_total)}
 
 
+class WorldSurfaceParams(C.Structure):
+    _fields_ = [("min_weight", C.c_uint), ("anchor_set", C.c_int), ("anchor", C.c_int32 * 3), ("dev", C.c_int),
+                ("reserved", C.c_int * 6)]
+
+
+class WorldSurfaceResult(C.Structure):
+    _fields_ = [("crossings", C.c_uint32), ("points", C.c_uint32), ("bricks", C.c_uint32), ("window_bricks", C.c_uint32),
+                ("launches", C.c_uint32), ("anchor", C.c_int32 * 3), ("ms_total", C.c_float)]
+
+    def asdict(self):
+        return {"crossings": int(self.crossings), "points": int(self.points), "bricks": int(self.bricks),
+                "window_bricks": int(self.window_bricks), "launches": int(self.launches),
+                "anchor": tuple(int(x) for x in self.anchor), "ms_total": float(self.ms_total)}
+
+
 class NormalsParams(C.Structure):
     _fields_ = [("radius", C.c_float), ("min_neighbours", C.c_uint), ("viewpoint", C.c_float * 3), ("orient", C.c_int),
                 ("line_ratio", C.c_float), ("reserved", C.c_int * 4)]
@@ -488,6 +503,12 @@ _SIGNATURES = {
     "oslam_world_stats_get": (_i, [_vp, C.POINTER(WorldStats)]),
     "oslam_world_put": (_i, [_vp, _vp, _vp, _sz]),
     "oslam_world_box": (_i, [_vp, _vp, _vp, _vp, _i]),
+    "oslam_world_surface_params_default": (_i, [C.POINTER(WorldSurfaceParams)]),
+    "oslam_world_surface": (_i, [_vp, _vp, C.POINTER(WorldSurfaceParams), _vp, _vp, _vp, _sz, C.POINTER(_sz),
+                                 C.POINTER(WorldSurfaceResult)]),
+    "oslam_world_bricks": (_i, [_vp, _vp, _sz, C.POINTER(_sz)]),
+    "oslam_scene_from_world": (_i, [_vp, _vp, C.POINTER(WorldSurfaceParams), _f, _f, _u, C.POINTER(Params), C.POINTER(_vp),
+                                    C.POINTER(_sz)]),
     "oslam_volume_shift_world": (_i, [_vp, _vp, _vp, C.POINTER(ReloadResult)]),
     "oslam_volume_pack": (_i, [_vp, _vp, _vp, _vp, _sz, C.POINTER(_sz)]),
     "oslam_mesh_params_default": (_i, [C.POINTER(MeshParams)]),
@@ -1089,6 +1110,23 @@ class Scene:
         n = C.c_size_t(0)
         _check(lib().oslam_scene_from_volume(vol._h, C.byref(sp), float(leaf), self.d_dist, self.df, C.byref(self.params),
                                              C.byref(self._h), C.byref(n)))
+        self.n = n.value
+        return self
+
+    @classmethod
+    def from_world(cls, world, vol=None, leaf=0.0, d_dist=0.0, ref_point_downsample_factor=1, min_weight=1, anchor=None, dev=0,
+                   params=None):
+        """The surface of the whole map, the voxel store `world` plus the window of `vol` (None: the store alone, on
+        device dev) -> voxel grid (leaf > 0) -> Scene in one call, the extracted cloud staying in HBM
+        (oslam_scene_from_world).  The scene is in the volume frame."""
+        self = cls.__new__(cls)
+        self._h = C.c_void_p(0)
+        self.params = params if params is not None else default_params()
+        self.d_dist, self.df = float(d_dist), int(ref_point_downsample_factor)
+        sp = _world_surface_params(min_weight, anchor, dev)
+        n = C.c_size_t(0)
+        _check(lib().oslam_scene_from_world(world._h, vol._h if vol is not None else None, C.byref(sp), float(leaf), self.d_dist,
+                                            self.df, C.byref(self.params), C.byref(self._h), C.byref(n)))
         self.n = n.value
         return self
 
@@ -2024,6 +2062,26 @@ def default_surface_params(**kw):
     return p
 
 
+def default_world_surface_params(**fields):
+    """oslam_world_surface_params_default, then the fields given as keywords (anchor: three ints)."""
+    p = WorldSurfaceParams()
+    _check(lib().oslam_world_surface_params_default(C.byref(p)))
+    for k, v in fields.items():
+        if not hasattr(p, k) or k == "reserved":
+            raise TypeError("unknown world surface parameter %r" % k)
+        if k == "anchor":
+            p.anchor[:] = [int(x) for x in _shift3(v)]
+        else:
+            setattr(p, k, v)
+    return p
+
+
+def _world_surface_params(min_weight, anchor, dev):
+    if anchor is None:
+        return default_world_surface_params(min_weight=min_weight, dev=int(dev))
+    return default_world_surface_params(min_weight=min_weight, dev=int(dev), anchor_set=1, anchor=anchor)
+
+
 def default_mesh_params(**kw):
     """oslam_mesh_params_default, then the fields given as keywords."""
     p = MeshParams()
@@ -2086,6 +2144,34 @@ class World:
         out = np.zeros(tuple(max(int(hi[a]) - int(lo[a]), 0) for a in (2, 1, 0)), np.uint32)
         _check(lib().oslam_world_box(self._h, _p(lo), _p(hi), _p(out), int(bool(take))))
         return out
+
+    def bricks(self):
+        """The keys floor(g / 8) of the store's 8 x 8 x 8 bricks, int32 [n,3], ascending by (bz, by, bx)
+        (oslam_world_bricks)."""
+        n = C.c_size_t(0)
+        _check(lib().oslam_world_bricks(self._h, None, 0, C.byref(n)))
+        keys = np.zeros((n.value, 3), np.int32)
+        if n.value:
+            _check(lib().oslam_world_bricks(self._h, _p(keys), n.value, C.byref(n)))
+        return keys
+
+    def surface(self, vol=None, min_weight=1, anchor=None, keys=False, dev=0):
+        """Every zero crossing of the whole map, this store plus the window of the Volume vol (None: the store alone, on
+        device dev), as a point with its outward normal in the volume frame (oslam_world_surface): -> (points [n,3],
+        normals [n,3]) and with keys=True also int32 [n,4], (g_x, g_y, g_z, axis) of every point.  Bricks ascend by
+        (bz, by, bx), a brick's points by voxel and axis; anchor (three ints, default the window's offset, or 0) picks the
+        frame the floats are formed in.  The result dict of the call is kept as self.last_surface."""
+        sp = _world_surface_params(min_weight, anchor, dev)
+        vh = vol._h if vol is not None else None
+        n, res = C.c_size_t(0), WorldSurfaceResult()
+        _check(lib().oslam_world_surface(self._h, vh, C.byref(sp), None, None, None, 0, C.byref(n), C.byref(res)))
+        po, no = np.zeros((n.value, 3), np.float32), np.zeros((n.value, 3), np.float32)
+        ko = np.zeros((n.value, 4), np.int32)
+        if n.value:
+            _check(lib().oslam_world_surface(self._h, vh, C.byref(sp), _p(po), _p(no), _p(ko) if keys else None, n.value,
+                                             C.byref(n), C.byref(res)))
+        self.last_surface = res.asdict()
+        return (po, no, ko) if keys else (po, no)
 
     def stats(self):
         s = WorldStats()

@@ -1130,6 +1130,50 @@ def reload(calls=20):
     return out
 
 
+def worldsurface(calls=20):
+    """The surface of the whole map (oslam_world_surface) on the reload configuration's map after its stream: the 256^3
+    volume after the out-and-back stream, shifted through a store by (64, 0, 0) so that a slab of the surface lies in
+    the store.  In one run and alternately, so that drift hits both alike: the median of `calls` calls of
+    World.surface(vol) and of Volume.surface(), which sees the window alone (the yardstick).  The brick counts, the
+    points of both and the library's own clock are in the output."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import camera_ref as E
+    world = E.make_world(synth, 0)
+    sweep = E.trajectory(synth, 0, frames=10)
+    cam = E.CAM
+    rendered = [ppf.View(E.render(synth, world, T), cam["fx"], cam["fy"], cam["cx"], cam["cy"], z_min=cam["z_min"],
+                         z_max=cam["z_max"], max_jump=E.MAX_JUMP) for T in sweep]
+    spec = dict(nx=256, ny=256, nz=256, voxel=0.036, origin=[-2.9, -4.3, 0.3], mu=0.288)
+    vol = ppf.Volume(**spec)
+    steps = [vol.step(rendered[k]) for k in list(range(10)) + list(range(8, -1, -1))]
+    store = ppf.World(vol)
+    _, _, before = vol.surface()
+    moved = vol.shift((64, 0, 0), store)
+    store.surface(vol)                                              # the staging buffer and the kept device blocks
+    vol.surface()
+    ms_w, ms_v, lib_w = [], [], []
+    for _ in range(calls):
+        t = time.perf_counter(); pw, _ = store.surface(vol); ms_w.append(1e3 * (time.perf_counter() - t))
+        lib_w.append(store.last_surface["ms_total"])
+        t = time.perf_counter(); pv, _, vres = vol.surface(); ms_v.append(1e3 * (time.perf_counter() - t))
+    t = time.perf_counter(); store.surface(vol, keys=True); ms_keys = 1e3 * (time.perf_counter() - t)
+    wres, st = store.last_surface, store.stats()
+    out = {"config": "worldsurface (oslam_world_surface): the reload configuration's 256^3 map after its 19-frame stream, shifted by (64, 0, 0) through the store",
+           "volume": spec, "calls": calls, "step_ok": [None if r is None else r["ok"] for _, r in steps],
+           "stored_by_the_shift": moved["stored"], "store": st,
+           "world_surface_ms_median": float(np.median(ms_w)), "world_surface_ms_library_median": float(np.median(lib_w)),
+           "world_surface_with_keys_ms_once": ms_keys, "volume_surface_ms_median": float(np.median(ms_v)),
+           "world_over_volume": float(np.median(ms_w) / np.median(ms_v)),
+           "bricks": wres["bricks"], "window_bricks": wres["window_bricks"], "store_bricks": st["bricks"], "launches": wres["launches"],
+           "world_crossings": wres["crossings"], "world_points": len(pw), "window_crossings": vres["crossings"], "window_points": len(pv),
+           "points_before_the_shift": before["points"], "brick_bytes_on_device": 2048 * wres["bricks"], "store_bytes_over_the_link": 2048 * st["bricks"]}
+    for v in rendered:
+        v.close()
+    store.close()
+    vol.close()
+    return out
+
+
 def pyramid(calls=20):
     """Image pyramids (oslam_pyramid_create, oslam_pyramid_egomotion) on frames 0 and 1 of the camera configuration's
     640x480 stream: the median of `calls` calls of Pyramid(view), of egomotion_pyramid and, in the same run, of egomotion
@@ -1270,4 +1314,4 @@ if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "cfg3"
     print(json.dumps({"cfg2": cfg2, "cfg3": cfg3, "cfg3db": cfg3db, "cfg4": cfg4, "cfg5": cfg5, "planes": planes, "db50": db50,
                       "refine": refine, "verify": verify, "instances": instances, "arbitrate": arbitrate, "explain": explain, "track": track, "camera": camera,
-                      "fusion": fusion, "colour": colour, "surface": surface, "mesh": mesh, "shift": shift, "reload": reload, "pyramid": pyramid, "bilateral": bilateral, "normals": normals}[which]()), flush=True)
+                      "fusion": fusion, "colour": colour, "surface": surface, "mesh": mesh, "shift": shift, "reload": reload, "worldsurface": worldsurface, "pyramid": pyramid, "bilateral": bilateral, "normals": normals}[which]()), flush=True)
