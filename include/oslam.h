@@ -1589,8 +1589,8 @@ int oslam_volume_follow(oslam_volume *vol, const float T_vol_cam[16], const osla
  * oslam_volume_pack is a test tap and changes nothing: the records {lin, word} that k_tsdf_pack_count and
  *   k_tsdf_pack_emit make for this shift, lin = (k * ny + j) * nx + i of the old window, ascending.  cap == 0 counts only
  *   (the outputs may be NULL); more records than cap is OSLAM_E_LIMIT with the count in *n_out and nothing written.
- * Out of scope: one mesh of store plus window (their one surface: oslam_world_surface below), store files on disk,
- *   colour, several GPUs, any change to oslam_tracker. */
+ * Out of scope: store files on disk, colour, several GPUs, any change to oslam_tracker.  (The one surface of store plus
+ *   window is oslam_world_surface below, their one mesh oslam_world_mesh.) */
 typedef struct oslam_world oslam_world;
 typedef struct oslam_world_params {
     float voxel;               /* the voxel size of the volumes the store serves, metres */
@@ -1672,7 +1672,7 @@ int oslam_volume_pack(oslam_volume *vol, const int shift[3], uint32_t *lin_out, 
  *   and yields nothing.  Then k_brick_count, one k_surface_scan per 2^17 bricks, one copy back and host wait for the
  *   totals, k_brick_emit into a block of exactly the points' size and one more wait.  Device memory is freed before
  *   return on every path.
- * Out of scope: the mesh of the whole map, colour, store files on disk, several GPUs. */
+ * Out of scope: colour, store files on disk, several GPUs.  (The mesh of the whole map is oslam_world_mesh below.) */
 typedef struct oslam_world_surface_params {
     unsigned min_weight;       /* 1..65535, default 1: a voxel is seen from this weight on */
     int anchor_set;            /* 0: the window's offset, or 0 without a volume */
@@ -1698,6 +1698,67 @@ int oslam_world_bricks(oslam_world *w, int32_t *keys_out, size_t cap, size_t *n_
 int oslam_scene_from_world(oslam_world *w, oslam_volume *vol, const oslam_world_surface_params *sp, float leaf, float d_dist,
                            unsigned ref_point_downsample_factor, const oslam_params *params, oslam_scene **out,
                            size_t *n_points_out);
+
+/* ---- the mesh of the whole map: voxel store plus window as one marching-cubes mesh, extracted on the device from the
+ * sparse 8 x 8 x 8 bricks of oslam_world_surface with no dense box anywhere.  The restatement in numpy is
+ * tests/world_mesh_ref.py; device and restatement agree bit for bit, order included.
+ *
+ * Map, frame, anchor and "seen" are oslam_world_surface's, word for word: the map G(g) with "a store entry inside the
+ *   window's box is ignored" and the store alone for vol == NULL; the anchor A, |A_a| <= 2^20, by default the window's
+ *   offset or 0; O = origin(A) and r = g - A; a voxel is seen iff w >= min_weight.
+ * Vertices.  Vertex v is the v-th crossing of oslam_world_surface's rule in its order, with or without a normal: bricks
+ *   ascending by (bz, by, bx), inside a brick 3 * (i + 8 * (j + 8 * k)) + a.  Its position is that rule's P; its normal
+ *   comes from the same six trilinear reads, and a crossing without a normal keeps its vertex and gets (0, 0, 0).  So the
+ *   number of vertices equals oslam_world_surface_result.crossings, and the vertices with a non-zero normal, in order, are
+ *   oslam_world_surface's points, normals and keys bit for bit.  With nrm_out == NULL the six reads are not made.
+ * Cubes.  Every global voxel g is the corner of a cube; there is no box, so there is no last-cube rule.  A cube is full iff
+ *   all eight G(g + (dx, dy, dz)) are seen.  Corner numbering, the integer sign test, the edge numbering e = 4 * a + m, the
+ *   table and its row order are oslam_volume_mesh's.  Cubes that are not full emit nothing, so a cube next to an absent
+ *   brick is silent, and the vertices on its edges stay in the output, unreferenced.
+ * Triangles.  Table entries ascend; inside a brick the cube's corner voxel ascends by i + 8 * (j + 8 * k); then the row's
+ *   order.  A triangle is three uint32 vertex indices; zero-area triangles are kept.
+ * Equality with a dense volume.  Take oslam_world_surface's dense volume: the same voxel and created origin, at offset A,
+ *   whose words are G over a box that holds every seen voxel of the map with a margin of at least 3.  oslam_volume_mesh on
+ *   it gives the same vertices bit for bit, by that rule's argument.  With each vertex index mapped to its key (g_x, g_y,
+ *   g_z, a) the triangles are the same triples of keys in the same rotation, and sorted (stably) by the cube's (g_z, g_y,
+ *   g_x) they stand in the dense volume's order.
+ * Determinism.  Two calls give the same bytes; there are no float atomics.
+ * oslam_world_mesh: the parameters are oslam_world_surface's.  The output conventions are oslam_volume_mesh's: xyz_out
+ *   [v_cap][3] and tri_out [t_cap][3] are both given or both NULL; both NULL needs both caps 0 (and no nrm_out or key_out)
+ *   and only counts; nrm_out [v_cap][3] and key_out int32 [v_cap][4] = (g_x, g_y, g_z, a), one row per vertex, are optional
+ *   alongside xyz_out.  *nv_out and *nt_out = the numbers of vertices and triangles in every case that reached the
+ *   device; OSLAM_E_LIMIT when outputs are given and either cap is below its count, with the counts and the result filled
+ *   in and nothing written.  A triangle corner whose edge has no vertex (it cannot happen under the rule; the kernel
+ *   checks it like its index checks) fails the call with OSLAM_E_DEVICE and nothing written.
+ *   Refused before any device call with OSLAM_E_INVALID, in oslam_world_surface's order: NULL w, nv_out or nt_out, one of
+ *   xyz_out and tri_out without the other, NULL outputs with a cap > 0 or with nrm_out or key_out, a min_weight outside
+ *   1..65535, an anchor beyond 2^20, a volume whose voxel or created origin bits are not the store's.  OSLAM_E_LIMIT also
+ *   for a map of more than 2^22 bricks and for a vertex or triangle total beyond uint32 (the chunks' sums are added in 64
+ *   bits on the host; *nv_out and *nt_out hold the totals, the result's fields their limit).  The lock of the calls on
+ *   volumes is taken, then the store's; neither the store nor the volume changes; device memory is freed before return on
+ *   every path; an empty store without a volume returns zero counts without a device call.
+ * Cost.  The map goes up as for oslam_world_surface.  k_wmesh_count writes two counters per table entry, each array is
+ *   scanned in chunks of 2^17 entries; one copy back and host wait; k_wmesh_vertices and k_wmesh_triangles write into
+ *   blocks of exactly the two totals; one more wait.  A triangle corner's vertex lies in the brick of its edge's start
+ *   voxel, this one or a +x/+y/+z neighbour: its index is that entry's first vertex plus the rank of 3 * (voxel in the
+ *   brick) + a among the entry's at most 1536 ids, found by binary search.  Device memory besides the map and the outputs:
+ *   those two counters and one uint32 id per vertex; nothing proportional to the number of voxels.
+ * Out of scope: colour (the store keeps none; oslam_volume_colours answers for vertices inside the window), merging or
+ *   decimating triangles, dropping unreferenced vertices, store files on disk, several GPUs. */
+typedef struct oslam_world_mesh_result {
+    uint32_t vertices;         /* crossings: equals oslam_world_surface_result.crossings */
+    uint32_t triangles;
+    uint32_t cubes;            /* full cubes with a case other than 0 and 255 */
+    uint32_t bricks;           /* table entries: the store's bricks united with the window's */
+    uint32_t window_bricks;    /* aligned bricks the window's box overlaps */
+    uint32_t launches;
+    int32_t anchor[3];         /* the anchor in force */
+    float ms_total;            /* whole call, host clock */
+} oslam_world_mesh_result;
+
+int oslam_world_mesh(oslam_world *w, oslam_volume *vol, const oslam_world_surface_params *sp, float *xyz_out, float *nrm_out,
+                     int32_t *key_out, size_t v_cap, uint32_t *tri_out, size_t t_cap, size_t *nv_out, size_t *nt_out,
+                     oslam_world_mesh_result *res);
 
 /* ---- normals for clouds and meshes that come without them.  Every entry into the recognition path takes points and
  * normals; the reference made them outside its program (matlab/compute_normals.m for meshes, PCL for scans).  Two entry

@@ -344,6 +344,20 @@ int oslam_world_surface_check_params(const oslam_world_surface_params *sp, oslam
  * p: checked parameters.  Takes the volume lock and the store's for the extraction */
 int oslam_world_surface_cloud(oslam_world *w, oslam_volume *vol, const oslam_world_surface_params *p, int *dev, float **d_pts6,
                               uint32_t *np);
+/* The whole map on the device for one extraction (oslam_world_surface.c): the table of brick keys and slots, the store's
+ * bricks sent up and the window's words written into theirs (include/oslam.h at oslam_world_surface, "Cost").  bricks == 0
+ * is an empty map, for which no device call was made.  p: checked parameters.  Called with the volume lock and the
+ * store's held; refuses a volume the store was not made for.  On failure nothing is left to free; after success the
+ * caller waits for the stream and then calls oslam_world_map_close */
+typedef struct oslam_world_map {
+    oslamk_brick_map m;
+    uint8_t *d_map;
+    uint32_t bricks, window_bricks, launches;
+    int32_t anchor[3];
+    int dev;
+} oslam_world_map;
+int oslam_world_map_open(oslam_world *w, oslam_volume *vol, const oslam_world_surface_params *p, void *stream, oslam_world_map *out);
+void oslam_world_map_close(oslam_world_map *wm);
 /* the arbitration's parameter check (oslam_arbitrate.c) */
 int oslam_arbitrate_check_params(const oslam_arbitrate_params *ap, oslam_arbitrate_params *out);
 

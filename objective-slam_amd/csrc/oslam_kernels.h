@@ -774,6 +774,26 @@ int oslamk_brick_count(const oslamk_brick_map *map, uint32_t min_weight, uint32_
 int oslamk_brick_emit(const oslamk_brick_map *map, uint32_t min_weight, const uint32_t *offsets, const oslamk_brick_bases *bases,
                       uint32_t n_points, float *out6, int32_t *key_out, void *stream);
 
+
+/* ---- the mesh of the whole map from the same bricks (oslam_world_mesh.hip; semantics in include/oslam.h at
+ * oslam_world_mesh; host side: oslam_world_mesh.c).  The map is the surface's, window written in by oslamk_brick_window ---- */
+/* first pass and scans: vcounts and tcounts [map->n] leave as the exclusive offsets of the entries' vertices and triangles
+ * inside each chunk of 2^17 entries, vsums[c] and tsums[c] = the sums of chunk c (device, OSLAMK_BRICK_CHUNKS each);
+ * totals[OSLAMK_MESH_T_CUBES] += full cubes with a case other than 0 and 255 (zeroed by the caller) */
+int oslamk_brick_mesh_count(const oslamk_brick_map *map, uint32_t min_weight, uint32_t *vcounts, uint32_t *tcounts, uint32_t *totals,
+                            uint32_t *vsums, uint32_t *tsums, void *stream);
+/* second pass: xyz [n_verts][3], nrm [n_verts][3] or NULL (the normals are then not computed), key_out [n_verts][4] (g_x g_y
+ * g_z axis, 16-byte aligned) or NULL, edge_id [n_verts] = 3 * (voxel in its brick) + axis, ascending inside an entry */
+int oslamk_brick_mesh_vertices(const oslamk_brick_map *map, uint32_t min_weight, const uint32_t *voffsets,
+                               const oslamk_brick_bases *vbases, uint32_t n_verts, float *xyz, float *nrm, int32_t *key_out,
+                               uint32_t *edge_id, void *stream);
+/* third pass: tri [n_tris][3] vertex indices, found by binary search in the run of edge_id that belongs to the entry of the
+ * edge's start voxel; totals[OSLAMK_MESH_T_MISS] += misses (zeroed by the caller; stays 0) */
+int oslamk_brick_mesh_triangles(const oslamk_brick_map *map, uint32_t min_weight, const uint32_t *toffsets,
+                                const oslamk_brick_bases *tbases, uint32_t n_tris, const uint32_t *voffsets,
+                                const oslamk_brick_bases *vbases, const uint32_t *edge_id, uint32_t n_verts, uint32_t *tri,
+                                uint32_t *totals, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,7 @@
 /*
  * oslam_world_surface.c -- the surface of the whole map, voxel store plus window (include/oslam.h at
- * oslam_world_surface): the host side of the kernels in oslam_world_surface.hip.  A call unites the store's brick keys
+ * oslam_world_surface): the host side of the kernels in oslam_world_surface.hip, and the map on the device that the mesh
+ * of the whole map (oslam_world_mesh.c) extracts from too (oslam_world_map_open).  A call unites the store's brick keys
  * (oslam_world.c) with the keys of the bricks the window's box overlaps into one ascending table, sends the table and the
  * store's bricks up in one copy from the store's pinned buffer, lets the device write the window's words into their
  * bricks, counts, waits for the totals, allocates exactly that and emits, under the volume lock and the store's.
@@ -24,15 +25,6 @@ int oslam_world_surface_check_params(const oslam_world_surface_params *sp, oslam
     return OSLAM_OK;
 }
 
-/* what one extraction leaves: the device blocks (NULL without points, or when they were not asked for) and the figures */
-typedef struct world_run {
-    float *d_out6;
-    int32_t *d_key;
-    uint32_t crossings, points, bricks, window_bricks, launches;
-    int32_t anchor[3];
-    int dev;
-} world_run;
-
 /* the aligned bricks that the window's box overlaps: the first key and the number of keys per axis */
 static void window_bricks(const oslam_volume *vol, int kb0[3], int nb[3])
 {
@@ -44,26 +36,17 @@ static void window_bricks(const oslam_volume *vol, int kb0[3], int nb[3])
     }
 }
 
-/* The extraction after the argument checks.  cap: the most points the caller takes; with_out 0 only counts; with_keys:
- * the points' keys too.  p is checked.  Both locks are taken here and every device block but the outputs is freed */
-static int world_surface_run(oslam_world *w, oslam_volume *vol, const oslam_world_surface_params *p, size_t cap, int with_out,
-                             int with_keys, world_run *o)
+int oslam_world_map_open(oslam_world *w, oslam_volume *vol, const oslam_world_surface_params *p, void *stream, oslam_world_map *o)
 {
     int rc = OSLAM_OK, a, kb0[3] = {0, 0, 0}, nb[3] = {0, 0, 0}, launched = 0;
     float voxel, origin0[3];
     int32_t *skeys = NULL;
     uint8_t *d_map = NULL;
-    uint32_t *d_cnt = NULL, tot[64];
-    size_t ns, nw = 0, n = 0, i, j, off_slots, off_words, c;
+    size_t ns, nw = 0, n = 0, i, j, off_slots, off_words;
     oslamk_brick_map m;
-    oslamk_brick_bases bases;
     oslam_world_stage *st;
-    void *stream = oslam_stream();
     memset(o, 0, sizeof *o);
     memset(&m, 0, sizeof m);
-    memset(&bases, 0, sizeof bases);
-    oslam_volume_lock();
-    oslam_world_lock(w);
     oslam_world_frame(w, &voxel, origin0);
     if (vol && !oslam_world_compatible(w, vol->p.voxel, vol->p.origin)) {
         rc = fail(OSLAM_E_INVALID, "the voxel store was made for another voxel size or origin");
@@ -88,7 +71,7 @@ static int world_surface_run(oslam_world *w, oslam_volume *vol, const oslam_worl
         nw = (size_t)nb[0] * (size_t)nb[1] * (size_t)nb[2];
     }
     o->window_bricks = (uint32_t)nw;
-    if (ns + nw == 0) goto done;                                    /* an empty map: no points, no device call */
+    if (ns + nw == 0) goto done;                                    /* an empty map: no device call */
     if (ns > OSLAMK_BRICK_MAX || ns + nw > OSLAMK_BRICK_MAX) { rc = fail(OSLAM_E_LIMIT, "a map holds at most 2^22 bricks"); goto done; }
     if (vol) o->dev = vol->dev;
     else {
@@ -133,7 +116,6 @@ static int world_surface_run(oslam_world *w, oslam_volume *vol, const oslam_worl
             }
             n++;
         }
-        o->bricks = (uint32_t)n;
         /* the device block: the same layout, then the window-only bricks, zeroed */
         KCHK(oslam_dev_alloc((void **)&d_map, off_words + sizeof(uint32_t) * OSLAMK_BRICK_WORDS * n));
         HIPCHK(hipMemcpyAsync(d_map, st[1].p, off_words + sizeof(uint32_t) * OSLAMK_BRICK_WORDS * ns, hipMemcpyHostToDevice,
@@ -151,8 +133,59 @@ static int world_surface_run(oslam_world *w, oslam_volume *vol, const oslam_worl
         KCHK(oslamk_brick_window(&m, &vol->k, vol->off, kb0, nb, stream));
         o->launches++;
     }
+    o->m = m;
+    o->d_map = d_map;
+    o->bricks = (uint32_t)n;
+done:
+    if (rc != OSLAM_OK) {
+        if (launched) (void)hipStreamSynchronize((hipStream_t)stream);
+        if (d_map) oslam_dev_free(d_map);
+    }
+    free(skeys);
+    return rc;
+}
+
+void oslam_world_map_close(oslam_world_map *o)
+{
+    if (o->d_map) oslam_dev_free(o->d_map);
+    o->d_map = NULL;
+}
+
+/* what one extraction leaves: the device blocks (NULL without points, or when they were not asked for) and the figures */
+typedef struct world_run {
+    float *d_out6;
+    int32_t *d_key;
+    uint32_t crossings, points, bricks, window_bricks, launches;
+    int32_t anchor[3];
+    int dev;
+} world_run;
+
+/* The extraction after the argument checks.  cap: the most points the caller takes; with_out 0 only counts; with_keys:
+ * the points' keys too.  p is checked.  Both locks are taken here and every device block but the outputs is freed */
+static int world_surface_run(oslam_world *w, oslam_volume *vol, const oslam_world_surface_params *p, size_t cap, int with_out,
+                             int with_keys, world_run *o)
+{
+    int rc = OSLAM_OK, launched = 0;
+    uint32_t *d_cnt = NULL, tot[64];
+    size_t n, c;
+    oslam_world_map wm;
+    oslamk_brick_bases bases;
+    void *stream = oslam_stream();
+    memset(o, 0, sizeof *o);
+    memset(&bases, 0, sizeof bases);
+    oslam_volume_lock();
+    oslam_world_lock(w);
+    rc = oslam_world_map_open(w, vol, p, stream, &wm);
+    memcpy(o->anchor, wm.anchor, sizeof o->anchor);
+    o->window_bricks = wm.window_bricks;
+    o->bricks = wm.bricks;
+    o->launches = wm.launches;
+    o->dev = wm.dev;
+    n = wm.bricks;
+    if (rc != OSLAM_OK || n == 0) goto done;                        /* an empty map: no points, no device call */
+    launched = 1;
     KCHK(oslam_counters_open(&d_cnt, n, stream));
-    KCHK(oslamk_brick_count(&m, p->min_weight, d_cnt + 64, d_cnt, stream));
+    KCHK(oslamk_brick_count(&wm.m, p->min_weight, d_cnt + 64, d_cnt, stream));
     o->launches += 1 + (uint32_t)((n + OSLAMK_BRICK_SCAN - 1) / OSLAMK_BRICK_SCAN);
     HIPCHK(hipMemcpyAsync(tot, d_cnt, sizeof tot, hipMemcpyDeviceToHost, (hipStream_t)stream));
     HIPCHK(hipStreamSynchronize((hipStream_t)stream));
@@ -169,7 +202,7 @@ static int world_surface_run(oslam_world *w, oslam_volume *vol, const oslam_worl
     if (with_out && o->points > 0 && (size_t)o->points <= cap) {
         KCHK(oslam_dev_alloc((void **)&o->d_out6, sizeof(float) * 6 * (size_t)o->points));
         if (with_keys) KCHK(oslam_dev_alloc((void **)&o->d_key, sizeof(int32_t) * 4 * (size_t)o->points));
-        KCHK(oslamk_brick_emit(&m, p->min_weight, d_cnt + 64, &bases, o->points, o->d_out6, o->d_key, stream));
+        KCHK(oslamk_brick_emit(&wm.m, p->min_weight, d_cnt + 64, &bases, o->points, o->d_out6, o->d_key, stream));
         HIPCHK(hipStreamSynchronize((hipStream_t)stream));
         o->launches++;
     }
@@ -182,8 +215,7 @@ done:
     oslam_world_unlock(w);
     oslam_volume_unlock();
     if (d_cnt) oslam_dev_free(d_cnt);
-    if (d_map) oslam_dev_free(d_map);
-    free(skeys);
+    oslam_world_map_close(&wm);
     return rc;
 }
 

@@ -342,6 +342,16 @@ class WorldSurfaceResult(C.Structure):
                 "anchor": tuple(int(x) for x in self.anchor), "ms_total": float(self.ms_total)}
 
 
+class WorldMeshResult(C.Structure):
+    _fields_ = [("vertices", C.c_uint32), ("triangles", C.c_uint32), ("cubes", C.c_uint32), ("bricks", C.c_uint32),
+                ("window_bricks", C.c_uint32), ("launches", C.c_uint32), ("anchor", C.c_int32 * 3), ("ms_total", C.c_float)]
+
+    def asdict(self):
+        return {"vertices": int(self.vertices), "triangles": int(self.triangles), "cubes": int(self.cubes),
+                "bricks": int(self.bricks), "window_bricks": int(self.window_bricks), "launches": int(self.launches),
+                "anchor": tuple(int(x) for x in self.anchor), "ms_total": float(self.ms_total)}
+
+
 class NormalsParams(C.Structure):
     _fields_ = [("radius", C.c_float), ("min_neighbours", C.c_uint), ("viewpoint", C.c_float * 3), ("orient", C.c_int),
                 ("line_ratio", C.c_float), ("reserved", C.c_int * 4)]
@@ -506,6 +516,8 @@ _SIGNATURES = {
     "oslam_world_surface_params_default": (_i, [C.POINTER(WorldSurfaceParams)]),
     "oslam_world_surface": (_i, [_vp, _vp, C.POINTER(WorldSurfaceParams), _vp, _vp, _vp, _sz, C.POINTER(_sz),
                                  C.POINTER(WorldSurfaceResult)]),
+    "oslam_world_mesh": (_i, [_vp, _vp, C.POINTER(WorldSurfaceParams), _vp, _vp, _vp, _sz, _vp, _sz, C.POINTER(_sz),
+                              C.POINTER(_sz), C.POINTER(WorldMeshResult)]),
     "oslam_world_bricks": (_i, [_vp, _vp, _sz, C.POINTER(_sz)]),
     "oslam_scene_from_world": (_i, [_vp, _vp, C.POINTER(WorldSurfaceParams), _f, _f, _u, C.POINTER(Params), C.POINTER(_vp),
                                     C.POINTER(_sz)]),
@@ -2172,6 +2184,26 @@ class World:
                                              C.byref(n), C.byref(res)))
         self.last_surface = res.asdict()
         return (po, no, ko) if keys else (po, no)
+
+    def mesh(self, vol=None, min_weight=1, normals=True, anchor=None, keys=False, dev=0):
+        """The marching-cubes mesh of the whole map, this store plus the window of the Volume vol (None: the store alone,
+        on device dev) (oslam_world_mesh): -> (vertices [nv,3], normals [nv,3] or None, triangles uint32 [nt,3], result
+        dict) and with keys=True also int32 [nv,4], (g_x, g_y, g_z, axis) of every vertex.  The vertices are every
+        crossing of World.surface's rule in its order, (0, 0, 0) as the normal where there is none; normals=False skips
+        the trilinear reads.  ply_write_mesh takes the output as it is.  The result dict is kept as self.last_mesh."""
+        sp = _world_surface_params(min_weight, anchor, dev)
+        vh = vol._h if vol is not None else None
+        nv, nt, res = C.c_size_t(0), C.c_size_t(0), WorldMeshResult()
+        _check(lib().oslam_world_mesh(self._h, vh, C.byref(sp), None, None, None, 0, None, 0, C.byref(nv), C.byref(nt), C.byref(res)))
+        xyz = np.zeros((nv.value, 3), np.float32)
+        nrm = np.zeros((nv.value, 3), np.float32) if normals else None
+        ko = np.zeros((nv.value, 4), np.int32)
+        tri = np.zeros((nt.value, 3), np.uint32)
+        if nv.value:
+            _check(lib().oslam_world_mesh(self._h, vh, C.byref(sp), _p(xyz), _p(nrm) if normals else None, _p(ko) if keys else None,
+                                          nv.value, _p(tri), nt.value, C.byref(nv), C.byref(nt), C.byref(res)))
+        self.last_mesh = res.asdict()
+        return (xyz, nrm, tri, self.last_mesh, ko) if keys else (xyz, nrm, tri, self.last_mesh)
 
     def stats(self):
         s = WorldStats()

@@ -1174,6 +1174,58 @@ def worldsurface(calls=20):
     return out
 
 
+def worldmesh(calls=20):
+    """The mesh of the whole map (oslam_world_mesh) on worldsurface's map: the reload configuration's 256^3 volume after
+    its out-and-back stream, shifted through a store by (64, 0, 0).  In one run and alternately, so that drift hits
+    both alike: the median of `calls` calls of World.mesh(vol) and of World.surface(vol); then, alternately as well,
+    Volume.mesh() and Volume.surface(), which see the window alone.  Vertices, triangles, cubes, bricks and the
+    library's own clock are in the output."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import camera_ref as E
+    world = E.make_world(synth, 0)
+    sweep = E.trajectory(synth, 0, frames=10)
+    cam = E.CAM
+    rendered = [ppf.View(E.render(synth, world, T), cam["fx"], cam["fy"], cam["cx"], cam["cy"], z_min=cam["z_min"],
+                         z_max=cam["z_max"], max_jump=E.MAX_JUMP) for T in sweep]
+    spec = dict(nx=256, ny=256, nz=256, voxel=0.036, origin=[-2.9, -4.3, 0.3], mu=0.288)
+    vol = ppf.Volume(**spec)
+    steps = [vol.step(rendered[k]) for k in list(range(10)) + list(range(8, -1, -1))]
+    store = ppf.World(vol)
+    moved = vol.shift((64, 0, 0), store)
+    store.mesh(vol); store.surface(vol)                             # the staging buffer and the kept device blocks
+    vol.mesh(); vol.surface()
+    ms_m, ms_s, lib_m, lib_s, ms_vm, ms_vs = [], [], [], [], [], []
+    for _ in range(calls):
+        t = time.perf_counter(); store.mesh(vol); ms_m.append(1e3 * (time.perf_counter() - t))
+        lib_m.append(store.last_mesh["ms_total"])
+        t = time.perf_counter(); store.surface(vol); ms_s.append(1e3 * (time.perf_counter() - t))
+        lib_s.append(store.last_surface["ms_total"])
+    for _ in range(calls):
+        t = time.perf_counter(); _, _, _, vm = vol.mesh(); ms_vm.append(1e3 * (time.perf_counter() - t))
+        t = time.perf_counter(); _, _, vs = vol.surface(); ms_vs.append(1e3 * (time.perf_counter() - t))
+    t = time.perf_counter(); store.mesh(vol, normals=False); ms_bare = 1e3 * (time.perf_counter() - t)
+    mres, sres, st = store.last_mesh, store.last_surface, store.stats()
+    out = {"config": "worldmesh (oslam_world_mesh): the reload configuration's 256^3 map after its 19-frame stream, shifted by (64, 0, 0) through the store",
+           "volume": spec, "calls": calls, "step_ok": [None if r is None else r["ok"] for _, r in steps],
+           "stored_by_the_shift": moved["stored"], "store": st,
+           "world_mesh_ms_median": float(np.median(ms_m)), "world_mesh_ms_library_median": float(np.median(lib_m)),
+           "world_surface_ms_median": float(np.median(ms_s)), "world_surface_ms_library_median": float(np.median(lib_s)),
+           "world_mesh_over_world_surface": float(np.median(ms_m) / np.median(ms_s)),
+           "world_mesh_without_normals_ms_once": ms_bare,
+           "volume_mesh_ms_median": float(np.median(ms_vm)), "volume_surface_ms_median": float(np.median(ms_vs)),
+           "volume_mesh_over_volume_surface": float(np.median(ms_vm) / np.median(ms_vs)),
+           "world_mesh_over_volume_mesh": float(np.median(ms_m) / np.median(ms_vm)),
+           "vertices": mres["vertices"], "triangles": mres["triangles"], "cubes": mres["cubes"], "bricks": mres["bricks"],
+           "window_bricks": mres["window_bricks"], "store_bricks": st["bricks"], "launches": mres["launches"],
+           "world_surface_points": sres["points"], "window_vertices": vm["vertices"], "window_triangles": vm["triangles"],
+           "window_cubes": vm["cubes"], "window_points": vs["points"]}
+    for v in rendered:
+        v.close()
+    store.close()
+    vol.close()
+    return out
+
+
 def pyramid(calls=20):
     """Image pyramids (oslam_pyramid_create, oslam_pyramid_egomotion) on frames 0 and 1 of the camera configuration's
     640x480 stream: the median of `calls` calls of Pyramid(view), of egomotion_pyramid and, in the same run, of egomotion
@@ -1314,4 +1366,4 @@ if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "cfg3"
     print(json.dumps({"cfg2": cfg2, "cfg3": cfg3, "cfg3db": cfg3db, "cfg4": cfg4, "cfg5": cfg5, "planes": planes, "db50": db50,
                       "refine": refine, "verify": verify, "instances": instances, "arbitrate": arbitrate, "explain": explain, "track": track, "camera": camera,
-                      "fusion": fusion, "colour": colour, "surface": surface, "mesh": mesh, "shift": shift, "reload": reload, "worldsurface": worldsurface, "pyramid": pyramid, "bilateral": bilateral, "normals": normals}[which]()), flush=True)
+                      "fusion": fusion, "colour": colour, "surface": surface, "mesh": mesh, "shift": shift, "reload": reload, "worldsurface": worldsurface, "worldmesh": worldmesh, "pyramid": pyramid, "bilateral": bilateral, "normals": normals}[which]()), flush=True)
