@@ -1943,6 +1943,13 @@ int oslam_model_key_numbers(oslam_model *m, uint32_t *keys_out, uint32_t *number
 int oslam_vote_ref_order(const uint32_t *keep, size_t n, uint32_t *order_out);
 /* Dense accumulator acc[M][32] of scene reference point ref_index after voting. */
 int oslam_vote_accumulator(oslam_model *m, oslam_scene *s, size_t ref_index, uint32_t *acc_out);
+/* The hit list of scene reference point ref_index as the votes read it, sorted by key number: per hit the number of
+ * its key (oslam_model_key_numbers), theta_v in units of 2^-22 turn (0xffffffff: always re-evaluated) and the scene
+ * index of the pair's second point; at most cap of each are copied (any may be NULL), *n_out = the number of hits.
+ * *keep_out (may be NULL) = the pairs of the reference point whose distance bin can reach a model key: the places
+ * its list was given. */
+int oslam_vote_hits(oslam_model *m, oslam_scene *s, size_t ref_index, uint32_t *numbers_out, uint32_t *theta_out,
+                    uint32_t *idx_out, size_t cap, size_t *n_out, uint32_t *keep_out);
 /* Cells kept by the last oslam_align / oslam_align_finish on this model, in
  * the order (count desc, code asc); poses_out (may be NULL) gets 16 floats per cell. */
 int oslam_last_cells(oslam_model *m, oslam_cell *cells_out, float *poses_out, size_t cap,

@@ -77,9 +77,11 @@ struct oslam_scene {
     unsigned df;
     int rank, world;
     int n_ref;
-    uint32_t *h_ref_idx, *d_ref_idx;
+    uint32_t *h_ref_idx, *d_ref_idx;  /* d_ref_idx and d_tsg: pieces of d_block */
     float *d_tsg;
     float *d_Ts16;                    /* frames of every reference-point candidate (index % df == 0, all ranks) */
+    uint32_t *d_block;                /* one block: the points in Morton order, the permutation, the group boxes; d_ref_idx; d_tsg */
+    oslamk_order order;               /* the first of its pieces (oslam_scene.c: scene_order_fill) */
     struct oslam_scene_grid *grids;   /* uniform grids of the refinement stage (oslam_refine.c), NULL until the first */
 };
 
@@ -211,6 +213,8 @@ typedef struct oslam_vote_times {
     uint32_t launches;                /* batches */
     uint64_t probed;                  /* pairs within reach */
 } oslam_vote_times;
+int oslam_pool_read_hits(const scratch_pool *p, uint32_t *numbers_out, uint32_t *theta_out, uint32_t *idx_out, size_t cap,
+                         size_t *n_out, uint32_t *keep_out);
 int oslam_run_votes_group(scratch_pool *pool, oslam_model *const *ms, int nm, oslam_scene *s, const uint32_t *d_ref_idx,
                           const float *d_tsg, int n_ref, uint32_t fixed_gmax, uint32_t *acc_dump, oslamk_counters *cnt,
                           oslam_vote_times *t);

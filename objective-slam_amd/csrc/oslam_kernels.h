@@ -73,6 +73,20 @@ typedef struct oslamk_cloud {
     int n;
 } oslamk_cloud;
 
+/* A scene's points a second time, in an order that keeps neighbours together (Morton order of the positions: oslam_scene.c), for
+ * phase 1 of the scene-key kernels alone: 64 consecutive points of it are one group with a bounding box, and a
+ * (reference point, group) whose box cannot hold a pair within reach is dropped with one test instead of 64.
+ *   sx sy sz : the positions in that order (the same floats as scene.px py pz)
+ *   perm     : perm[k] = the scene's own index of the point at place k
+ *   box      : [ceil(n / 64)][6] min x y z, max x y z of each group; all NaN for a group that holds a coordinate
+ *              that is not finite (pc_box_bin_range then gives no range and the group is never dropped) */
+typedef struct oslamk_order {
+    const float *sx, *sy, *sz;
+    const uint32_t *perm;
+    const float *box;
+} oslamk_order;
+#define OSLAMK_ORDER_GROUP 64
+
 /* Bucket of one key in one slice, addressed directly by the key's slot in the union table:
  * what a vote workgroup reads instead of probing (the scene-key kernel already found the slot). */
 typedef struct oslamk_uinfo {
@@ -220,6 +234,7 @@ typedef struct oslamk_vote_args {
      * permutation of 0 .. n_launch-1; NULL = identity.  The host orders it by descending demand, so that the last
      * rounds of workgroups are light ones.  A value outside the batch means no work */
     const uint32_t *ref_order;
+    oslamk_order order;        /* the scene in groups of neighbours, what phase 1 of the scene-key kernels walks */
 } oslamk_vote_args;
 
 /* fill t.uinfo from the slice tables (after oslamk_table_scan / oslamk_union_build and the fill pass) */

@@ -175,7 +175,10 @@ int oslam_vote_ref_order(const uint32_t *keep, size_t n, uint32_t *order_out)
     return OSLAM_OK;
 }
 
-int oslam_vote_accumulator(oslam_model *m, oslam_scene *s, size_t ref_index, uint32_t *acc_out)
+/* one reference point through the kernels of a registration: its accumulator (acc_out, may be NULL) and, with n_out, its
+ * sorted hit list and demand (oslam_pool_read_hits) */
+static int tap_one_ref(oslam_model *m, oslam_scene *s, size_t ref_index, uint32_t *acc_out, uint32_t *numbers_out,
+                       uint32_t *theta_out, uint32_t *idx_out, size_t cap, size_t *n_out, uint32_t *keep_out)
 {
     int rc = OSLAM_OK;
     uint32_t *d_dump = NULL, *d_ref = NULL, *h_dump = NULL;
@@ -187,7 +190,7 @@ int oslam_vote_accumulator(oslam_model *m, oslam_scene *s, size_t ref_index, uin
     size_t cells;
     rc = oslam_check_pair(m, s);
     if (rc != OSLAM_OK) return rc;
-    if (!acc_out || ref_index >= (size_t)s->c.n) return fail(OSLAM_E_INVALID, "bad reference index");
+    if (ref_index >= (size_t)s->c.n) return fail(OSLAM_E_INVALID, "bad reference index");
     cells = (size_t)m->table.n_slices * OSLAMK_SLICE * OSLAMK_NBIN;
     oslam_T_g_rows(s->c.h_xyz, s->c.h_nrm, &ref, 1, rows);
     rc = oslam_pool_enter(m->dev, &pool);
@@ -200,10 +203,16 @@ int oslam_vote_accumulator(oslam_model *m, oslam_scene *s, size_t ref_index, uin
     /* one reference point through the same kernels; fixed_gmax = all ones: nothing is emitted */
     rc = oslam_run_votes_group(pool, &m, 1, s, d_ref, d_tsg, 1, 0xffffffffu, d_dump, &cnt, NULL);
     if (rc != OSLAM_OK) goto done;
-    h_dump = (uint32_t *)malloc(sizeof(uint32_t) * cells);
-    if (!h_dump) { rc = fail(OSLAM_E_NOMEM, "host allocation failed"); goto done; }
-    HIPCHK(hipMemcpy(h_dump, d_dump, sizeof(uint32_t) * cells, hipMemcpyDeviceToHost));
-    memcpy(acc_out, h_dump, sizeof(uint32_t) * OSLAMK_NBIN * (size_t)m->c.n);
+    if (n_out) {
+        rc = oslam_pool_read_hits(pool, numbers_out, theta_out, idx_out, cap, n_out, keep_out);
+        if (rc != OSLAM_OK) goto done;
+    }
+    if (acc_out) {
+        h_dump = (uint32_t *)malloc(sizeof(uint32_t) * cells);
+        if (!h_dump) { rc = fail(OSLAM_E_NOMEM, "host allocation failed"); goto done; }
+        HIPCHK(hipMemcpy(h_dump, d_dump, sizeof(uint32_t) * cells, hipMemcpyDeviceToHost));
+        memcpy(acc_out, h_dump, sizeof(uint32_t) * OSLAMK_NBIN * (size_t)m->c.n);
+    }
 done:
     oslam_pool_unlock(pool);
     free(h_dump);
@@ -211,6 +220,20 @@ done:
     if (d_ref) (void)hipFree(d_ref);
     if (d_tsg) (void)hipFree(d_tsg);
     return rc;
+}
+
+int oslam_vote_accumulator(oslam_model *m, oslam_scene *s, size_t ref_index, uint32_t *acc_out)
+{
+    if (!acc_out) return fail(OSLAM_E_INVALID, "bad reference index");
+    return tap_one_ref(m, s, ref_index, acc_out, NULL, NULL, NULL, 0, NULL, NULL);
+}
+
+int oslam_vote_hits(oslam_model *m, oslam_scene *s, size_t ref_index, uint32_t *numbers_out, uint32_t *theta_out,
+                    uint32_t *idx_out, size_t cap, size_t *n_out, uint32_t *keep_out)
+{
+    if (!n_out) return fail(OSLAM_E_INVALID, "NULL argument");
+    *n_out = 0;
+    return tap_one_ref(m, s, ref_index, NULL, numbers_out, theta_out, idx_out, cap, n_out, keep_out);
 }
 
 /* the taps read the last result from the host: fetch it if it is still on the device */

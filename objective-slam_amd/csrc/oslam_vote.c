@@ -210,6 +210,41 @@ static void carve_scratch(oslamk_vote_args *a, const scratch_pool *p, size_t slo
     a->hit_key = (uint32_t *)b;
 }
 
+/* Parity tap: the sorted hit list of the pass that just ran in the pool with ONE reference point (oslam_run_votes_group,
+ * waited for): per hit the key's number, theta_v (oslamk_pay.theta_t22) and the scene index, at most cap of each, *n_out
+ * = the number of hits; *keep_out = the reference point's demand (k_scene_count).  The caller holds the pool. */
+int oslam_pool_read_hits(const scratch_pool *p, uint32_t *numbers_out, uint32_t *theta_out, uint32_t *idx_out, size_t cap,
+                         size_t *n_out, uint32_t *keep_out)
+{
+    int rc = OSLAM_OK;
+    oslamk_vote_args a;
+    oslamk_pay *pay = NULL;
+    uint32_t n = 0;
+    size_t i, m;
+    *n_out = 0;
+    if (keep_out) *keep_out = ((const uint32_t *)p->b[BUF_COUNTS].h)[0];
+    if (p->plan.nb < 1) return OSLAM_OK;             /* no pair within reach: no batch, no list */
+    carve_scratch(&a, p, p->plan.b[0].slots);
+    HIPCHK(hipMemcpy(&n, (const uint32_t *)p->b[BUF_COUNTS].d + p->b[BUF_COUNTS].cap, sizeof n, hipMemcpyDeviceToHost));
+    *n_out = n;
+    m = n < cap ? n : cap;
+    if (!m) return OSLAM_OK;
+    pay = (oslamk_pay *)malloc(sizeof *pay * m);
+    if (!pay) return fail(OSLAM_E_NOMEM, "host allocation failed");
+    HIPCHK(hipMemcpy(pay, a.hit_sorted, sizeof *pay * m, hipMemcpyDeviceToHost));
+    if (numbers_out) {
+        HIPCHK(hipMemcpy(numbers_out, a.hit_key, sizeof(uint32_t) * m, hipMemcpyDeviceToHost));
+        for (i = 0; i < m; i++) numbers_out[i] &= 0x7fffffffu;        /* bit 31: the run holds a marker */
+    }
+    for (i = 0; i < m; i++) {
+        if (theta_out) theta_out[i] = pay[i].theta_t22;
+        if (idx_out) idx_out[i] = pay[i].idx;
+    }
+done:
+    free(pay);
+    return rc;
+}
+
 /* The order in which the vote grid takes the n reference points of a batch: order[p] = the reference point of dispatch
  * position p, by descending demand keep[] (the pairs within reach: what the hit lists are sized by, and a measure of
  * the votes that needs no pass of its own).  The vote workgroups fill a CU each and go out in position order, so the
@@ -287,6 +322,7 @@ static void pass_open(vote_pass *v, scratch_pool *pool, oslam_model *const *ms, 
     for (j = 1; j < nm && v->one_grid; j++)
         if ((ms[j]->params.vote_mode == OSLAM_VOTE_FAST) != (ms[0]->params.vote_mode == OSLAM_VOTE_FAST)) v->one_grid = 0;
     v->a.scene = s->c.k;
+    v->a.order = s->order;
     v->a.ref_idx = d_ref_idx;
     v->a.tsg = d_tsg;
     v->a.n_ref = n_ref;

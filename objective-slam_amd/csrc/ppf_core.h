@@ -39,6 +39,34 @@ PM_HD int pc_pair_dist_bin(float dx, float dy, float dz, float d_dist, float inv
     return k;
 }
 
+/* The distance bins that the pairs (p, any point of an axis-aligned box) can fall into: *kmin <= pc_pair_dist_bin of
+ * every such pair <= *kmax.  box = {min x, y, z, max x, y, z}.  Returns 0 where no range can be given (a coordinate
+ * that is not finite, a quotient beyond 2^20 bins, or box and point closer than 1e-15, where the squares underflow):
+ * the caller then has to look at the pairs themselves.  Conservative, never tight.
+ * The slack: against the real distance, the float distance of a pair is off by at most 3.5 u relative (u = 2^-24: one
+ * rounding of each difference, 3 u on its square, 2 u on the sums, halved by the root, one more for the root), and
+ * so are the two bounds here against the real nearest and farthest distance; inv_d_dist, the product with it and
+ * the product with 1 +- slack add 3 u.  pc_pair_dist_bin is the exact floor of the pair's float distance over
+ * d_dist, so 10 u = 6e-7 covers everything; the slack is 2^-16 = 256 u. */
+#define PC_BOX_SLACK 1.52587890625e-05f
+PM_HD int pc_box_bin_range(const float *box, float px, float py, float pz, float inv_d_dist, int *kmin, int *kmax)
+{
+    const float ax = box[0] - px, bx = px - box[3];        /* > 0: p lies below / above the box on this axis */
+    const float ay = box[1] - py, by = py - box[4];
+    const float az = box[2] - pz, bz = pz - box[5];
+    const float mx = ax > bx ? ax : bx, my = ay > by ? ay : by, mz = az > bz ? az : bz;
+    const float lx = mx > 0.0f ? mx : 0.0f, ly = my > 0.0f ? my : 0.0f, lz = mz > 0.0f ? mz : 0.0f;
+    const float hx = -ax > -bx ? -ax : -bx, hy = -ay > -by ? -ay : -by, hz = -az > -bz ? -az : -bz;
+    const float h2 = hx * hx + hy * hy + hz * hz;
+    const float lo = pm_sqrtf(lx * lx + ly * ly + lz * lz) * inv_d_dist * (1.0f - PC_BOX_SLACK);
+    const float hi = pm_sqrtf(h2) * inv_d_dist * (1.0f + PC_BOX_SLACK);
+    /* written so that a NaN anywhere fails the test: a + b = min - max of the box, NaN if either is or the point is */
+    if (!(ax + bx <= 0.0f && ay + by <= 0.0f && az + bz <= 0.0f && h2 >= 1e-30f && hi < 1048576.0f && lo <= hi)) return 0;
+    *kmin = (int)lo;
+    *kmax = (int)hi;
+    return 1;
+}
+
 /* Key of the ordered pair (p1,n1) -> (p2,n2); 0 when the distance is not a
  * finite number (the reference maps NaN in .x to key 0, kernel.cu:467-469).
  * n1n = norm(n1) is passed in because the caller keeps it per point. */

@@ -550,6 +550,7 @@ _SIGNATURES = {
     "oslam_model_bucket": (_i, [_vp, C.c_uint32, _vp, _sz, C.POINTER(_sz)]),
     "oslam_model_bucket_words": (_i, [_vp, C.c_uint32, _i, _vp, _sz, C.POINTER(_sz)]),
     "oslam_vote_accumulator": (_i, [_vp, _vp, _sz, _vp]),
+    "oslam_vote_hits": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _sz, C.POINTER(_sz), C.POINTER(C.c_uint32)]),
     "oslam_model_key_numbers": (_i, [_vp, _vp, _vp, _vp, _sz, C.POINTER(_sz)]),
     "oslam_vote_ref_order": (_i, [_vp, _sz, _vp]),
     "oslam_last_cells": (_i, [_vp, _vp, _vp, _sz, C.POINTER(_sz)]),
@@ -1384,6 +1385,16 @@ class Model:
         acc = np.zeros((self.n, 32), np.uint32)
         _check(lib().oslam_vote_accumulator(self._h, scene._h, int(ref_index), _p(acc)))
         return acc
+
+    def vote_hits(self, scene, ref_index):
+        """(numbers, theta_v, scene indices, keep) of one scene reference point: its hit list as the votes read it,
+        sorted by key number, and the places the list was given (the pairs whose distance bin is within reach)."""
+        n, keep = C.c_size_t(0), C.c_uint32(0)
+        _check(lib().oslam_vote_hits(self._h, scene._h, int(ref_index), None, None, None, 0, C.byref(n), C.byref(keep)))
+        num, th, idx = (np.zeros(n.value, np.uint32) for _ in range(3))
+        if n.value:
+            _check(lib().oslam_vote_hits(self._h, scene._h, int(ref_index), _p(num), _p(th), _p(idx), n.value, C.byref(n), C.byref(keep)))
+        return num, th, idx, int(keep.value)
 
     def close(self):
         if getattr(self, "_db", None) is not None:
