@@ -1589,14 +1589,44 @@ int oslam_volume_follow(oslam_volume *vol, const float T_vol_cam[16], const osla
  * oslam_volume_pack is a test tap and changes nothing: the records {lin, word} that k_tsdf_pack_count and
  *   k_tsdf_pack_emit make for this shift, lin = (k * ny + j) * nx + i of the old window, ascending.  cap == 0 counts only
  *   (the outputs may be NULL); more records than cap is OSLAM_E_LIMIT with the count in *n_out and nothing written.
- * Out of scope: store files on disk, colour, several GPUs, any change to oslam_tracker.  (The one surface of store plus
- *   window is oslam_world_surface below, their one mesh oslam_world_mesh.) */
+ * Colour.  A store keeps colour when it is created with oslam_world_params.colour = 1 (oslam_world_params_of writes 0:
+ *   the store of before, bit for bit: 2064 bytes per brick, the same stats, the same launches).  A colour store's bricks
+ *   carry a second array of 512 colour words (4112 bytes per brick; bytes, max_bytes and the rollback count that): a
+ *   voxel's colour word r | g << 8 | b << 16 | wc << 24 is stored under its g, as it is, whenever its TSDF word is stored.
+ *   That means seen voxels only, whatever their wc; the colour of an unseen voxel that leaves is dropped.  The bricks are
+ *   created with both arrays, so storing still cannot fail.  The restatement in numpy is tests/reload_colour_ref.py.
+ *   oslam_world_has_colour: 1 for a colour store, 0 otherwise (NULL included).  oslam_world_put_colour is oslam_world_put
+ *   with the colour word of every record (colours [n]); OSLAM_E_INVALID on a plain store.  On a colour store plain
+ *   oslam_world_put stores colour 0 (a later record wins, colour included).  oslam_world_box_colour is oslam_world_box with
+ *   a second dense output for the colour words, 0 where nothing is stored; take removes word and colour; oslam_world_box's
+ *   limits; OSLAM_E_INVALID on a plain store.  Plain oslam_world_box on a colour store reads the words.
+ *   The shift.  With a coloured volume and a colour store every leaving record takes its voxel's colour word along, and
+ *   every reloaded record brings its colour word back, into the colour buffer that the shift of the colours wrote and
+ *   that is swapped in with it.  A colour store with a volume without colour is OSLAM_E_INVALID before any device call,
+ *   with nothing changed.  A coloured volume through a plain store behaves as before: the colours move with the window,
+ *   what leaves loses its colour and what is reloaded comes back with wc = 0.
+ *   The invariant, extended: with no integration in between, a path of shifts that returns to an earlier offset restores
+ *   the colour words of the window's seen voxels bit for bit and leaves the store as it was.  Colour words of unseen
+ *   voxels behave as their TSDF words do under the plain shift: kept while they stay in the window, 0 once they have left.
+ *   Cost.  A record crosses the host link as 12 bytes instead of 8: the colours are gathered behind k_tsdf_pack_emit into
+ *   the block that holds the records (k_pack_colours, one thread per record, by the record's lin) and go down in the
+ *   records' copy; on the way up they ride in the records' copy too and are scattered behind the colours' k_tsdf_shift
+ *   (k_unpack_colours).  The pinned staging buffers are sized for it.  The number of host waits does not grow.  launches
+ *   = the count above for a coloured volume (one more than for a volume without colour) + 1 when something seen leaves +
+ *   1 when something is reloaded: 8 with records on both sides, 4 with none.  Failure changes nothing, as above, for both
+ *   buffers and the store.
+ *   oslam_volume_pack_colour is oslam_volume_pack with the records' colour words (colour_out [cap]), as a colour store
+ *   gets them; OSLAM_E_INVALID on a volume without colour.
+ * Out of scope: store files on disk, colour in the hand-over list of oslam_volume_leaving, several GPUs, any change to
+ *   oslam_tracker.  (The one surface of store plus window is oslam_world_surface below, their one mesh oslam_world_mesh,
+ *   the colour at their points oslam_world_colours.) */
 typedef struct oslam_world oslam_world;
 typedef struct oslam_world_params {
     float voxel;               /* the voxel size of the volumes the store serves, metres */
     float origin0[3];          /* their created origin */
     uint64_t max_bytes;        /* bound on bricks plus table, 0 = 1 GiB */
-    int reserved[4];
+    int colour;                /* 1 = a colour store: every brick keeps a colour word next to each TSDF word; 0 = none */
+    int reserved[3];
 } oslam_world_params;
 
 typedef struct oslam_world_stats {
@@ -1622,6 +1652,12 @@ int oslam_world_put(oslam_world *w, const int32_t *g, const uint32_t *words, siz
 int oslam_world_box(oslam_world *w, const int32_t lo[3], const int32_t hi[3], uint32_t *words_out, int take);
 int oslam_volume_shift_world(oslam_volume *vol, oslam_world *w, const int shift[3], oslam_reload_result *res);
 int oslam_volume_pack(oslam_volume *vol, const int shift[3], uint32_t *lin_out, uint32_t *word_out, size_t cap, size_t *n_out);
+int oslam_world_has_colour(const oslam_world *w);
+int oslam_world_put_colour(oslam_world *w, const int32_t *g, const uint32_t *words, const uint32_t *colours, size_t n);
+int oslam_world_box_colour(oslam_world *w, const int32_t lo[3], const int32_t hi[3], uint32_t *words_out, uint32_t *colours_out,
+                           int take);
+int oslam_volume_pack_colour(oslam_volume *vol, const int shift[3], uint32_t *lin_out, uint32_t *word_out, uint32_t *colour_out,
+                             size_t cap, size_t *n_out);
 
 /* ---- the surface of the whole map: voxel store plus window as one cloud, extracted on the device from sparse
  * 8 x 8 x 8 bricks with no dense box anywhere.  The restatement in numpy is tests/world_surface_ref.py; device and
@@ -1672,7 +1708,8 @@ int oslam_volume_pack(oslam_volume *vol, const int shift[3], uint32_t *lin_out, 
  *   and yields nothing.  Then k_brick_count, one k_surface_scan per 2^17 bricks, one copy back and host wait for the
  *   totals, k_brick_emit into a block of exactly the points' size and one more wait.  Device memory is freed before
  *   return on every path.
- * Out of scope: colour, store files on disk, several GPUs.  (The mesh of the whole map is oslam_world_mesh below.) */
+ * Out of scope: colours written by the extraction itself (oslam_world_colours below colours the points afterwards), store
+ *   files on disk, several GPUs.  (The mesh of the whole map is oslam_world_mesh below.) */
 typedef struct oslam_world_surface_params {
     unsigned min_weight;       /* 1..65535, default 1: a voxel is seen from this weight on */
     int anchor_set;            /* 0: the window's offset, or 0 without a volume */
@@ -1743,8 +1780,8 @@ int oslam_scene_from_world(oslam_world *w, oslam_volume *vol, const oslam_world_
  *   voxel, this one or a +x/+y/+z neighbour: its index is that entry's first vertex plus the rank of 3 * (voxel in the
  *   brick) + a among the entry's at most 1536 ids, found by binary search.  Device memory besides the map and the outputs:
  *   those two counters and one uint32 id per vertex; nothing proportional to the number of voxels.
- * Out of scope: colour (the store keeps none; oslam_volume_colours answers for vertices inside the window), merging or
- *   decimating triangles, dropping unreferenced vertices, store files on disk, several GPUs. */
+ * Out of scope: colours written by the extraction itself (oslam_world_colours below colours the vertices afterwards),
+ *   merging or decimating triangles, dropping unreferenced vertices, store files on disk, several GPUs. */
 typedef struct oslam_world_mesh_result {
     uint32_t vertices;         /* crossings: equals oslam_world_surface_result.crossings */
     uint32_t triangles;
@@ -1882,15 +1919,46 @@ int oslam_ply_read_mesh(const char *path, float **xyz_out, float **nrm_out, uint
  *   *painted_out (may be NULL) = the pixels that got a colour.
  * The moving window: oslam_volume_shift moves the colours with the TSDF words (the same kernel on the colour buffer into
  *   a second spare buffer: oslam_shift_result.launches is 2 on a coloured volume; when a spare cannot be allocated
- *   neither buffer moves).  oslam_volume_shift_world shifts the colours the same way (one launch more), but the voxel
- *   store keeps no colour: voxels that leave lose theirs, and voxels that are reloaded come back with wc = 0 until they
- *   are seen again.
+ *   neither buffer moves).  oslam_volume_shift_world shifts the colours the same way (one launch more).  Through a
+ *   plain store voxels that leave lose their colour, and voxels that are reloaded come back with wc = 0 until they are
+ *   seen again; a colour store (oslam_world_params.colour) keeps the colour word of every voxel it keeps and gives it
+ *   back (above, at oslam_volume_shift_world, "Colour").
  * The PLY writers with colour write the vertex element of oslam_ply_write / oslam_ply_write_mesh plus property uchar
  *   red, green, blue; oslam_ply_read and oslam_ply_read_mesh skip them.
  * Arguments are checked before any device call: NULL pointers, a pose that is not rigid, parameters outside their
  *   ranges, views and volumes on different devices, a c without colour or with another size or other intrinsics, and a
  *   volume without colour where one is needed are OSLAM_E_INVALID, with nothing changed.
- * Out of scope: colour in the voxel store, colour through bilateral, mask and pyramid views, a colour term in tracking,
+ * The colour of the whole map.  oslam_world_colours(w, vol, sp, xyz, n, stride_bytes, rgb_out, valid_out, n_valid_out) is
+ *   oslam_volume_colours against colour store plus window, with its arguments and outputs; it serves the points of
+ *   oslam_world_surface and the vertices of oslam_world_mesh, which go up from the host as they do for the volume.  The
+ *   restatement in numpy is tests/world_colour_ref.py; device and restatement agree byte for byte.
+ *   The map.  Gc(g) is the volume's colour word inside the window's box and the store's colour word elsewhere, or 0:
+ *   oslam_world_surface's G with "a store entry inside the window's box is ignored".  With vol == NULL the store stands
+ *   alone.  The frame.  sp (NULL = defaults) gives the anchor A and with it O = origin(A), oslam_world_surface's word for
+ *   word; sp->dev picks the device when vol is NULL; min_weight is checked and not used.  Points are to be coloured with
+ *   the anchor they were extracted with.
+ *   The rule is the colour at a volume-frame point above, float sequence unchanged: u = (P - O) * inv_voxel, g = u - 0.5f,
+ *   b = floorf(g), f = g - b; the range test on b becomes "finite and |b| < 2^22"; the eight corners are Gc at A + b +
+ *   (0|1); with all eight wc > 0 the channels are blended, rounded and clipped as there.  Otherwise the voxel A +
+ *   floorf(u), under the same range test, gives its colour if its wc > 0; it is looked up on its own, not taken from the
+ *   corners.  Otherwise there is no colour: valid 0 and rgb 0.  A NaN or infinite coordinate reads nothing.
+ *   Two pins.  (a) A dense coloured oslam_volume with the same voxel and created origin, at offset A, that holds G and Gc
+ *   over a box that contains every coloured voxel of the map gives the same bytes through oslam_volume_colours at every
+ *   point; no margin is needed, because outside the box both read "uncoloured".  (b) With the default anchor a point whose
+ *   eight corners and nearest voxel all lie inside the window gets the bytes oslam_volume_colours(vol) gives it.
+ *   Device side.  The ascending key table of oslam_world_surface with the brick array holding colour words: the store's
+ *   colour bricks go up through the pinned buffer, window-only bricks are zeroed, k_brick_window writes the volume's
+ *   colour buffer over the window's box.  k_brick_colours runs one thread per point: one binary search finds the base
+ *   corner's brick and the eight words come from it when the stencil does not cross a brick face (all three local
+ *   coordinates <= 6), otherwise each corner is searched for; no LDS, no scratch, one integer atomic per wave for the
+ *   count.  2 launches with a volume, 1 without; one host wait.
+ *   Refusals, all before any device call, OSLAM_E_INVALID with nothing written: NULL w, a NULL output with n > 0, a bad
+ *   stride or n >= 2^31 (oslam_volume_colours' rules), an anchor beyond 2^20 or min_weight outside 1..65535, a store without
+ *   colour, a volume without colour, a volume whose voxel or created-origin bits are not the store's.  A map of more than
+ *   2^22 bricks is OSLAM_E_LIMIT.  n == 0 and an empty map return zeros without a device call.  Nothing changes in store
+ *   or volume; the locks are taken in the usual order (volume, then store); device memory is freed on every path.
+ * Out of scope: colours written inside the extraction kernels so that points never go up again, colour through bilateral,
+ *   mask and pyramid views, a colour term in tracking,
  *   verification or arbitration, keeping surface points in HBM between the extraction and oslam_volume_colours, several
  *   GPUs. */
 typedef struct oslam_colour_params {
@@ -1917,6 +1985,8 @@ int oslam_volume_paint_view(oslam_volume *vol, const float T_vol_cam[16], oslam_
 int oslam_ply_write_colour(const char *path, const float *xyz, const float *nrm, const uint8_t *rgb, size_t n, int binary);
 int oslam_ply_write_mesh_colour(const char *path, const float *xyz, const float *nrm, const uint8_t *rgb, size_t nv,
                                 const uint32_t *tri, size_t nt, int binary);
+int oslam_world_colours(oslam_world *w, oslam_volume *vol, const oslam_world_surface_params *sp, const float *xyz, size_t n,
+                        size_t stride_bytes, uint8_t *rgb_out, uint8_t *valid_out, size_t *n_valid_out);
 
 /* ---- parity taps (tests): values the reference materialises as arrays.
  * Scene::getHashKeys row r (scene.cu:49-54): keys_out[n] of reference point r,

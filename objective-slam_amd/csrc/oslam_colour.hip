@@ -29,6 +29,7 @@
 #include <stdint.h>
 
 #include "oslam_block_scan.h"
+#include "oslam_colour_lerp.h"
 #include "oslam_kernels.h"
 
 __global__ __launch_bounds__(256) void k_tsdf_colour(const oslamk_volume vol, const oslamk_colour col, const oslamk_view v,
@@ -73,19 +74,6 @@ __global__ __launch_bounds__(256) void k_tsdf_colour(const oslamk_volume vol, co
     /* every lane of the wave arrives here: the wave's count, one integer add */
     const uint32_t s = wave_sum(mine);
     if ((threadIdx.x & 63) == 0 && s) atomicAdd(count, s);
-}
-
-__device__ __forceinline__ float colour_lerp(float a, float b, float f) { return a * (1.0f - f) + b * f; }
-
-/* one channel (bits sh .. sh + 7) of the eight corners, trilinear with the ray cast's order, rounded and clipped */
-__device__ __forceinline__ uint32_t colour_channel(const uint32_t c[8], int sh, float fx, float fy, float fz)
-{
-    const float c00 = colour_lerp((float)((c[0] >> sh) & 0xffu), (float)((c[1] >> sh) & 0xffu), fx);
-    const float c10 = colour_lerp((float)((c[2] >> sh) & 0xffu), (float)((c[3] >> sh) & 0xffu), fx);
-    const float c01 = colour_lerp((float)((c[4] >> sh) & 0xffu), (float)((c[5] >> sh) & 0xffu), fx);
-    const float c11 = colour_lerp((float)((c[6] >> sh) & 0xffu), (float)((c[7] >> sh) & 0xffu), fx);
-    const float val = floorf(colour_lerp(colour_lerp(c00, c10, fy), colour_lerp(c01, c11, fy), fz) + 0.5f);
-    return (uint32_t)fminf(fmaxf(val, 0.0f), 255.0f);
 }
 
 /* the colour at the volume-frame point (x, y, z) as an image word: a = 255 with a colour, the word 0 without */

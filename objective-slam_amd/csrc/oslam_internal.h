@@ -350,7 +350,9 @@ int oslam_world_surface_cloud(oslam_world *w, oslam_volume *vol, const oslam_wor
                               uint32_t *np);
 /* The whole map on the device for one extraction (oslam_world_surface.c): the table of brick keys and slots, the store's
  * bricks sent up and the window's words written into theirs (include/oslam.h at oslam_world_surface, "Cost").  bricks == 0
- * is an empty map, for which no device call was made.  p: checked parameters.  Called with the volume lock and the
+ * is an empty map, for which no device call was made.  p: checked parameters.  plane picks what the brick array holds:
+ * the TSDF words, or the colour words of a colour store and a coloured volume (the caller has checked both), laid out and
+ * united the same way (include/oslam.h at oslam_world_colours).  Called with the volume lock and the
  * store's held; refuses a volume the store was not made for.  On failure nothing is left to free; after success the
  * caller waits for the stream and then calls oslam_world_map_close */
 typedef struct oslam_world_map {
@@ -360,7 +362,9 @@ typedef struct oslam_world_map {
     int32_t anchor[3];
     int dev;
 } oslam_world_map;
-int oslam_world_map_open(oslam_world *w, oslam_volume *vol, const oslam_world_surface_params *p, void *stream, oslam_world_map *out);
+enum { OSLAM_MAP_TSDF = 0, OSLAM_MAP_COLOUR = 1 };
+int oslam_world_map_open(oslam_world *w, oslam_volume *vol, const oslam_world_surface_params *p, int plane, void *stream,
+                         oslam_world_map *out);
 void oslam_world_map_close(oslam_world_map *wm);
 /* the arbitration's parameter check (oslam_arbitrate.c) */
 int oslam_arbitrate_check_params(const oslam_arbitrate_params *ap, oslam_arbitrate_params *out);

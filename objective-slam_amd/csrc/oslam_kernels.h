@@ -727,6 +727,14 @@ int oslamk_tsdf_pack_emit(const oslamk_volume *vol, const int shift[3], uint32_t
 /* dst[lin] = word for each of the n_rec records of recs = device [n_rec][2] (8-byte aligned, distinct lin, n_rec at most
  * nx * ny * nz); a record whose lin is not below nx * ny * nz is skipped */
 int oslamk_tsdf_unpack(uint32_t *dst, int nx, int ny, int nz, const uint32_t *recs, uint32_t n_rec, void *stream);
+/* the colour words next to those records, through a colour store (oslam_reload_colour.hip): colours_out[r] =
+ * colours[lin of record r] behind oslamk_tsdf_pack_emit, and dst[lin of record r] = colours_in[r] behind the colour
+ * buffer's oslamk_tsdf_shift.  recs as above, colours_out / colours_in = device [n_rec]; a lin not below nx * ny * nz
+ * reads as 0 and writes nothing */
+int oslamk_pack_colours(const uint32_t *colours, int nx, int ny, int nz, const uint32_t *recs, uint32_t n_rec, uint32_t *colours_out,
+                        void *stream);
+int oslamk_unpack_colours(uint32_t *dst, int nx, int ny, int nz, const uint32_t *recs, const uint32_t *colours_in, uint32_t n_rec,
+                          void *stream);
 
 /* ---- the colour volume (oslam_colour.hip; semantics in include/oslam.h at oslam_volume_integrate_colour,
  * oslam_volume_colours and oslam_volume_paint_view).  A voxel's colour word is r | g << 8 | b << 16 | wc << 24, an image's
@@ -789,6 +797,11 @@ int oslamk_brick_count(const oslamk_brick_map *map, uint32_t min_weight, uint32_
 int oslamk_brick_emit(const oslamk_brick_map *map, uint32_t min_weight, const uint32_t *offsets, const oslamk_brick_bases *bases,
                       uint32_t n_points, float *out6, int32_t *key_out, void *stream);
 
+/* ---- the colour at points of the whole map (oslam_world_colour.hip; semantics in include/oslam.h at oslam_world_colours;
+ * host side: oslam_world_colour.c).  The map is the surface's with the brick array holding colour words ---- */
+/* out[t] = the image word of the colour at the volume-frame point xyz[t] (device [n][3], 0 < n < 2^31), 0 without a colour;
+ * *count (zeroed by the caller) += points with a colour */
+int oslamk_brick_colours(const oslamk_brick_map *map, const float *xyz, uint32_t n, uint32_t *out, uint32_t *count, void *stream);
 
 /* ---- the mesh of the whole map from the same bricks (oslam_world_mesh.hip; semantics in include/oslam.h at
  * oslam_world_mesh; host side: oslam_world_mesh.c).  The map is the surface's, window written in by oslamk_brick_window ---- */

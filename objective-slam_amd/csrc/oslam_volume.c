@@ -481,9 +481,11 @@ int oslam_world_params_of(const oslam_volume *vol, oslam_world_params *p)
 
 /* The two passes of the pack, with g_vol_mu held and the volume's device bound: *n_rec = the seen voxels that leave
  * under shift; at most cap of them are packed, into *d_rec = device [n_rec][2] (NULL otherwise).  One host wait, for the
- * total; the second pass is only launched.  The caller frees *d_cnt and *d_rec after its own wait */
-static int pack_leaving(oslam_volume *vol, const int shift[3], size_t cap, uint32_t **d_cnt, uint32_t **d_rec, uint32_t *n_rec,
-                        uint32_t *launches)
+ * total; the second pass is only launched.  With colours (the volume's colour buffer, or NULL) *d_rec is [n_rec][2]
+ * followed by [n_rec] colour words, gathered behind the second pass: one buffer, so one copy takes both down.  The caller
+ * frees *d_cnt and *d_rec after its own wait */
+static int pack_leaving(oslam_volume *vol, const int shift[3], size_t cap, const uint32_t *colours, uint32_t **d_cnt, uint32_t **d_rec,
+                        uint32_t *n_rec, uint32_t *launches)
 {
     int rc = OSLAM_OK;
     const uint32_t n_groups = oslamk_pack_groups(&vol->k);
@@ -495,9 +497,13 @@ static int pack_leaving(oslam_volume *vol, const int shift[3], size_t cap, uint3
     HIPCHK(hipMemcpyAsync(n_rec, *d_cnt, sizeof *n_rec, hipMemcpyDeviceToHost, (hipStream_t)stream));
     HIPCHK(hipStreamSynchronize((hipStream_t)stream));
     if (*n_rec > 0 && (size_t)*n_rec <= cap) {
-        KCHK(oslam_dev_alloc((void **)d_rec, sizeof(uint32_t) * 2 * (size_t)*n_rec));
+        KCHK(oslam_dev_alloc((void **)d_rec, sizeof(uint32_t) * (colours ? 3 : 2) * (size_t)*n_rec));
         KCHK(oslamk_tsdf_pack_emit(&vol->k, shift, n_groups, *d_cnt + 64, *n_rec, *d_rec, stream));
         *launches += 1;
+        if (colours) {
+            KCHK(oslamk_pack_colours(colours, vol->k.nx, vol->k.ny, vol->k.nz, *d_rec, *n_rec, *d_rec + 2 * (size_t)*n_rec, stream));
+            *launches += 1;
+        }
     }
 done:
     return rc;
@@ -569,28 +575,30 @@ static void global_of(const oslam_volume *vol, uint32_t lin, int32_t g[3])
 
 typedef struct enter_ctx {
     uint32_t *rec;                                                  /* [n][2]: lin in the new window, word */
+    uint32_t *col;                                                  /* [n]: the colour stored with it, or NULL */
     size_t n;
     int off[3];
     size_t nx, ny;
 } enter_ctx;
 
-static void enter_record(void *ctx, const int32_t g[3], uint32_t word)
+static void enter_record(void *ctx, const int32_t g[3], uint32_t word, uint32_t colour)
 {
     enter_ctx *e = (enter_ctx *)ctx;
     e->rec[2 * e->n] = (uint32_t)(((size_t)(g[2] - e->off[2]) * e->ny + (size_t)(g[1] - e->off[1])) * e->nx + (size_t)(g[0] - e->off[0]));
     e->rec[2 * e->n + 1] = word;
+    if (e->col) e->col[e->n] = colour;
     e->n++;
 }
 
 int oslam_volume_shift_world(oslam_volume *vol, oslam_world *w, const int shift[3], oslam_reload_result *res)
 {
-    int rc = OSLAM_OK, a, b, nb = 0, off[3], locked = 0, reserved = 0;
+    int rc = OSLAM_OK, a, b, nb = 0, off[3], locked = 0, reserved = 0, cs = 0;
     const double t0 = now_ms();
     uint32_t *d_cnt = NULL, *d_out = NULL, *d_in = NULL, *d_kept = NULL, *spare = NULL;
     uint32_t n_out = 0, kept = 0, launches = 0, r;
-    size_t n_in = 0, mark = 0;
+    size_t n_in = 0, mark = 0, rec_words = 2;
     int32_t lo[7][3], hi[7][3], g[3];
-    const uint32_t *rec_out = NULL;
+    const uint32_t *rec_out = NULL, *col_out = NULL;
     oslam_world_stage *st = NULL;
     void *stream = oslam_stream();
     if (!vol || !w || !shift) return fail(OSLAM_E_INVALID, "NULL argument");
@@ -602,6 +610,12 @@ int oslam_volume_shift_world(oslam_volume *vol, oslam_world *w, const int shift[
         rc = fail(OSLAM_E_INVALID, "the voxel store was made for another voxel size or origin");
         goto done;
     }
+    cs = oslam_world_coloured(w);                                   /* fixed when the store was created */
+    if (cs && !vol->colour.words) {
+        rc = fail(OSLAM_E_INVALID, "a colour store needs a volume with colour");
+        goto done;
+    }
+    rec_words = cs ? 3 : 2;                                         /* a record crosses the host link as 12 bytes or as 8 */
     if (res) memset(res, 0, sizeof *res);
     if (!(shift[0] | shift[1] | shift[2])) {
         if (res) memcpy(res->offset, off, sizeof off);
@@ -611,18 +625,19 @@ int oslam_volume_shift_world(oslam_volume *vol, oslam_world *w, const int shift[
     rc = shift_spares(vol);
     if (rc != OSLAM_OK) goto done;
     spare = vol->spare;
-    /* 1. pack what leaves and copy it down */
-    rc = pack_leaving(vol, shift, (size_t)-1, &d_cnt, &d_out, &n_out, &launches);
+    /* 1. pack what leaves, with its colours for a colour store, and copy it down */
+    rc = pack_leaving(vol, shift, (size_t)-1, cs ? vol->colour.words : NULL, &d_cnt, &d_out, &n_out, &launches);
     if (rc != OSLAM_OK) goto done;
     oslam_world_lock(w);
     locked = 1;
     st = oslam_world_stages(w);
     if (n_out) {
-        rc = oslam_world_stage_fit(&st[0], sizeof(uint32_t) * 2 * (size_t)n_out);
+        rc = oslam_world_stage_fit(&st[0], sizeof(uint32_t) * rec_words * (size_t)n_out);
         if (rc != OSLAM_OK) goto done;
-        HIPCHK(hipMemcpyAsync(st[0].p, d_out, sizeof(uint32_t) * 2 * (size_t)n_out, hipMemcpyDeviceToHost, (hipStream_t)stream));
+        HIPCHK(hipMemcpyAsync(st[0].p, d_out, sizeof(uint32_t) * rec_words * (size_t)n_out, hipMemcpyDeviceToHost, (hipStream_t)stream));
         HIPCHK(hipStreamSynchronize((hipStream_t)stream));
         rec_out = (const uint32_t *)st[0].p;
+        if (cs) col_out = rec_out + 2 * (size_t)n_out;
     }
     /* 2. the bricks the leaving records need, still empty */
     mark = oslam_world_mark(w);
@@ -640,24 +655,29 @@ int oslam_volume_shift_world(oslam_volume *vol, oslam_world *w, const int shift[
     for (b = 0; b < nb; b++) n_in += oslam_world_visit(w, lo[b], hi[b], 0, NULL, NULL);
     if (n_in) {
         enter_ctx e;
-        rc = oslam_world_stage_fit(&st[1], sizeof(uint32_t) * 2 * n_in);
+        rc = oslam_world_stage_fit(&st[1], sizeof(uint32_t) * rec_words * n_in);
         if (rc != OSLAM_OK) goto done;
         e.rec = (uint32_t *)st[1].p;
+        e.col = cs ? e.rec + 2 * n_in : NULL;
         e.n = 0;
         memcpy(e.off, off, sizeof off);
         e.nx = vol->p.nx;
         e.ny = vol->p.ny;
-        for (b = 0; b < nb; b++) (void)oslam_world_visit(w, lo[b], hi[b], 0, enter_record, &e);
+        for (b = 0; b < nb; b++) (void)oslam_world_visit_colour(w, lo[b], hi[b], 0, enter_record, &e);
         /* 4. copy up; shift and unpack in stream order */
-        KCHK(oslam_dev_alloc((void **)&d_in, sizeof(uint32_t) * 2 * n_in));
-        HIPCHK(hipMemcpyAsync(d_in, st[1].p, sizeof(uint32_t) * 2 * n_in, hipMemcpyHostToDevice, (hipStream_t)stream));
+        KCHK(oslam_dev_alloc((void **)&d_in, sizeof(uint32_t) * rec_words * n_in));
+        HIPCHK(hipMemcpyAsync(d_in, st[1].p, sizeof(uint32_t) * rec_words * n_in, hipMemcpyHostToDevice, (hipStream_t)stream));
     }
     KCHK(oslam_counters_open(&d_kept, 0, stream));
     KCHK(oslamk_tsdf_shift(&vol->k, spare, shift, d_kept, stream));
     launches++;
-    if (vol->colour.words) {                                            /* the store keeps no colour: what is reloaded has wc = 0 */
+    if (vol->colour.words) {                                            /* a plain store keeps no colour: what it reloads has wc = 0 */
         KCHK(shift_colours(vol, shift, d_kept + 1, stream));
         launches++;
+        if (cs && n_in) {                                               /* a colour store's colours, into the buffer that shift wrote */
+            KCHK(oslamk_unpack_colours(vol->colour_spare, vol->k.nx, vol->k.ny, vol->k.nz, d_in, d_in + 2 * n_in, (uint32_t)n_in, stream));
+            launches++;
+        }
     }
     if (n_in) {
         KCHK(oslamk_tsdf_unpack(spare, vol->k.nx, vol->k.ny, vol->k.nz, d_in, (uint32_t)n_in, stream));
@@ -668,7 +688,7 @@ int oslam_volume_shift_world(oslam_volume *vol, oslam_world *w, const int shift[
     /* 5. commit: nothing below can fail */
     for (r = 0; r < n_out; r++) {
         global_of(vol, rec_out[2 * r], g);
-        oslam_world_store(w, g, rec_out[2 * r + 1]);
+        oslam_world_store_colour(w, g, rec_out[2 * r + 1], col_out ? col_out[r] : 0u);
     }
     for (b = 0; b < nb; b++) (void)oslam_world_visit(w, lo[b], hi[b], 1, NULL, NULL);
     reserved = 0;
@@ -697,28 +717,34 @@ done:
     return rc;
 }
 
-int oslam_volume_pack(oslam_volume *vol, const int shift[3], uint32_t *lin_out, uint32_t *word_out, size_t cap, size_t *n_out)
+/* the tap of the pack, without colours (colour_out == NULL, want_colour == 0) or with them */
+static int pack_tap(oslam_volume *vol, const int shift[3], uint32_t *lin_out, uint32_t *word_out, uint32_t *colour_out, int want_colour,
+                    size_t cap, size_t *n_out)
 {
     int rc = OSLAM_OK;
     uint32_t *d_cnt = NULL, *d_rec = NULL, *h = NULL, n = 0, launches = 0, r;
+    const size_t rec_words = want_colour ? 3 : 2;
     if (!vol || !shift || !n_out) return fail(OSLAM_E_INVALID, "NULL argument");
-    if (cap != 0 && (!lin_out || !word_out)) return fail(OSLAM_E_INVALID, "lin_out and word_out must be given with cap != 0");
+    if (cap != 0 && (!lin_out || !word_out || (want_colour && !colour_out)))
+        return fail(OSLAM_E_INVALID, "the outputs must be given with cap != 0");
+    if (want_colour && !vol->colour.words) return fail(OSLAM_E_INVALID, "the volume has no colour");
     if (!oslamk_shift_ok(shift)) return fail(OSLAM_E_INVALID, "a shift is at most 2^20 voxels");
     *n_out = 0;
     if (!(shift[0] | shift[1] | shift[2])) return OSLAM_OK;
     if (hipSetDevice(vol->dev) != hipSuccess) return fail(OSLAM_E_DEVICE, "hipSetDevice failed");
     pthread_mutex_lock(&g_vol_mu);
-    rc = pack_leaving(vol, shift, cap, &d_cnt, &d_rec, &n, &launches);
+    rc = pack_leaving(vol, shift, cap, want_colour ? vol->colour.words : NULL, &d_cnt, &d_rec, &n, &launches);
     if (rc != OSLAM_OK) goto done;
     *n_out = n;
     if (cap != 0 && (size_t)n > cap) { rc = fail(OSLAM_E_LIMIT, "output capacity too small"); goto done; }
     if (d_rec) {
-        h = (uint32_t *)malloc(sizeof(uint32_t) * 2 * (size_t)n);
+        h = (uint32_t *)malloc(sizeof(uint32_t) * rec_words * (size_t)n);
         if (!h) { rc = fail(OSLAM_E_NOMEM, "host allocation failed"); goto done; }
-        HIPCHK(hipMemcpy(h, d_rec, sizeof(uint32_t) * 2 * (size_t)n, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(h, d_rec, sizeof(uint32_t) * rec_words * (size_t)n, hipMemcpyDeviceToHost));
         for (r = 0; r < n; r++) {
             lin_out[r] = h[2 * r];
             word_out[r] = h[2 * r + 1];
+            if (want_colour) colour_out[r] = h[2 * (size_t)n + r];
         }
     }
 done:
@@ -728,6 +754,17 @@ done:
     if (d_rec) oslam_dev_free(d_rec);
     if (d_cnt) oslam_dev_free(d_cnt);
     return rc;
+}
+
+int oslam_volume_pack(oslam_volume *vol, const int shift[3], uint32_t *lin_out, uint32_t *word_out, size_t cap, size_t *n_out)
+{
+    return pack_tap(vol, shift, lin_out, word_out, NULL, 0, cap, n_out);
+}
+
+int oslam_volume_pack_colour(oslam_volume *vol, const int shift[3], uint32_t *lin_out, uint32_t *word_out, uint32_t *colour_out,
+                             size_t cap, size_t *n_out)
+{
+    return pack_tap(vol, shift, lin_out, word_out, colour_out, 1, cap, n_out);
 }
 
 int oslam_volume_window(oslam_volume *vol, int offset_out[3], float origin_out[3])

@@ -4,7 +4,8 @@
  * it: oslam_volume.c; its view of the store: oslam_world.h).  Bricks of 8 x 8 x 8 words, keyed by floor(g / 8) per axis,
  * in a table with linear probing that doubles when half full; removal shifts the following entries back, so there are
  * no tombstones and a lookup that misses stops at the first empty slot.  Every stored word is seen (w > 0), so a zero
- * word in a brick means "nothing stored".  The bricks' keys in ascending order, for the extraction of the whole map's
+ * word in a brick means "nothing stored".  A colour store's bricks carry a second array of 512 colour words, each kept
+ * under its g as it is whenever the TSDF word is stored and cleared with it.  The bricks' keys in ascending order, for the extraction of the whole map's
  * surface (oslam_world_surface.c), are made here too.  No device call and no HIP header: this file links alone.
  */
 #include <math.h>
@@ -26,12 +27,14 @@ typedef struct brick {
     int32_t key[3];                           /* floor(g_a / 8) */
     uint32_t count;                           /* words != 0 */
     uint32_t words[BRICK_WORDS];              /* [z][y][x] */
+    uint32_t colours[];                       /* [BRICK_WORDS] in a colour store, absent otherwise */
 } brick;
 
 struct oslam_world {
     pthread_mutex_t mu;
     float voxel, origin0[3];
     uint64_t max_bytes;
+    int colour;                               /* the bricks carry colours[] */
     brick **slots;                            /* [cap], NULL = empty */
     size_t cap, n_bricks;                     /* cap a power of two, n_bricks * 2 <= cap */
     uint64_t n_voxels;
@@ -51,7 +54,12 @@ static size_t slot_of(const int32_t key[3], size_t cap)
 
 static int same_key(const brick *b, const int32_t key[3]) { return b->key[0] == key[0] && b->key[1] == key[1] && b->key[2] == key[2]; }
 
-static uint64_t bytes_of(size_t n_bricks, size_t cap) { return (uint64_t)n_bricks * sizeof(brick) + (uint64_t)cap * sizeof(brick *); }
+static size_t brick_bytes(const oslam_world *w) { return sizeof(brick) + (w->colour ? BRICK_WORDS * sizeof(uint32_t) : 0); }
+
+static uint64_t bytes_of(const oslam_world *w, size_t n_bricks, size_t cap)
+{
+    return (uint64_t)n_bricks * brick_bytes(w) + (uint64_t)cap * sizeof(brick *);
+}
 
 static size_t table_find(const oslam_world *w, const int32_t key[3])
 {
@@ -149,8 +157,8 @@ int oslam_world_reserve(oslam_world *w, const int32_t g[3])
     key_of(g, key, &local);
     if (table_find(w, key) != NO_SLOT) return OSLAM_OK;
     if ((w->n_bricks + 1) * 2 > cap) cap *= 2;
-    if (bytes_of(w->n_bricks + 1, cap) > w->max_bytes) return oslam_fail(OSLAM_E_LIMIT, "the voxel store's max_bytes is exceeded");
-    b = (brick *)calloc(1, sizeof *b);
+    if (bytes_of(w, w->n_bricks + 1, cap) > w->max_bytes) return oslam_fail(OSLAM_E_LIMIT, "the voxel store's max_bytes is exceeded");
+    b = (brick *)calloc(1, brick_bytes(w));
     if (!b || (cap != w->cap && table_resize(w, cap) != 0)) {
         free(b);
         return oslam_fail(OSLAM_E_NOMEM, "host allocation failed");
@@ -167,7 +175,11 @@ void oslam_world_rollback(oslam_world *w, size_t mark)
     if (w->cap != mark && w->n_bricks * 2 <= mark) (void)table_resize(w, mark);
 }
 
-void oslam_world_store(oslam_world *w, const int32_t g[3], uint32_t word)
+void oslam_world_store(oslam_world *w, const int32_t g[3], uint32_t word) { oslam_world_store_colour(w, g, word, 0u); }
+
+int oslam_world_coloured(const oslam_world *w) { return w->colour; }
+
+void oslam_world_store_colour(oslam_world *w, const int32_t g[3], uint32_t word, uint32_t colour)
 {
     int32_t key[3];
     unsigned local;
@@ -179,14 +191,15 @@ void oslam_world_store(oslam_world *w, const int32_t g[3], uint32_t word)
         w->n_voxels++;
     }
     b->words[local] = word;
+    if (w->colour) b->colours[local] = colour;
 }
 
 static int imax(int a, int b) { return a > b ? a : b; }
 static int imin(int a, int b) { return a < b ? a : b; }
 
 /* the words of b inside the box; -> how many */
-static size_t visit_brick(oslam_world *w, brick *b, const int32_t lo[3], const int32_t hi[3], int take, oslam_world_visit_fn fn,
-                          void *ctx)
+static size_t visit_brick(oslam_world *w, brick *b, const int32_t lo[3], const int32_t hi[3], int take,
+                          oslam_world_visit_colour_fn fn, void *ctx)
 {
     int a, x, y, z, c0[3], c1[3];
     size_t n = 0;
@@ -199,15 +212,17 @@ static size_t visit_brick(oslam_world *w, brick *b, const int32_t lo[3], const i
     for (z = c0[2]; z < c1[2]; z++)
         for (y = c0[1]; y < c1[1]; y++)
             for (x = c0[0]; x < c1[0]; x++) {
-                uint32_t *p = &b->words[(z * BRICK_SIDE + y) * BRICK_SIDE + x];
+                const int local = (z * BRICK_SIDE + y) * BRICK_SIDE + x;
+                uint32_t *p = &b->words[local];
                 if (*p == 0u) continue;
                 {
                     const int32_t g[3] = {b->key[0] * BRICK_SIDE + x, b->key[1] * BRICK_SIDE + y, b->key[2] * BRICK_SIDE + z};
-                    if (fn) fn(ctx, g, *p);
+                    if (fn) fn(ctx, g, *p, w->colour ? b->colours[local] : 0u);
                 }
                 n++;
                 if (take) {
                     *p = 0u;
+                    if (w->colour) b->colours[local] = 0u;
                     b->count--;
                     w->n_voxels--;
                 }
@@ -215,7 +230,28 @@ static size_t visit_brick(oslam_world *w, brick *b, const int32_t lo[3], const i
     return n;
 }
 
+typedef struct plain_visit {
+    oslam_world_visit_fn fn;
+    void *ctx;
+} plain_visit;
+
+static void visit_plain(void *ctx, const int32_t g[3], uint32_t word, uint32_t colour)
+{
+    const plain_visit *p = (const plain_visit *)ctx;
+    (void)colour;
+    p->fn(p->ctx, g, word);
+}
+
 size_t oslam_world_visit(oslam_world *w, const int32_t lo[3], const int32_t hi[3], int take, oslam_world_visit_fn fn, void *ctx)
+{
+    plain_visit p;
+    p.fn = fn;
+    p.ctx = ctx;
+    return oslam_world_visit_colour(w, lo, hi, take, fn ? visit_plain : NULL, &p);
+}
+
+size_t oslam_world_visit_colour(oslam_world *w, const int32_t lo[3], const int32_t hi[3], int take, oslam_world_visit_colour_fn fn,
+                                void *ctx)
 {
     int a;
     int32_t k0[3], k1[3], key[3];
@@ -259,6 +295,7 @@ int oslam_world_create(const oslam_world_params *p, oslam_world **out)
     if (!isfinite(p->voxel) || !isfinite(p->origin0[0]) || !isfinite(p->origin0[1]) || !isfinite(p->origin0[2]))
         return oslam_fail(OSLAM_E_INVALID, "voxel and origin0 must be finite");
     if (!(p->voxel > 0.0f)) return oslam_fail(OSLAM_E_INVALID, "voxel must be > 0");
+    if (p->colour != 0 && p->colour != 1) return oslam_fail(OSLAM_E_INVALID, "colour must be 0 or 1");
     w = (oslam_world *)calloc(1, sizeof *w);
     if (!w) return oslam_fail(OSLAM_E_NOMEM, "host allocation failed");
     w->slots = (brick **)calloc(TABLE_MIN, sizeof *w->slots);
@@ -270,6 +307,7 @@ int oslam_world_create(const oslam_world_params *p, oslam_world **out)
     w->voxel = p->voxel;
     memcpy(w->origin0, p->origin0, sizeof w->origin0);
     w->max_bytes = p->max_bytes ? p->max_bytes : WORLD_DEFAULT_BYTES;
+    w->colour = p->colour;
     pthread_mutex_init(&w->mu, NULL);
     *out = w;
     return OSLAM_OK;
@@ -318,7 +356,7 @@ int oslam_world_stats_get(oslam_world *w, oslam_world_stats *out)
     pthread_mutex_lock(&w->mu);
     out->voxels = w->n_voxels;
     out->bricks = w->n_bricks;
-    out->bytes = bytes_of(w->n_bricks, w->cap);
+    out->bytes = bytes_of(w, w->n_bricks, w->cap);
     for (s = 0; s < w->cap; s++) {
         const brick *b = w->slots[s];
         if (!b) continue;
@@ -338,11 +376,13 @@ int oslam_world_stats_get(oslam_world *w, oslam_world_stats *out)
     return OSLAM_OK;
 }
 
-int oslam_world_put(oslam_world *w, const int32_t *g, const uint32_t *words, size_t n)
+int oslam_world_has_colour(const oslam_world *w) { return w && w->colour; }
+
+/* colours == NULL: colour 0 */
+static int put(oslam_world *w, const int32_t *g, const uint32_t *words, const uint32_t *colours, size_t n)
 {
     int rc = OSLAM_OK;
     size_t i, mark;
-    if (!w || (n && (!g || !words))) return oslam_fail(OSLAM_E_INVALID, "NULL argument");
     for (i = 0; i < 3 * n; i++)
         if (g[i] < -OSLAM_WORLD_G_MAX || g[i] > OSLAM_WORLD_G_MAX)
             return oslam_fail(OSLAM_E_INVALID, "a global voxel coordinate is at most 2^20 + 512 in size");
@@ -353,24 +393,40 @@ int oslam_world_put(oslam_world *w, const int32_t *g, const uint32_t *words, siz
     if (rc != OSLAM_OK) oslam_world_rollback(w, mark);
     else
         for (i = 0; i < n; i++)
-            if (words[i] >> 16) oslam_world_store(w, g + 3 * i, words[i]);
+            if (words[i] >> 16) oslam_world_store_colour(w, g + 3 * i, words[i], colours ? colours[i] : 0u);
     pthread_mutex_unlock(&w->mu);
     return rc;
 }
 
+int oslam_world_put(oslam_world *w, const int32_t *g, const uint32_t *words, size_t n)
+{
+    if (!w || (n && (!g || !words))) return oslam_fail(OSLAM_E_INVALID, "NULL argument");
+    return put(w, g, words, NULL, n);
+}
+
+int oslam_world_put_colour(oslam_world *w, const int32_t *g, const uint32_t *words, const uint32_t *colours, size_t n)
+{
+    if (!w || (n && (!g || !words || !colours))) return oslam_fail(OSLAM_E_INVALID, "NULL argument");
+    if (!w->colour) return oslam_fail(OSLAM_E_INVALID, "the voxel store keeps no colour");
+    return put(w, g, words, colours, n);
+}
+
 typedef struct dense_ctx {
-    uint32_t *out;
+    uint32_t *out, *colours;                  /* colours may be NULL */
     int32_t lo[3];
     size_t nx, ny;
 } dense_ctx;
 
-static void dense_write(void *ctx, const int32_t g[3], uint32_t word)
+static void dense_write(void *ctx, const int32_t g[3], uint32_t word, uint32_t colour)
 {
     const dense_ctx *d = (const dense_ctx *)ctx;
-    d->out[((size_t)(g[2] - d->lo[2]) * d->ny + (size_t)(g[1] - d->lo[1])) * d->nx + (size_t)(g[0] - d->lo[0])] = word;
+    const size_t at = ((size_t)(g[2] - d->lo[2]) * d->ny + (size_t)(g[1] - d->lo[1])) * d->nx + (size_t)(g[0] - d->lo[0]);
+    d->out[at] = word;
+    if (d->colours) d->colours[at] = colour;
 }
 
-int oslam_world_box(oslam_world *w, const int32_t lo[3], const int32_t hi[3], uint32_t *words_out, int take)
+static int box(oslam_world *w, const int32_t lo[3], const int32_t hi[3], uint32_t *words_out, uint32_t *colours_out, int want_colours,
+               int take)
 {
     int a;
     uint64_t n = 1;
@@ -383,16 +439,31 @@ int oslam_world_box(oslam_world *w, const int32_t lo[3], const int32_t hi[3], ui
         if (n > WORLD_BOX_MAX) return oslam_fail(OSLAM_E_LIMIT, "a box holds at most 2^27 voxels");
     }
     if (n == 0) return OSLAM_OK;
-    if (!words_out) return oslam_fail(OSLAM_E_INVALID, "NULL argument");
+    if (!words_out || (want_colours && !colours_out)) return oslam_fail(OSLAM_E_INVALID, "NULL argument");
     memset(words_out, 0, (size_t)n * sizeof *words_out);
+    if (want_colours) memset(colours_out, 0, (size_t)n * sizeof *colours_out);
     d.out = words_out;
+    d.colours = want_colours ? colours_out : NULL;
     memcpy(d.lo, lo, sizeof d.lo);
     d.nx = (size_t)(hi[0] - lo[0]);
     d.ny = (size_t)(hi[1] - lo[1]);
     pthread_mutex_lock(&w->mu);
-    (void)oslam_world_visit(w, lo, hi, take, dense_write, &d);
+    (void)oslam_world_visit_colour(w, lo, hi, take, dense_write, &d);
     pthread_mutex_unlock(&w->mu);
     return OSLAM_OK;
+}
+
+int oslam_world_box(oslam_world *w, const int32_t lo[3], const int32_t hi[3], uint32_t *words_out, int take)
+{
+    return box(w, lo, hi, words_out, NULL, 0, take);
+}
+
+int oslam_world_box_colour(oslam_world *w, const int32_t lo[3], const int32_t hi[3], uint32_t *words_out, uint32_t *colours_out,
+                           int take)
+{
+    if (!w) return oslam_fail(OSLAM_E_INVALID, "NULL argument");
+    if (!w->colour) return oslam_fail(OSLAM_E_INVALID, "the voxel store keeps no colour");
+    return box(w, lo, hi, words_out, colours_out, 1, take);
 }
 
 /* ---- brick enumeration (include/oslam.h at oslam_world_surface; its device side: oslam_world_surface.c) ---- */
@@ -425,6 +496,12 @@ const uint32_t *oslam_world_brick_words(const oslam_world *w, const int32_t key[
 {
     const size_t s = table_find(w, key);
     return s == NO_SLOT ? NULL : w->slots[s]->words;
+}
+
+const uint32_t *oslam_world_brick_colours(const oslam_world *w, const int32_t key[3])
+{
+    const size_t s = table_find(w, key);
+    return s == NO_SLOT || !w->colour ? NULL : w->slots[s]->colours;
 }
 
 int oslam_world_bricks(oslam_world *w, int32_t *keys_out, size_t cap, size_t *n_out)

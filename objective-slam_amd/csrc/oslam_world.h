@@ -36,12 +36,20 @@ size_t oslam_world_mark(const oslam_world *w);
 int oslam_world_reserve(oslam_world *w, const int32_t g[3]);
 /* frees every empty brick and takes the table back to the capacity it had at the mark */
 void oslam_world_rollback(oslam_world *w, size_t mark);
-/* stores a seen word under g, whose brick exists (oslam_world_reserve): cannot fail */
+/* stores a seen word under g, whose brick exists (oslam_world_reserve): cannot fail.  On a colour store the colour word
+ * goes in next to it as it is (oslam_world_store: 0); a plain store drops it */
 void oslam_world_store(oslam_world *w, const int32_t g[3], uint32_t word);
+void oslam_world_store_colour(oslam_world *w, const int32_t g[3], uint32_t word, uint32_t colour);
+/* the store's bricks carry colour words (oslam_world_params.colour) */
+int oslam_world_coloured(const oslam_world *w);
 /* calls fn(ctx, g, word) for every stored word with lo <= g < hi; take != 0 removes them and frees the bricks that
  * become empty.  -> the number of words visited */
 typedef void (*oslam_world_visit_fn)(void *ctx, const int32_t g[3], uint32_t word);
 size_t oslam_world_visit(oslam_world *w, const int32_t lo[3], const int32_t hi[3], int take, oslam_world_visit_fn fn, void *ctx);
+/* the same visit, handing out the colour word stored with each word too (0 on a plain store) */
+typedef void (*oslam_world_visit_colour_fn)(void *ctx, const int32_t g[3], uint32_t word, uint32_t colour);
+size_t oslam_world_visit_colour(oslam_world *w, const int32_t lo[3], const int32_t hi[3], int take, oslam_world_visit_colour_fn fn,
+                                void *ctx);
 /* the float bits the store was made for */
 void oslam_world_frame(const oslam_world *w, float *voxel, float origin0[3]);
 /* the store's bricks for the extraction of the whole map (oslam_world_surface.c): how many; their keys floor(g / 8) as
@@ -50,5 +58,7 @@ void oslam_world_frame(const oslam_world *w, float *voxel, float origin0[3]);
 size_t oslam_world_brick_count(const oslam_world *w);
 void oslam_world_brick_keys(const oslam_world *w, int32_t *keys_out);
 const uint32_t *oslam_world_brick_words(const oslam_world *w, const int32_t key[3]);
+/* the 512 colour words of that brick, laid out as its words: NULL without the brick or on a plain store */
+const uint32_t *oslam_world_brick_colours(const oslam_world *w, const int32_t key[3]);
 
 #endif /* OSLAM_WORLD_H */

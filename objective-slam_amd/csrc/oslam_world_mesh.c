@@ -41,7 +41,7 @@ int oslam_world_mesh(oslam_world *w, oslam_volume *vol, const oslam_world_surfac
     memset(tot, 0, sizeof tot);
     oslam_volume_lock();
     oslam_world_lock(w);
-    rc = oslam_world_map_open(w, vol, &p, stream, &wm);
+    rc = oslam_world_map_open(w, vol, &p, OSLAM_MAP_TSDF, stream, &wm);
     launches = wm.launches;
     n = wm.bricks;
     if (rc != OSLAM_OK || n == 0) goto done;                        /* an empty map: zero counts, no device call */

@@ -36,7 +36,8 @@ static void window_bricks(const oslam_volume *vol, int kb0[3], int nb[3])
     }
 }
 
-int oslam_world_map_open(oslam_world *w, oslam_volume *vol, const oslam_world_surface_params *p, void *stream, oslam_world_map *o)
+int oslam_world_map_open(oslam_world *w, oslam_volume *vol, const oslam_world_surface_params *p, int plane, void *stream,
+                         oslam_world_map *o)
 {
     int rc = OSLAM_OK, a, kb0[3] = {0, 0, 0}, nb[3] = {0, 0, 0}, launched = 0;
     float voxel, origin0[3];
@@ -44,6 +45,7 @@ int oslam_world_map_open(oslam_world *w, oslam_volume *vol, const oslam_world_su
     uint8_t *d_map = NULL;
     size_t ns, nw = 0, n = 0, i, j, off_slots, off_words;
     oslamk_brick_map m;
+    oslamk_volume kv;
     oslam_world_stage *st;
     memset(o, 0, sizeof *o);
     memset(&m, 0, sizeof m);
@@ -101,7 +103,9 @@ int oslam_world_map_open(oslam_world *w, oslam_volume *vol, const oslam_world_su
             if (ks <= kw) {
                 hk[n] = ks;
                 hs[n] = (uint32_t)i;
-                memcpy(hw + OSLAMK_BRICK_WORDS * i, oslam_world_brick_words(w, skeys + 3 * i), sizeof(uint32_t) * OSLAMK_BRICK_WORDS);
+                memcpy(hw + OSLAMK_BRICK_WORDS * i,
+                       plane == OSLAM_MAP_COLOUR ? oslam_world_brick_colours(w, skeys + 3 * i) : oslam_world_brick_words(w, skeys + 3 * i),
+                       sizeof(uint32_t) * OSLAMK_BRICK_WORDS);
                 i++;
             } else {
                 hk[n] = kw;
@@ -130,7 +134,9 @@ int oslam_world_map_open(oslam_world *w, oslam_volume *vol, const oslam_world_su
     m.words = (uint32_t *)(d_map + off_words);
     m.n = (uint32_t)n;
     if (nw) {
-        KCHK(oslamk_brick_window(&m, &vol->k, vol->off, kb0, nb, stream));
+        kv = vol->k;                                                /* the kernel copies words whatever they mean */
+        if (plane == OSLAM_MAP_COLOUR) kv.words = vol->colour.words;
+        KCHK(oslamk_brick_window(&m, &kv, vol->off, kb0, nb, stream));
         o->launches++;
     }
     o->m = m;
@@ -175,7 +181,7 @@ static int world_surface_run(oslam_world *w, oslam_volume *vol, const oslam_worl
     memset(&bases, 0, sizeof bases);
     oslam_volume_lock();
     oslam_world_lock(w);
-    rc = oslam_world_map_open(w, vol, p, stream, &wm);
+    rc = oslam_world_map_open(w, vol, p, OSLAM_MAP_TSDF, stream, &wm);
     memcpy(o->anchor, wm.anchor, sizeof o->anchor);
     o->window_bricks = wm.window_bricks;
     o->bricks = wm.bricks;

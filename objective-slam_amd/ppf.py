@@ -308,6 +308,9 @@ class FollowParams(C.Structure):
 class WorldParams(C.Structure):
     _fields_ = [("voxel", C.c_float), ("origin0", C.c_float * 3), ("max_bytes", C.c_uint64), ("reserved", C.c_int * 4)]
 
+    # oslam_world_params.colour is the first of these four ints (the C structure names it; the layout is one)
+    colour = property(lambda self: int(self.reserved[0]), lambda self, v: self.reserved.__setitem__(0, int(v)))
+
 
 class WorldStats(C.Structure):
     _fields_ = [("voxels", C.c_uint64), ("bricks", C.c_uint64), ("bytes", C.c_uint64), ("lo", C.c_int32 * 3),
@@ -513,6 +516,10 @@ _SIGNATURES = {
     "oslam_world_stats_get": (_i, [_vp, C.POINTER(WorldStats)]),
     "oslam_world_put": (_i, [_vp, _vp, _vp, _sz]),
     "oslam_world_box": (_i, [_vp, _vp, _vp, _vp, _i]),
+    "oslam_world_has_colour": (_i, [_vp]),
+    "oslam_world_put_colour": (_i, [_vp, _vp, _vp, _vp, _sz]),
+    "oslam_world_box_colour": (_i, [_vp, _vp, _vp, _vp, _vp, _i]),
+    "oslam_world_colours": (_i, [_vp, _vp, C.POINTER(WorldSurfaceParams), _vp, _sz, _sz, _vp, _vp, C.POINTER(_sz)]),
     "oslam_world_surface_params_default": (_i, [C.POINTER(WorldSurfaceParams)]),
     "oslam_world_surface": (_i, [_vp, _vp, C.POINTER(WorldSurfaceParams), _vp, _vp, _vp, _sz, C.POINTER(_sz),
                                  C.POINTER(WorldSurfaceResult)]),
@@ -523,6 +530,7 @@ _SIGNATURES = {
                                     C.POINTER(_sz)]),
     "oslam_volume_shift_world": (_i, [_vp, _vp, _vp, C.POINTER(ReloadResult)]),
     "oslam_volume_pack": (_i, [_vp, _vp, _vp, _vp, _sz, C.POINTER(_sz)]),
+    "oslam_volume_pack_colour": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(_sz)]),
     "oslam_mesh_params_default": (_i, [C.POINTER(MeshParams)]),
     "oslam_volume_mesh": (_i, [_vp, C.POINTER(MeshParams), _vp, _vp, _sz, _vp, _sz, C.POINTER(_sz), C.POINTER(_sz),
                                C.POINTER(MeshResult)]),
@@ -2138,9 +2146,11 @@ class World:
     """The voxel store (oslam_world): a host-side map from global voxel coordinates g = window index + window offset to
     TSDF words, which keeps what leaves a volume's shifting window (Volume.shift(s, world=...)) and gives it back when
     the window returns.  vol_or_params: a Volume, whose voxel size and created origin the store takes, or a
-    WorldParams.  max_bytes bounds the store's memory, 0 = 1 GiB.  Needs no device."""
+    WorldParams.  max_bytes bounds the store's memory, 0 = 1 GiB.  colour=True makes a colour store: every voxel keeps
+    its colour word next to its TSDF word, so a coloured volume's voxels leave and come back with their colour (a brick
+    then takes 4112 bytes instead of 2064; the volume needs enable_colour()).  Needs no device."""
 
-    def __init__(self, vol_or_params, max_bytes=0):
+    def __init__(self, vol_or_params, max_bytes=0, colour=False):
         self._h = C.c_void_p(0)
         if isinstance(vol_or_params, WorldParams):
             p = WorldParams.from_buffer_copy(vol_or_params)
@@ -2149,22 +2159,41 @@ class World:
             _check(lib().oslam_world_params_of(vol_or_params._h, C.byref(p)))
         if max_bytes:
             p.max_bytes = int(max_bytes)
+        if colour:
+            p.colour = 1
         self.params = p
         _check(lib().oslam_world_create(C.byref(p), C.byref(self._h)))
 
-    def put(self, g, words):
-        """Stores words uint32 [n] under g int32 [n,3]; unseen words (w == 0) are skipped, a later record wins."""
+    def has_colour(self):
+        """Whether this is a colour store (oslam_world_has_colour)."""
+        return bool(lib().oslam_world_has_colour(self._h))
+
+    def put(self, g, words, colours=None):
+        """Stores words uint32 [n] under g int32 [n,3]; unseen words (w == 0) are skipped, a later record wins.
+        colours: uint32 [n], the colour word of each record, on a colour store only (oslam_world_put_colour); without
+        them a colour store keeps colour 0 for these records."""
         g = np.ascontiguousarray(g, np.int32).reshape(-1, 3)
         words = np.ascontiguousarray(words, np.uint32).ravel()
         if len(g) != len(words):
             raise ValueError("g must be [n,3] and words [n]")
-        _check(lib().oslam_world_put(self._h, _p(g), _p(words), len(words)))
+        if colours is None:
+            _check(lib().oslam_world_put(self._h, _p(g), _p(words), len(words)))
+            return
+        colours = np.ascontiguousarray(colours, np.uint32).ravel()
+        if len(colours) != len(words):
+            raise ValueError("colours must be [n]")
+        _check(lib().oslam_world_put_colour(self._h, _p(g), _p(words), _p(colours), len(words)))
 
-    def box(self, lo, hi, take=False):
+    def box(self, lo, hi, take=False, colours=False):
         """The words with lo <= g < hi as uint32 [hz-lz, hy-ly, hx-lx], 0 where nothing is stored; take=True also
-        removes them from the store."""
+        removes them from the store.  colours=True, on a colour store: -> (words, colours), the colour words laid out
+        alike (oslam_world_box_colour)."""
         lo, hi = _shift3(lo), _shift3(hi)
         out = np.zeros(tuple(max(int(hi[a]) - int(lo[a]), 0) for a in (2, 1, 0)), np.uint32)
+        if colours:
+            col = np.zeros_like(out)
+            _check(lib().oslam_world_box_colour(self._h, _p(lo), _p(hi), _p(out), _p(col), int(bool(take))))
+            return out, col
         _check(lib().oslam_world_box(self._h, _p(lo), _p(hi), _p(out), int(bool(take))))
         return out
 
@@ -2178,12 +2207,26 @@ class World:
             _check(lib().oslam_world_bricks(self._h, _p(keys), n.value, C.byref(n)))
         return keys
 
-    def surface(self, vol=None, min_weight=1, anchor=None, keys=False, dev=0):
+    def colours(self, points, vol=None, anchor=None, dev=0):
+        """The fused colour of the whole map, this colour store plus the window of the coloured Volume vol (None: the
+        store alone, on device dev), at volume-frame points [n,3] (oslam_world_colours): -> (rgb uint8 [n,3], valid bool
+        [n]).  Volume.colours' rule against the map; anchor as in surface(): the points of surface() and the vertices of
+        mesh() are to be coloured with the anchor they were made with."""
+        sp = _world_surface_params(1, anchor, dev)
+        p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        rgb, valid, n = np.zeros((len(p), 3), np.uint8), np.zeros(len(p), np.uint8), C.c_size_t(0)
+        _check(lib().oslam_world_colours(self._h, vol._h if vol is not None else None, C.byref(sp), _p(p), len(p), 0, _p(rgb),
+                                         _p(valid), C.byref(n)))
+        assert n.value == int(valid.sum())
+        return rgb, valid.astype(bool)
+
+    def surface(self, vol=None, min_weight=1, anchor=None, keys=False, dev=0, colour=False):
         """Every zero crossing of the whole map, this store plus the window of the Volume vol (None: the store alone, on
         device dev), as a point with its outward normal in the volume frame (oslam_world_surface): -> (points [n,3],
         normals [n,3]) and with keys=True also int32 [n,4], (g_x, g_y, g_z, axis) of every point.  Bricks ascend by
         (bz, by, bx), a brick's points by voxel and axis; anchor (three ints, default the window's offset, or 0) picks the
-        frame the floats are formed in.  The result dict of the call is kept as self.last_surface."""
+        frame the floats are formed in.  With colour=True rgb uint8 [n,3] and valid bool [n], colours() of the points,
+        follow (ply_write(..., rgb=) takes them).  The result dict of the call is kept as self.last_surface."""
         sp = _world_surface_params(min_weight, anchor, dev)
         vh = vol._h if vol is not None else None
         n, res = C.c_size_t(0), WorldSurfaceResult()
@@ -2194,14 +2237,16 @@ class World:
             _check(lib().oslam_world_surface(self._h, vh, C.byref(sp), _p(po), _p(no), _p(ko) if keys else None, n.value,
                                              C.byref(n), C.byref(res)))
         self.last_surface = res.asdict()
-        return (po, no, ko) if keys else (po, no)
+        out = (po, no, ko) if keys else (po, no)
+        return out + self.colours(po, vol, anchor, dev) if colour else out
 
     def mesh(self, vol=None, min_weight=1, normals=True, anchor=None, keys=False, dev=0):
         """The marching-cubes mesh of the whole map, this store plus the window of the Volume vol (None: the store alone,
         on device dev) (oslam_world_mesh): -> (vertices [nv,3], normals [nv,3] or None, triangles uint32 [nt,3], result
         dict) and with keys=True also int32 [nv,4], (g_x, g_y, g_z, axis) of every vertex.  The vertices are every
         crossing of World.surface's rule in its order, (0, 0, 0) as the normal where there is none; normals=False skips
-        the trilinear reads.  ply_write_mesh takes the output as it is.  The result dict is kept as self.last_mesh."""
+        the trilinear reads.  ply_write_mesh takes the output as it is.  The result dict is kept as self.last_mesh.
+        mesh_colour() is this call with the vertices' colours."""
         sp = _world_surface_params(min_weight, anchor, dev)
         vh = vol._h if vol is not None else None
         nv, nt, res = C.c_size_t(0), C.c_size_t(0), WorldMeshResult()
@@ -2215,6 +2260,13 @@ class World:
                                           nv.value, _p(tri), nt.value, C.byref(nv), C.byref(nt), C.byref(res)))
         self.last_mesh = res.asdict()
         return (xyz, nrm, tri, self.last_mesh, ko) if keys else (xyz, nrm, tri, self.last_mesh)
+
+    def mesh_colour(self, vol=None, min_weight=1, normals=True, anchor=None, keys=False, dev=0):
+        """mesh() with the colour of every vertex: its outputs, then rgb uint8 [nv,3] and valid bool [nv], colours() of
+        the vertices with the same volume and anchor, as Volume.mesh(colour=True) appends them; ply_write_mesh(..., rgb=)
+        takes them.  (A method of its own: mesh()'s parameter list is pinned by tests/test_world_mesh_host.py.)"""
+        out = self.mesh(vol, min_weight, normals, anchor, keys, dev)
+        return out + self.colours(out[0], vol, anchor, dev)
 
     def stats(self):
         s = WorldStats()
@@ -2345,7 +2397,8 @@ class Volume:
         closed before returning.
         colour: the View that carries the frame's colour image, usually view itself.  Every integration of the step then
         fuses it too (integrate(..., colour=)); with static and smooth the z comes from the masked view and the colour
-        from this raw one.  With world the reloaded voxels come back without colour.
+        from this raw one.  With a world made with colour=True the voxels leave and come back with their colour; a
+        plain world keeps none, and what it reloads comes back without colour.
         self.last_integrate keeps the result dict of the frame's integration."""
         if static is not None:
             masked, mres = mask_view(view, static, "remove")
@@ -2385,7 +2438,8 @@ class Volume:
     def shift(self, s, world=None):
         """Moves the window of voxels by s = (sx, sy, sz) whole voxels (oslam_volume_shift): -> result dict.
         world: a World.  The seen voxels that leave go into it and those it holds for the entering region come back
-        (oslam_volume_shift_world); the result also has "stored" and "reloaded"."""
+        (oslam_volume_shift_world); the result also has "stored" and "reloaded".  A colour store (World(colour=True))
+        carries the voxels' colour words along both ways."""
         if world is not None:
             res = ReloadResult()
             _check(lib().oslam_volume_shift_world(self._h, world._h, _p(_shift3(s)), C.byref(res)))
@@ -2394,11 +2448,19 @@ class Volume:
         _check(lib().oslam_volume_shift(self._h, _p(_shift3(s)), C.byref(res)))
         return res.asdict()
 
-    def packed(self, s):
+    def packed(self, s, colours=False):
         """The records the device makes of the seen voxels that shift(s) would move out, as a test tap
-        (oslam_volume_pack): -> (lin uint32 [n], ascending linear indices (k * ny + j) * nx + i; words uint32 [n])."""
+        (oslam_volume_pack): -> (lin uint32 [n], ascending linear indices (k * ny + j) * nx + i; words uint32 [n]).
+        colours=True, on a volume with colour: -> (lin, words, colours uint32 [n]), the colour word of each record as a
+        colour store gets it (oslam_volume_pack_colour)."""
         s = _shift3(s)
         n = C.c_size_t(0)
+        if colours:
+            _check(lib().oslam_volume_pack_colour(self._h, _p(s), None, None, None, 0, C.byref(n)))
+            lin, words, col = (np.zeros(n.value, np.uint32) for _ in range(3))
+            if n.value:
+                _check(lib().oslam_volume_pack_colour(self._h, _p(s), _p(lin), _p(words), _p(col), n.value, C.byref(n)))
+            return lin, words, col
         _check(lib().oslam_volume_pack(self._h, _p(s), None, None, 0, C.byref(n)))
         lin, words = np.zeros(n.value, np.uint32), np.zeros(n.value, np.uint32)
         if n.value:

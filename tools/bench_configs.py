@@ -1226,6 +1226,120 @@ def worldmesh(calls=20):
     return out
 
 
+def worldcolour(calls=20):
+    """Colour through the voxel store and the colour of the whole map (oslam_volume_shift_world with a colour store,
+    oslam_world_colours) on the reload and worldmesh configurations' 256^3 map, fused with the colour images of
+    tests/colour_world.py.  Two measurements, each against its yardstick in the same run and alternately, so that drift
+    hits both alike.  The shift pair (+-8 on x and, as in reload, on the axis with the most seen voxels in its outer 8
+    planes) of the coloured volume through a colour store next to the same pair through a plain store: medians of `calls`
+    pairs, the records and launches of both.  Then, with the window moved by (64, 0, 0) through the colour store:
+    World.colours on the vertices of World.mesh(vol) next to Volume.colours on the vertices of Volume.mesh(), per call
+    and per point."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import camera_ref as E
+    import colour_world as W
+    world = E.make_world(synth, 0)
+    rgb = W.world_colours(world, 0)
+    sweep = E.trajectory(synth, 0, frames=10)
+    cam = E.CAM
+    rendered = []
+    for T in sweep:
+        depth, img, ok = W.render(synth, world, rgb, T)
+        v = ppf.View(depth, cam["fx"], cam["fy"], cam["cx"], cam["cy"], z_min=cam["z_min"], z_max=cam["z_max"], max_jump=E.MAX_JUMP)
+        v.set_colour(img, ok)
+        rendered.append(v)
+    spec = dict(nx=256, ny=256, nz=256, voxel=0.036, origin=[-2.9, -4.3, 0.3], mu=0.288)
+    vol = ppf.Volume(**spec)
+    vol.enable_colour()
+    steps = [vol.step(rendered[k], colour=rendered[k]) for k in list(range(10)) + list(range(8, -1, -1))]
+    q, w = vol.voxels()
+    c = vol.colour_words()
+    seen = w > 0                                                    # [nz, ny, nx]
+    slab = {"x-": int(seen[:, :, :8].sum()), "x+": int(seen[:, :, -8:].sum()), "y-": int(seen[:, :8, :].sum()),
+            "y+": int(seen[:, -8:, :].sum()), "z-": int(seen[:8, :, :].sum()), "z+": int(seen[-8:, :, :].sum())}
+    best = max(slab, key=lambda k: slab[k])
+    axis, sign = "xyz".index(best[0]), 1 if best[1] == "-" else -1  # a positive shift moves the low planes out
+    pairs = [("x", (8, 0, 0))]
+    if best != "x-":
+        s = [0, 0, 0]
+        s[axis] = 8 * sign
+        pairs.append((best, tuple(s)))
+    cstore, pstore = ppf.World(vol, colour=True), ppf.World(vol)
+    out = {"config": "worldcolour (oslam_volume_shift_world through a colour store, oslam_world_colours): the reload configuration's 256^3 "
+                     "volume after its 19-frame stream, fused with colour",
+           "volume": spec, "calls": calls, "step_ok": [None if r is None else r["ok"] for _, r in steps],
+           "coloured_voxels": int((c >> np.uint32(24) != 0).sum()), "seen_voxels": int(seen.sum()),
+           "seen_in_the_outer_8_planes": slab, "axis_with_surface": best, "pairs": []}
+
+    def restore():
+        vol.set_voxels(q, w)
+        vol.set_colour_words(c)
+
+    for name, s in pairs:
+        back = tuple(-x for x in s)
+        for store in (cstore, pstore):                              # the second buffers, the staging buffers, the bricks
+            vol.shift(s, store); vol.shift(back, store)
+            restore()
+        ms_c, ms_p, lib_c, lib_p, rc_out, rc_back, rp_out = [], [], [], [], None, None, None
+        for k in range(calls):                                      # alternately: a pair through the colour store, a pair through the plain one
+            t = time.perf_counter(); rc_out = vol.shift(s, cstore); rc_back = vol.shift(back, cstore); ms_c.append(0.5e3 * (time.perf_counter() - t))
+            lib_c.append(0.5 * (rc_out["ms_total"] + rc_back["ms_total"]))
+            if k == 0:
+                same = bool((vol.colour_words() == c)[seen].all())  # the seen voxels' colours came back
+                restore()
+            t = time.perf_counter(); rp_out = vol.shift(s, pstore); rp_back = vol.shift(back, pstore); ms_p.append(0.5e3 * (time.perf_counter() - t))
+            lib_p.append(0.5 * (rp_out["ms_total"] + rp_back["ms_total"]))
+            restore()
+        vol.shift(s, cstore)
+        bytes_c = cstore.stats()["bytes"]
+        vol.shift(back, cstore)
+        vol.shift(s, pstore)
+        bytes_p = pstore.stats()["bytes"]
+        vol.shift(back, pstore)
+        restore()
+        out["pairs"].append({"axis": name, "shift": list(s), "colour_store_shift_ms_median": float(np.median(ms_c)),
+                             "plain_store_shift_ms_median": float(np.median(ms_p)),
+                             "colour_over_plain": float(np.median(ms_c) / np.median(ms_p)),
+                             "colour_store_shift_ms_library_median": float(np.median(lib_c)),
+                             "plain_store_shift_ms_library_median": float(np.median(lib_p)),
+                             "stored_out_back": [rc_out["stored"], rc_back["stored"]], "reloaded_out_back": [rc_out["reloaded"], rc_back["reloaded"]],
+                             "launches_out_back": [rc_out["launches"], rc_back["launches"]],
+                             "plain_store_launches_out_back": [rp_out["launches"], rp_back["launches"]],
+                             "record_bytes_over_the_link_out": [12 * rc_out["stored"], 8 * rp_out["stored"]],
+                             "colour_store_bytes": bytes_c, "plain_store_bytes": bytes_p,
+                             "seen_colours_restored_bit_for_bit": same})
+    # the colour of the whole map's mesh vertices next to the window's
+    moved = vol.shift((64, 0, 0), cstore)
+    wx, _, wt, wres = cstore.mesh(vol, normals=False)
+    vx, _, vt, vres = vol.mesh(normals=False)
+    cstore.colours(wx, vol); vol.colours(vx)
+    ms_w, ms_v, wvalid, vvalid = [], [], None, None
+    for _ in range(calls):
+        t = time.perf_counter(); _, wvalid = cstore.colours(wx, vol); ms_w.append(1e3 * (time.perf_counter() - t))
+        t = time.perf_counter(); _, vvalid = vol.colours(vx); ms_v.append(1e3 * (time.perf_counter() - t))
+    t = time.perf_counter(); cstore.mesh_colour(vol); ms_mesh_colour = 1e3 * (time.perf_counter() - t)
+    t = time.perf_counter(); cstore.mesh(vol); ms_mesh = 1e3 * (time.perf_counter() - t)
+    inside = vol.colours(wx)[1]
+    st = cstore.stats()
+    out["colours"] = {"stored_by_the_shift": moved["stored"], "store": st,
+                      "world_colours_ms_median": float(np.median(ms_w)), "volume_colours_ms_median": float(np.median(ms_v)),
+                      "world_vertices": len(wx), "window_vertices": len(vx),
+                      "world_colours_ns_per_point": float(1e6 * np.median(ms_w) / max(len(wx), 1)),
+                      "volume_colours_ns_per_point": float(1e6 * np.median(ms_v) / max(len(vx), 1)),
+                      "world_over_volume_per_point": float((np.median(ms_w) / max(len(wx), 1)) / (np.median(ms_v) / max(len(vx), 1))),
+                      "world_vertices_with_colour": int(wvalid.sum()), "window_vertices_with_colour": int(vvalid.sum()),
+                      "world_vertices_coloured_only_through_the_store": int((wvalid & ~inside).sum()),
+                      "bricks": wres["bricks"], "window_bricks": wres["window_bricks"], "store_bricks": st["bricks"],
+                      "colour_brick_bytes_over_the_link": 2048 * st["bricks"], "point_bytes_over_the_link": 12 * len(wx),
+                      "world_mesh_with_colour_ms_once": ms_mesh_colour, "world_mesh_ms_once": ms_mesh}
+    for v in rendered:
+        v.close()
+    cstore.close()
+    pstore.close()
+    vol.close()
+    return out
+
+
 def pyramid(calls=20):
     """Image pyramids (oslam_pyramid_create, oslam_pyramid_egomotion) on frames 0 and 1 of the camera configuration's
     640x480 stream: the median of `calls` calls of Pyramid(view), of egomotion_pyramid and, in the same run, of egomotion
@@ -1366,4 +1480,4 @@ if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "cfg3"
     print(json.dumps({"cfg2": cfg2, "cfg3": cfg3, "cfg3db": cfg3db, "cfg4": cfg4, "cfg5": cfg5, "planes": planes, "db50": db50,
                       "refine": refine, "verify": verify, "instances": instances, "arbitrate": arbitrate, "explain": explain, "track": track, "camera": camera,
-                      "fusion": fusion, "colour": colour, "surface": surface, "mesh": mesh, "shift": shift, "reload": reload, "worldsurface": worldsurface, "worldmesh": worldmesh, "pyramid": pyramid, "bilateral": bilateral, "normals": normals}[which]()), flush=True)
+                      "fusion": fusion, "colour": colour, "surface": surface, "mesh": mesh, "shift": shift, "reload": reload, "worldsurface": worldsurface, "worldmesh": worldmesh, "worldcolour": worldcolour, "pyramid": pyramid, "bilateral": bilateral, "normals": normals}[which]()), flush=True)

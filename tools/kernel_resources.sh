@@ -7,7 +7,7 @@
 # vote addresses are computed on denormal floats (VoteRegs::vote) and need 3 there, denormals kept in and out.
 cd "$(dirname "$0")/../objective-slam_amd/csrc"
 units="$*"
-[ -z "$units" ] && units="oslam_kernels oslam_vote_wide oslam_sort oslam_posegpu oslam_voxel oslam_depth oslam_refine oslam_verify oslam_arbitrate oslam_track oslam_ego oslam_pyramid oslam_bilateral oslam_volume oslam_surface oslam_mesh oslam_shift oslam_reload oslam_normals oslam_colour oslam_world_surface oslam_world_mesh"
+[ -z "$units" ] && units="oslam_kernels oslam_vote_wide oslam_sort oslam_posegpu oslam_voxel oslam_depth oslam_refine oslam_verify oslam_arbitrate oslam_track oslam_ego oslam_pyramid oslam_bilateral oslam_volume oslam_surface oslam_mesh oslam_shift oslam_reload oslam_normals oslam_colour oslam_world_surface oslam_world_mesh oslam_reload_colour oslam_world_colour"
 for f in $units; do
   fl=""; [ $f = oslam_vote_wide ] && fl="-mllvm -disable-machine-licm"
   echo "== $f.hip $fl"
