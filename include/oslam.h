@@ -2024,6 +2024,17 @@ int oslam_vote_hits(oslam_model *m, oslam_scene *s, size_t ref_index, uint32_t *
  * the order (count desc, code asc); poses_out (may be NULL) gets 16 floats per cell. */
 int oslam_last_cells(oslam_model *m, oslam_cell *cells_out, float *poses_out, size_t cap,
                      size_t *n_out);
+/* The clustering scores of a NAMED pose tail over the n peak records `cells` (as oslam_align_finish takes them, with
+ * the global maximum): path 0 = the host loop, 1 = the host tail with the scores from the device kernel at any number
+ * of poses (production asks the kernel from 2048 poses on), 2 = the device tail at any number (production: from
+ * oslam_params.pose_gpu_min records on; it needs two kept cells, else OSLAM_E_NO_VOTES).  The scores oslam_last_result
+ * returns are always recomputed by the host loop; these are the ones the tail itself made.  cells_out / scores_out (may
+ * be NULL) receive at most cap kept cells in (count desc, code asc) order and the score of each; *n_out = the number
+ * kept, *max_idx_out the winner's index, T its matrix, *path_out the tail that really made the scores (a device tail
+ * that fell back to the host loop reports 0).  The model's last result is dropped by path 2. */
+int oslam_tail_scores(oslam_model *m, oslam_scene *s, const oslam_cell *cells, size_t n, uint32_t global_max, int path,
+                      oslam_cell *cells_out, float *scores_out, size_t cap, size_t *n_out, uint32_t *max_idx_out,
+                      float T[16], int *path_out);
 
 /* Launch stream for all kernels of this thread's calls (hipStream_t as void*;
  * NULL = the default stream).  bench.py passes torch's current stream. */

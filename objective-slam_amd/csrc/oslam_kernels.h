@@ -334,6 +334,8 @@ int oslamk_pose_finish_async(uint32_t n, const oslamk_cell *d_sel, const float *
                              uint32_t gmax, uint32_t model_points, uint32_t scene_points, int two_sorts,
                              const oslamk_inst_args *ia, uint32_t slot, void *stream);
 void oslamk_pose_result(uint32_t slot, uint32_t *best_out, float T_best[16]);
+/* test tap: the clustering scores [n] of the last chain over n records, to the host */
+int oslamk_pose_scores(uint32_t n, float *h_score, void *stream);
 /* the instance selection of a chain that was given ia (after the wait) */
 void oslamk_pose_instances(uint32_t slot, oslamk_inst_out *out);
 

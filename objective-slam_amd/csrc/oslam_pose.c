@@ -232,6 +232,13 @@ static inline unsigned char wait_flag(const unsigned char *flag)
 
 static __thread oslam_cluster_hook g_cluster_hook;
 void oslam_pose_set_cluster_hook(oslam_cluster_hook hook) { g_cluster_hook = hook; }
+/* the pose count from which the hook is asked (tests lower it: oslam_tail_scores), and whether the last clustering
+ * stage of this thread took its scores from the hook */
+#define CLUSTER_HOOK_MIN 2048
+static __thread size_t g_cluster_hook_min = CLUSTER_HOOK_MIN;
+static __thread int g_cluster_hook_used;
+void oslam_pose_set_cluster_hook_min(size_t n) { g_cluster_hook_min = n ? n : CLUSTER_HOOK_MIN; }
+int oslam_pose_cluster_hook_used(void) { return g_cluster_hook_used; }
 
 /* ---- K6 + K8 + K9 + argmax: returns max_idx ---- */
 #define NO_MEMORY ((size_t)-1)
@@ -269,9 +276,10 @@ static size_t cluster_by_cells(const oslam_cell *cells, size_t n, float *trans, 
      * index order, and a pose waits for a neighbour o < i only when it meets one (the lowest unfinished
      * index never waits, so the loop cannot lock up); the reads of o > i go to a copy of the original
      * translations.  The start of a cell's poses in the sorted list comes from a table, not a search. */
-    if (!averaged && n >= 2048 && g_cluster_hook &&
+    g_cluster_hook_used = 0;
+    if (!averaged && n >= g_cluster_hook_min && g_cluster_hook &&
         g_cluster_hook(n, trans, quat, wv, cell, (const uint32_t *)hi, d_dist, use_l1, score) == 0) {
-        /* scores are in place */
+        g_cluster_hook_used = 1;                     /* scores are in place */
     } else {
         int threads = 1;
         size_t cap = 64, next = 0;

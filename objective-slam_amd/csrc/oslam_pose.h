@@ -33,6 +33,11 @@ typedef int (*oslam_cluster_hook)(size_t n, const float *trans, const float *qua
                                   const int32_t *cell, const uint32_t *hash_idx, float d_dist, int use_l1,
                                   float *score);
 void oslam_pose_set_cluster_hook(oslam_cluster_hook hook);
+/* Both per thread, like the hook.  The hook is asked from n poses on: 0 = the default (2048), which production never
+ * changes; oslam_tail_scores lowers it so that small made-up pose sets reach the kernel.  _used: did the last clustering
+ * stage of this thread take its scores from the hook (1) or from the host loop (0)? */
+void oslam_pose_set_cluster_hook_min(size_t n);
+int oslam_pose_cluster_hook_used(void);
 
 /* instance candidates (include/oslam.h at oslam_align_instances), in candidate order: T [n][16], score [n], index [n]
  * (kept-cell index, or the head of a greedy cluster) */

@@ -569,6 +569,23 @@ extern "C" void oslamk_pose_result(uint32_t slot, uint32_t *best_out, float T_be
     memcpy(T_best, p->h_pin + (size_t)POSE_SLOT_WORDS * slot + 2, 16 * sizeof(float));
 }
 
+/* Test tap (oslam_tail_scores): the clustering scores [n] of the last chain over n records, copied to the host out of the
+ * work space, where they stay until the next chain (k_pose_instances does not write them); the caller still holds the
+ * device's lock. */
+extern "C" int oslamk_pose_scores(uint32_t n, float *h_score, void *stream_)
+{
+    pose_pool *p = cur_pool();
+    int rc = 0;
+    pose_carve c;
+    if (!p || !p->d || !h_score || n < 2) return (int)hipErrorInvalidValue;
+    carve_for(n, &c);
+    if (c.total > p->cap) return (int)hipErrorInvalidValue;
+    PCHK(hipStreamSynchronize((hipStream_t)stream_));
+    PCHK(hipMemcpy(h_score, p->d + c.score, sizeof(float) * n, hipMemcpyDeviceToHost));
+done:
+    return rc;
+}
+
 extern "C" void oslamk_pose_instances(uint32_t slot, oslamk_inst_out *out)
 {
     pose_pool *p = cur_pool();

@@ -301,6 +301,85 @@ int oslam_last_cells(oslam_model *m, oslam_cell *cells_out, float *poses_out, si
     return OSLAM_OK;
 }
 
+/* The clustering scores a chosen pose tail really computed (oslam_last_result's are always the host loop's).  The records
+ * go through the tail as oslam_align_finish's do, but the tail is named, not chosen by size: path 0 = the host loop,
+ * 1 = the host tail with k_cluster_scores behind the hook from two poses on, 2 = the device tail from two kept cells
+ * on.  *path_out says which of the three made the scores: a tail that fell back to the host loop reports 0. */
+int oslam_tail_scores(oslam_model *m, oslam_scene *s, const oslam_cell *cells, size_t n, uint32_t global_max, int path,
+                      oslam_cell *cells_out, float *scores_out, size_t cap, size_t *n_out, uint32_t *max_idx_out,
+                      float T[16], int *path_out)
+{
+    int rc;
+    oslam_cell *tmp = NULL;
+    float *sc = NULL;
+    uint32_t best = 0;
+    size_t kept = 0, i;
+    scratch_pool *pool = NULL;
+    if (!n_out || !path_out || !T || (!cells && n) || path < 0 || path > 2) return fail(OSLAM_E_INVALID, "bad argument");
+    *n_out = 0;
+    *path_out = -1;
+    if (max_idx_out) *max_idx_out = 0;
+    memset(T, 0, 16 * sizeof(float));
+    rc = oslam_check_pair(m, s);
+    if (rc != OSLAM_OK) return rc;
+    if (m->params.cpu_clustering || m->params.use_averaged_clusters)
+        return fail(OSLAM_E_INVALID, "the host-only clustering variants have no device tail");
+    for (i = 0; i < n; i++) {
+        const uint32_t sr = (uint32_t)(cells[i].code >> 32), mr = ((uint32_t)cells[i].code) >> 6;
+        if (sr >= (uint32_t)s->c.n || sr % s->df != 0 || mr >= (uint32_t)m->c.n)
+            return fail(OSLAM_E_INVALID, "a record names no reference point of this scene or no point of this model");
+    }
+    rc = oslam_pool_enter(m->dev, &pool);
+    if (rc != OSLAM_OK) return rc;
+    tmp = (oslam_cell *)malloc(sizeof(oslam_cell) * (n ? n : 1));
+    sc = (float *)calloc(n ? n : 1, sizeof(float));
+    if (!tmp || !sc) { rc = fail(OSLAM_E_NOMEM, "host allocation failed"); goto done; }
+    if (path == 2) {
+        uint32_t n_kept = 0;
+        int k;
+        if (n > m->out_cap) { rc = fail(OSLAM_E_LIMIT, "more records than the record buffer holds"); goto done; }
+        oslam_drop_last(m);                        /* the chain writes the buffers a result left on the device lives in */
+        rc = oslam_pose_tables(m, s);
+        if (rc == OSLAM_OK) rc = oslam_ensure_pose_buffers(m, n);
+        if (rc != OSLAM_OK) goto done;
+        if (n) HIPCHK(hipMemcpy(m->d_out, cells, sizeof(oslam_cell) * n, hipMemcpyHostToDevice));
+        k = oslamk_pose_stage(m->d_out, (uint32_t)n, m->params.vote_count_threshold * global_max, m->d_Tm16, s->d_Ts16, s->df,
+                              m->d_weights, oslam_rotx(), m->d_dist, m->params.use_l1_norm, m->d_pose_cells, m->d_pose_T, global_max,
+                              (uint32_t)m->c.n, (uint32_t)s->c.n, m->params.pose_two_sorts, NULL, &n_kept, &best, T, NULL,
+                              oslam_stream());
+        if (k == -2) { rc = fail(OSLAM_E_NOMEM, "host allocation failed"); goto done; }
+        if (k != 0) { rc = fail(OSLAM_E_DEVICE, hipGetErrorString((hipError_t)k)); goto done; }
+        if (n_kept < 2) { rc = fail(OSLAM_E_NO_VOTES, "fewer than two cells survive: the device tail leaves them to the host"); goto done; }
+        kept = n_kept;
+        KCHK(oslamk_pose_scores(n_kept, sc, oslam_stream()));
+        HIPCHK(hipMemcpy(tmp, m->d_pose_cells, sizeof(oslam_cell) * kept, hipMemcpyDeviceToHost));
+        *path_out = 2;
+    } else {
+        if (n) memcpy(tmp, cells, sizeof(oslam_cell) * n);
+        kept = oslam_filter_cells(tmp, n, m->params.vote_count_threshold, global_max);
+        oslam_sort_cells(tmp, kept);
+        if (path == 1) {
+            oslam_pose_set_cluster_hook(oslam_cluster_scores_on_device);
+            oslam_pose_set_cluster_hook_min(1);
+        }
+        rc = oslam_pose_stage_ex(tmp, kept, m->c.h_xyz, m->c.h_nrm, (size_t)m->c.n, s->c.h_xyz, s->c.h_nrm, (size_t)s->c.n,
+                                 m->d_dist, 0, m->params.use_l1_norm, 0, m->weights, T, NULL, NULL, NULL, sc, &best);
+        oslam_pose_set_cluster_hook(NULL);
+        oslam_pose_set_cluster_hook_min(0);
+        if (rc != OSLAM_OK) { rc = fail(rc, rc == OSLAM_E_NO_VOTES ? "no record above the threshold" : "pose stage failed"); goto done; }
+        *path_out = kept > 1 && oslam_pose_cluster_hook_used() ? 1 : 0;
+    }
+    if (cells_out) memcpy(cells_out, tmp, sizeof(oslam_cell) * (kept < cap ? kept : cap));
+    if (scores_out) memcpy(scores_out, sc, sizeof(float) * (kept < cap ? kept : cap));
+    if (max_idx_out) *max_idx_out = best;
+    *n_out = kept;
+done:
+    oslam_pool_unlock(pool);
+    free(tmp);
+    free(sc);
+    return rc;
+}
+
 /* ------------------------------------------------------------------------ */
 static uint64_t sm64(uint64_t *s)
 {

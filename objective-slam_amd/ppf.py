@@ -562,6 +562,8 @@ _SIGNATURES = {
     "oslam_model_key_numbers": (_i, [_vp, _vp, _vp, _vp, _sz, C.POINTER(_sz)]),
     "oslam_vote_ref_order": (_i, [_vp, _sz, _vp]),
     "oslam_last_cells": (_i, [_vp, _vp, _vp, _sz, C.POINTER(_sz)]),
+    "oslam_tail_scores": (_i, [_vp, _vp, _vp, _sz, C.c_uint32, _i, _vp, _vp, _sz, C.POINTER(_sz), C.POINTER(C.c_uint32), _vp,
+                               C.POINTER(_i)]),
     "oslam_set_stream": (_i, [_vp]),
     "oslam_last_error": (C.c_char_p, []),
     "oslam_set_host_threads": (_i, [_i]),
@@ -1359,6 +1361,18 @@ class Model:
         best = C.c_uint32(0)
         _check(lib().oslam_last_result(self._h, scene._h, _p(tr), _p(ro), _p(sc), k, C.byref(n), C.byref(best)))
         return tr[: n.value], ro[: n.value], sc[: n.value], int(best.value)
+
+    def tail_scores(self, scene, cells, global_max, path):
+        """The peak records through a named pose tail (oslam_tail_scores; path 0: host loop, 1: host tail with the scores
+        from the device kernel, 2: device tail): -> (kept cells in order, the score of each as that tail computed it,
+        the winner's index, its T 4x4, the tail that really ran)."""
+        cells = np.ascontiguousarray(cells, CELL_DTYPE)
+        k = max(len(cells), 1)
+        kept, sc, T = np.zeros(k, CELL_DTYPE), np.zeros(k, np.float32), np.zeros(16, np.float32)
+        n, best, ran = C.c_size_t(0), C.c_uint32(0), C.c_int(-1)
+        _check(lib().oslam_tail_scores(self._h, scene._h, _p(cells), len(cells), int(global_max), int(path), _p(kept), _p(sc), k,
+                                       C.byref(n), C.byref(best), _p(T), C.byref(ran)))
+        return kept[: n.value].copy(), sc[: n.value].copy(), int(best.value), T.reshape(4, 4), int(ran.value)
 
     def getHashKeys(self, ref_index):
         out = np.zeros(self.n, np.uint32)
