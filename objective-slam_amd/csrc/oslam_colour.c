@@ -3,7 +3,7 @@
  * kernels in oslam_colour.hip.  A view can carry a registered colour image and a volume a colour buffer of one word per
  * voxel; an integration with colour is oslam_volume_integrate plus one launch in the same call (the body is
  * oslam_volume_integrate_views of oslam_volume.c), and the colour comes back at points (oslam_volume_colours) or into a
- * view's colour image (oslam_volume_paint_view).  The shift of the colour buffer is in oslam_volume.c with the TSDF's.
+ * view's colour image (oslam_volume_paint_view).  The shift of the colour buffer is in oslam_window.c with the TSDF's.
  * Every call here that reads or writes a colour image or a colour buffer holds the volume lock.
  */
 #include <math.h>

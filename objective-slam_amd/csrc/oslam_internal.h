@@ -99,7 +99,7 @@ struct oslam_volume {
     int dev;                          /* stays the first field, as in oslam_view (the argument tests write it) */
     oslamk_volume k;                  /* k.origin follows off (oslam_volume_shift); p.origin stays the created one */
     oslam_volume_params p;
-    int off[3];                       /* the window's offset in voxels */
+    int off[3];                       /* the window's offset in voxels: the shift's commit writes it (oslam_window.c) */
     uint32_t *spare;                  /* the second buffer of oslam_volume_shift, NULL until the first shift */
     oslamk_colour colour;             /* the colour buffer (oslam_colour.c); words NULL until oslam_volume_colour_enable */
     uint32_t *colour_spare;           /* its second buffer for a shift, NULL until the first shift of a coloured volume */
@@ -340,7 +340,7 @@ int oslam_surface_check_params(const oslam_surface_params *sp, oslam_surface_par
 int oslam_volume_surface_cloud(oslam_volume *vol, unsigned min_weight, int *dev, float **d_pts6, uint32_t *np);
 /* ---- the surface of the whole map (oslam_world_surface.c) ---- */
 struct oslam_world_stage;
-/* a pinned staging buffer of a voxel store with room for bytes, with the store's lock held (oslam_volume.c) */
+/* a pinned staging buffer of a voxel store with room for bytes, with the store's lock held (oslam_window.c) */
 int oslam_world_stage_fit(struct oslam_world_stage *st, size_t bytes);
 /* sp NULL = defaults; checks them as oslam_world_surface does, before any handle is read; *out = the parameters in force */
 int oslam_world_surface_check_params(const oslam_world_surface_params *sp, oslam_world_surface_params *out);

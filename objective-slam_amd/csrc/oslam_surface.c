@@ -1,8 +1,9 @@
 /*
  * oslam_surface.c -- the fused surface of a TSDF volume as a cloud (include/oslam.h at oslam_volume_surface) and as a
  * triangle mesh (oslam_volume_mesh): the host side of the kernels in oslam_surface.hip and oslam_mesh.hip, and of the
- * extraction of what a shift loses (oslam_volume_leaving; the same launchers of oslam_surface.hip with a shift).  A call
- * counts, waits for the totals, allocates exactly that and emits, under the volume lock of oslam_volume.c.
+ * extraction of what a shift loses (oslam_volume_leaving; the same launchers of oslam_surface.hip with a shift; the shift
+ * itself is oslam_window.c).  A call counts, waits for the totals, allocates exactly that and emits, under the volume
+ * lock of oslam_volume.c.
  */
 #include "oslam_internal.h"
 #include "oslam_mc_table.h"

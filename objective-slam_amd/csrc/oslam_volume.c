@@ -4,20 +4,18 @@
  * counter block, runs one kernel and reads the counters back with one host wait.  oslam_volume_track is glue over the
  * ray cast and oslam_view_egomotion, oslam_volume_track_pyramid over the ray cast, a pyramid of it and
  * oslam_pyramid_egomotion (one body, track_from_raycast); oslam_view_to_cloud runs the depth front end's compaction
- * over a view's maps.  oslam_volume_shift moves the window of voxels the volume holds (k_tsdf_shift of oslam_shift.hip
- * into a second buffer, then a swap of the two), oslam_volume_follow decides such a move on the host,
- * oslam_volume_shift_world makes it through a voxel store that keeps what leaves and gives back what returns (the store:
- * oslam_world.c; kernels: oslam_reload.hip).  The extraction of
- * the fused volume, or of what a shift loses, as a cloud or a triangle list is oslam_surface.c (kernels: oslam_surface.hip
- * and oslam_mesh.hip).  The limits of a volume's sides and of a shift are oslam_kernels.h's.  A volume with colour
- * (oslam_colour.c) gets its colour pass from the integration's body here, in the same call, and its colour buffer moves
- * with every shift.
+ * over a view's maps.  Here too: a volume's parameters, create, destroy and reset, the view read-backs, the voxel get and
+ * set, and the volume lock that every call on a volume takes.  The moving window (oslam_volume_shift,
+ * oslam_volume_shift_world, the pack's tap, oslam_volume_follow) is oslam_window.c, its arithmetic oslam_window.h.  The
+ * extraction of the fused volume, or of what a shift loses, as a cloud or a triangle list is oslam_surface.c (kernels:
+ * oslam_surface.hip and oslam_mesh.hip).  The limits of a volume's sides are oslam_kernels.h's.  A volume with colour
+ * (oslam_colour.c) gets its colour pass from the integration's body here, in the same call.
  */
 #include <math.h>
 #include <pthread.h>
 
 #include "oslam_internal.h"
-#include "oslam_world.h"
+#include "oslam_window.h"
 
 /* calls on volumes, oslam_view_to_cloud and oslam_view_maps take turns.  Lock order: g_vol_mu, then the lock of oslam_view_egomotion, then the views' maps */
 static pthread_mutex_t g_vol_mu = PTHREAD_MUTEX_INITIALIZER;
@@ -102,20 +100,6 @@ int oslam_volume_destroy(oslam_volume *vol)
     return OSLAM_OK;
 }
 
-/* the origin of the window at vol->off, derived from the created origin and never accumulated (include/oslam.h at
- * oslam_volume_shift): one float multiply, then one float add */
-static void window_origin(const oslam_volume *vol, const int off[3], float origin[3])
-{
-    int a;
-    for (a = 0; a < 3; a++) {
-        origin[a] = vol->p.origin[a];
-        if (off[a] != 0) {
-            const float step = (float)off[a] * vol->p.voxel;
-            origin[a] = vol->p.origin[a] + step;
-        }
-    }
-}
-
 int oslam_volume_reset(oslam_volume *vol)
 {
     int rc = OSLAM_OK;
@@ -126,7 +110,7 @@ int oslam_volume_reset(oslam_volume *vol)
     if (vol->colour.words) HIPCHK(hipMemsetAsync(vol->colour.words, 0, oslam_volume_bytes(&vol->p), (hipStream_t)oslam_stream()));
     HIPCHK(hipStreamSynchronize((hipStream_t)oslam_stream()));
     memset(vol->off, 0, sizeof vol->off);
-    window_origin(vol, vol->off, vol->k.origin);
+    oslam_window_origin(vol->p.origin, vol->p.voxel, vol->off, vol->k.origin);
 done:
     pthread_mutex_unlock(&g_vol_mu);
     return rc;
@@ -389,439 +373,4 @@ done:
     pthread_mutex_unlock(&g_vol_mu);
     free(h);
     return rc;
-}
-
-/* ---- the shifting window (include/oslam.h at oslam_volume_shift; kernel: oslam_shift.hip) ---- */
-/* the second buffers a shift needs, with g_vol_mu held and the volume's device bound: the TSDF's and, on a coloured
- * volume, the colours'.  Both exist afterwards or the call fails before anything moved */
-static int shift_spares(oslam_volume *vol)
-{
-    uint32_t **want[2] = {&vol->spare, vol->colour.words ? &vol->colour_spare : NULL};
-    int b;
-    for (b = 0; b < 2; b++) {
-        if (!want[b] || *want[b]) continue;
-        if (hipMalloc((void **)want[b], oslam_volume_bytes(&vol->p)) != hipSuccess) {
-            (void)hipGetLastError();
-            *want[b] = NULL;
-            return fail(OSLAM_E_NOMEM, "no device memory for the second buffer of the shift");
-        }
-    }
-    return OSLAM_OK;
-}
-
-/* the colours of a coloured volume moved as k_tsdf_shift moves words, into colour_spare: launched behind the TSDF's shift;
- * scratch = a zeroed counter for the kernel's count, which nobody reads.  The caller swaps after its wait */
-static int shift_colours(const oslam_volume *vol, const int shift[3], uint32_t *scratch, void *stream)
-{
-    oslamk_volume k = vol->k;
-    k.words = vol->colour.words;
-    return oslamk_tsdf_shift(&k, vol->colour_spare, shift, scratch, stream);
-}
-
-static void swap_colours(oslam_volume *vol)
-{
-    uint32_t *t = vol->colour.words;
-    vol->colour.words = vol->colour_spare;
-    vol->colour_spare = t;
-}
-
-int oslam_volume_shift(oslam_volume *vol, const int shift[3], oslam_shift_result *res)
-{
-    int rc = OSLAM_OK, a, off[3];
-    const double t0 = now_ms();
-    uint32_t *d_cnt = NULL, *spare = NULL, kept = 0;
-    void *stream = oslam_stream();
-    if (!vol || !shift) return fail(OSLAM_E_INVALID, "NULL argument");
-    if (!oslamk_shift_ok(shift)) return fail(OSLAM_E_INVALID, "a shift is at most 2^20 voxels");
-    pthread_mutex_lock(&g_vol_mu);
-    for (a = 0; a < 3; a++) off[a] = vol->off[a] + shift[a];
-    if (!oslamk_shift_ok(off)) { rc = fail(OSLAM_E_INVALID, "the window's offset is at most 2^20 voxels"); goto done; }
-    if (res) memset(res, 0, sizeof *res);
-    if (!(shift[0] | shift[1] | shift[2])) {
-        if (res) memcpy(res->offset, off, sizeof off);
-        goto done;
-    }
-    if (hipSetDevice(vol->dev) != hipSuccess) { rc = fail(OSLAM_E_DEVICE, "hipSetDevice failed"); goto done; }
-    rc = shift_spares(vol);
-    if (rc != OSLAM_OK) goto done;
-    spare = vol->spare;
-    KCHK(oslam_counters_open(&d_cnt, 0, stream));
-    KCHK(oslamk_tsdf_shift(&vol->k, spare, shift, d_cnt, stream));
-    if (vol->colour.words) KCHK(shift_colours(vol, shift, d_cnt + 1, stream));
-    HIPCHK(hipMemcpyAsync(&kept, d_cnt, sizeof kept, hipMemcpyDeviceToHost, (hipStream_t)stream));
-    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-    vol->spare = vol->k.words;
-    vol->k.words = spare;
-    if (vol->colour.words) swap_colours(vol);
-    memcpy(vol->off, off, sizeof off);
-    window_origin(vol, vol->off, vol->k.origin);
-    if (res) {
-        memcpy(res->offset, off, sizeof off);
-        res->kept = kept;
-        res->launches = vol->colour.words ? 2 : 1;
-    }
-done:
-    if (rc != OSLAM_OK && d_cnt) (void)hipStreamSynchronize((hipStream_t)stream);
-    pthread_mutex_unlock(&g_vol_mu);
-    if (d_cnt) oslam_dev_free(d_cnt);
-    if (rc == OSLAM_OK && res) res->ms_total = (float)(now_ms() - t0);
-    return rc;
-}
-
-/* ---- the shift through the voxel store (include/oslam.h at oslam_volume_shift_world; kernels: oslam_reload.hip; the
- * store: oslam_world.c) ---- */
-int oslam_world_params_of(const oslam_volume *vol, oslam_world_params *p)
-{
-    if (!vol || !p) return fail(OSLAM_E_INVALID, "NULL argument");
-    memset(p, 0, sizeof *p);
-    p->voxel = vol->p.voxel;
-    memcpy(p->origin0, vol->p.origin, sizeof p->origin0);
-    return OSLAM_OK;
-}
-
-/* The two passes of the pack, with g_vol_mu held and the volume's device bound: *n_rec = the seen voxels that leave
- * under shift; at most cap of them are packed, into *d_rec = device [n_rec][2] (NULL otherwise).  One host wait, for the
- * total; the second pass is only launched.  With colours (the volume's colour buffer, or NULL) *d_rec is [n_rec][2]
- * followed by [n_rec] colour words, gathered behind the second pass: one buffer, so one copy takes both down.  The caller
- * frees *d_cnt and *d_rec after its own wait */
-static int pack_leaving(oslam_volume *vol, const int shift[3], size_t cap, const uint32_t *colours, uint32_t **d_cnt, uint32_t **d_rec,
-                        uint32_t *n_rec, uint32_t *launches)
-{
-    int rc = OSLAM_OK;
-    const uint32_t n_groups = oslamk_pack_groups(&vol->k);
-    void *stream = oslam_stream();
-    *n_rec = 0;
-    KCHK(oslam_counters_open(d_cnt, n_groups, stream));            /* the total in the first 256 bytes, then one counter per workgroup */
-    KCHK(oslamk_tsdf_pack_count(&vol->k, shift, n_groups, *d_cnt + 64, *d_cnt, stream));
-    *launches += 2;
-    HIPCHK(hipMemcpyAsync(n_rec, *d_cnt, sizeof *n_rec, hipMemcpyDeviceToHost, (hipStream_t)stream));
-    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-    if (*n_rec > 0 && (size_t)*n_rec <= cap) {
-        KCHK(oslam_dev_alloc((void **)d_rec, sizeof(uint32_t) * (colours ? 3 : 2) * (size_t)*n_rec));
-        KCHK(oslamk_tsdf_pack_emit(&vol->k, shift, n_groups, *d_cnt + 64, *n_rec, *d_rec, stream));
-        *launches += 1;
-        if (colours) {
-            KCHK(oslamk_pack_colours(colours, vol->k.nx, vol->k.ny, vol->k.nz, *d_rec, *n_rec, *d_rec + 2 * (size_t)*n_rec, stream));
-            *launches += 1;
-        }
-    }
-done:
-    return rc;
-}
-
-static void stage_release(void *p) { (void)hipHostFree(p); }
-
-/* a pinned staging buffer of the store with room for bytes: grown by half as much again, so a stream of similar shifts
- * allocates once (oslam_world_surface.c stages the store's bricks through it too) */
-int oslam_world_stage_fit(oslam_world_stage *st, size_t bytes)
-{
-    void *p = NULL;
-    const size_t want = bytes + bytes / 2;
-    if (st->bytes >= bytes) return OSLAM_OK;
-    if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(OSLAM_E_NOMEM, "no pinned host memory for the records of the shift");
-    }
-    if (st->p) st->release(st->p);
-    st->p = p;
-    st->bytes = want;
-    st->release = stage_release;
-    return OSLAM_OK;
-}
-
-/* The entering region, the window at off_new minus the window at off_old in global coordinates, as at most 7 disjoint
- * boxes lo <= g < hi: axis by axis, the slabs of what remains that lie outside the old window, then the rest restricted
- * to the overlap; all of what remains as soon as an axis has no overlap.  -> the number of boxes */
-static int entering_boxes(const int off_old[3], const int off_new[3], const unsigned n[3], int32_t lo[7][3], int32_t hi[7][3])
-{
-    int a, nb = 0;
-    int32_t cl[3], ch[3];
-    for (a = 0; a < 3; a++) {
-        cl[a] = off_new[a];
-        ch[a] = off_new[a] + (int)n[a];
-    }
-    for (a = 0; a < 3; a++) {
-        const int32_t ol = cl[a] > off_old[a] ? cl[a] : off_old[a];
-        const int32_t oh = ch[a] < off_old[a] + (int)n[a] ? ch[a] : off_old[a] + (int)n[a];
-        if (ol >= oh) {
-            memcpy(lo[nb], cl, sizeof cl);
-            memcpy(hi[nb], ch, sizeof ch);
-            return nb + 1;
-        }
-        if (cl[a] < ol) {
-            memcpy(lo[nb], cl, sizeof cl);
-            memcpy(hi[nb], ch, sizeof ch);
-            hi[nb++][a] = ol;
-        }
-        if (oh < ch[a]) {
-            memcpy(lo[nb], cl, sizeof cl);
-            memcpy(hi[nb], ch, sizeof ch);
-            lo[nb++][a] = oh;
-        }
-        cl[a] = ol;
-        ch[a] = oh;
-    }
-    return nb;                                                      /* what remains is the overlap: it does not enter */
-}
-
-/* the global coordinate of the old window's voxel lin */
-static void global_of(const oslam_volume *vol, uint32_t lin, int32_t g[3])
-{
-    const uint32_t row = lin / vol->p.nx;
-    g[0] = (int32_t)(lin - row * vol->p.nx) + vol->off[0];
-    g[1] = (int32_t)(row % vol->p.ny) + vol->off[1];
-    g[2] = (int32_t)(row / vol->p.ny) + vol->off[2];
-}
-
-typedef struct enter_ctx {
-    uint32_t *rec;                                                  /* [n][2]: lin in the new window, word */
-    uint32_t *col;                                                  /* [n]: the colour stored with it, or NULL */
-    size_t n;
-    int off[3];
-    size_t nx, ny;
-} enter_ctx;
-
-static void enter_record(void *ctx, const int32_t g[3], uint32_t word, uint32_t colour)
-{
-    enter_ctx *e = (enter_ctx *)ctx;
-    e->rec[2 * e->n] = (uint32_t)(((size_t)(g[2] - e->off[2]) * e->ny + (size_t)(g[1] - e->off[1])) * e->nx + (size_t)(g[0] - e->off[0]));
-    e->rec[2 * e->n + 1] = word;
-    if (e->col) e->col[e->n] = colour;
-    e->n++;
-}
-
-int oslam_volume_shift_world(oslam_volume *vol, oslam_world *w, const int shift[3], oslam_reload_result *res)
-{
-    int rc = OSLAM_OK, a, b, nb = 0, off[3], locked = 0, reserved = 0, cs = 0;
-    const double t0 = now_ms();
-    uint32_t *d_cnt = NULL, *d_out = NULL, *d_in = NULL, *d_kept = NULL, *spare = NULL;
-    uint32_t n_out = 0, kept = 0, launches = 0, r;
-    size_t n_in = 0, mark = 0, rec_words = 2;
-    int32_t lo[7][3], hi[7][3], g[3];
-    const uint32_t *rec_out = NULL, *col_out = NULL;
-    oslam_world_stage *st = NULL;
-    void *stream = oslam_stream();
-    if (!vol || !w || !shift) return fail(OSLAM_E_INVALID, "NULL argument");
-    if (!oslamk_shift_ok(shift)) return fail(OSLAM_E_INVALID, "a shift is at most 2^20 voxels");
-    pthread_mutex_lock(&g_vol_mu);
-    for (a = 0; a < 3; a++) off[a] = vol->off[a] + shift[a];
-    if (!oslamk_shift_ok(off)) { rc = fail(OSLAM_E_INVALID, "the window's offset is at most 2^20 voxels"); goto done; }
-    if (!oslam_world_compatible(w, vol->p.voxel, vol->p.origin)) {
-        rc = fail(OSLAM_E_INVALID, "the voxel store was made for another voxel size or origin");
-        goto done;
-    }
-    cs = oslam_world_coloured(w);                                   /* fixed when the store was created */
-    if (cs && !vol->colour.words) {
-        rc = fail(OSLAM_E_INVALID, "a colour store needs a volume with colour");
-        goto done;
-    }
-    rec_words = cs ? 3 : 2;                                         /* a record crosses the host link as 12 bytes or as 8 */
-    if (res) memset(res, 0, sizeof *res);
-    if (!(shift[0] | shift[1] | shift[2])) {
-        if (res) memcpy(res->offset, off, sizeof off);
-        goto done;
-    }
-    if (hipSetDevice(vol->dev) != hipSuccess) { rc = fail(OSLAM_E_DEVICE, "hipSetDevice failed"); goto done; }
-    rc = shift_spares(vol);
-    if (rc != OSLAM_OK) goto done;
-    spare = vol->spare;
-    /* 1. pack what leaves, with its colours for a colour store, and copy it down */
-    rc = pack_leaving(vol, shift, (size_t)-1, cs ? vol->colour.words : NULL, &d_cnt, &d_out, &n_out, &launches);
-    if (rc != OSLAM_OK) goto done;
-    oslam_world_lock(w);
-    locked = 1;
-    st = oslam_world_stages(w);
-    if (n_out) {
-        rc = oslam_world_stage_fit(&st[0], sizeof(uint32_t) * rec_words * (size_t)n_out);
-        if (rc != OSLAM_OK) goto done;
-        HIPCHK(hipMemcpyAsync(st[0].p, d_out, sizeof(uint32_t) * rec_words * (size_t)n_out, hipMemcpyDeviceToHost, (hipStream_t)stream));
-        HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-        rec_out = (const uint32_t *)st[0].p;
-        if (cs) col_out = rec_out + 2 * (size_t)n_out;
-    }
-    /* 2. the bricks the leaving records need, still empty */
-    mark = oslam_world_mark(w);
-    reserved = 1;
-    for (r = 0; r < n_out; r++) {
-        global_of(vol, rec_out[2 * r], g);
-        rc = oslam_world_reserve(w, g);
-        if (rc != OSLAM_OK) goto done;
-    }
-    /* 3. the entering records: counted, then read; the store does not change */
-    {
-        const unsigned n[3] = {vol->p.nx, vol->p.ny, vol->p.nz};
-        nb = entering_boxes(vol->off, off, n, lo, hi);
-    }
-    for (b = 0; b < nb; b++) n_in += oslam_world_visit(w, lo[b], hi[b], 0, NULL, NULL);
-    if (n_in) {
-        enter_ctx e;
-        rc = oslam_world_stage_fit(&st[1], sizeof(uint32_t) * rec_words * n_in);
-        if (rc != OSLAM_OK) goto done;
-        e.rec = (uint32_t *)st[1].p;
-        e.col = cs ? e.rec + 2 * n_in : NULL;
-        e.n = 0;
-        memcpy(e.off, off, sizeof off);
-        e.nx = vol->p.nx;
-        e.ny = vol->p.ny;
-        for (b = 0; b < nb; b++) (void)oslam_world_visit_colour(w, lo[b], hi[b], 0, enter_record, &e);
-        /* 4. copy up; shift and unpack in stream order */
-        KCHK(oslam_dev_alloc((void **)&d_in, sizeof(uint32_t) * rec_words * n_in));
-        HIPCHK(hipMemcpyAsync(d_in, st[1].p, sizeof(uint32_t) * rec_words * n_in, hipMemcpyHostToDevice, (hipStream_t)stream));
-    }
-    KCHK(oslam_counters_open(&d_kept, 0, stream));
-    KCHK(oslamk_tsdf_shift(&vol->k, spare, shift, d_kept, stream));
-    launches++;
-    if (vol->colour.words) {                                            /* a plain store keeps no colour: what it reloads has wc = 0 */
-        KCHK(shift_colours(vol, shift, d_kept + 1, stream));
-        launches++;
-        if (cs && n_in) {                                               /* a colour store's colours, into the buffer that shift wrote */
-            KCHK(oslamk_unpack_colours(vol->colour_spare, vol->k.nx, vol->k.ny, vol->k.nz, d_in, d_in + 2 * n_in, (uint32_t)n_in, stream));
-            launches++;
-        }
-    }
-    if (n_in) {
-        KCHK(oslamk_tsdf_unpack(spare, vol->k.nx, vol->k.ny, vol->k.nz, d_in, (uint32_t)n_in, stream));
-        launches++;
-    }
-    HIPCHK(hipMemcpyAsync(&kept, d_kept, sizeof kept, hipMemcpyDeviceToHost, (hipStream_t)stream));
-    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-    /* 5. commit: nothing below can fail */
-    for (r = 0; r < n_out; r++) {
-        global_of(vol, rec_out[2 * r], g);
-        oslam_world_store_colour(w, g, rec_out[2 * r + 1], col_out ? col_out[r] : 0u);
-    }
-    for (b = 0; b < nb; b++) (void)oslam_world_visit(w, lo[b], hi[b], 1, NULL, NULL);
-    reserved = 0;
-    vol->spare = vol->k.words;
-    vol->k.words = spare;
-    if (vol->colour.words) swap_colours(vol);
-    memcpy(vol->off, off, sizeof off);
-    window_origin(vol, vol->off, vol->k.origin);
-    if (res) {
-        memcpy(res->offset, off, sizeof off);
-        res->kept = kept + (uint32_t)n_in;                          /* the reloaded words are seen and their voxels were 0 */
-        res->stored = n_out;
-        res->reloaded = (uint32_t)n_in;
-        res->launches = launches;
-    }
-done:
-    if (rc != OSLAM_OK && d_cnt) (void)hipStreamSynchronize((hipStream_t)stream);
-    if (reserved) oslam_world_rollback(w, mark);
-    if (locked) oslam_world_unlock(w);
-    pthread_mutex_unlock(&g_vol_mu);
-    if (d_kept) oslam_dev_free(d_kept);
-    if (d_in) oslam_dev_free(d_in);
-    if (d_out) oslam_dev_free(d_out);
-    if (d_cnt) oslam_dev_free(d_cnt);
-    if (rc == OSLAM_OK && res) res->ms_total = (float)(now_ms() - t0);
-    return rc;
-}
-
-/* the tap of the pack, without colours (colour_out == NULL, want_colour == 0) or with them */
-static int pack_tap(oslam_volume *vol, const int shift[3], uint32_t *lin_out, uint32_t *word_out, uint32_t *colour_out, int want_colour,
-                    size_t cap, size_t *n_out)
-{
-    int rc = OSLAM_OK;
-    uint32_t *d_cnt = NULL, *d_rec = NULL, *h = NULL, n = 0, launches = 0, r;
-    const size_t rec_words = want_colour ? 3 : 2;
-    if (!vol || !shift || !n_out) return fail(OSLAM_E_INVALID, "NULL argument");
-    if (cap != 0 && (!lin_out || !word_out || (want_colour && !colour_out)))
-        return fail(OSLAM_E_INVALID, "the outputs must be given with cap != 0");
-    if (want_colour && !vol->colour.words) return fail(OSLAM_E_INVALID, "the volume has no colour");
-    if (!oslamk_shift_ok(shift)) return fail(OSLAM_E_INVALID, "a shift is at most 2^20 voxels");
-    *n_out = 0;
-    if (!(shift[0] | shift[1] | shift[2])) return OSLAM_OK;
-    if (hipSetDevice(vol->dev) != hipSuccess) return fail(OSLAM_E_DEVICE, "hipSetDevice failed");
-    pthread_mutex_lock(&g_vol_mu);
-    rc = pack_leaving(vol, shift, cap, want_colour ? vol->colour.words : NULL, &d_cnt, &d_rec, &n, &launches);
-    if (rc != OSLAM_OK) goto done;
-    *n_out = n;
-    if (cap != 0 && (size_t)n > cap) { rc = fail(OSLAM_E_LIMIT, "output capacity too small"); goto done; }
-    if (d_rec) {
-        h = (uint32_t *)malloc(sizeof(uint32_t) * rec_words * (size_t)n);
-        if (!h) { rc = fail(OSLAM_E_NOMEM, "host allocation failed"); goto done; }
-        HIPCHK(hipMemcpy(h, d_rec, sizeof(uint32_t) * rec_words * (size_t)n, hipMemcpyDeviceToHost));
-        for (r = 0; r < n; r++) {
-            lin_out[r] = h[2 * r];
-            word_out[r] = h[2 * r + 1];
-            if (want_colour) colour_out[r] = h[2 * (size_t)n + r];
-        }
-    }
-done:
-    if (d_cnt) (void)hipStreamSynchronize((hipStream_t)oslam_stream());
-    pthread_mutex_unlock(&g_vol_mu);
-    free(h);
-    if (d_rec) oslam_dev_free(d_rec);
-    if (d_cnt) oslam_dev_free(d_cnt);
-    return rc;
-}
-
-int oslam_volume_pack(oslam_volume *vol, const int shift[3], uint32_t *lin_out, uint32_t *word_out, size_t cap, size_t *n_out)
-{
-    return pack_tap(vol, shift, lin_out, word_out, NULL, 0, cap, n_out);
-}
-
-int oslam_volume_pack_colour(oslam_volume *vol, const int shift[3], uint32_t *lin_out, uint32_t *word_out, uint32_t *colour_out,
-                             size_t cap, size_t *n_out)
-{
-    return pack_tap(vol, shift, lin_out, word_out, colour_out, 1, cap, n_out);
-}
-
-int oslam_volume_window(oslam_volume *vol, int offset_out[3], float origin_out[3])
-{
-    if (!vol || !offset_out || !origin_out) return fail(OSLAM_E_INVALID, "NULL argument");
-    pthread_mutex_lock(&g_vol_mu);
-    memcpy(offset_out, vol->off, sizeof vol->off);
-    memcpy(origin_out, vol->k.origin, sizeof vol->k.origin);
-    pthread_mutex_unlock(&g_vol_mu);
-    return OSLAM_OK;
-}
-
-int oslam_follow_params_default(const oslam_volume *vol, oslam_follow_params *fp)
-{
-    unsigned n_min;
-    if (!vol || !fp) return fail(OSLAM_E_INVALID, "NULL argument");
-    memset(fp, 0, sizeof *fp);
-    n_min = vol->p.nx < vol->p.ny ? vol->p.nx : vol->p.ny;
-    if (vol->p.nz < n_min) n_min = vol->p.nz;
-    fp->lookahead = (float)(0.5 * (double)vol->p.nz * (double)vol->p.voxel);
-    fp->threshold = (float)n_min / 4.0f;
-    fp->granule = 8;
-    return OSLAM_OK;
-}
-
-int oslam_volume_follow(oslam_volume *vol, const float T_vol_cam[16], const oslam_follow_params *fp, int shift_out[3])
-{
-    int rc, a, moved = 0;
-    oslam_follow_params p;
-    float origin[3];
-    double d[3];
-    if (!vol || !T_vol_cam || !shift_out) return fail(OSLAM_E_INVALID, "NULL argument");
-    if (fp && (!isfinite(fp->lookahead) || !isfinite(fp->threshold) || !(fp->lookahead >= 0.0f) || !(fp->threshold >= 0.0f)))
-        return fail(OSLAM_E_INVALID, "lookahead and threshold must be finite and not negative");
-    if (fp && (fp->granule < 1 || fp->granule > 64)) return fail(OSLAM_E_INVALID, "granule must lie in 1..64");
-    rc = oslam_refine_check_rigid(T_vol_cam);
-    if (rc != OSLAM_OK) return rc;
-    if (fp) p = *fp;
-    else oslam_follow_params_default(vol, &p);
-    pthread_mutex_lock(&g_vol_mu);
-    memcpy(origin, vol->k.origin, sizeof origin);
-    pthread_mutex_unlock(&g_vol_mu);
-    {
-        const unsigned n[3] = {vol->p.nx, vol->p.ny, vol->p.nz};
-        const double h = (double)vol->p.voxel;
-        for (a = 0; a < 3; a++) {
-            const double c = (double)T_vol_cam[4 * a + 3] + (double)p.lookahead * (double)T_vol_cam[4 * a + 2];
-            const double centre = (double)origin[a] + 0.5 * (double)n[a] * h;
-            d[a] = (c - centre) / h;
-            if (!(fabs(d[a]) <= (double)p.threshold)) moved = 1;
-        }
-        for (a = 0; a < 3; a++) {
-            double s = moved ? (double)p.granule * rint(d[a] / (double)p.granule) : 0.0;
-            if (s > (double)n[a]) s = (double)n[a];
-            if (s < -(double)n[a]) s = -(double)n[a];
-            shift_out[a] = (int)s;
-        }
-    }
-    return OSLAM_OK;
 }

@@ -1,5 +1,5 @@
 /*
- * oslam_world.h -- the voxel store as oslam_volume.c uses it (semantics: include/oslam.h at oslam_volume_shift_world;
+ * oslam_world.h -- the voxel store as oslam_window.c uses it (semantics: include/oslam.h at oslam_volume_shift_world;
  * the store itself: oslam_world.c).  Nothing here needs a device: the staging buffers are kept as plain pointers with
  * the function that frees them, both given by the caller that allocated them.
  */

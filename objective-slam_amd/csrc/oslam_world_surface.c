@@ -7,6 +7,7 @@
  * bricks, counts, waits for the totals, allocates exactly that and emits, under the volume lock and the store's.
  */
 #include "oslam_internal.h"
+#include "oslam_window.h"
 #include "oslam_world.h"
 
 int oslam_world_surface_params_default(oslam_world_surface_params *p)
@@ -23,17 +24,6 @@ int oslam_world_surface_check_params(const oslam_world_surface_params *sp, oslam
     if (out->min_weight < 1 || out->min_weight > 65535) return fail(OSLAM_E_INVALID, "min_weight must lie in 1..65535");
     if (out->anchor_set && !oslamk_shift_ok(out->anchor)) return fail(OSLAM_E_INVALID, "an anchor is at most 2^20 voxels");
     return OSLAM_OK;
-}
-
-/* the aligned bricks that the window's box overlaps: the first key and the number of keys per axis */
-static void window_bricks(const oslam_volume *vol, int kb0[3], int nb[3])
-{
-    const int n[3] = {(int)vol->p.nx, (int)vol->p.ny, (int)vol->p.nz};
-    int a;
-    for (a = 0; a < 3; a++) {
-        kb0[a] = vol->off[a] >> 3;                                  /* arithmetic: floor for a negative offset */
-        nb[a] = ((vol->off[a] + n[a] - 1) >> 3) - kb0[a] + 1;
-    }
 }
 
 int oslam_world_map_open(oslam_world *w, oslam_volume *vol, const oslam_world_surface_params *p, int plane, void *stream,
@@ -57,19 +47,16 @@ int oslam_world_map_open(oslam_world *w, oslam_volume *vol, const oslam_world_su
     for (a = 0; a < 3; a++) {
         m.anchor[a] = p->anchor_set ? p->anchor[a] : vol ? vol->off[a] : 0;
         o->anchor[a] = m.anchor[a];
-        m.origin[a] = origin0[a];
-        if (m.anchor[a] != 0) {                                     /* oslam_volume_shift's origin of an offset */
-            const float step = (float)m.anchor[a] * voxel;
-            m.origin[a] = origin0[a] + step;
-        }
     }
+    oslam_window_origin(origin0, voxel, m.anchor, m.origin);        /* oslam_volume_shift's origin of an offset */
     m.voxel = voxel;
     m.inv_voxel = 1.0f / voxel;
     /* the table: the store's keys and the window's, both ascending, united; a store brick's slot is its rank among the
      * store's, a window-only brick's follows them */
     ns = oslam_world_brick_count(w);
     if (vol) {
-        window_bricks(vol, kb0, nb);
+        const unsigned sides[3] = {vol->p.nx, vol->p.ny, vol->p.nz};
+        oslam_window_bricks(sides, vol->off, kb0, nb);
         nw = (size_t)nb[0] * (size_t)nb[1] * (size_t)nb[2];
     }
     o->window_bricks = (uint32_t)nw;
