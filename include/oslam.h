@@ -1797,6 +1797,86 @@ int oslam_world_mesh(oslam_world *w, oslam_volume *vol, const oslam_world_surfac
                      int32_t *key_out, size_t v_cap, uint32_t *tri_out, size_t t_cap, size_t *nv_out, size_t *nt_out,
                      oslam_world_mesh_result *res);
 
+/* ---- the whole map ray-cast back into a view: voxel store plus window seen from a pose, marched on the device through
+ * the sparse 8 x 8 x 8 bricks of oslam_world_surface with no dense box anywhere.  The result is a genuine oslam_view, so
+ * whatever takes a ray-cast view of the window (oslam_view_egomotion, oslam_track, oslam_verify, oslam_arbitrate,
+ * oslam_view_to_cloud) can look at what the store keeps, without shifting the window back.  The restatement in numpy is
+ * tests/world_raycast_ref.py; device and restatement agree byte for byte.
+ *
+ * The rule is oslam_volume_raycast's, float sequence and grouping unchanged, with four substitutions.
+ * Map and frame.  G(g), the anchor A, O = origin(A) and r = g - A are oslam_world_surface's, word for word: inside the
+ *   window's box G is the window's word, elsewhere the store's or 0; a store entry inside the window's box is ignored; with
+ *   vol == NULL the map is the store alone.  The default anchor is the window's offset, or 0 without a volume; the
+ *   caller may set it, |A_a| <= 2^20.  origin becomes O, voxel and inv_voxel = 1.0f / voxel are the store's, mu is
+ *   params.mu, or the volume's when that is 0.  The trilinear read is oslam_world_surface's: c_a = (P_a - O_a) *
+ *   inv_voxel - 0.5f, b = floorf(c), the range test "finite and |b_a| < 2^22", the eight corners G at A + b + (0|1), each
+ *   needing w > 0.
+ * Box.  The dense rule takes its interval from the volume's box; here it comes from a box B = [box_lo, box_hi) in global
+ *   voxels: by default the bounding box of the map's bricks, 8 * (the least brick coordinate) to 8 * (the greatest + 1)
+ *   per axis, the bricks the window's box overlaps included; otherwise the caller's (box_set != 0).  With r_lo = box_lo_a
+ *   - A_a and r_hi = box_hi_a - A_a: lo = O_a + (float)(r_lo + 1) * voxel and hi = O_a + (float)(r_hi - 1) * voxel, each
+ *   one convert, one multiply and one add, not fused.  The slab test, tn, tf, t_k = tn + (float)k * step and step = 0.5f *
+ *   mu are unchanged.  A box is needed although the map has none: the samples hang on tn, so two calls see the same
+ *   samples only under the same box.
+ * Sample.  The word is G at A_a + floorf((P_a - O_a) * inv_voxel) per axis, under the range test "finite and below 2^22
+ *   in size", made in float before the conversion; it is 0 (w = 0) otherwise.  Samples are not confined to B.
+ * Step bound.  The march runs while t_k <= tf and k < 65536.  A call with (double)(z_max - z_min) / (double)step >= 65535
+ *   is refused with OSLAM_E_LIMIT, so the bound never ends a ray.
+ * The crossing, t*, the six-read gradient, the normal into the camera frame and its facing test are unchanged, and so are
+ *   the view's records: the z image, the 32-byte map records x y z 1 | nx ny nz 0, max_jump from cam.  The view is the
+ *   caller's (oslam_view_destroy), on the volume's device or on params.dev.
+ * Three pins.  (a) Dense.  Take a dense oslam_volume with the same voxel, created origin and mu, at offset A = box_lo with
+ *   sides box_hi - box_lo, holding G over B, and let the map have no seen voxel outside B: oslam_volume_raycast gives the
+ *   same z image and maps byte for byte, and the same hits and normals.  (b) Window alone.  With an empty store, the
+ *   default anchor and B the window's box the call equals oslam_volume_raycast(vol, ...) byte for byte.  (c) Walk.  Fuse
+ *   frames, ray-cast the volume, shift it away through a store with no integration in between: this call with anchor =
+ *   the old offset and B = the old window's box gives the bytes the volume gave.
+ * Refused before any device call, with nothing written, OSLAM_E_INVALID: NULL w, T_vol_cam, cam or view_out; a pose that
+ *   is not rigid; a camera oslam_view_create would refuse; a size outside 1..16384; an anchor beyond 2^20; a box with
+ *   hi_a - lo_a < 2 or a corner beyond 2^20 + 520 in size; a mu that is not finite, is negative or, when set, lies below 2
+ *   voxels; mu == 0 without a volume; a volume whose voxel or created-origin bits are not the store's.  OSLAM_E_LIMIT: the
+ *   step bound above, and a map of more than 2^22 bricks.  An empty map (no store bricks, no volume) returns a view of
+ *   zeros with launches == 0.  The lock of the calls on volumes is taken, then the store's; neither changes; device memory
+ *   other than the view is freed on every path.
+ * Device side.  The map goes up as for oslam_world_surface.  k_brick_raycast runs one thread per pixel in k_tsdf_raycast's
+ *   32 x 8 tiles; every read goes through the table, and a lane keeps the brick of its last sample (key and slot, "absent"
+ *   included), which only memoises the search.  No LDS, no scratch, no float atomic; hits and normals are counted by
+ *   ballots; two calls give the same bytes.  One launch besides the map's (k_brick_window with a volume), one host wait.
+ * oslam_world_track is oslam_volume_track's glue with this ray cast at its head: the map is ray-cast at T_vol_cam_prev with
+ *   the frame's own camera and size, then oslam_view_egomotion and the product as there; launches + the ray cast's.  A map
+ *   without a volume goes to the view's device (rp->dev is not read).  Under pin (b) it equals oslam_volume_track bit for
+ *   bit.  It integrates nothing.
+ * Out of scope: a map kept on the device between calls (every call sends the store's bricks up again), skipping absent
+ *   bricks by jumping k, integration into bricks, several GPUs. */
+typedef struct oslam_world_raycast_params {
+    int anchor_set;            /* 0: the window's offset, or 0 without a volume */
+    int32_t anchor[3];
+    int box_set;               /* 0: the bounding box of the map's bricks */
+    int32_t box_lo[3], box_hi[3];   /* global voxels, hi exclusive */
+    float mu;                  /* 0 = the volume's; needed (> 0) without a volume */
+    int dev;                   /* read only when vol == NULL */
+    int reserved[6];
+} oslam_world_raycast_params;
+
+typedef struct oslam_world_raycast_result {
+    uint32_t hits;             /* pixels with a hit */
+    uint32_t normals;          /* pixels with a normal */
+    uint32_t bricks;           /* table entries: the store's bricks united with the window's */
+    uint32_t window_bricks;    /* aligned bricks the window's box overlaps */
+    uint32_t launches;
+    int32_t anchor[3], box_lo[3], box_hi[3];   /* in force */
+    float ms_total;            /* whole call, host clock */
+} oslam_world_raycast_result;
+
+int oslam_world_raycast_params_default(oslam_world_raycast_params *p);
+/* vol, rp (defaults) and res may be NULL */
+int oslam_world_raycast(oslam_world *w, oslam_volume *vol, const oslam_world_raycast_params *rp, const float T_vol_cam[16],
+                        const oslam_camera *cam, int width, int height, oslam_view **view_out, oslam_world_raycast_result *res);
+/* vol, rp, ep (defaults) and ego_res may be NULL */
+int oslam_world_track(oslam_world *w, oslam_volume *vol, const oslam_world_raycast_params *rp, oslam_view *v,
+                      const float T_vol_cam_prev[16], const oslam_egomotion_params *ep, float T_vol_cam_out[16],
+                      oslam_egomotion_result *ego_res);
+
 /* ---- normals for clouds and meshes that come without them.  Every entry into the recognition path takes points and
  * normals; the reference made them outside its program (matlab/compute_normals.m for meshes, PCL for scans).  Two entry
  * points, because the two kinds of input need different sign rules: a cloud seen from somewhere (oslam_cloud_normals, on
@@ -1987,6 +2067,15 @@ int oslam_ply_write_mesh_colour(const char *path, const float *xyz, const float 
                                 const uint32_t *tri, size_t nt, int binary);
 int oslam_world_colours(oslam_world *w, oslam_volume *vol, const oslam_world_surface_params *sp, const float *xyz, size_t n,
                         size_t stride_bytes, uint8_t *rgb_out, uint8_t *valid_out, size_t *n_valid_out);
+/* oslam_volume_paint_view against the whole map: the colour of oslam_world_colours at the volume-frame point of every
+ * pixel of v with z > 0, seen from T_vol_cam, into the view's colour image (the word 0 elsewhere); *painted_out = the
+ * pixels with a colour.  The vertex, its transform and the image word are oslam_volume_paint_view's, the read is
+ * oslam_world_colours' (k_brick_colour_view next to k_brick_colours, the same function for the colour at a point).  sp
+ * gives the anchor; a map without a volume goes to the view's device (sp->dev is not read).  Refusals are
+ * oslam_world_colours' together with oslam_volume_paint_view's (NULL w, T_vol_cam or v, a pose that is not rigid, volume
+ * and view on different devices), before any device call.  An empty map paints zeros without a launch */
+int oslam_world_paint_view(oslam_world *w, oslam_volume *vol, const oslam_world_surface_params *sp, const float T_vol_cam[16],
+                           oslam_view *v, uint32_t *painted_out);
 
 /* ---- parity taps (tests): values the reference materialises as arrays.
  * Scene::getHashKeys row r (scene.cu:49-54): keys_out[n] of reference point r,

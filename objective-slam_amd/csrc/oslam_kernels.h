@@ -804,6 +804,23 @@ int oslamk_brick_emit(const oslamk_brick_map *map, uint32_t min_weight, const ui
 /* out[t] = the image word of the colour at the volume-frame point xyz[t] (device [n][3], 0 < n < 2^31), 0 without a colour;
  * *count (zeroed by the caller) += points with a colour */
 int oslamk_brick_colours(const oslamk_brick_map *map, const float *xyz, uint32_t n, uint32_t *out, uint32_t *count, void *stream);
+/* oslamk_colour_view against the map: out [h][w] = the image word of the colour at every pixel of v with z > 0, seen from
+ * T12 = rows of T_vol_cam, 0 elsewhere; *count (zeroed by the caller) += pixels with a colour */
+int oslamk_brick_colour_view(const oslamk_brick_map *map, const oslamk_view *v, const float *T12, uint32_t *out, uint32_t *count,
+                             void *stream);
+
+/* ---- the whole map ray-cast back into a view (oslam_world_raycast.hip; semantics in include/oslam.h at
+ * oslam_world_raycast; host side: oslam_world_raycast.c).  The map is the surface's, TSDF words in the bricks ---- */
+#define OSLAMK_WRAY_MAX_STEPS 65536   /* samples of one ray at most; the host refuses a (z_max - z_min) / step that reaches it */
+/* the box of the slab test as voxel indices r = g - anchor (hi exclusive, hi - lo >= 2 per axis), and the truncation mu */
+typedef struct oslamk_wray {
+    int r_lo[3], r_hi[3];
+    float mu;
+} oslamk_wray;
+/* oslamk_tsdf_raycast against the map: z_out [w*h], maps [w*h][8]; count[0] += pixels with a hit, count[1] += pixels with
+ * a normal (zeroed by the caller) */
+int oslamk_brick_raycast(const oslamk_brick_map *map, const oslamk_wray *box, const oslamk_view *v, const float *T12, float *z_out,
+                         float *maps, uint32_t *count, void *stream);
 
 /* ---- the mesh of the whole map from the same bricks (oslam_world_mesh.hip; semantics in include/oslam.h at
  * oslam_world_mesh; host side: oslam_world_mesh.c).  The map is the surface's, window written in by oslamk_brick_window ---- */

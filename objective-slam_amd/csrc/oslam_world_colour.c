@@ -3,6 +3,8 @@
  * oslam_world_colours): the host side of k_brick_colours in oslam_world_colour.hip.  A call builds the map of
  * oslam_world_surface.c with colour words in its bricks (oslam_world_map_open, plane OSLAM_MAP_COLOUR), sends the points
  * up as oslam_volume_colours does, runs one kernel and unpacks the words, under the volume lock and the store's.
+ * oslam_world_paint_view builds the same map and runs k_brick_colour_view over a view's pixels, as
+ * oslam_volume_paint_view does with the volume alone.
  */
 #include "oslam_internal.h"
 #include "oslam_world.h"
@@ -77,5 +79,60 @@ done:
     if (opened) oslam_world_map_close(&wm);
     free(h_out);
     free(h_xyz);
+    return rc;
+}
+
+int oslam_world_paint_view(oslam_world *w, oslam_volume *vol, const oslam_world_surface_params *sp, const float T_vol_cam[16],
+                           oslam_view *v, uint32_t *painted_out)
+{
+    int rc, fresh = 0, launched = 0, opened = 0;
+    uint32_t *d_cnt = NULL, *d_img = NULL, painted = 0;
+    oslam_world_surface_params p;
+    oslam_world_map wm;
+    void *stream = oslam_stream();
+    if (!w || !T_vol_cam || !v) return fail(OSLAM_E_INVALID, "NULL argument");
+    rc = oslam_refine_check_rigid(T_vol_cam);
+    if (rc == OSLAM_OK) rc = oslam_world_surface_check_params(sp, &p);
+    if (rc != OSLAM_OK) return rc;
+    if (painted_out) *painted_out = 0;
+    if (vol && vol->dev != v->dev) return fail(OSLAM_E_INVALID, "volume and view live on different devices");
+    if (!oslam_world_coloured(w)) return fail(OSLAM_E_INVALID, "the voxel store keeps no colour");
+    p.dev = v->dev;                                                 /* a map without a volume goes where the view is */
+    memset(&wm, 0, sizeof wm);
+    oslam_volume_lock();
+    oslam_world_lock(w);
+    if (vol && !vol->colour.words) { rc = fail(OSLAM_E_INVALID, "the volume has no colour"); goto done; }
+    rc = oslam_world_map_open(w, vol, &p, OSLAM_MAP_COLOUR, stream, &wm);
+    if (rc != OSLAM_OK) goto done;
+    if (wm.bricks == 0) {                                           /* an empty map: no colour anywhere, no launch */
+        rc = oslam_pick_device(v->dev, &wm.dev);
+        if (rc != OSLAM_OK) goto done;
+    } else
+        opened = launched = 1;
+    d_img = v->d_colour;
+    if (!d_img) {
+        HIPCHK(hipMalloc((void **)&d_img, sizeof(uint32_t) * (size_t)v->k.w * (size_t)v->k.h));
+        fresh = 1;
+    }
+    launched = 1;
+    if (wm.bricks == 0)
+        HIPCHK(hipMemsetAsync(d_img, 0, sizeof(uint32_t) * (size_t)v->k.w * (size_t)v->k.h, (hipStream_t)stream));
+    else {
+        KCHK(oslam_counters_open(&d_cnt, 0, stream));
+        KCHK(oslamk_brick_colour_view(&wm.m, &v->k, T_vol_cam, d_img, d_cnt, stream));
+        HIPCHK(hipMemcpyAsync(&painted, d_cnt, sizeof painted, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    }
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    launched = 0;
+    v->d_colour = d_img;
+    fresh = 0;
+    if (painted_out) *painted_out = painted;
+done:
+    if (launched) (void)hipStreamSynchronize((hipStream_t)stream);
+    if (fresh && d_img) (void)hipFree(d_img);
+    oslam_world_unlock(w);
+    oslam_volume_unlock();
+    if (d_cnt) oslam_dev_free(d_cnt);
+    if (opened) oslam_world_map_close(&wm);
     return rc;
 }

@@ -11,7 +11,10 @@
  *                     blended (oslam_colour_lerp.h); otherwise the voxel that holds the point, A + floorf(u), is looked up
  *                     on its own: in float arithmetic it is not shown to be one of the eight corners.  Points with a
  *                     colour are counted by a ballot and one integer atomic per wave.  No LDS, no scratch, no float atomic.
- * Bounds.  A thread's index is checked against n before anything.  b and floorf(u) are range-checked in float (finite and
+ *   k_brick_colour_view   one thread per pixel in 32 x 8 tiles (k_colour_view's tiling and arithmetic): the pixel's vertex
+ *                     from its z, into the volume frame, the same read, the word into the view's colour image
+ *                     (oslam_world_paint_view).
+ * Bounds.  A thread's index is checked against n before anything, a pixel against (w, h).  b and floorf(u) are range-checked in float (finite and
  * below 2^22 in size) before they become ints, so with |A_a| <= 2^20 every global coordinate read is below 2^23 in size and
  * its brick coordinate fits the key's 21 bits.  brick_find gives a slot below m.n or none, so every load from the brick
  * array lies inside its n * 512 words; a local index is below 512 by construction, and the in-brick stencil adds at most
@@ -81,6 +84,39 @@ __global__ __launch_bounds__(256) void k_brick_colours(const oslamk_brick_map m,
     }
     const uint32_t n_has = (uint32_t)__popcll(__ballot(word != 0u));
     if ((threadIdx.x & 63) == 0 && n_has) atomicAdd(count, n_has);
+}
+
+/* k_colour_view against the map: the pixel's vertex from its z, into the volume frame, wcol_at there */
+__global__ __launch_bounds__(256) void k_brick_colour_view(const oslamk_brick_map m, const oslamk_view v, const oslamk_pose P,
+                                                           uint32_t *__restrict__ out, uint32_t *count)
+{
+    const int u = blockIdx.x * 32 + (threadIdx.x & 31), vv = blockIdx.y * 8 + (threadIdx.x >> 5);
+    uint32_t word = 0u;
+    if (u < v.w && vv < v.h) {
+        const size_t i = (size_t)vv * v.w + u;
+        const float z = v.z[i];
+        if (z > 0.0f) {
+            const float *M = P.T;
+            const float dx = ((float)u - v.cx) / v.fx, dy = ((float)vv - v.cy) / v.fy;
+            const float vx = dx * z, vy = dy * z;
+            word = wcol_at(m, ((M[0] * vx + M[1] * vy) + M[2] * z) + M[3], ((M[4] * vx + M[5] * vy) + M[6] * z) + M[7],
+                           ((M[8] * vx + M[9] * vy) + M[10] * z) + M[11]);
+        }
+        out[i] = word;
+    }
+    const uint32_t n_has = (uint32_t)__popcll(__ballot(word != 0u));
+    if ((threadIdx.x & 63) == 0 && n_has) atomicAdd(count, n_has);
+}
+
+extern "C" int oslamk_brick_colour_view(const oslamk_brick_map *map, const oslamk_view *v, const float *T12, uint32_t *out,
+                                        uint32_t *count, void *stream)
+{
+    oslamk_pose P;
+    if (!brick_map_ok(map) || !v || !v->z || v->w <= 0 || v->h <= 0 || !T12 || !out || !count) return (int)hipErrorInvalidValue;
+    for (int k = 0; k < 12; k++) P.T[k] = T12[k];
+    hipLaunchKernelGGL(k_brick_colour_view, dim3((v->w + 31) / 32, (v->h + 7) / 8), dim3(256), 0, (hipStream_t)stream, *map, *v, P,
+                       out, count);
+    return (int)hipGetLastError();
 }
 
 extern "C" int oslamk_brick_colours(const oslamk_brick_map *map, const float *xyz, uint32_t n, uint32_t *out, uint32_t *count,

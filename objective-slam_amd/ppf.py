@@ -355,6 +355,23 @@ class WorldMeshResult(C.Structure):
                 "anchor": tuple(int(x) for x in self.anchor), "ms_total": float(self.ms_total)}
 
 
+class WorldRaycastParams(C.Structure):
+    _fields_ = [("anchor_set", C.c_int), ("anchor", C.c_int32 * 3), ("box_set", C.c_int), ("box_lo", C.c_int32 * 3),
+                ("box_hi", C.c_int32 * 3), ("mu", C.c_float), ("dev", C.c_int), ("reserved", C.c_int * 6)]
+
+
+class WorldRaycastResult(C.Structure):
+    _fields_ = [("hits", C.c_uint32), ("normals", C.c_uint32), ("bricks", C.c_uint32), ("window_bricks", C.c_uint32),
+                ("launches", C.c_uint32), ("anchor", C.c_int32 * 3), ("box_lo", C.c_int32 * 3), ("box_hi", C.c_int32 * 3),
+                ("ms_total", C.c_float)]
+
+    def asdict(self):
+        return {"hits": int(self.hits), "normals": int(self.normals), "bricks": int(self.bricks),
+                "window_bricks": int(self.window_bricks), "launches": int(self.launches),
+                "anchor": tuple(int(x) for x in self.anchor), "box_lo": tuple(int(x) for x in self.box_lo),
+                "box_hi": tuple(int(x) for x in self.box_hi), "ms_total": float(self.ms_total)}
+
+
 class NormalsParams(C.Structure):
     _fields_ = [("radius", C.c_float), ("min_neighbours", C.c_uint), ("viewpoint", C.c_float * 3), ("orient", C.c_int),
                 ("line_ratio", C.c_float), ("reserved", C.c_int * 4)]
@@ -526,6 +543,12 @@ _SIGNATURES = {
     "oslam_world_mesh": (_i, [_vp, _vp, C.POINTER(WorldSurfaceParams), _vp, _vp, _vp, _sz, _vp, _sz, C.POINTER(_sz),
                               C.POINTER(_sz), C.POINTER(WorldMeshResult)]),
     "oslam_world_bricks": (_i, [_vp, _vp, _sz, C.POINTER(_sz)]),
+    "oslam_world_raycast_params_default": (_i, [C.POINTER(WorldRaycastParams)]),
+    "oslam_world_raycast": (_i, [_vp, _vp, C.POINTER(WorldRaycastParams), _vp, _vp, _i, _i, C.POINTER(_vp),
+                                 C.POINTER(WorldRaycastResult)]),
+    "oslam_world_track": (_i, [_vp, _vp, C.POINTER(WorldRaycastParams), _vp, _vp, C.POINTER(EgomotionParams), _vp,
+                               C.POINTER(EgomotionResult)]),
+    "oslam_world_paint_view": (_i, [_vp, _vp, C.POINTER(WorldSurfaceParams), _vp, _vp, C.POINTER(C.c_uint32)]),
     "oslam_scene_from_world": (_i, [_vp, _vp, C.POINTER(WorldSurfaceParams), _f, _f, _u, C.POINTER(Params), C.POINTER(_vp),
                                     C.POINTER(_sz)]),
     "oslam_volume_shift_world": (_i, [_vp, _vp, _vp, C.POINTER(ReloadResult)]),
@@ -2281,6 +2304,55 @@ class World:
         takes them.  (A method of its own: mesh()'s parameter list is pinned by tests/test_world_mesh_host.py.)"""
         out = self.mesh(vol, min_weight, normals, anchor, keys, dev)
         return out + self.colours(out[0], vol, anchor, dev)
+
+    @staticmethod
+    def _raycast_params(anchor, box, mu, dev):
+        p = WorldRaycastParams()
+        _check(lib().oslam_world_raycast_params_default(C.byref(p)))
+        if anchor is not None:
+            p.anchor_set, p.anchor[:] = 1, [int(x) for x in _shift3(anchor)]
+        if box is not None:
+            p.box_set = 1
+            p.box_lo[:], p.box_hi[:] = [int(x) for x in _shift3(box[0])], [int(x) for x in _shift3(box[1])]
+        p.mu, p.dev = float(mu), int(dev)
+        return p
+
+    def raycast(self, T_vol_cam, fx, fy, cx, cy, width, height, vol=None, anchor=None, box=None, mu=0.0, z_min=0.1, z_max=10.0,
+                max_jump=0.05, dev=0):
+        """The whole map, this store plus the window of the Volume vol (None: the store alone, on device dev), seen from
+        T_vol_cam (oslam_world_raycast): -> (View, result dict), as Volume.raycast.  Volume.raycast's rule against the
+        map.  anchor (three ints, default the window's offset, or 0) picks the frame the floats are formed in; box =
+        (lo, hi) in global voxels, hi exclusive, bounds the march (default: the bounding box of the map's bricks, which
+        the result names as box_lo and box_hi); mu 0.0 = the volume's, and is needed without one."""
+        cam = Camera(fx, fy, cx, cy, 1.0, z_min, z_max, max_jump)
+        rp, res = self._raycast_params(anchor, box, mu, dev), WorldRaycastResult()
+        v = View.__new__(View)
+        v._h = C.c_void_p(0)
+        v.width, v.height = int(width), int(height)
+        _check(lib().oslam_world_raycast(self._h, vol._h if vol is not None else None, C.byref(rp), _p(_pose16(T_vol_cam)),
+                                         C.byref(cam), int(width), int(height), C.byref(v._h), C.byref(res)))
+        return v, res.asdict()
+
+    def track(self, view, T_prev, vol=None, params=None, anchor=None, box=None, mu=0.0):
+        """Frame-to-model camera tracking against the whole map (oslam_world_track): Volume.track with raycast() at its
+        head, on the view's device.  -> (T_vol_cam float32 4x4, egomotion result dict).  It integrates nothing."""
+        p = params if params is not None else default_egomotion_params()
+        rp = self._raycast_params(anchor, box, mu, 0)
+        To = np.zeros(16, np.float32)
+        res = EgomotionResult()
+        _check(lib().oslam_world_track(self._h, vol._h if vol is not None else None, C.byref(rp), view._h, _p(_pose16(T_prev)),
+                                       C.byref(p), _p(To), C.byref(res)))
+        return To.reshape(4, 4), res.asdict()
+
+    def paint(self, view, T_vol_cam, vol=None, anchor=None):
+        """The colour of the whole map, this colour store plus the window of the coloured Volume vol, at every pixel of
+        view seen from T_vol_cam, into the view's colour image (oslam_world_paint_view; View.colour() reads it): -> the
+        number of pixels painted.  Volume.paint with colours()' read; anchor as in raycast()."""
+        sp = _world_surface_params(1, anchor, 0)
+        n = C.c_uint32(0)
+        _check(lib().oslam_world_paint_view(self._h, vol._h if vol is not None else None, C.byref(sp), _p(_pose16(T_vol_cam)),
+                                            view._h, C.byref(n)))
+        return int(n.value)
 
     def stats(self):
         s = WorldStats()

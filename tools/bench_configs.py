@@ -1174,6 +1174,62 @@ def worldsurface(calls=20):
     return out
 
 
+def worldraycast(calls=20):
+    """The ray cast of the whole map (oslam_world_raycast) on worldsurface's map: the reload configuration's 256^3 volume
+    after its out-and-back stream, shifted through a store by (64, 0, 0).  In one run and alternately, so that drift hits
+    both alike: the median of `calls` calls of World.raycast(vol) at 640 x 480 from the current camera pose and of
+    Volume.raycast of the same window from the same pose (the yardstick: code this configuration's subject does not
+    touch).  The same pair once from the stream's first pose, where the window alone sees little.  The map's share of a
+    call is the median of the same call with an image of one pixel: the table, the bricks over the host link and
+    k_brick_window are all there, the march is not.  Kernel times proper come from a kernel trace of this configuration in
+    a run of its own."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import camera_ref as E
+    world = E.make_world(synth, 0)
+    sweep = E.trajectory(synth, 0, frames=10)
+    cam = E.CAM
+    rendered = [ppf.View(E.render(synth, world, T), cam["fx"], cam["fy"], cam["cx"], cam["cy"], z_min=cam["z_min"],
+                         z_max=cam["z_max"], max_jump=E.MAX_JUMP) for T in sweep]
+    spec = dict(nx=256, ny=256, nz=256, voxel=0.036, origin=[-2.9, -4.3, 0.3], mu=0.288)
+    vol = ppf.Volume(**spec)
+    steps = [vol.step(rendered[k]) for k in list(range(10)) + list(range(8, -1, -1))]
+    store = ppf.World(vol)
+    moved = vol.shift((64, 0, 0), store)
+    kw = dict(z_min=cam["z_min"], z_max=cam["z_max"], max_jump=E.MAX_JUMP)
+    size = (cam["fx"], cam["fy"], cam["cx"], cam["cy"], 640, 480)
+
+    def both(T, n):
+        ms_w, ms_v, lib_w, lib_v, ms_1 = [], [], [], [], []
+        for _ in range(n):
+            t = time.perf_counter(); v, wres = store.raycast(T, *size, vol=vol, **kw); ms_w.append(1e3 * (time.perf_counter() - t))
+            v.close(); lib_w.append(wres["ms_total"])
+            t = time.perf_counter(); v, vres = vol.raycast(T, *size, **kw); ms_v.append(1e3 * (time.perf_counter() - t))
+            v.close(); lib_v.append(vres["ms_total"])
+            t = time.perf_counter(); v, _ = store.raycast(T, cam["fx"], cam["fy"], 0.0, 0.0, 1, 1, vol=vol, **kw)
+            ms_1.append(1e3 * (time.perf_counter() - t)); v.close()
+        return {"world_raycast_ms_median": float(np.median(ms_w)), "world_raycast_ms_library_median": float(np.median(lib_w)),
+                "volume_raycast_ms_median": float(np.median(ms_v)), "volume_raycast_ms_library_median": float(np.median(lib_v)),
+                "world_over_volume": float(np.median(ms_w) / np.median(ms_v)),
+                "world_raycast_one_pixel_ms_median": float(np.median(ms_1)),
+                "world_raycast_minus_one_pixel_ms": float(np.median(ms_w) - np.median(ms_1)),
+                "world_hits": wres["hits"], "world_normals": wres["normals"], "window_hits": vres["hits"], "window_normals": vres["normals"],
+                "launches": wres["launches"], "box_lo": wres["box_lo"], "box_hi": wres["box_hi"]}
+
+    both(vol.T, 3)                                                  # the staging buffer, the kept device blocks, the code objects
+    now = both(vol.T, calls)
+    first = both(np.eye(4, dtype=np.float32), 3)
+    st = store.stats()
+    out = {"config": "worldraycast (oslam_world_raycast): the reload configuration's 256^3 map after its 19-frame stream, shifted by (64, 0, 0) through the store",
+           "volume": spec, "calls": calls, "step_ok": [None if r is None else r["ok"] for _, r in steps], "image": [640, 480],
+           "stored_by_the_shift": moved["stored"], "store": st, "store_bricks": st["bricks"],
+           "store_bytes_over_the_link": 2048 * st["bricks"], "current_pose": now, "first_pose_3_calls": first}
+    for v in rendered:
+        v.close()
+    store.close()
+    vol.close()
+    return out
+
+
 def worldmesh(calls=20):
     """The mesh of the whole map (oslam_world_mesh) on worldsurface's map: the reload configuration's 256^3 volume after
     its out-and-back stream, shifted through a store by (64, 0, 0).  In one run and alternately, so that drift hits
@@ -1480,4 +1536,4 @@ if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "cfg3"
     print(json.dumps({"cfg2": cfg2, "cfg3": cfg3, "cfg3db": cfg3db, "cfg4": cfg4, "cfg5": cfg5, "planes": planes, "db50": db50,
                       "refine": refine, "verify": verify, "instances": instances, "arbitrate": arbitrate, "explain": explain, "track": track, "camera": camera,
-                      "fusion": fusion, "colour": colour, "surface": surface, "mesh": mesh, "shift": shift, "reload": reload, "worldsurface": worldsurface, "worldmesh": worldmesh, "worldcolour": worldcolour, "pyramid": pyramid, "bilateral": bilateral, "normals": normals}[which]()), flush=True)
+                      "fusion": fusion, "colour": colour, "surface": surface, "mesh": mesh, "shift": shift, "reload": reload, "worldsurface": worldsurface, "worldraycast": worldraycast, "worldmesh": worldmesh, "worldcolour": worldcolour, "pyramid": pyramid, "bilateral": bilateral, "normals": normals}[which]()), flush=True)
