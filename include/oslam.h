@@ -2102,13 +2102,26 @@ int oslam_model_key_numbers(oslam_model *m, uint32_t *keys_out, uint32_t *number
 int oslam_vote_ref_order(const uint32_t *keep, size_t n, uint32_t *order_out);
 /* Dense accumulator acc[M][32] of scene reference point ref_index after voting. */
 int oslam_vote_accumulator(oslam_model *m, oslam_scene *s, size_t ref_index, uint32_t *acc_out);
-/* The hit list of scene reference point ref_index as the votes read it, sorted by key number: per hit the number of
+/* The hit list of scene reference point ref_index as the votes read it, sorted by key number (a list above one segment
+ * of the sort -- 16384 hits, 8192 from 2^18 key numbers on -- segment by segment): per hit the number of
  * its key (oslam_model_key_numbers), theta_v in units of 2^-22 turn (0xffffffff: always re-evaluated) and the scene
  * index of the pair's second point; at most cap of each are copied (any may be NULL), *n_out = the number of hits.
  * *keep_out (may be NULL) = the pairs of the reference point whose distance bin can reach a model key: the places
  * its list was given. */
 int oslam_vote_hits(oslam_model *m, oslam_scene *s, size_t ref_index, uint32_t *numbers_out, uint32_t *theta_out,
                     uint32_t *idx_out, size_t cap, size_t *n_out, uint32_t *keep_out);
+/* The hit sort alone (k_sort_hits), on n_lists hit lists the caller supplies, in one launch.  List l owns the slots
+ * offsets[l] .. offsets[l + 1] of every per-hit array and holds min(counts[l], its slots) hits in arrival order: the
+ * number of the hit's key (below 2^id_bits), theta_v and the scene index.  Every array comes back whole: numbers_out =
+ * the key numbers in sorted order | (the hit's run holds a marker) << 31, and the input past the hits; theta_out /
+ * idx_out = the payloads in sorted order; runs_out[r] = {number | (hits - 1) << 26, first hit | marker << 31} for the
+ * run_counts_out[l] runs of list l, from its first slot on.  theta_out, idx_out, runs_out and run_counts_out are filled
+ * with 0xA5 bytes before the launch: the words the kernel does not own keep them.  The contract is DESIGN.md's at the
+ * hit sort; tests/sort_ref.py restates it.  OSLAM_E_INVALID before any device call: a NULL array, offsets that
+ * descend, id_bits outside 1 .. 26, a number at or above 2^id_bits. */
+int oslam_sort_hits_tap(const uint32_t *numbers, const uint32_t *theta, const uint32_t *idx, const uint32_t *offsets,
+                        const uint32_t *counts, size_t n_lists, uint32_t id_bits, int dev, uint32_t *numbers_out,
+                        uint32_t *theta_out, uint32_t *idx_out, uint32_t *runs_out, uint32_t *run_counts_out);
 /* Cells kept by the last oslam_align / oslam_align_finish on this model, in
  * the order (count desc, code asc); poses_out (may be NULL) gets 16 floats per cell. */
 int oslam_last_cells(oslam_model *m, oslam_cell *cells_out, float *poses_out, size_t cap,

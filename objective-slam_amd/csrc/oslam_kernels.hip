@@ -103,6 +103,11 @@ __global__ void k_model_count(oslamk_cloud c, float d_dist, float inv_d_dist, os
             return;
         }
         slot = (slot + 1) & mask;
+        /* a table that gets more than half full is thrown away and counted again at twice the size
+         * (oslam_model_create): its pairs need not be counted, and must not walk a full table slot by slot (a model
+         * of 4.6e5 keys spent seconds in the three passes that fill 2^16 .. 2^18 slots).  Looked at on long walks only;
+         * the pass that is kept never gets there */
+        if ((probe & 31u) == 31u && __hip_atomic_load(&n_unique[slice], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > t.cap / 2u) return;
     }
     atomicExch(overflow, 1u);
 }

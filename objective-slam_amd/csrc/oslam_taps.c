@@ -236,6 +236,90 @@ int oslam_vote_hits(oslam_model *m, oslam_scene *s, size_t ref_index, uint32_t *
     return tap_one_ref(m, s, ref_index, NULL, numbers_out, theta_out, idx_out, cap, n_out, keep_out);
 }
 
+/* k_sort_hits alone, on lists the caller supplies: one launch over n_lists lists, every array copied back whole.  What
+ * the kernel does not own (hit_sorted, runs and run_count past a list's hits) is filled with 0xA5 bytes before the launch */
+int oslam_sort_hits_tap(const uint32_t *numbers, const uint32_t *theta, const uint32_t *idx, const uint32_t *offsets,
+                        const uint32_t *counts, size_t n_lists, uint32_t id_bits, int dev, uint32_t *numbers_out,
+                        uint32_t *theta_out, uint32_t *idx_out, uint32_t *runs_out, uint32_t *run_counts_out)
+{
+    int rc = OSLAM_OK, devsel;
+    size_t total, i, slots;
+    oslamk_pay *h_pay = NULL;
+    uint32_t *d_off = NULL, *d_cnt = NULL, *d_key = NULL, *d_rc = NULL;
+    oslamk_pay *d_pay = NULL, *d_sorted = NULL;
+    oslamk_run *d_runs = NULL;
+    oslamk_vote_args a;
+    hipStream_t st;
+    if (!numbers || !theta || !idx || !offsets || !counts || !numbers_out || !theta_out || !idx_out || !runs_out || !run_counts_out)
+        return fail(OSLAM_E_INVALID, "NULL argument");
+    if (id_bits < 1u || id_bits > OSLAMK_RUN_SHIFT) return fail(OSLAM_E_INVALID, "id_bits outside 1 .. 26");
+    if (n_lists > 0x7fffffffu) return fail(OSLAM_E_INVALID, "too many lists");
+    for (i = 0; i < n_lists; i++)
+        if (offsets[i + 1] < offsets[i]) return fail(OSLAM_E_INVALID, "the offsets descend");
+    total = offsets[n_lists];
+    for (i = 0; i < total; i++)
+        if (numbers[i] >> id_bits) return fail(OSLAM_E_INVALID, "a key number does not fit id_bits");
+    if (n_lists == 0) return OSLAM_OK;
+    rc = oslam_pick_device(dev, &devsel);
+    if (rc != OSLAM_OK) return rc;
+    st = (hipStream_t)oslam_stream();
+    slots = total ? total : 1;
+    h_pay = (oslamk_pay *)malloc(sizeof *h_pay * slots);
+    if (!h_pay) return fail(OSLAM_E_NOMEM, "host allocation failed");
+    for (i = 0; i < total; i++) {
+        h_pay[i].theta_t22 = theta[i];
+        h_pay[i].idx = idx[i];
+    }
+    HIPCHK(hipMalloc((void **)&d_off, sizeof(uint32_t) * (n_lists + 1)));
+    HIPCHK(hipMalloc((void **)&d_cnt, sizeof(uint32_t) * n_lists));
+    HIPCHK(hipMalloc((void **)&d_rc, sizeof(uint32_t) * n_lists));
+    HIPCHK(hipMalloc((void **)&d_key, sizeof(uint32_t) * slots));
+    HIPCHK(hipMalloc((void **)&d_pay, sizeof(oslamk_pay) * slots));
+    HIPCHK(hipMalloc((void **)&d_sorted, sizeof(oslamk_pay) * slots));
+    HIPCHK(hipMalloc((void **)&d_runs, sizeof(oslamk_run) * slots));
+    HIPCHK(hipMemcpy(d_off, offsets, sizeof(uint32_t) * (n_lists + 1), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_cnt, counts, sizeof(uint32_t) * n_lists, hipMemcpyHostToDevice));
+    if (total) {
+        HIPCHK(hipMemcpy(d_key, numbers, sizeof(uint32_t) * total, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_pay, h_pay, sizeof(oslamk_pay) * total, hipMemcpyHostToDevice));
+    }
+    HIPCHK(hipMemsetAsync(d_sorted, 0xA5, sizeof(oslamk_pay) * slots, st));
+    HIPCHK(hipMemsetAsync(d_runs, 0xA5, sizeof(oslamk_run) * slots, st));
+    HIPCHK(hipMemsetAsync(d_rc, 0xA5, sizeof(uint32_t) * n_lists, st));
+    memset(&a, 0, sizeof a);                   /* only what k_sort_hits reads */
+    a.hit_off = d_off;
+    a.hit_count = d_cnt;
+    a.hit_key = d_key;
+    a.hit_pay = d_pay;
+    a.hit_sorted = d_sorted;
+    a.runs = d_runs;
+    a.run_count = d_rc;
+    a.table.id_bits = id_bits;
+    a.n_launch = (int)n_lists;
+    KCHK(oslamk_sort_hits(&a, st));
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipMemcpy(run_counts_out, d_rc, sizeof(uint32_t) * n_lists, hipMemcpyDeviceToHost));
+    if (total) {
+        HIPCHK(hipMemcpy(numbers_out, d_key, sizeof(uint32_t) * total, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(runs_out, d_runs, sizeof(oslamk_run) * total, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(h_pay, d_sorted, sizeof(oslamk_pay) * total, hipMemcpyDeviceToHost));
+        for (i = 0; i < total; i++) {
+            theta_out[i] = h_pay[i].theta_t22;
+            idx_out[i] = h_pay[i].idx;
+        }
+    }
+done:
+    free(h_pay);
+    if (d_off) (void)hipFree(d_off);
+    if (d_cnt) (void)hipFree(d_cnt);
+    if (d_rc) (void)hipFree(d_rc);
+    if (d_key) (void)hipFree(d_key);
+    if (d_pay) (void)hipFree(d_pay);
+    if (d_sorted) (void)hipFree(d_sorted);
+    if (d_runs) (void)hipFree(d_runs);
+    return rc;
+}
+
 /* the taps read the last result from the host: fetch it if it is still on the device */
 static int materialise_last(oslam_model *m)
 {

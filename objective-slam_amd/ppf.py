@@ -582,6 +582,7 @@ _SIGNATURES = {
     "oslam_model_bucket_words": (_i, [_vp, C.c_uint32, _i, _vp, _sz, C.POINTER(_sz)]),
     "oslam_vote_accumulator": (_i, [_vp, _vp, _sz, _vp]),
     "oslam_vote_hits": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _sz, C.POINTER(_sz), C.POINTER(C.c_uint32)]),
+    "oslam_sort_hits_tap": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, C.c_uint32, _i, _vp, _vp, _vp, _vp, _vp]),
     "oslam_model_key_numbers": (_i, [_vp, _vp, _vp, _vp, _sz, C.POINTER(_sz)]),
     "oslam_vote_ref_order": (_i, [_vp, _sz, _vp]),
     "oslam_last_cells": (_i, [_vp, _vp, _vp, _sz, C.POINTER(_sz)]),
@@ -640,6 +641,23 @@ def vote_ref_order(keep):
     out = np.zeros(len(keep), np.uint32)
     _check(lib().oslam_vote_ref_order(_p(keep), len(keep), _p(out)))
     return out
+
+
+def sort_hits(numbers, theta, idx, offsets, counts, id_bits, dev=0):
+    """k_sort_hits alone on the lists given (oslam_sort_hits_tap): list l owns the slots offsets[l] .. offsets[l + 1] and
+    holds min(counts[l], its slots) hits.  -> (numbers, theta, idx, runs [slots, 2], run_counts), every array whole."""
+    numbers, theta, idx, offsets, counts = (np.ascontiguousarray(a, np.uint32) for a in (numbers, theta, idx, offsets, counts))
+    n_lists = len(counts)
+    if len(offsets) != n_lists + 1:
+        raise ValueError("offsets holds one word more than counts")
+    total = int(offsets[-1])
+    if not (len(numbers) == len(theta) == len(idx) == total):
+        raise ValueError("numbers, theta and idx hold offsets[-1] words each")
+    num_o, th_o, idx_o = (np.zeros(max(total, 1), np.uint32) for _ in range(3))
+    runs, rc = np.zeros((max(total, 1), 2), np.uint32), np.zeros(max(n_lists, 1), np.uint32)
+    _check(lib().oslam_sort_hits_tap(_p(numbers), _p(theta), _p(idx), _p(offsets), _p(counts), n_lists, int(id_bits), int(dev),
+                                     _p(num_o), _p(th_o), _p(idx_o), _p(runs), _p(rc)))
+    return num_o[:total], th_o[:total], idx_o[:total], runs[:total], rc[:n_lists]
 
 
 def default_refine_params(**kw):
@@ -1433,7 +1451,8 @@ class Model:
 
     def vote_hits(self, scene, ref_index):
         """(numbers, theta_v, scene indices, keep) of one scene reference point: its hit list as the votes read it,
-        sorted by key number, and the places the list was given (the pairs whose distance bin is within reach)."""
+        sorted by key number (segment by segment above 16384 hits, or 8192 from 2^18 key numbers on), and the places the
+        list was given (the pairs whose distance bin is within reach)."""
         n, keep = C.c_size_t(0), C.c_uint32(0)
         _check(lib().oslam_vote_hits(self._h, scene._h, int(ref_index), None, None, None, 0, C.byref(n), C.byref(keep)))
         num, th, idx = (np.zeros(n.value, np.uint32) for _ in range(3))

@@ -88,7 +88,10 @@ def _check_scene(ppf, model, keys, nums, sp, sn, d, refs):
         want = np.stack([nums[at[hit]].astype(np.int64), np.nonzero(hit)[0].astype(np.int64)], 1)
         got = np.stack([num.astype(np.int64), idx.astype(np.int64)], 1)
         want = want[np.lexsort((want[:, 1], want[:, 0]))]
-        assert np.all(num[1:] >= num[:-1])                                  # the list is sorted by key number
+        # the list is sorted by key number: the whole list up to one segment of the sort (every list here but those of
+        # test_gpu_wide_keys), segment by segment beyond (tests/sort_ref.py: 16384 hits, 8192 from 2^18 key numbers on)
+        seg = 16384 if len(keys) <= 1 << 18 else 8192
+        assert all(np.all(num[s + 1:s + seg] >= num[s:s + seg][:-1]) for s in range(0, len(num), seg))
         got = got[np.lexsort((got[:, 1], got[:, 0]))]
         assert np.array_equal(got, want), (r, len(got), len(want))
         assert np.all(kept[idx]) and len(got) <= keep                       # every hit was a kept pair
