@@ -2122,6 +2122,38 @@ int oslam_vote_hits(oslam_model *m, oslam_scene *s, size_t ref_index, uint32_t *
 int oslam_sort_hits_tap(const uint32_t *numbers, const uint32_t *theta, const uint32_t *idx, const uint32_t *offsets,
                         const uint32_t *counts, size_t n_lists, uint32_t id_bits, int dev, uint32_t *numbers_out,
                         uint32_t *theta_out, uint32_t *idx_out, uint32_t *runs_out, uint32_t *run_counts_out);
+/* The two ordering kernels of the model build alone (k_bucket_spread, k_bucket_psort), on n_buckets buckets the caller
+ * supplies, in one launch each.  Bucket b holds lens[b] entries and starts at the running sum of (len + 3) & ~3 over
+ * the buckets before it, as the build's scan places it; its slot carries the key keys[b] (keys NULL: b + 1; a slot
+ * with key 0 is skipped by both kernels, whatever its length).  e4 / uv (two floats per entry) / mi hold the entries in
+ * arrival order with the padding words behind every bucket, `total` = the end of the last bucket of each; they go up as
+ * given.  spread 0 leaves k_bucket_spread out (oslam_params.no_bucket_spread), with_uv 0 is the fast-mode build: the
+ * kernels get no uv (uv_out = uv as given) and k_bucket_psort is not launched.  Every array comes back whole: e4_out / uv_out / mi_out [total]
+ * in the spread's order, pw_out / puv_out [total] the second order and pdir_out [total + 256] its directories; the last
+ * three are filled with 0xA5 bytes before the launches and the places the kernels do not own keep them.  The contract
+ * is oslamk_entries' (DESIGN.md at the model build); tests/bucket_ref.py restates it.  OSLAM_E_INVALID before any
+ * device call: a NULL array (but keys), a bucket above 2^20 entries, a total above 2^24. */
+int oslam_bucket_order_tap(const uint32_t *lens, const uint32_t *keys, size_t n_buckets, const uint32_t *e4, const float *uv,
+                           const uint16_t *mi, int with_uv, int spread, int dev, uint32_t *e4_out, float *uv_out,
+                           uint16_t *mi_out, uint32_t *pw_out, float *puv_out, uint16_t *pdir_out);
+/* A built model's tables as they lie in device memory, copied back without sorting or interpreting: the same for a
+ * created model, a loaded one and a member of a database group (which shows its group's union tables: ukeys, uids,
+ * weights, reach, kmap, and its own slots, uinfo and entries).  Size, then fill: *info always receives the scalars, which
+ * give every array's length; each array whose pointer is not NULL is then copied whole:
+ *   slots [n_slices * cap][4] (key, start, len, cur)   ukeys, uids [ucap]   weights [ucap] (64-bit)   reach [512]
+ *   kmap [kmap_bins * 4913]   uinfo [n_slices * uinfo_stride][2] (start, len | marker << 31)
+ *   e4 [n_entries + 256]   mi [n_entries]   pw [n_entries]   puv [n_entries][2]   pdir [n_entries + 256]
+ * pw, puv and pdir exist only when info->has_pw (not in a fast-mode model: asking for them there is OSLAM_E_INVALID);
+ * the places of pw, puv and pdir the build does not own are whatever the allocation held.  The layout is
+ * csrc/oslam_kernels.h's (DESIGN.md at the model build); tests/model_ref.py restates what is determined of it. */
+typedef struct oslam_model_tables {
+    uint32_t cap, shift, n_slices, ucap, ushift, n_entries, n_ids, id_bits, uinfo_stride, kmap_bins, reach_words, has_pw;
+    uint64_t num_model_keys;
+    uint32_t reserved[2];
+} oslam_model_tables;
+int oslam_model_tables_tap(oslam_model *m, oslam_model_tables *info, uint32_t *slots, uint32_t *ukeys, uint32_t *uids,
+                           uint64_t *weights, uint32_t *reach, uint32_t *kmap, uint32_t *uinfo, uint32_t *e4, uint16_t *mi,
+                           uint32_t *pw, float *puv, uint16_t *pdir);
 /* Cells kept by the last oslam_align / oslam_align_finish on this model, in
  * the order (count desc, code asc); poses_out (may be NULL) gets 16 floats per cell. */
 int oslam_last_cells(oslam_model *m, oslam_cell *cells_out, float *poses_out, size_t cap,

@@ -1,6 +1,6 @@
 /*
- * oslam_taps.c -- the parity taps (pair keys, buckets, the accumulator of one reference point, the last
- * result) and the device math self-test.
+ * oslam_taps.c -- the parity taps (pair keys, buckets, the accumulator of one reference point, the hit sort and the
+ * bucket orders alone, a model's tables, the last result) and the device math self-test.
  */
 
 #include "oslam_internal.h"
@@ -317,6 +317,140 @@ done:
     if (d_pay) (void)hipFree(d_pay);
     if (d_sorted) (void)hipFree(d_sorted);
     if (d_runs) (void)hipFree(d_runs);
+    return rc;
+}
+
+/* k_bucket_spread and k_bucket_psort alone, on buckets the caller supplies: a slot table of one slice with one slot per
+ * bucket, in bucket order (the kernels read t.slots[blockIdx.x] and nothing else of the table, so its cap need not be a
+ * power of two), start as k_table_scan gives it, cur = len.  pw, puv and pdir are filled with 0xA5 bytes before the
+ * launches; all six arrays are copied back whole */
+#define BUCKET_TAP_MAX_LEN (1u << 20)
+#define BUCKET_TAP_MAX_TOTAL ((size_t)1 << 24)
+int oslam_bucket_order_tap(const uint32_t *lens, const uint32_t *keys, size_t n_buckets, const uint32_t *e4, const float *uv,
+                           const uint16_t *mi, int with_uv, int spread, int dev, uint32_t *e4_out, float *uv_out,
+                           uint16_t *mi_out, uint32_t *pw_out, float *puv_out, uint16_t *pdir_out)
+{
+    int rc = OSLAM_OK, devsel;
+    size_t total = 0, i, places;
+    oslamk_slot *h_slots = NULL;
+    oslamk_table t;
+    oslamk_entries ent;
+    oslamk_uv *d_uv = NULL;
+    hipStream_t st;
+    memset(&t, 0, sizeof t);
+    memset(&ent, 0, sizeof ent);
+    if (!lens || !e4 || !uv || !mi || !e4_out || !uv_out || !mi_out || !pw_out || !puv_out || !pdir_out)
+        return fail(OSLAM_E_INVALID, "NULL argument");
+    if (n_buckets > BUCKET_TAP_MAX_TOTAL) return fail(OSLAM_E_INVALID, "too many buckets");
+    for (i = 0; i < n_buckets; i++) {
+        if (lens[i] > BUCKET_TAP_MAX_LEN) return fail(OSLAM_E_INVALID, "a bucket is longer than 2^20 entries");
+        total += ((size_t)lens[i] + 3u) & ~(size_t)3u;
+        if (total > BUCKET_TAP_MAX_TOTAL) return fail(OSLAM_E_INVALID, "the buckets hold more than 2^24 entries");
+    }
+    if (n_buckets == 0) return OSLAM_OK;
+    rc = oslam_pick_device(dev, &devsel);
+    if (rc != OSLAM_OK) return rc;
+    st = (hipStream_t)oslam_stream();
+    h_slots = (oslamk_slot *)malloc(sizeof *h_slots * n_buckets);
+    if (!h_slots) return fail(OSLAM_E_NOMEM, "host allocation failed");
+    for (i = 0, total = 0; i < n_buckets; i++) {
+        h_slots[i].key = keys ? keys[i] : (uint32_t)i + 1u;
+        h_slots[i].start = (uint32_t)total;
+        h_slots[i].len = h_slots[i].cur = lens[i];
+        total += ((size_t)lens[i] + 3u) & ~(size_t)3u;
+    }
+    places = total ? total : 4;
+    t.cap = (uint32_t)n_buckets;
+    t.n_slices = 1;
+    HIPCHK(hipMalloc((void **)&t.slots, sizeof(oslamk_slot) * n_buckets));
+    HIPCHK(hipMalloc((void **)&ent.e4, sizeof(uint32_t) * places));
+    HIPCHK(hipMalloc((void **)&d_uv, sizeof(oslamk_uv) * places));
+    HIPCHK(hipMalloc((void **)&ent.mi, sizeof(uint16_t) * places));
+    HIPCHK(hipMalloc((void **)&ent.pw, sizeof(uint32_t) * places));
+    HIPCHK(hipMalloc((void **)&ent.puv, sizeof(oslamk_uv) * places));
+    HIPCHK(hipMalloc((void **)&ent.pdir, sizeof(uint16_t) * ((total + 256) << OSLAMK_PDIR_SHIFT)));
+    HIPCHK(hipMemcpy(t.slots, h_slots, sizeof(oslamk_slot) * n_buckets, hipMemcpyHostToDevice));
+    if (total) {
+        HIPCHK(hipMemcpy(ent.e4, e4, sizeof(uint32_t) * total, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_uv, uv, sizeof(oslamk_uv) * total, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(ent.mi, mi, sizeof(uint16_t) * total, hipMemcpyHostToDevice));
+    }
+    HIPCHK(hipMemsetAsync(ent.pw, 0xA5, sizeof(uint32_t) * places, st));
+    HIPCHK(hipMemsetAsync(ent.puv, 0xA5, sizeof(oslamk_uv) * places, st));
+    HIPCHK(hipMemsetAsync(ent.pdir, 0xA5, sizeof(uint16_t) * ((total + 256) << OSLAMK_PDIR_SHIFT), st));
+    ent.uv = with_uv ? d_uv : NULL;            /* the fast-mode build has none */
+    ent.n_real = (uint32_t)total;
+    if (spread) KCHK(oslamk_bucket_spread(t, ent, st));
+    if (with_uv) KCHK(oslamk_bucket_psort(t, ent, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (total) {
+        HIPCHK(hipMemcpy(e4_out, ent.e4, sizeof(uint32_t) * total, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(uv_out, d_uv, sizeof(oslamk_uv) * total, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(mi_out, ent.mi, sizeof(uint16_t) * total, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(pw_out, ent.pw, sizeof(uint32_t) * total, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(puv_out, ent.puv, sizeof(oslamk_uv) * total, hipMemcpyDeviceToHost));
+    }
+    HIPCHK(hipMemcpy(pdir_out, ent.pdir, sizeof(uint16_t) * ((total + 256) << OSLAMK_PDIR_SHIFT), hipMemcpyDeviceToHost));
+done:
+    free(h_slots);
+    if (t.slots) (void)hipFree(t.slots);
+    if (ent.e4) (void)hipFree(ent.e4);
+    if (d_uv) (void)hipFree(d_uv);
+    if (ent.mi) (void)hipFree(ent.mi);
+    if (ent.pw) (void)hipFree(ent.pw);
+    if (ent.puv) (void)hipFree(ent.puv);
+    if (ent.pdir) (void)hipFree(ent.pdir);
+    return rc;
+}
+
+/* a built model's tables as they lie in device memory -- created, loaded or a member of a database group alike (a member
+ * shows its group's union tables): the scalars into *info, then every array whose pointer is given, copied whole.  Nothing
+ * is sorted or interpreted here */
+int oslam_model_tables_tap(oslam_model *m, oslam_model_tables *info, uint32_t *slots, uint32_t *ukeys, uint32_t *uids,
+                           uint64_t *weights, uint32_t *reach, uint32_t *kmap, uint32_t *uinfo, uint32_t *e4, uint16_t *mi,
+                           uint32_t *pw, float *puv, uint16_t *pdir)
+{
+    int rc = OSLAM_OK;
+    size_t n_slots, ne;
+    const oslamk_table *t;
+    if (!m || !info) return fail(OSLAM_E_INVALID, "NULL argument");
+    memset(info, 0, sizeof *info);
+    t = &m->table;
+    if (m->unusable || !t->slots || !t->ukeys || !t->uids || !t->reach || !t->uinfo || !m->ent.e4 || !m->ent.mi)
+        return fail(OSLAM_E_INVALID, "this model has no key tables");
+    info->cap = t->cap;
+    info->shift = t->shift;
+    info->n_slices = (uint32_t)t->n_slices;
+    info->ucap = t->ucap;
+    info->ushift = t->ushift;
+    info->n_entries = m->n_entries;
+    info->n_ids = t->n_ids;
+    info->id_bits = t->id_bits;
+    info->uinfo_stride = t->uinfo_stride;
+    info->kmap_bins = t->kmap_bins;
+    info->reach_words = t->reach_words;
+    info->has_pw = m->ent.pw != NULL;
+    info->num_model_keys = m->num_model_keys;
+    if (!m->ent.pw && (pw || puv || pdir)) return fail(OSLAM_E_INVALID, "a fast-mode model has no second order");
+    if (!slots && !ukeys && !uids && !weights && !reach && !kmap && !uinfo && !e4 && !mi && !pw && !puv && !pdir) return OSLAM_OK;
+    if (hipSetDevice(m->dev) != hipSuccess) return fail(OSLAM_E_DEVICE, "hipSetDevice failed");
+    n_slots = (size_t)t->cap * (size_t)t->n_slices;
+    ne = m->n_entries;
+    HIPCHK(hipStreamSynchronize((hipStream_t)oslam_stream()));
+    if (slots) HIPCHK(hipMemcpy(slots, t->slots, sizeof(oslamk_slot) * n_slots, hipMemcpyDeviceToHost));
+    if (ukeys) HIPCHK(hipMemcpy(ukeys, t->ukeys, sizeof(uint32_t) * t->ucap, hipMemcpyDeviceToHost));
+    if (uids) HIPCHK(hipMemcpy(uids, t->uids, sizeof(uint32_t) * t->ucap, hipMemcpyDeviceToHost));
+    if (weights) HIPCHK(hipMemcpy(weights, OSLAMK_UWEIGHTS(*t), sizeof(uint64_t) * t->ucap, hipMemcpyDeviceToHost));
+    if (reach) HIPCHK(hipMemcpy(reach, t->reach, sizeof(uint32_t) * (OSLAMK_REACH_BINS / 32), hipMemcpyDeviceToHost));
+    if (kmap && t->kmap_bins)
+        HIPCHK(hipMemcpy(kmap, t->kmap, sizeof(uint32_t) * (size_t)t->kmap_bins * PC_ANGLE_COMBOS, hipMemcpyDeviceToHost));
+    if (uinfo) HIPCHK(hipMemcpy(uinfo, t->uinfo, sizeof(oslamk_uinfo) * (size_t)t->n_slices * t->uinfo_stride, hipMemcpyDeviceToHost));
+    if (e4) HIPCHK(hipMemcpy(e4, m->ent.e4, sizeof(uint32_t) * (ne + 256), hipMemcpyDeviceToHost));
+    if (mi && ne) HIPCHK(hipMemcpy(mi, m->ent.mi, sizeof(uint16_t) * ne, hipMemcpyDeviceToHost));
+    if (pw && ne) HIPCHK(hipMemcpy(pw, m->ent.pw, sizeof(uint32_t) * ne, hipMemcpyDeviceToHost));
+    if (puv && ne) HIPCHK(hipMemcpy(puv, m->ent.puv, sizeof(oslamk_uv) * ne, hipMemcpyDeviceToHost));
+    if (pdir) HIPCHK(hipMemcpy(pdir, m->ent.pdir, sizeof(uint16_t) * ((ne + 256) << OSLAMK_PDIR_SHIFT), hipMemcpyDeviceToHost));
+done:
     return rc;
 }
 

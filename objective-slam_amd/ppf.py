@@ -372,6 +372,15 @@ class WorldRaycastResult(C.Structure):
                 "box_hi": tuple(int(x) for x in self.box_hi), "ms_total": float(self.ms_total)}
 
 
+class ModelTables(C.Structure):
+    _fields_ = [(f, C.c_uint32) for f in ("cap", "shift", "n_slices", "ucap", "ushift", "n_entries", "n_ids", "id_bits",
+                                          "uinfo_stride", "kmap_bins", "reach_words", "has_pw")] + \
+               [("num_model_keys", C.c_uint64), ("reserved", C.c_uint32 * 2)]
+
+    def asdict(self):
+        return {f: int(getattr(self, f)) for f, _ in self._fields_ if f != "reserved"}
+
+
 class NormalsParams(C.Structure):
     _fields_ = [("radius", C.c_float), ("min_neighbours", C.c_uint), ("viewpoint", C.c_float * 3), ("orient", C.c_int),
                 ("line_ratio", C.c_float), ("reserved", C.c_int * 4)]
@@ -583,6 +592,8 @@ _SIGNATURES = {
     "oslam_vote_accumulator": (_i, [_vp, _vp, _sz, _vp]),
     "oslam_vote_hits": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _sz, C.POINTER(_sz), C.POINTER(C.c_uint32)]),
     "oslam_sort_hits_tap": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, C.c_uint32, _i, _vp, _vp, _vp, _vp, _vp]),
+    "oslam_bucket_order_tap": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "oslam_model_tables_tap": (_i, [_vp, C.POINTER(ModelTables)] + [_vp] * 12),
     "oslam_model_key_numbers": (_i, [_vp, _vp, _vp, _vp, _sz, C.POINTER(_sz)]),
     "oslam_vote_ref_order": (_i, [_vp, _sz, _vp]),
     "oslam_last_cells": (_i, [_vp, _vp, _vp, _sz, C.POINTER(_sz)]),
@@ -658,6 +669,29 @@ def sort_hits(numbers, theta, idx, offsets, counts, id_bits, dev=0):
     _check(lib().oslam_sort_hits_tap(_p(numbers), _p(theta), _p(idx), _p(offsets), _p(counts), n_lists, int(id_bits), int(dev),
                                      _p(num_o), _p(th_o), _p(idx_o), _p(runs), _p(rc)))
     return num_o[:total], th_o[:total], idx_o[:total], runs[:total], rc[:n_lists]
+
+
+def bucket_order(lens, e4, uv, mi, keys=None, with_uv=True, spread=True, dev=0):
+    """k_bucket_spread and k_bucket_psort alone on the buckets given (oslam_bucket_order_tap): bucket b holds lens[b]
+    entries from the running sum of (len + 3) & ~3 on, under the key keys[b] (None: b + 1).  e4 [total] uint32,
+    uv [total, 2] float32, mi [total] uint16 with their padding.  -> (e4, uv, mi, pw, puv, pdir [total + 256]), whole."""
+    lens = np.ascontiguousarray(lens, np.uint32)
+    e4, uv, mi = np.ascontiguousarray(e4, np.uint32), np.ascontiguousarray(uv, np.float32), np.ascontiguousarray(mi, np.uint16)
+    total = int((((lens.astype(np.int64) + 3) >> 2) << 2).sum())
+    if keys is not None:
+        keys = np.ascontiguousarray(keys, np.uint32)
+        if len(keys) != len(lens):
+            raise ValueError("keys holds one word per bucket")
+    if e4.shape != (total,) or uv.shape != (total, 2) or mi.shape != (total,):
+        raise ValueError("e4, uv and mi hold the padded lengths' sum of entries each")
+    room = max(total, 1)
+    e4_o, pw = np.zeros(room, np.uint32), np.zeros(room, np.uint32)
+    uv_o, puv = np.zeros((room, 2), np.float32), np.zeros((room, 2), np.float32)
+    mi_o, pdir = np.zeros(room, np.uint16), np.zeros(total + 256, np.uint16)
+    _check(lib().oslam_bucket_order_tap(_p(lens), None if keys is None else _p(keys), len(lens), _p(e4), _p(uv), _p(mi),
+                                        int(bool(with_uv)), int(bool(spread)), int(dev), _p(e4_o), _p(uv_o), _p(mi_o),
+                                        _p(pw), _p(puv), _p(pdir)))
+    return e4_o[:total], uv_o[:total], mi_o[:total], pw[:total], puv[:total], pdir
 
 
 def default_refine_params(**kw):
@@ -1443,6 +1477,25 @@ class Model:
         if n.value:
             _check(lib().oslam_model_key_numbers(self._h, _p(keys), _p(nums), _p(w), n.value, C.byref(n)))
         return keys, nums, w
+
+    def tables(self):
+        """The model's tables as they lie in device memory (oslam_model_tables_tap): a dict of the scalars and of slots
+        [n_slices, cap, 4], ukeys, uids, weights [ucap], reach [512], kmap [kmap_bins, 4913], uinfo [n_slices, stride, 2],
+        e4 [n_entries + 256], mi [n_entries] and, when has_pw, pw, puv [n_entries, 2] (float32), pdir [n_entries + 256]."""
+        info = ModelTables()
+        _check(lib().oslam_model_tables_tap(self._h, C.byref(info), *([None] * 12)))
+        t = info.asdict()
+        ne = t["n_entries"]
+        a = dict(slots=np.zeros((t["n_slices"], t["cap"], 4), np.uint32), ukeys=np.zeros(t["ucap"], np.uint32),
+                 uids=np.zeros(t["ucap"], np.uint32), weights=np.zeros(t["ucap"], np.uint64), reach=np.zeros(512, np.uint32),
+                 kmap=np.zeros((t["kmap_bins"], 4913), np.uint32), uinfo=np.zeros((t["n_slices"], t["uinfo_stride"], 2), np.uint32),
+                 e4=np.zeros(ne + 256, np.uint32), mi=np.zeros(ne, np.uint16))
+        if t["has_pw"]:
+            a.update(pw=np.zeros(ne, np.uint32), puv=np.zeros((ne, 2), np.float32), pdir=np.zeros(ne + 256, np.uint16))
+        order = ("slots", "ukeys", "uids", "weights", "reach", "kmap", "uinfo", "e4", "mi", "pw", "puv", "pdir")
+        _check(lib().oslam_model_tables_tap(self._h, C.byref(info), *[_p(a[k]) if k in a and a[k].size else None for k in order]))
+        t.update(a)
+        return t
 
     def vote_accumulator(self, scene, ref_index):
         acc = np.zeros((self.n, 32), np.uint32)
