@@ -1,6 +1,6 @@
 /*
  * oslam_host.c -- the C-ABI of include/oslam.h: host orchestration in C over
- * the gfx950 kernels of oslam_kernels.hip.  This file: what every stage shares
+ * the gfx950 kernels of the .hip files beside it (oslam_kernels.h).  This file: what every stage shares
  * (oslam_internal.h); each stage has a file of its own beside it.
  *
  * Mirrors the reference's host layer (pcl/alignment/src/cuda/{ppf,model,scene}.cu)

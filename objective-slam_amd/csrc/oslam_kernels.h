@@ -1,8 +1,32 @@
 /*
- * oslam_kernels.h -- C launch interface of the gfx950 kernels
- * (oslam_kernels.hip).  Internal to liboslam_hip.so; the public boundary is
- * include/oslam.h.  All pointers are device pointers unless noted; `stream` is
- * a hipStream_t passed as void*.  Launchers return a hipError_t as int.
+ * oslam_kernels.h -- C launch interface of the gfx950 (MI355X / CDNA4) kernels, one .hip file per stage beside this
+ * header.  Internal to liboslam_hip.so; the public boundary is include/oslam.h.  All pointers are device pointers
+ * unless noted; `stream` is a hipStream_t passed as void*.  Launchers return a hipError_t as int.
+ *
+ * The PPF registration path.  What the reference does with N^2-sized arrays and Thrust sorts
+ * (pcl/alignment/src/cuda/{scene,model}.cu) is fused; wave = 64 lanes throughout:
+ *   model build  (oslam_model.hip) pair key -> per-slice open-addressing table -> bucketed 4-byte pair entries (two
+ *                counting passes, no sort); union table of all keys, and per slice the bucket of every key; bitset of
+ *                the distance bins that can reach a key; key map (distance bin, three angle bins) -> key number;
+ *                entries ordered inside each bucket for the LDS banks;
+ *   scene count  (oslam_scene.hip) per reference point, the pairs whose distance bin can reach a model key: sizes the
+ *                hit lists by demand;
+ *   scene keys   (oslam_scene.hip) per (8 reference points, tile of scene points): distance bin of every pair,
+ *                unreachable bins dropped, the rest compacted in LDS; the pair's feature as bins -> key map (one load,
+ *                no hash, no probing) -> per-reference hit list {key number} + {theta_v, i} written by
+ *                wave-aggregated appends;
+ *   hit sort     (oslam_sort.hip) per reference point, hits ordered by key number (LDS radix sort) and the list of
+ *                runs of equal keys;
+ *   voting       (oslam_vote.hip, oslam_vote_wide.hip; the workgroup: oslam_vote_body.inc) one workgroup per (scene
+ *                reference point, model slice of 2046 points): a run finds its bucket with one load (no probing); very
+ *                long items are cut into units dealt to the 16 waves, the rest is handed out dynamically a few runs at
+ *                a time; a wave streams a bucket once for all hits that share it (16 bytes = 4 entries per lane, four
+ *                steps' loads in flight) -> integer alpha bin -> LDS accumulator [1023 rows + sink][31 words], two
+ *                16-bit counters per word; votes near a bin edge are cast, noted and re-checked with the reference's
+ *                float sequence; in-kernel peak extraction;
+ *   pose tail    (oslam_posegpu.hip) poses of the peaks and their clustering scores (one wave per four poses).
+ * The stages after registration (refinement, verification, ..., the whole map) have a .hip each whose head says what
+ * its kernels do.
  */
 #ifndef OSLAM_KERNELS_H
 #define OSLAM_KERNELS_H
@@ -17,6 +41,15 @@ extern "C" {
 #define OSLAMK_SLICE 2046      /* model reference points per table slice: two per 32-bit counter word of a row (ppf_core.h) */
 #define OSLAMK_ROWS 1024       /* rows of the LDS accumulator: one per reference point of the slice + the sink row of padding entries */
 #define OSLAMK_NBIN 32         /* alpha bins per accumulator row (reference uses 0..30) */
+/* The accumulator of a vote workgroup in LDS: OSLAMK_ROWS rows of ACC_STRIDE words (bins 0..29 + one unused).
+ * The stride is odd on purpose: the LDS bank of a vote is (row * 31 + bin) mod 32 = (bin - row) mod 32, so votes
+ * of one instruction that fall into the same bin of different rows do not meet on a bank, and k_bucket_spread
+ * can order a bucket so that the 32 lanes the LDS serves together land on 32 different banks whatever the
+ * hit's angle is (a stride of 32 would make the bank the bin alone: 30 banks, and as crowded as the model's
+ * angles are). */
+#ifndef ACC_STRIDE
+#define ACC_STRIDE 31
+#endif
 
 /* One slot of a slice's open-addressing table, keyed by the 32-bit PPF key. */
 typedef struct oslamk_slot {
@@ -125,6 +158,17 @@ typedef struct oslamk_table {
 #define OSLAMK_UWEIGHTS(t) ((unsigned long long *)((t).uids + (t).ucap))
 #define OSLAMK_KMAP_NONE 0xffffffffu
 #define OSLAMK_KMAP_MAX_BINS 2048
+
+/* The slot rule of the slice tables (shift = table.shift) and of the union table (table.ushift): where the probe
+ * sequence of a key starts.  The one text of it, for the kernels that build and probe the tables and for the host
+ * taps that read them back. */
+#ifdef __HIPCC__
+__host__ __device__
+#endif
+static inline uint32_t oslamk_slot_of(uint32_t key, uint32_t shift)
+{
+    return (key * 2654435761u) >> shift;
+}
 
 #define OSLAMK_REACH_BINS 16384
 

@@ -19,9 +19,9 @@
 #include <hip/hip_runtime.h>
 
 #include "oslam_kernels.h"
+#include "oslam_lane.h"
 #include "ppf_core.h"
 
-#define WAVE 64
 #define SORT_THREADS 1024
 #define SORT_WAVES (SORT_THREADS / WAVE)
 #define SORT_IDX_BITS 14

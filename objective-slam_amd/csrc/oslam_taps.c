@@ -62,7 +62,7 @@ int oslam_model_bucket(oslam_model *m, uint32_t key, uint32_t *pairs_out, size_t
     }
     for (s = 0; s < m->table.n_slices; s++) {
         const oslamk_slot *tab = m->h_slots + (size_t)s * m->table.cap;
-        uint32_t mask = m->table.cap - 1, slot = (key * 2654435761u) >> m->table.shift, probe;
+        uint32_t mask = m->table.cap - 1, slot = oslamk_slot_of(key, m->table.shift), probe;
         for (probe = 0; probe <= mask; probe++) {
             if (tab[slot].key == key) {
                 uint32_t len = tab[slot].len, e;
@@ -99,7 +99,7 @@ int oslam_model_bucket_words(oslam_model *m, uint32_t key, int slice, uint32_t *
     if (!tab) return fail(OSLAM_E_NOMEM, "host allocation failed");
     HIPCHK(hipMemcpy(tab, m->table.slots + (size_t)slice * m->table.cap, sizeof(oslamk_slot) * m->table.cap, hipMemcpyDeviceToHost));
     mask = m->table.cap - 1;
-    slot = (key * 2654435761u) >> m->table.shift;
+    slot = oslamk_slot_of(key, m->table.shift);
     for (probe = 0; probe <= mask; probe++, slot = (slot + 1) & mask) {
         if (tab[slot].key == key) {
             size_t n = tab[slot].len < cap ? tab[slot].len : cap;

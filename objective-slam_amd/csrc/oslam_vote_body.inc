@@ -1,26 +1,20 @@
 /*
  * oslam_vote_body.inc -- the vote workgroup of the PPF registration path (gfx950): everything between a reference
  * point's sorted hit list and its accumulator peaks (ComputeUniqueVotes, model.cu:95-171; K3/K4, kernel.cu:480-554).
- * Included by two translation units: oslam_kernels.hip (k_vote: the launch every registration runs) and
+ * Included by two translation units: oslam_vote.hip (k_vote: the launch every registration runs) and
  * oslam_vote_wide.hip (k_vote_wide: the rare re-vote of workgroups whose 16-bit counters overflowed, which walks a
- * list in a loop and is built with its own flag, see there).  Expects oslam_kernels.h and ppf_core.h.
+ * list in a loop and is built with its own flag, see there).  Expects oslam_kernels.h and ppf_core.h; the lane
+ * helpers (WAVE, wave_sum_*, readlane_*, uni_*) are oslam_lane.h's.
  */
 #ifndef OSLAM_VOTE_BODY_INC
 #define OSLAM_VOTE_BODY_INC
 
-#define WAVE 64
+#include "oslam_lane.h"
+
 #ifndef VOTE_THREADS
 #define VOTE_THREADS 1024
 #endif
-/* The accumulator of a vote workgroup in LDS: OSLAMK_ROWS rows of ACC_STRIDE words (bins 0..29 + one unused).
- * The stride is odd on purpose: the LDS bank of a vote is (row * 31 + bin) mod 32 = (bin - row) mod 32, so votes
- * of one instruction that fall into the same bin of different rows do not meet on a bank, and k_bucket_spread
- * can order a bucket so that the 32 lanes the LDS serves together land on 32 different banks whatever the
- * hit's angle is (a stride of 32 would make the bank the bin alone: 30 banks, and as crowded as the model's
- * angles are). */
-#ifndef ACC_STRIDE
-#define ACC_STRIDE 31
-#endif
+/* the accumulator of a vote workgroup in LDS: OSLAMK_ROWS rows of ACC_STRIDE words (oslam_kernels.h) */
 #define ACC_CELLS (OSLAMK_ROWS * ACC_STRIDE)
 #define ACC_REAL_CELLS (1023 * ACC_STRIDE)       /* counter words without the sink row; each holds two 16-bit counters */
 
@@ -30,33 +24,6 @@ static __device__ const uint32_t k_alpha_thr[32] = {PC_ALPHA_THR_FLAT};
 /* --------------------------------------------------------------------------
  * voting
  * ------------------------------------------------------------------------*/
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v)
-{
-    for (int o = 32; o > 0; o >>= 1) {
-        uint32_t w = __shfl_xor(v, o, WAVE);
-        v = v > w ? v : w;
-    }
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, WAVE);
-    return v;
-}
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, WAVE);
-    return v;
-}
-
-__device__ __forceinline__ float readlane_f(float v, int l)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l));
-}
-__device__ __forceinline__ uint32_t readlane_u(uint32_t v, int l)
-{
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, l);
-}
 /* bin and position inside the bin of one vote, from tm = hit base - entry word (a 32-bit fraction of a turn; the
  * subtraction wraps with the angle): tm * 30 = bin * 2^32 + position.  The vote loop takes the high word alone
  * (v_mul_hi_u32, VoteRegs::vote); the re-evaluation of the near-edge votes wants both.  The empty asm keeps the
@@ -67,12 +34,6 @@ __device__ __forceinline__ void vote_product(uint32_t tm8, uint32_t &bin, uint32
     bin = (uint32_t)(p >> 32);
     pos = (uint32_t)p;
     asm("" : "+v"(bin));
-}
-/* a value every lane holds, moved to scalar registers */
-__device__ __forceinline__ uint32_t uni_u32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ __forceinline__ unsigned long long uni_u64(unsigned long long v)
-{
-    return ((unsigned long long)uni_u32((uint32_t)(v >> 32)) << 32) | uni_u32((uint32_t)v);
 }
 
 /* ---- the vote of one (model pair entry, scene hit) ---------------------------

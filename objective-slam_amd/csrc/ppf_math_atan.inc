@@ -2,7 +2,7 @@
  * ppf_math_atan.inc -- atanf / atan2f (fdlibm sequences) and the exact alpha bin built on them.
  *
  * Included by ppf_math.h with PM_FN(n) = n and plain constants: the functions every caller uses.  Included once
- * more by oslam_kernels.hip with PM_FN(n) = n##_cold and constants that are materialised where they are used
+ * more by oslam_vote_body.inc (the vote units oslam_vote.hip and oslam_vote_wide.hip) with PM_FN(n) = n##_cold and constants that are materialised where they are used
  * (PM_KF / PM_KU as volatile moves): the vote kernel evaluates this formula only on its coldest path, and the
  * compiler would otherwise hoist the two dozen literals into vector registers for the whole kernel.  One source
  * text for both, so the arithmetic cannot diverge.

@@ -1,4 +1,4 @@
-"""The two orders inside a model's buckets restated (k_bucket_spread and k_bucket_psort, csrc/oslam_kernels.hip; the
+"""The two orders inside a model's buckets restated (k_bucket_spread and k_bucket_psort, csrc/oslam_model.hip; the
 contract is oslamk_entries' in csrc/oslam_kernels.h and DESIGN.md's at the model build).  numpy and integers only;
 written from the comments, not from the kernel's rank expression.
 

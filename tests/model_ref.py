@@ -1,5 +1,5 @@
 """A model's tables restated from its cloud and parameters alone (oslam_model_create, oslam_model_load, oslam_db_create:
-csrc/oslam_model.c, csrc/oslam_db.c and the build kernels of csrc/oslam_kernels.hip; the layout is csrc/oslam_kernels.h's).
+csrc/oslam_model.c, csrc/oslam_db.c and the build kernels of csrc/oslam_model.hip; the layout is csrc/oslam_kernels.h's).
 
 Where the values come from:
   * the key of every ordered pair: the CPU oracle (oracle.ppf_all_pairs), which shares no code with the library;

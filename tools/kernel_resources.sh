@@ -7,14 +7,14 @@
 # vote addresses are computed on denormal floats (VoteRegs::vote) and need 3 there, denormals kept in and out.
 cd "$(dirname "$0")/../objective-slam_amd/csrc"
 units="$*"
-[ -z "$units" ] && units="oslam_kernels oslam_vote_wide oslam_sort oslam_posegpu oslam_voxel oslam_depth oslam_refine oslam_verify oslam_arbitrate oslam_track oslam_ego oslam_pyramid oslam_bilateral oslam_volume oslam_surface oslam_mesh oslam_shift oslam_reload oslam_normals oslam_colour oslam_world_surface oslam_world_mesh oslam_reload_colour oslam_world_colour"
+[ -z "$units" ] && units="$(ls *.hip | sed 's/\.hip$//')"      # every kernel unit
 for f in $units; do
   fl=""; [ $f = oslam_vote_wide ] && fl="-mllvm -disable-machine-licm"
   echo "== $f.hip $fl"
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -ffp-contract=off -fno-fast-math -I../../include -I. $EXTRA $fl \
       -Rpass-analysis=kernel-resource-usage -c $f.hip -o /tmp/kr_$$.o 2>&1 \
     | grep -E "Function Name|TotalSGPRs|VGPRs:|AGPRs:|ScratchSize|Occupancy|SGPRs Spill|VGPRs Spill|LDS Size" | sed 's/.*remark: *//; s/ \[-Rpass.*//'
-  case $f in oslam_kernels|oslam_vote_wide)
+  case $f in oslam_vote|oslam_vote_wide)
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -ffp-contract=off -fno-fast-math -I../../include -I. $EXTRA $fl \
         --offload-device-only -S $f.hip -o - 2>/dev/null \
       | awk '/^[ \t]*\.amdhsa_kernel /{k=$2} /\.amdhsa_float_denorm_mode_32/ && k ~ /^_Z[0-9]+k_vote/ {print "float_denorm_mode_32 " $2 "  " k}' ;;
