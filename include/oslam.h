@@ -1961,6 +1961,93 @@ int oslam_mesh_normals(const float *xyz, size_t nv, size_t stride_bytes, const u
 int oslam_ply_read_mesh(const char *path, float **xyz_out, float **nrm_out, uint32_t **tri_out, size_t *nv_out,
                         size_t *nt_out);
 
+/* ---- the dominant planes of a view, found and removed on the device.  In an indoor frame almost all of the scene is
+ * floor and wall; KinFu-based object pipelines (SLAM++) take the supporting planes away before they look for objects.
+ * oslam_view_planes finds up to OSLAM_PLANES_MAX planes of a view and labels their pixels, oslam_view_remove_planes returns
+ * the view without them or with them alone.  The restatement in numpy is tests/planes_ref.py; device and restatement agree
+ * bit for bit, and two calls give the same bytes: every gate is a float32 expression with the grouping written here
+ * (the build's -ffp-contract=off keeps the operations apart) and every sum is a whole number, so nothing depends on the
+ * order of pixels, waves or workgroups.
+ *
+ * Inputs per pixel: the view's z image and its vertex and normal maps (oslam_view_maps' [h][w][8], built when absent).  The
+ *   point of a valid pixel (z > 0) is p = ((((float)u - cx) * z) / fx, (((float)v - cy) * z) / fy, z), the vertex map's
+ *   value bit for bit where the pixel has a normal (has == 1).  A pixel is free when it is valid and carries no label yet.
+ * Rounds r = 0 .. max_planes - 1 peel one plane each:
+ *   1. Candidates.  The 256 nodes of a 16 x 16 lattice: node (a, b), index 16 b + a, is pixel u = ((2a + 1) * w) / 32,
+ *      v = ((2b + 1) * h) / 32 in integer division.  A node is a candidate of this round when its pixel is free and has a
+ *      normal; its plane is the pixel's own normal n0 with d0 = -((n0x*p0x + n0y*p0y) + n0z*p0z).  On small images nodes
+ *      coincide; duplicates stay.
+ *   2. Score.  count[c] = the free pixels with a normal that pass fabsf(((n0x*px + n0y*py) + n0z*pz) + d0) <= dist_tol and
+ *      (n0x*nx + n0y*ny) + n0z*nz >= min_normal_dot; 0 for a node that is no candidate.  The winner is the candidate with
+ *      the largest count, the lowest index on a tie.  The search ends when no node is a candidate or the winner's count is
+ *      below min_pixels (0 = w * h / 50 in integer division); everything found so far stands.
+ *   3. Refit.  Over the winner's inliers (the pixels its count counted), moments as whole numbers as in oslam_cloud_normals:
+ *      f_a = (p_a - p0_a) * scale in float32 with the winner's point p0 and scale = 16.0f / dist_tol (float32, made once by
+ *      the host); a pixel with some fabsf(f_a) > 131072 (2^17) is left out of the fit, and of the fit only: it was counted
+ *      and it can be labelled.  Otherwise q_a = (int32) rintf(f_a) and ten int64 sums: n, Sq_a (x y z), Sqq_ab (xx xy xz yy
+ *      yz zz).  No sum can overflow: |q_a| <= 2^17, so a product is at most 2^34 and a sum over w * h <= 2^28 pixels at
+ *      most 2^62 < 2^63.  The covariance in double in oslam_cloud_normals' operation order (its step 3), its
+ *      OSLAM_NORMALS_SWEEPS Jacobi sweeps (step 4), the normal = the column under the smallest diagonal element (lowest
+ *      index on a tie) divided by its length.  Fewer than 3 pixels in the fit, or lmid <= (double)0.01f * lmax (a strip:
+ *      the normals stage's line_ratio), end the search like a low count.  Centroid c_a = (double)p0_a + (Sq_a / n) /
+ *      (double)scale; the normal is negated when (nx*cx + ny*cy) + nz*cz > 0, then d = -((nx*cx + ny*cy) + nz*cz); both
+ *      are rounded to float32.  support = n, rms = (float)(sqrt(max(lmin, 0)) / (double)scale), candidate = the winner's
+ *      index.
+ *   4. Label.  Every free pixel, with or without a normal, gets label r when fabsf(((nx*px + ny*py) + nz*pz) + d) <=
+ *      dist_tol with the float32 plane of step 3 and, if it has a normal n, (nx*n_x + ny*n_y) + nz*n_z >= label_min_dot.
+ *      pixels counts them.  A pixel without a normal is labelled by distance alone: the frame's depth edges belong to the
+ *      planes as much as their interiors.
+ * Cost: two memsets, four kernels per round enqueued for every r < max_planes whatever the image holds (a `done` word in
+ *   the call's device block is set where the search ends; every later kernel reads it and leaves at once), one copy back,
+ *   one host wait.  launches == 4 * max_planes, plus 1 when the view's maps had to be built.
+ * oslam_planes keeps the labels on the device.  oslam_planes_get copies the plane records (OSLAM_E_LIMIT and *n_out when
+ *   cap is too small), oslam_planes_labels the label image [h][w] (-1 = none), oslam_planes_rounds is the test tap: the
+ *   counts [max_planes][256] and moments [max_planes][10] of every round as the device left them (zero for a round that
+ *   did not run; the round that ended the search by its count keeps its counts); either may be NULL.
+ * oslam_view_remove_planes: a pixel is a plane pixel iff z > 0 and its label l >= 0 (with only >= 0: l == only).
+ *   OSLAM_MASK_REMOVE writes plane ? 0 : z, OSLAM_MASK_KEEP plane ? z : 0 into a new view with v's camera and max_jump
+ *   that the caller owns (oslam_view_destroy); every stage takes it unchanged.  valid_in counts z > 0, object_pixels the
+ *   plane pixels, valid_out the valid pixels of the output.  One memset, one kernel, one copy back; launches == 1.
+ * Checks, before any device call: NULL v / out / p (pp and res may be NULL), a dist_tol that is not finite and > 0 (or so
+ *   small that 16 / dist_tol is no finite float), a min_normal_dot or label_min_dot outside [-1, 1], max_planes 0 or above
+ *   OSLAM_PLANES_MAX, a mode other than the two, only < -1; then the handles: a planes object of another device or image
+ *   size than the view, only >= n_planes: all OSLAM_E_INVALID.  OSLAM_E_DEVICE without a device.  A refused call writes
+ *   nothing but *out = NULL.
+ * Known limit: the normals of the reduced view are made again from the reduced image, so a kept pixel that touches a
+ *   removed one loses its normal (DESIGN.md has the share on the calibration room).
+ * Out of scope: connected components of a plane, merging planes across frames, planes of a cloud that has no image,
+ *   folding the stage into oslam_db_detect or the tracker, a "stands on the plane" constraint for hypotheses. */
+#define OSLAM_PLANES_MAX 8
+typedef struct oslam_planes_params {
+    float dist_tol;            /* metres, > 0, default 0.02 (calibration: DESIGN.md 7za) */
+    float min_normal_dot;      /* the score's and the fit's normal gate, default 0.9 */
+    float label_min_dot;       /* the label's normal gate, default 0 */
+    unsigned max_planes;       /* 1..OSLAM_PLANES_MAX, default 4 */
+    unsigned min_pixels;       /* 0 (default) = w * h / 50 */
+    int reserved[4];
+} oslam_planes_params;
+typedef struct oslam_plane {
+    float normal[3], d;        /* n . p + d = 0, n . centroid <= 0: the normal faces the camera */
+    uint32_t support;          /* the fit's n */
+    uint32_t pixels;           /* labelled */
+    uint32_t candidate;        /* the winner's lattice index */
+    float rms;                 /* of the fit, metres */
+} oslam_plane;
+typedef struct oslam_planes_result {
+    uint32_t n_planes, valid_in, labelled, launches;
+    float ms_total;
+} oslam_planes_result;
+typedef struct oslam_planes oslam_planes;
+
+int oslam_planes_params_default(oslam_planes_params *p);
+int oslam_view_planes(oslam_view *v, const oslam_planes_params *pp, oslam_planes **out, oslam_planes_result *res);
+int oslam_planes_get(const oslam_planes *p, oslam_plane *planes_out, size_t cap, size_t *n_out);
+int oslam_planes_labels(oslam_planes *p, int32_t *labels_out);
+int oslam_planes_rounds(oslam_planes *p, uint32_t *counts_out, int64_t *moments_out);
+int oslam_view_remove_planes(const oslam_view *v, const oslam_planes *p, int mode, int32_t only, oslam_view **out,
+                             oslam_mask_result *res);
+int oslam_planes_destroy(oslam_planes *p);
+
 /* ---- colour next to the TSDF (KinFu's colour volume): a view can carry the colour image its sensor registered with the
  * depth image, a volume a colour per voxel, and the fused colour comes back at the points of the surface and the mesh and
  * as the picture of a view.  No stage that existed before reads colour: a view or a volume without it behaves bit for

@@ -119,6 +119,16 @@ struct oslam_render {
     float *d_tol;
 };
 
+struct oslam_planes {
+    int dev;                          /* stays the first field, as in oslam_view; w and h follow it (the argument tests write them) */
+    int w, h;
+    uint32_t n_planes, max_planes;
+    int32_t *d_labels;                /* [h * w] on the device, -1 = no plane */
+    oslam_plane planes[OSLAM_PLANES_MAX];
+    uint32_t counts[OSLAM_PLANES_MAX][OSLAMK_PLANES_CAND];    /* the rounds' counts and moments, as the device left them */
+    int64_t moments[OSLAM_PLANES_MAX][10];
+};
+
 typedef struct db_group {
     int n;
     size_t *members;                  /* indices into db->models */

@@ -627,6 +627,49 @@ int oslamk_render_resolve(const unsigned long long *keys, int w, int h, const os
 int oslamk_view_mask(const oslamk_view *v, const float *z_r, const int32_t *labels, const float *tol, int mode, int dilate,
                      int32_t only, float *z_out, uint32_t *counts, void *stream);
 
+/* ---- planes stage (oslam_planes.hip; semantics in include/oslam.h at oslam_view_planes) ---- */
+#define OSLAMK_PLANES_MAX 8           /* rounds of one call at most */
+#define OSLAMK_PLANES_CAND 256        /* the 16 x 16 lattice nodes: one thread of a workgroup each */
+#define OSLAMK_PLANES_MAX_GROUPS 512  /* workgroups of the score and moments kernels at most */
+#define OSLAMK_PLANES_BOUND 131072.0f /* |(p_a - p0_a) * scale| above this leaves a pixel out of the fit */
+
+/* one plane: the layout of oslam_plane */
+typedef struct oslamk_plane {
+    float normal[3], d;
+    uint32_t support, pixels, candidate;
+    float rms;
+} oslamk_plane;
+
+/* the device block of one call, zeroed before the first launch */
+typedef struct oslamk_planes_block {
+    uint32_t done;             /* 0 while the search runs; 1 = count below min_pixels, 2 = degenerate fit, 3 = no candidate */
+    uint32_t n_planes;
+    uint32_t valid_in;         /* pixels with z > 0 (round 0's score kernel counts them) */
+    uint32_t pad;
+    uint32_t counts[OSLAMK_PLANES_MAX][OSLAMK_PLANES_CAND];
+    unsigned long long moments[OSLAMK_PLANES_MAX][10];    /* int64 sums, added as two's complement */
+    oslamk_plane rec[OSLAMK_PLANES_MAX];
+} oslamk_planes_block;
+
+typedef struct oslamk_planes_args {
+    oslamk_view v;
+    const float *maps;         /* [h][w][8]: x y z has | nx ny nz 0 */
+    int32_t *labels;           /* [h][w], all -1 before the first launch */
+    oslamk_planes_block *blk;
+    float dist_tol, min_normal_dot, label_min_dot;
+    float scale;               /* 16.0f / dist_tol, made once by the host */
+    uint32_t min_pixels;       /* resolved: never the 0 of the parameters */
+    double line_ratio;
+} oslamk_planes_args;
+
+/* every kernel of a call: per round k_planes_score, k_planes_moments, k_planes_round, k_planes_label; 4 * max_planes
+ * launches whatever the image holds */
+int oslamk_planes_find(const oslamk_planes_args *a, unsigned max_planes, void *stream);
+/* *v without (mode 0) or with only (mode 1) the pixels whose label is >= 0 (only >= 0: == only) -> z_out [w * h];
+ * counts[0 .. 3) (zeroed by the caller) += valid pixels of *v, plane pixels among them, valid pixels of z_out */
+int oslamk_planes_mask(const oslamk_view *v, const int32_t *labels, int mode, int32_t only, float *z_out, uint32_t *counts,
+                       void *stream);
+
 /* ---- explain stage (oslam_explain.hip; semantics in include/oslam.h at oslam_explain) ---- */
 /* the private z-buffer of one hypothesis: pixels [x0, x0 + w) x [y0, y0 + h) of the image, row-major from word `off` of
  * the pool; w == 0 or h == 0: it can draw nothing */

@@ -212,6 +212,32 @@ class MaskResult(C.Structure):
 MASK_REMOVE, MASK_KEEP = 0, 1
 
 
+class PlanesParams(C.Structure):
+    _fields_ = [("dist_tol", C.c_float), ("min_normal_dot", C.c_float), ("label_min_dot", C.c_float),
+                ("max_planes", C.c_uint), ("min_pixels", C.c_uint), ("reserved", C.c_int * 4)]
+
+
+class Plane(C.Structure):
+    _fields_ = [("normal", C.c_float * 3), ("d", C.c_float), ("support", C.c_uint32), ("pixels", C.c_uint32),
+                ("candidate", C.c_uint32), ("rms", C.c_float)]
+
+    def asdict(self):
+        return dict(normal=tuple(self.normal), d=self.d, support=self.support, pixels=self.pixels,
+                    candidate=self.candidate, rms=self.rms)
+
+
+class PlanesResult(C.Structure):
+    _fields_ = [("n_planes", C.c_uint32), ("valid_in", C.c_uint32), ("labelled", C.c_uint32), ("launches", C.c_uint32),
+                ("ms_total", C.c_float)]
+
+    def asdict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+PLANES_MAX = 8
+PLANES_CANDIDATES = 256
+
+
 class BilateralParams(C.Structure):
     _fields_ = [("radius", C.c_uint), ("sigma_space", C.c_float), ("sigma_depth", C.c_float), ("reserved", C.c_int * 4)]
 
@@ -522,6 +548,13 @@ _SIGNATURES = {
     "oslam_view_info": (_i, [_vp, _vp, C.POINTER(_i), C.POINTER(_i)]),
     "oslam_mask_params_default": (_i, [C.POINTER(MaskParams)]),
     "oslam_view_mask": (_i, [_vp, _vp, C.POINTER(MaskParams), C.POINTER(_vp), C.POINTER(MaskResult)]),
+    "oslam_planes_params_default": (_i, [C.POINTER(PlanesParams)]),
+    "oslam_view_planes": (_i, [_vp, C.POINTER(PlanesParams), C.POINTER(_vp), C.POINTER(PlanesResult)]),
+    "oslam_planes_get": (_i, [_vp, _vp, _sz, C.POINTER(_sz)]),
+    "oslam_planes_labels": (_i, [_vp, _vp]),
+    "oslam_planes_rounds": (_i, [_vp, _vp, _vp]),
+    "oslam_view_remove_planes": (_i, [_vp, _vp, _i, C.c_int32, C.POINTER(_vp), C.POINTER(MaskResult)]),
+    "oslam_planes_destroy": (_i, [_vp]),
     "oslam_bilateral_params_default": (_i, [C.POINTER(BilateralParams)]),
     "oslam_view_bilateral": (_i, [_vp, C.POINTER(BilateralParams), C.POINTER(_vp), C.POINTER(BilateralResult)]),
     "oslam_gauss_table": (_i, [_u, C.POINTER(_f)]),
@@ -1227,6 +1260,20 @@ class Scene:
                                             self.df, C.byref(self.params), C.byref(self._h), C.byref(n)))
         self.n = n.value
         return self
+
+    @classmethod
+    def from_view(cls, view, planes=None, leaf=None, d_dist=None, ref_point_downsample_factor=1, params=None, dev=0):
+        """The view's pixels that have a normal as a scene: remove_planes (planes: a Planes of this view, None = keep
+        everything), view_to_cloud, a voxel_grid when leaf is given, then Scene(...)."""
+        reduced = remove_planes(view, planes) if planes is not None else None
+        try:
+            pts, nrm = view_to_cloud(reduced if reduced is not None else view)
+        finally:
+            if reduced is not None:
+                reduced.close()
+        if leaf:
+            pts, nrm = voxel_grid(pts, nrm, leaf=leaf, dev=dev)
+        return cls(pts, nrm, d_dist=d_dist, ref_point_downsample_factor=ref_point_downsample_factor, params=params)
 
     def numPoints(self):
         return self.n
@@ -2115,6 +2162,81 @@ def mask_view(view, render, mode="remove", dilate=2, only=-1):
     v.width, v.height = view.width, view.height
     _check(lib().oslam_view_mask(view._h, render._h, C.byref(p), C.byref(v._h), C.byref(res)))
     return v, res.asdict()
+
+
+def default_planes_params(**kw):
+    """oslam_planes_params_default, then the fields given as keywords."""
+    p = PlanesParams()
+    _check(lib().oslam_planes_params_default(C.byref(p)))
+    for k, v in kw.items():
+        if not hasattr(p, k) or k == "reserved":
+            raise TypeError("unknown planes parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+class Planes:
+    """The dominant planes of a view (oslam_planes): .planes is a list of dicts (normal, d, support, pixels, candidate,
+    rms), .labels() the int32 [h, w] label image (-1 = no plane), .rounds() the test tap (counts uint32 [max_planes, 256],
+    moments int64 [max_planes, 10]), .result a dict (n_planes, valid_in, labelled, launches, ms_total).  Made by
+    find_planes()."""
+
+    def __init__(self, view, params):
+        self._h = C.c_void_p(0)
+        res = PlanesResult()
+        _check(lib().oslam_view_planes(view._h, C.byref(params), C.byref(self._h), C.byref(res)))
+        self.width, self.height, self.max_planes = view.width, view.height, int(params.max_planes)
+        self.result = res.asdict()
+        rec, n = (Plane * PLANES_MAX)(), C.c_size_t(0)
+        _check(lib().oslam_planes_get(self._h, rec, PLANES_MAX, C.byref(n)))
+        self.planes = [rec[k].asdict() for k in range(n.value)]
+        self.records = np.frombuffer(bytes(rec), np.uint32).reshape(PLANES_MAX, 8)[: n.value].copy()   # the records' words
+
+    def labels(self):
+        out = np.zeros(self.width * self.height, np.int32)
+        _check(lib().oslam_planes_labels(self._h, _p(out)))
+        return out.reshape(self.height, self.width)
+
+    def rounds(self):
+        counts = np.zeros((self.max_planes, PLANES_CANDIDATES), np.uint32)
+        moments = np.zeros((self.max_planes, 10), np.int64)
+        _check(lib().oslam_planes_rounds(self._h, _p(counts), _p(moments)))
+        return counts, moments
+
+    def close(self):
+        if self._h:
+            lib().oslam_planes_destroy(self._h)
+            self._h = C.c_void_p(0)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def find_planes(view, params=None, **fields):
+    """Up to 8 dominant planes of the view and the label of every pixel (oslam_view_planes).  params: a PlanesParams;
+    otherwise the defaults with the fields given as keywords.  -> a Planes."""
+    if params is not None and fields:
+        raise TypeError("give params or fields, not both")
+    return Planes(view, params if params is not None else default_planes_params(**fields))
+
+
+def remove_planes(view, planes, mode="remove", only=-1):
+    """The view without (mode "remove") or with only (mode "keep") the pixels of the planes, or of plane `only` alone
+    (oslam_view_remove_planes).  -> a View owned by the caller; its .mask_result is the dict of mask_view (valid_in,
+    object_pixels = the plane pixels, valid_out, launches, ms_total)."""
+    modes = {"remove": MASK_REMOVE, "keep": MASK_KEEP, MASK_REMOVE: MASK_REMOVE, MASK_KEEP: MASK_KEEP}
+    if mode not in modes:
+        raise ValueError("mode must be 'remove' or 'keep'")
+    res = MaskResult()
+    v = View.__new__(View)
+    v._h = C.c_void_p(0)
+    v.width, v.height = view.width, view.height
+    _check(lib().oslam_view_remove_planes(view._h, planes._h, modes[mode], int(only), C.byref(v._h), C.byref(res)))
+    v.mask_result = res.asdict()
+    return v
 
 
 def default_bilateral_params(**kw):

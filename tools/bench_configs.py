@@ -49,6 +49,10 @@ configuration; these are not bench lines).  Needs a HIP device.
                                          the surface's points, median of 20 calls each, Volume.step in frames/s without
                                          and with colour, and the coloured mesh of the calibration room written as PLY
                                          with its colour error
+  python tools/bench_configs.py findplanes  frame 0 of the camera configuration's room at 640x480: find_planes and
+                                         remove_planes, median of 20 calls each, the scene points before and after, and
+                                         the recognition chain on the full scene next to plane finding + removal + the
+                                         chain on the reduced scene, alternating (`planes` is the plane-dominated clouds)
 One JSON line each."""
 import importlib, json, os, sys, time
 
@@ -1532,8 +1536,86 @@ def normals(calls=20, warm=5):
     return out
 
 
+def findplanes(calls=20, warm=3):
+    """The planes stage (oslam_view_planes, oslam_view_remove_planes) on frame 0 of the camera configuration's room at
+    640x480: the median of `calls` calls of find_planes (host clock and the library's) and of remove_planes, the scene
+    points before and after, and the recognition chain (align + refine + verify of the room's three objects, the
+    verification against the original view) on the full scene next to plane finding + removal + the chain on the reduced
+    scene, the two alternating in one process.  `findplanes only` runs the find_planes calls alone, for a kernel trace."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import camera_ref as E
+    import planes_inputs as PI
+    import refine_ref
+    img, cam = PI.room_frame(synth, 0, "full")
+    view = PI.view_of(ppf, dict(depth=img, cam=cam, max_jump=E.MAX_JUMP))
+    for _ in range(warm):
+        ppf.find_planes(view).close()
+    t_find, t_lib, t_rm = [], [], []
+    for _ in range(calls):
+        t = time.perf_counter(); pl = ppf.find_planes(view); t_find.append(1e3 * (time.perf_counter() - t))
+        t_lib.append(pl.result["ms_total"])
+        if len(sys.argv) > 2 and sys.argv[2] == "only":
+            pl.close()
+            continue
+        t = time.perf_counter(); rv = ppf.remove_planes(view, pl); t_rm.append(1e3 * (time.perf_counter() - t))
+        last = (pl.planes, pl.result, rv.mask_result)
+        rv.close()
+        pl.close()
+    out = {"config": "planes stage (oslam_view_planes): frame 0 of the room, 640x480", "calls": calls,
+           "library": os.path.basename(ppf.LIB_PATH), "find_planes_ms_median": float(np.median(t_find)),
+           "find_planes_ms_library_median": float(np.median(t_lib))}
+    if not t_rm:
+        return out
+    planes, res, mres = last
+    out.update({"remove_planes_ms_median": float(np.median(t_rm)),
+                "planes": [{"support": p["support"], "pixels": p["pixels"], "rms_mm": round(1e3 * p["rms"], 3)} for p in planes],
+                "result": {k: res[k] for k in ("n_planes", "valid_in", "labelled", "launches")},
+                "mask": {k: mres[k] for k in ("valid_in", "object_pixels", "valid_out")}})
+    models, d, truth = PI.room_models(ppf, synth)
+
+    def full_chain():
+        sc = ppf.Scene.from_view(view, None, leaf=d, d_dist=d, ref_point_downsample_factor=PI.E2E_DF)
+        r = PI.chain(ppf, models, sc, view)
+        n = sc.numPoints()
+        sc.close()
+        return r, n
+
+    def reduced_chain():
+        pl = ppf.find_planes(view)
+        sc = ppf.Scene.from_view(view, pl, leaf=d, d_dist=d, ref_point_downsample_factor=PI.E2E_DF)
+        r = PI.chain(ppf, models, sc, view)
+        n = sc.numPoints()
+        sc.close()
+        pl.close()
+        return r, n
+
+    full_chain(); reduced_chain()
+    t_full, t_red = [], []
+    for _ in range(calls):                                          # the two alternate, so that drift hits them alike
+        t = time.perf_counter(); ra, na = full_chain(); t_full.append(1e3 * (time.perf_counter() - t))
+        t = time.perf_counter(); rb, nb = reduced_chain(); t_red.append(1e3 * (time.perf_counter() - t))
+    n_before = len(ppf.view_to_cloud(view)[0])
+    pl = ppf.find_planes(view)
+    rv = ppf.remove_planes(view, pl)
+    n_after = len(ppf.view_to_cloud(rv)[0])
+    rv.close(); pl.close()
+
+    def report(r):
+        return [{"found": x["found"], "rot_deg_trans_m": [round(e, 5) for e in refine_ref.pose_error(x["T"], truth[k])]}
+                for k, x in enumerate(r)]
+    out.update({"points_with_normal_before": n_before, "points_with_normal_after": n_after,
+                "scene_points_full": na, "scene_points_reduced": nb, "leaf": d, "ref_point_df": PI.E2E_DF,
+                "chain_full_ms_median": float(np.median(t_full)), "chain_reduced_with_planes_ms_median": float(np.median(t_red)),
+                "ratio_full_over_reduced": float(np.median(t_full) / np.median(t_red)),
+                "full": report(ra), "reduced": report(rb)})
+    for m in models:
+        m.close()
+    view.close()
+    return out
+
+
 if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "cfg3"
     print(json.dumps({"cfg2": cfg2, "cfg3": cfg3, "cfg3db": cfg3db, "cfg4": cfg4, "cfg5": cfg5, "planes": planes, "db50": db50,
                       "refine": refine, "verify": verify, "instances": instances, "arbitrate": arbitrate, "explain": explain, "track": track, "camera": camera,
-                      "fusion": fusion, "colour": colour, "surface": surface, "mesh": mesh, "shift": shift, "reload": reload, "worldsurface": worldsurface, "worldraycast": worldraycast, "worldmesh": worldmesh, "worldcolour": worldcolour, "pyramid": pyramid, "bilateral": bilateral, "normals": normals}[which]()), flush=True)
+                      "fusion": fusion, "colour": colour, "surface": surface, "mesh": mesh, "shift": shift, "reload": reload, "worldsurface": worldsurface, "worldraycast": worldraycast, "worldmesh": worldmesh, "worldcolour": worldcolour, "pyramid": pyramid, "bilateral": bilateral, "normals": normals, "findplanes": findplanes}[which]()), flush=True)
