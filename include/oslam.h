@@ -2015,7 +2015,8 @@ int oslam_ply_read_mesh(const char *path, float **xyz_out, float **nrm_out, uint
  *   nothing but *out = NULL.
  * Known limit: the normals of the reduced view are made again from the reduced image, so a kept pixel that touches a
  *   removed one loses its normal (DESIGN.md has the share on the calibration room).
- * Out of scope: connected components of a plane, merging planes across frames, planes of a cloud that has no image,
+ * Connected regions of what the planes leave: oslam_view_segments, below.
+ * Out of scope: merging planes across frames, planes of a cloud that has no image,
  *   folding the stage into oslam_db_detect or the tracker, a "stands on the plane" constraint for hypotheses. */
 #define OSLAM_PLANES_MAX 8
 typedef struct oslam_planes_params {
@@ -2047,6 +2048,81 @@ int oslam_planes_rounds(oslam_planes *p, uint32_t *counts_out, int64_t *moments_
 int oslam_view_remove_planes(const oslam_view *v, const oslam_planes *p, int mode, int32_t only, oslam_view **out,
                              oslam_mask_result *res);
 int oslam_planes_destroy(oslam_planes *p);
+
+/* ---- the connected regions of a view, on the device.  With the supporting planes gone, what is left of a frame is a few
+ * objects and the crumbs along the planes' borders; SLAM++-style pipelines group those pixels into connected regions and
+ * treat each as an object candidate.  oslam_view_segments labels the regions of a view (optionally minus the pixels of a
+ * planes object) and describes the largest, oslam_view_select_segments returns the view with or without them.  The
+ * restatement in numpy is tests/segments_ref.py; device and restatement agree byte for byte, and two calls give the same
+ * bytes: nothing here is a float sum, every result is an integer or one float made from integers in a fixed order.
+ *
+ *   1. Pixels.  A pixel is in iff z > 0 and, when planes is given, its plane label is < 0.
+ *   2. Edges.  Two in pixels a, b that are 4-neighbours are joined iff
+ *      fabsf(za - zb) <= max_step + rel_step * fminf(za, zb), in float32 with this grouping (the build's
+ *      -ffp-contract=off keeps the operations apart).  max_step 0 = the view's max_jump.  Diagonal neighbours are never
+ *      joined.
+ *   3. Components are the transitive closure of the edges; a component's root is its smallest linear pixel index
+ *      v * w + u.  n_components counts the roots, valid_in the in pixels.
+ *   4. Selection.  A component is a candidate iff pixels >= min_pixels (0 = max(1, w * h / 1000) in integer division).
+ *      With more than OSLAM_SEGMENTS_CANDIDATES candidates the call returns OSLAM_E_LIMIT with *out = NULL; it sets
+ *      res->n_components and res->n_candidates and writes nothing else (candidates are bounded by w * h / min_pixels, so
+ *      the default can never overflow).  Candidates are ranked by pixels descending, then by root ascending; the first
+ *      max_segments ranks become segments 0 .., every other in pixel gets label -1.  labelled = the sum of the segments'
+ *      pixels.
+ *   5. Records.  pixels, root, the bounding box (inclusive) and sides, derived from the box against the image borders.
+ *      The centroid comes from three int64 sums of q_a = (int32) rintf(p_a * 8192.0f) over the segment's pixels, p =
+ *      ((((float)u - cx) * z) / fx, (((float)v - cy) * z) / fy, z); a pixel with some fabsf(p_a * 8192.0f) > 2^30 is left
+ *      out of the centroid, and of the centroid only.  No sum can overflow: |q_a| <= 2^30 and w * h <= 2^28 pixels give at
+ *      most 2^58 < 2^63.  centroid_a = (float)(((double)S_a / (double)n) / 8192.0) with n the pixels that entered the
+ *      sums, 0 when n is 0.  (The bound is 131072 m from the optical axis: no sane camera reaches it; the tests do with
+ *      a focal length of a thousandth of a pixel.)
+ * Cost: two memsets, OSLAM_SEGMENTS_LAUNCHES (6) kernels whatever the image holds, one copy back, one host wait, no host
+ *   round trip inside the call; launches == 6.  The view's maps are not needed.
+ * oslam_segments keeps the root and label images on the device.  oslam_segments_get copies the records (OSLAM_E_LIMIT
+ *   and *n_out when cap is too small), oslam_segments_labels the label image [h][w] (the segment's rank or -1),
+ *   oslam_segments_roots is the test tap: [h][w], the component's root or -1 for a pixel that is not in.
+ * oslam_view_select_segments is oslam_view_remove_planes' contract with the segment pixels (label >= 0; with only >= 0:
+ *   label == only) as the object pixels: OSLAM_MASK_REMOVE or OSLAM_MASK_KEEP, a genuine view with v's camera and max_jump
+ *   that the caller owns, the same three counters, one kernel (k_planes_mask on the label image); launches == 1.
+ * Checks, before any device call: NULL v / out / s (planes, sp and res may be NULL), a max_step or rel_step that is not
+ *   finite or is < 0, max_segments 0 or above OSLAM_SEGMENTS_MAX, a mode other than the two, only < -1; then the handles:
+ *   max_step 0 on a view whose max_jump is 0, planes or segments of another device or image size than the view,
+ *   only >= n_segments: all OSLAM_E_INVALID.  OSLAM_E_DEVICE without a device.  A refused call writes nothing but
+ *   *out = NULL.
+ * Out of scope: 8-connectivity, a normal term in the gate, merging segments across frames, segments of a cloud that has
+ *   no image, folding the stage into oslam_db_detect or the tracker's births. */
+#define OSLAM_SEGMENTS_MAX        64      /* records kept */
+#define OSLAM_SEGMENTS_CANDIDATES 4096    /* components that may pass min_pixels in one call */
+#define OSLAM_SEGMENTS_LAUNCHES   6
+typedef struct oslam_segments_params {
+    float max_step;            /* metres; 0 (default) = the view's max_jump */
+    float rel_step;            /* per metre of depth, >= 0, default 0 */
+    unsigned min_pixels;       /* 0 (default) = max(1, w * h / 1000) in integer division */
+    unsigned max_segments;     /* 1..OSLAM_SEGMENTS_MAX, default 16 */
+    int reserved[4];
+} oslam_segments_params;
+typedef struct oslam_segment {
+    uint32_t pixels;           /* of the component */
+    uint32_t root;             /* its smallest linear pixel index v * w + u */
+    uint16_t u0, v0, u1, v1;   /* bounding box, inclusive */
+    float centroid[3];         /* camera frame, metres */
+    uint32_t sides;            /* bit 0..3: touches the left, top, right, bottom image border */
+} oslam_segment;
+typedef struct oslam_segments_result {
+    uint32_t n_segments, n_components, n_candidates, valid_in, labelled, launches;
+    float ms_total;
+} oslam_segments_result;
+typedef struct oslam_segments oslam_segments;
+
+int oslam_segments_params_default(oslam_segments_params *p);
+int oslam_view_segments(const oslam_view *v, const oslam_planes *planes, const oslam_segments_params *sp, oslam_segments **out,
+                        oslam_segments_result *res);
+int oslam_segments_get(const oslam_segments *s, oslam_segment *out, size_t cap, size_t *n_out);
+int oslam_segments_labels(oslam_segments *s, int32_t *labels_out);
+int oslam_segments_roots(oslam_segments *s, int32_t *roots_out);
+int oslam_view_select_segments(const oslam_view *v, const oslam_segments *s, int mode, int32_t only, oslam_view **out,
+                               oslam_mask_result *res);
+int oslam_segments_destroy(oslam_segments *s);
 
 /* ---- colour next to the TSDF (KinFu's colour volume): a view can carry the colour image its sensor registered with the
  * depth image, a volume a colour per voxel, and the fused colour comes back at the points of the surface and the mesh and

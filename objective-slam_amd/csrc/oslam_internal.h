@@ -129,6 +129,15 @@ struct oslam_planes {
     int64_t moments[OSLAM_PLANES_MAX][10];
 };
 
+struct oslam_segments {
+    int dev;                          /* stays the first field, as in oslam_view; w and h follow it (the argument tests write them) */
+    int w, h;
+    uint32_t n_segments;
+    uint32_t *d_roots;                /* [h * w] on the device: the root of every in pixel, all ones elsewhere */
+    int32_t *d_labels;                /* [h * w] on the device, -1 = no segment */
+    oslam_segment seg[OSLAM_SEGMENTS_MAX];
+};
+
 typedef struct db_group {
     int n;
     size_t *members;                  /* indices into db->models */

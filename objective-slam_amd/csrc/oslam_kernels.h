@@ -670,6 +670,48 @@ int oslamk_planes_find(const oslamk_planes_args *a, unsigned max_planes, void *s
 int oslamk_planes_mask(const oslamk_view *v, const int32_t *labels, int mode, int32_t only, float *z_out, uint32_t *counts,
                        void *stream);
 
+/* ---- segments stage (oslam_segments.hip; semantics in include/oslam.h at oslam_view_segments) ---- */
+#define OSLAMK_SEG_MAX 64             /* segment records of one call at most */
+#define OSLAMK_SEG_CAND 4096          /* components that may pass min_pixels in one call */
+#define OSLAMK_SEG_TILE 32            /* side of k_seg_tile's tile in pixels */
+#define OSLAMK_SEG_LAUNCHES 6         /* kernels of one call, whatever the image holds */
+#define OSLAMK_SEG_SCALE 8192.0f      /* the centroid sums' units per metre */
+#define OSLAMK_SEG_BOUND 1073741824.0f /* |p_a * 8192| above this (2^30) leaves a pixel out of the centroid */
+
+/* one segment as the kernels leave it: the host turns it into an oslam_segment */
+typedef struct oslamk_seg_acc {
+    uint32_t pixels, root;
+    uint32_t u0, v0, u1, v1;   /* bounding box, inclusive; k_seg_rank presets u0 = v0 = all ones */
+    uint32_t n;                /* pixels that entered the sums */
+    uint32_t pad;
+    unsigned long long s[3];   /* int64 sums of q_a, added as two's complement */
+} oslamk_seg_acc;
+
+/* the device block of one call, zeroed before the first launch; the host reads it up to `cand` */
+typedef struct oslamk_seg_block {
+    uint32_t n_components, n_candidates, valid_in;
+    uint32_t overflow;         /* 1: more than OSLAMK_SEG_CAND candidates, nothing was ranked or labelled */
+    oslamk_seg_acc acc[OSLAMK_SEG_MAX];
+    uint32_t cand[OSLAMK_SEG_CAND][2];   /* pixels, root; in the order the list was filled */
+} oslamk_seg_block;
+
+typedef struct oslamk_seg_args {
+    oslamk_view v;
+    const int32_t *plane_labels;   /* [h][w] or NULL: a pixel with a label >= 0 is not in */
+    uint32_t *L;               /* [h][w]: the parent of every in pixel, OSLAM_SEG_NONE elsewhere; the roots at the end */
+    uint32_t *tcount;          /* [h][w] scratch: at a tile-local root the pixels of its part of the tile, 0 elsewhere */
+    uint32_t *count;           /* [h][w] scratch, zeroed before the first launch: at a root the pixels of the component,
+                                  after k_seg_rank 1 << 31 | rank at the roots of the segments */
+    int32_t *labels;           /* [h][w]: the rank of the pixel's segment or -1 */
+    oslamk_seg_block *blk;
+    float max_step, rel_step;
+    uint32_t min_pixels;       /* resolved: never the 0 of the parameters */
+    uint32_t max_segments;     /* 1..OSLAMK_SEG_MAX */
+} oslamk_seg_args;
+
+/* every kernel of a call: k_seg_tile, k_seg_seam, k_seg_flatten, k_seg_collect, k_seg_rank, k_seg_label */
+int oslamk_segments_find(const oslamk_seg_args *a, void *stream);
+
 /* ---- explain stage (oslam_explain.hip; semantics in include/oslam.h at oslam_explain) ---- */
 /* the private z-buffer of one hypothesis: pixels [x0, x0 + w) x [y0, y0 + h) of the image, row-major from word `off` of
  * the pool; w == 0 or h == 0: it can draw nothing */

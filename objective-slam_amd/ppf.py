@@ -238,6 +238,33 @@ PLANES_MAX = 8
 PLANES_CANDIDATES = 256
 
 
+class SegmentsParams(C.Structure):
+    _fields_ = [("max_step", C.c_float), ("rel_step", C.c_float), ("min_pixels", C.c_uint), ("max_segments", C.c_uint),
+                ("reserved", C.c_int * 4)]
+
+
+class Segment(C.Structure):
+    _fields_ = [("pixels", C.c_uint32), ("root", C.c_uint32), ("u0", C.c_uint16), ("v0", C.c_uint16), ("u1", C.c_uint16),
+                ("v1", C.c_uint16), ("centroid", C.c_float * 3), ("sides", C.c_uint32)]
+
+    def asdict(self):
+        return dict(pixels=self.pixels, root=self.root, box=(self.u0, self.v0, self.u1, self.v1),
+                    centroid=tuple(self.centroid), sides=self.sides)
+
+
+class SegmentsResult(C.Structure):
+    _fields_ = [("n_segments", C.c_uint32), ("n_components", C.c_uint32), ("n_candidates", C.c_uint32),
+                ("valid_in", C.c_uint32), ("labelled", C.c_uint32), ("launches", C.c_uint32), ("ms_total", C.c_float)]
+
+    def asdict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+SEGMENTS_MAX = 64
+SEGMENTS_CANDIDATES = 4096
+SEGMENTS_LAUNCHES = 6
+
+
 class BilateralParams(C.Structure):
     _fields_ = [("radius", C.c_uint), ("sigma_space", C.c_float), ("sigma_depth", C.c_float), ("reserved", C.c_int * 4)]
 
@@ -555,6 +582,13 @@ _SIGNATURES = {
     "oslam_planes_rounds": (_i, [_vp, _vp, _vp]),
     "oslam_view_remove_planes": (_i, [_vp, _vp, _i, C.c_int32, C.POINTER(_vp), C.POINTER(MaskResult)]),
     "oslam_planes_destroy": (_i, [_vp]),
+    "oslam_segments_params_default": (_i, [C.POINTER(SegmentsParams)]),
+    "oslam_view_segments": (_i, [_vp, _vp, C.POINTER(SegmentsParams), C.POINTER(_vp), C.POINTER(SegmentsResult)]),
+    "oslam_segments_get": (_i, [_vp, _vp, _sz, C.POINTER(_sz)]),
+    "oslam_segments_labels": (_i, [_vp, _vp]),
+    "oslam_segments_roots": (_i, [_vp, _vp]),
+    "oslam_view_select_segments": (_i, [_vp, _vp, _i, C.c_int32, C.POINTER(_vp), C.POINTER(MaskResult)]),
+    "oslam_segments_destroy": (_i, [_vp]),
     "oslam_bilateral_params_default": (_i, [C.POINTER(BilateralParams)]),
     "oslam_view_bilateral": (_i, [_vp, C.POINTER(BilateralParams), C.POINTER(_vp), C.POINTER(BilateralResult)]),
     "oslam_gauss_table": (_i, [_u, C.POINTER(_f)]),
@@ -1262,10 +1296,18 @@ class Scene:
         return self
 
     @classmethod
-    def from_view(cls, view, planes=None, leaf=None, d_dist=None, ref_point_downsample_factor=1, params=None, dev=0):
+    def from_view(cls, view, planes=None, leaf=None, d_dist=None, ref_point_downsample_factor=1, params=None, dev=0,
+                  segments=None, only=-1):
         """The view's pixels that have a normal as a scene: remove_planes (planes: a Planes of this view, None = keep
-        everything), view_to_cloud, a voxel_grid when leaf is given, then Scene(...)."""
-        reduced = remove_planes(view, planes) if planes is not None else None
+        everything), view_to_cloud, a voxel_grid when leaf is given, then Scene(...).  With segments (a Segments of this
+        view) the scene is that of select_segments(view, segments, "keep", only); the planes then went into
+        find_segments, and giving both is a TypeError."""
+        if segments is not None and planes is not None:
+            raise TypeError("give planes or segments, not both: the planes went into find_segments")
+        if segments is not None:
+            reduced = select_segments(view, segments, "keep", only)
+        else:
+            reduced = remove_planes(view, planes) if planes is not None else None
         try:
             pts, nrm = view_to_cloud(reduced if reduced is not None else view)
         finally:
@@ -2235,6 +2277,83 @@ def remove_planes(view, planes, mode="remove", only=-1):
     v._h = C.c_void_p(0)
     v.width, v.height = view.width, view.height
     _check(lib().oslam_view_remove_planes(view._h, planes._h, modes[mode], int(only), C.byref(v._h), C.byref(res)))
+    v.mask_result = res.asdict()
+    return v
+
+
+def default_segments_params(**kw):
+    """oslam_segments_params_default, then the fields given as keywords."""
+    p = SegmentsParams()
+    _check(lib().oslam_segments_params_default(C.byref(p)))
+    for k, v in kw.items():
+        if not hasattr(p, k) or k == "reserved":
+            raise TypeError("unknown segments parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+class Segments:
+    """The connected regions of a view (oslam_segments): .segments is a list of dicts (pixels, root, box = (u0, v0, u1,
+    v1), centroid, sides), .records the records' words uint32 [n_segments, 8], .labels() the int32 [h, w] label image (a
+    segment's rank or -1), .roots() the test tap (int32 [h, w], the component's root or -1), .result a dict (n_segments,
+    n_components, n_candidates, valid_in, labelled, launches, ms_total).  Made by find_segments()."""
+
+    def __init__(self, view, planes, params):
+        self._h = C.c_void_p(0)
+        res = SegmentsResult()
+        _check(lib().oslam_view_segments(view._h, planes._h if planes is not None else None, C.byref(params), C.byref(self._h),
+                                         C.byref(res)))
+        self.width, self.height = view.width, view.height
+        self.result = res.asdict()
+        rec, n = (Segment * SEGMENTS_MAX)(), C.c_size_t(0)
+        _check(lib().oslam_segments_get(self._h, rec, SEGMENTS_MAX, C.byref(n)))
+        self.segments = [rec[k].asdict() for k in range(n.value)]
+        self.records = np.frombuffer(bytes(rec), np.uint32).reshape(SEGMENTS_MAX, 8)[: n.value].copy()
+
+    def labels(self):
+        out = np.zeros(self.width * self.height, np.int32)
+        _check(lib().oslam_segments_labels(self._h, _p(out)))
+        return out.reshape(self.height, self.width)
+
+    def roots(self):
+        out = np.zeros(self.width * self.height, np.int32)
+        _check(lib().oslam_segments_roots(self._h, _p(out)))
+        return out.reshape(self.height, self.width)
+
+    def close(self):
+        if self._h:
+            lib().oslam_segments_destroy(self._h)
+            self._h = C.c_void_p(0)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def find_segments(view, planes=None, params=None, **fields):
+    """The connected regions of the view's pixels, without the pixels of `planes` (a Planes of this view) when given, and
+    the label of every pixel (oslam_view_segments).  params: a SegmentsParams; otherwise the defaults with the fields given
+    as keywords.  More than 4096 components of min_pixels or more raise OslamError (OSLAM_E_LIMIT) with both counts in the
+    message.  -> a Segments."""
+    if params is not None and fields:
+        raise TypeError("give params or fields, not both")
+    return Segments(view, planes, params if params is not None else default_segments_params(**fields))
+
+
+def select_segments(view, segs, mode="keep", only=-1):
+    """The view with only (mode "keep") or without (mode "remove") the pixels of the segments, or of segment `only` alone
+    (oslam_view_select_segments).  -> a View owned by the caller; its .mask_result is the dict of mask_view (valid_in,
+    object_pixels = the segment pixels, valid_out, launches, ms_total)."""
+    modes = {"remove": MASK_REMOVE, "keep": MASK_KEEP, MASK_REMOVE: MASK_REMOVE, MASK_KEEP: MASK_KEEP}
+    if mode not in modes:
+        raise ValueError("mode must be 'remove' or 'keep'")
+    res = MaskResult()
+    v = View.__new__(View)
+    v._h = C.c_void_p(0)
+    v.width, v.height = view.width, view.height
+    _check(lib().oslam_view_select_segments(view._h, segs._h, modes[mode], int(only), C.byref(v._h), C.byref(res)))
     v.mask_result = res.asdict()
     return v
 

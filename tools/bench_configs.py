@@ -53,6 +53,10 @@ configuration; these are not bench lines).  Needs a HIP device.
                                          remove_planes, median of 20 calls each, the scene points before and after, and
                                          the recognition chain on the full scene next to plane finding + removal + the
                                          chain on the reduced scene, alternating (`planes` is the plane-dominated clouds)
+  python tools/bench_configs.py segments  the same frame: find_planes + find_segments(view, planes) + select_segments,
+                                         median of 20 calls each, the chain of the three models on the reduced scene next
+                                         to the chain of each model on each of the three largest segments' scenes,
+                                         alternating (`segments only`: the find_segments calls alone)
 One JSON line each."""
 import importlib, json, os, sys, time
 
@@ -1614,8 +1618,91 @@ def findplanes(calls=20, warm=3):
     return out
 
 
+def segments(calls=20, warm=3):
+    """The segments stage (oslam_view_segments, oslam_view_select_segments) on frame 0 of the camera configuration's room
+    at 640x480: the medians of `calls` calls of find_planes, find_segments(view, planes) and select_segments, the chain
+    align + refine + verify of the room's three models on the reduced scene of the planes stage, and the same chain with
+    each model against the scene of each of the three largest segments (nine small registrations), the two alternating
+    in one process.  `segments only` runs the find_segments calls alone, for a kernel trace."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import camera_ref as E
+    import planes_inputs as PI
+    import refine_ref
+    img, cam = PI.room_frame(synth, 0, "full")
+    view = PI.view_of(ppf, dict(depth=img, cam=cam, max_jump=E.MAX_JUMP))
+    pl = ppf.find_planes(view)
+    for _ in range(warm):
+        ppf.find_segments(view, pl).close()
+    t_seg, t_lib = [], []
+    for _ in range(calls):
+        t = time.perf_counter(); sg = ppf.find_segments(view, pl); t_seg.append(1e3 * (time.perf_counter() - t))
+        t_lib.append(sg.result["ms_total"])
+        sg.close()
+    out = {"config": "segments stage (oslam_view_segments): frame 0 of the room, 640x480", "calls": calls,
+           "library": os.path.basename(ppf.LIB_PATH), "find_segments_ms_median": float(np.median(t_seg)),
+           "find_segments_ms_library_median": float(np.median(t_lib))}
+    if len(sys.argv) > 2 and sys.argv[2] == "only":
+        pl.close(); view.close()
+        return out
+    pl.close()
+    t_find, t_sel, t_all = [], [], []
+    for _ in range(calls):
+        t0 = time.perf_counter(); pl = ppf.find_planes(view); t_find.append(1e3 * (time.perf_counter() - t0))
+        sg = ppf.find_segments(view, pl)
+        t = time.perf_counter(); sv = ppf.select_segments(view, sg, "keep", 0); t_sel.append(1e3 * (time.perf_counter() - t))
+        t_all.append(1e3 * (time.perf_counter() - t0))
+        last = (sg.segments, sg.result, sv.mask_result)
+        sv.close(); sg.close(); pl.close()
+    segs, res, mres = last
+    out.update({"find_planes_ms_median": float(np.median(t_find)), "select_segments_ms_median": float(np.median(t_sel)),
+                "planes_segments_select_ms_median": float(np.median(t_all)),
+                "segments": [{"pixels": s["pixels"], "box": list(s["box"]), "centroid": [round(c, 4) for c in s["centroid"]],
+                              "sides": s["sides"]} for s in segs],
+                "result": {k: res[k] for k in ("n_segments", "n_components", "n_candidates", "valid_in", "labelled", "launches")},
+                "mask": {k: mres[k] for k in ("valid_in", "object_pixels", "valid_out")}})
+    models, d, truth = PI.room_models(ppf, synth)
+
+    def reduced_chain():
+        pl = ppf.find_planes(view)
+        sc = ppf.Scene.from_view(view, pl, leaf=d, d_dist=d, ref_point_downsample_factor=PI.E2E_DF)
+        r = PI.chain(ppf, models, sc, view)
+        n = sc.numPoints()
+        sc.close(); pl.close()
+        return r, n
+
+    def segment_chain():
+        pl = ppf.find_planes(view)
+        sg = ppf.find_segments(view, pl)
+        r, n = [], []
+        for k in range(min(3, len(sg.segments))):
+            sc = ppf.Scene.from_view(view, segments=sg, only=k, leaf=d, d_dist=d, ref_point_downsample_factor=PI.E2E_DF)
+            r.append(PI.chain(ppf, models, sc, view))
+            n.append(sc.numPoints())
+            sc.close()
+        sg.close(); pl.close()
+        return r, n
+
+    reduced_chain(); segment_chain()
+    t_red, t_sg = [], []
+    for _ in range(calls):                                          # the two alternate, so that drift hits them alike
+        t = time.perf_counter(); ra, na = reduced_chain(); t_red.append(1e3 * (time.perf_counter() - t))
+        t = time.perf_counter(); rb, nb = segment_chain(); t_sg.append(1e3 * (time.perf_counter() - t))
+
+    def report(r):
+        return [{"found": x["found"], "rot_deg_trans_m": [round(e, 5) for e in refine_ref.pose_error(x["T"], truth[k])]
+                 if x["T"].any() else None} for k, x in enumerate(r)]
+    out.update({"scene_points_reduced": na, "scene_points_segments": nb, "leaf": d, "ref_point_df": PI.E2E_DF,
+                "chain_reduced_with_planes_ms_median": float(np.median(t_red)),
+                "chain_nine_on_segments_with_planes_and_segments_ms_median": float(np.median(t_sg)),
+                "reduced": report(ra), "segments_by_rank": [report(r) for r in rb]})
+    for m in models:
+        m.close()
+    view.close()
+    return out
+
+
 if __name__ == "__main__":
     which = sys.argv[1] if len(sys.argv) > 1 else "cfg3"
     print(json.dumps({"cfg2": cfg2, "cfg3": cfg3, "cfg3db": cfg3db, "cfg4": cfg4, "cfg5": cfg5, "planes": planes, "db50": db50,
                       "refine": refine, "verify": verify, "instances": instances, "arbitrate": arbitrate, "explain": explain, "track": track, "camera": camera,
-                      "fusion": fusion, "colour": colour, "surface": surface, "mesh": mesh, "shift": shift, "reload": reload, "worldsurface": worldsurface, "worldraycast": worldraycast, "worldmesh": worldmesh, "worldcolour": worldcolour, "pyramid": pyramid, "bilateral": bilateral, "normals": normals, "findplanes": findplanes}[which]()), flush=True)
+                      "fusion": fusion, "colour": colour, "surface": surface, "mesh": mesh, "shift": shift, "reload": reload, "worldsurface": worldsurface, "worldraycast": worldraycast, "worldmesh": worldmesh, "worldcolour": worldcolour, "pyramid": pyramid, "bilateral": bilateral, "normals": normals, "findplanes": findplanes, "segments": segments}[which]()), flush=True)
